@@ -14,6 +14,7 @@ pyMPC/mpc.py:80), synthetic data, FP64, all inputs resident in HBM when the time
     python bench.py --workload cfg2                # BASELINE configs[1]: ONE cart-pole controller (4,1,20), latency per update()
     python bench.py --workload notebook            # examples/example_inverted_pendulum_kalman.ipynb shape (4,1,150,75), one controller
     ... bench.py --gpus N --total-batch 1024       # BASELINE configs[3] read as strong scaling: the SAME 1024 instances over N GPUs
+    python bench.py --dump-outputs DIR             # also write what the last timed step computed (DIR/<name>.npy) to compare two builds by
 
 Two ways through the same library, both measured, `--path` chooses which one is `value` (the other is `other_path`):
   device_loop (default): the K steps run inside mpcqp_mpc_loop launches (output -> plant -> update -> solve per
@@ -467,6 +468,7 @@ class Shard:
         r = self.timed('loop', lambda: last.update(o=run(0, warmup, False)) if warmup else None, lambda: last.update(o=run(warmup, steps, True)))
         self.x = last['o'][0][-1].clone()
         self.u.copy_(last['o'][1][-1])
+        r['last_step'] = (last['o'][2][-1].clone(), last['o'][3][-1].clone())      # (status, iters) of the last timed step
         r['chunk'] = chunk
         ms = [e0.elapsed_time(e1) for e0, e1, _ in marks]
         # the LAST timed launch, instance by instance: when its workgroup entered and left (the kernel stamps the chip's 100 MHz clock) and how many
@@ -484,6 +486,17 @@ class Shard:
 
     def measure(self, path, steps, warmup):
         return {'stepwise': self.measure_stepwise, 'device_loop': self.measure_device_loop}[path](steps, warmup)
+
+    def last_step_outputs(self, res):
+        """What the last timed step handed its caller, per instance of this shard, as host arrays: u* [B, nu], the plant state x [B, nx]
+        (device loop: the state the step's input drove the plant to; stepwise: the state the step's QP was posed at), the solver status
+        and the ADMM iterations [B].  Read right after measure(), before anything else moves the shard on."""
+        if 'last_step' in res:      # device loop: the last row of the launch's (x, u, status, iters) output
+            st, it = (t.cpu().numpy() for t in res['last_step'])
+        else:                       # stepwise: u0() and infos() after the last solve
+            infos = self.prob.infos()
+            st, it = np.array([i.status for i in infos]), np.array([i.iter for i in infos])
+        return {'u': self.u.cpu().numpy(), 'x': self.x.cpu().numpy(), 'status': st.astype(np.float64), 'iters': it.astype(np.float64)}
 
     def sample_point(self, nsample=U_ERR_SAMPLE):
         """One more (untimed) closed-loop step through the stepwise API: returns the sampled QPs (x0, u_{-1}) and the
@@ -616,6 +629,27 @@ class Shard:
                     frac_of_read_stream=achieved / stream, read_stream_GBps=stream / 1e9, lds_state=lds_state,
                     algorithmic_8d={'bytes_per_launch': alg8d / launches, 'bytes_per_iter_per_qp': b_it8d, 'nnzL': prob.nnzL,
                                     'GBps': alg8d / secs / 1e9, 'frac_8d': alg8d / secs / HBM_PEAK})
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, for comparing two builds
+# ----------------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET = 64 << 20      # bytes: what --dump-outputs may write in all
+DUMP_SEED = 0               # the instance sample --dump-outputs keeps when the outputs are larger than that
+
+
+def dump_outputs(dirname, arrays, total):
+    """--dump-outputs: every array of `arrays` (name -> [total, ...] float64, in instance order) as DIR/<name>.npy, and DIR/instance.npy the
+    global instance index of each row.  Beyond DUMP_BUDGET bytes the rows are a fixed, seeded sample of the instances (the same for every run
+    of the same command), so that two builds can be compared output for output."""
+    row_bytes = 8 * (1 + sum(int(np.prod(a.shape[1:])) for a in arrays.values()))
+    keep = max(1, DUMP_BUDGET // row_bytes)
+    idx = np.arange(total) if total <= keep else np.sort(np.random.default_rng(DUMP_SEED).choice(total, keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.shape[0] == total, (name, a.shape, total)
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a[idx], dtype=np.float64))
+    np.save(os.path.join(dirname, 'instance.npy'), idx.astype(np.float64))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -932,8 +966,16 @@ def main():
     ap.add_argument('--backend', default=None, choices=['sweeps', 'dense', 'bcr8'],
                     help='force a KKT backend for the headline shard (mpcqp_settings.backend; default: the library chooses) -- profiling runs of the bandwidth kernel at the headline batch')
     ap.add_argument('--tuning', type=int, default=None, help='mpcqp_settings.tuning for the headline shard (development: switch a mechanism off, see enum mpcqp_tuning)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step of --path computed for every instance (u, x, status, iters; '
+                         'see Shard.last_step_outputs) as DIR/<name>.npy in float64, with DIR/instance.npy the instance index of each row; '
+                         'at most 64 MB in all (a fixed seeded sample of the instances beyond that).  cfg3 / cfg5 only')
     ap.add_argument('--dry-run', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.workload not in WORKLOADS:
+        ap.error('--dump-outputs: only the batch workloads (%s)' % ', '.join(WORKLOADS))
     if args.shared_model:
         args.no_cpu_baseline = args.no_other_path = True      # (the CPU legs and the u* references rebuild instance i's OWN model from its seed)
     self_launch_if_needed(args)
@@ -964,6 +1006,14 @@ def main():
     B = sh.B                                                          # this rank's instances
     prob = sh.prob
     res = sh.measure(args.path, args.steps, args.warmup)
+    if args.dump_outputs:
+        dumped = sh.last_step_outputs(res)
+        if comm_on(world):
+            parts = [None] * world
+            dist.all_gather_object(parts, dumped)                    # (rank order = instance order: the shards are contiguous blocks)
+            dumped = {k: np.concatenate([p[k] for p in parts]) for k in dumped}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dumped, TOTAL)
     elapsed, iters, refacts, solves = res['elapsed'], res['iters'], res['refacts'], res['solves']
     infos = prob.infos()
     n_solved = sum(1 for i in infos if i.status == 1)

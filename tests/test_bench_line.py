@@ -5,6 +5,8 @@ import json
 import os
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -101,3 +103,24 @@ def test_emit_writes_side_file_and_prints_last(tmp_path, monkeypatch, capsys):
     with open(tmp_path / 'legs.json') as f:
         full = json.load(f)
     assert full['hbm_leg']['roofline']['kernel'] == out['hbm_leg']['roofline']['kernel']      # everything is in the side file
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: every row in instance order while it fits; beyond the budget the same seeded sample of instances every time, and
+    nothing but float64 files within the budget."""
+    rng = np.random.default_rng(1)
+    arrays = {'u': rng.standard_normal((40, 4)), 'x': rng.standard_normal((40, 12)), 'iters': np.arange(40.0)}
+    bench.dump_outputs(str(tmp_path / 'all'), arrays, 40)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / 'all' / (k + '.npy'))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    assert np.array_equal(np.load(tmp_path / 'all' / 'instance.npy'), np.arange(40.0))
+    monkeypatch.setattr(bench, 'DUMP_BUDGET', 8 * 18 * 10)          # ten rows of (u, x, iters, instance)
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), arrays, 40)
+    idx = np.load(tmp_path / 's1' / 'instance.npy')
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0)
+    assert sum(os.path.getsize(p) - 128 for p in (tmp_path / 's1').iterdir()) <= bench.DUMP_BUDGET
+    for k, a in arrays.items():
+        s1, s2 = np.load(tmp_path / 's1' / (k + '.npy')), np.load(tmp_path / 's2' / (k + '.npy'))
+        assert np.array_equal(s1, s2) and np.array_equal(s1, a[idx.astype(int)])

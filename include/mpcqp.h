@@ -97,6 +97,8 @@ enum mpcqp_tuning {
     MPCQP_TUNE_NO_PARTS = 32,   /* persistent closed-loop launches: an instance's whole loop is ONE queue item (no parts) */
     MPCQP_TUNE_QUEUE_SOLVES = 64, /* development: persistent launches for single solves (mpcqp_solve) too, not only for the closed loop */
     MPCQP_TUNE_EVEN_PARTS = 128, /* development: persistent closed-loop launches cut an instance's steps into EQUAL parts (default: decreasing) */
+    MPCQP_TUNE_ITEMS_SHIFT = 16, /* development: tuning bits 16..22 = queue items per resident workgroup slot of a persistent closed-loop launch (what its step-range parts are cut by); 0 = the library's choice */
+    MPCQP_TUNE_NO_CARRY = 1 << 23, /* development: the closed loop on the device leaves the latency round after every solve (write-back, begin, prologue) instead of carrying a converged solve's iterate in registers into the next step of the queue item (A/B switch: results and launch structure are the same) */
     MPCQP_TUNE_ONE_LAUNCH_SOLVES = 1 << 29, /* development: a solve of more instances than resident slots as ONE persistent launch (instances off the queue, longest expected work first, each run to its end) instead of two launches (one round for everybody, then the unfinished ones re-dealt) */
     MPCQP_TUNE_NO_SHARE = 1 << 30, /* every instance solves with its own factor even where mpcqp_setup finds instances identical to instance 0 (mpcqp_share_factor; measurement switch: results are the same either way) */
     MPCQP_TUNE_SLOTS_SHIFT = 24, /* development: tuning bits 24..28 = resident workgroup slots of a persistent closed-loop launch in eighths of a workgroup per compute unit (8 = one per unit); 0 = the library's choice */

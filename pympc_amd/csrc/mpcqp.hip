@@ -118,6 +118,7 @@ struct mpcqp_handle {
     int *vcur_dev, *vdone_dev; unsigned *vqueue_dev;   // persistent launches: [slots] map entry each workgroup is working on; [batch] closed-loop steps done; the queue position
     std::vector<double> work_ema; // per instance: smoothed ADMM iterations per balancing interval (host)
     int ncu, solves_since_balance, auto_balance;
+    int loop_parts;               // queue-item parts per instance of the last persistent closed-loop launch (0: not persistent; mpcqp_dev_carry_stats)
     void *run_buf; size_t run_bytes;     // staging of mpcqp_mpc_run (disturbances, plant, trajectories)
     bool profiling;
     hipEvent_t ev0[MAXEV], ev1[MAXEV];   // ring of event pairs around the solve-kernel launches
@@ -220,7 +221,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     if (device < 0 || device >= ndev) return fail(MPCQP_ERR_ARG, "mpcqp_create: bad device index");
     HIPCHK(hipSetDevice(device));
     mpcqp_handle *h = new mpcqp_handle();
-    h->device = device; h->batch = batch; h->is_setup = false; h->u0_dev = nullptr; h->run_buf = nullptr; h->run_bytes = 0; h->perm_dev = nullptr; h->vcur_dev = nullptr; h->vdone_dev = nullptr; h->vqueue_dev = nullptr; h->qperm_dev = nullptr; h->qperm_set = false; h->solves_since_balance = 0; h->auto_balance = 1; h->ncu = 0;
+    h->device = device; h->batch = batch; h->is_setup = false; h->u0_dev = nullptr; h->run_buf = nullptr; h->run_bytes = 0; h->perm_dev = nullptr; h->vcur_dev = nullptr; h->vdone_dev = nullptr; h->vqueue_dev = nullptr; h->qperm_dev = nullptr; h->qperm_set = false; h->solves_since_balance = 0; h->auto_balance = 1; h->ncu = 0; h->loop_parts = 0;
     h->profiling = false; h->run_ms = 0.0; h->run_launches = 0; h->ev_count = 0; h->nevents = 0; h->stream = nullptr; h->own_stream = false;
     h->warm_x_pending = false;
     h->csc = nullptr; h->vec_buf = nullptr; h->step_blank = false;
@@ -312,7 +313,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     if (L.NB == 128) rc |= dalloc(h, &P.bws, B * (size_t)HugeFmt::GWS);      // (the factorization's work matrices of 128-wide stages)
     if (L.border) { rc |= dalloc(h, &P.Bb, B * (size_t)L.nu * L.N * L.NB); rc |= dalloc(h, &P.Zb, B * (size_t)L.nu * L.N * L.NB); rc |= dalloc(h, &P.Sig, B * (size_t)L.nu * L.nu); }
     rc |= dalloc(h, &P.Dt, B * L.n); rc |= dalloc(h, &P.Et, B * L.m);
-    rc |= dalloc(h, &P.ctype, B * L.m); rc |= dalloc(h, &P.info, B); rc |= dalloc(h, &P.stats, 8);
+    rc |= dalloc(h, &P.ctype, B * L.m); rc |= dalloc(h, &P.info, B); rc |= dalloc(h, &P.stats, 10);
         rc |= dalloc(h, &h->u0_dev, B * L.nu);
     rc |= dalloc(h, &P.work, B); rc |= dalloc(h, &h->perm_dev, B);
     rc |= dalloc(h, &h->vcur_dev, (size_t)std::max(4 * h->ncu, 1)); rc |= dalloc(h, &h->vqueue_dev, 4); rc |= dalloc(h, &h->vdone_dev, B); rc |= dalloc(h, &h->qperm_dev, B);
@@ -688,7 +689,8 @@ static RunKArgs run_kernel_args(mpcqp_handle *h, const RunArgs &R0, int *grid) {
         // closed loop: an instance's steps in parts, about QUEUE_ITEMS_PER_SLOT items per slot in all (a launch ends within half an item of its ideal
         // length; an item costs a kernel prologue, ~ 10 us)
         if (R0.nsteps > 1 && !(h->S.tuning & MPCQP_TUNE_NO_PARTS)) {
-            const int per_slot = ((h->S.tuning >> 16) & 0xFF) ? ((h->S.tuning >> 16) & 0xFF) : QUEUE_ITEMS_PER_SLOT;      // (bits 16..23: development override)
+            const int ov = (h->S.tuning >> MPCQP_TUNE_ITEMS_SHIFT) & 0x7F;      // (bits 16..22: development override)
+            const int per_slot = ov ? ov : QUEUE_ITEMS_PER_SLOT;
             const int parts = std::min(R0.nsteps, (per_slot * slots + h->batch - 1) / h->batch);
             if (parts > 1) {
                 // part lengths fall off towards the end of the loop (each takes about 2 / (parts left + 1) of what is left: 20 steps in 4 parts = 8, 6, 4, 2): the
@@ -706,6 +708,7 @@ static RunKArgs run_kernel_args(mpcqp_handle *h, const RunArgs &R0, int *grid) {
             }
         }
     }
+    if (R0.nsteps > 0) h->loop_parts = A.R.vcur ? std::max(1, A.R.vparts) : 0;
     return A;
 }
 template <int NB, bool LDSS, int NXT, int NUT, int MODE>
@@ -1154,19 +1157,31 @@ extern "C" int mpcqp_step_host(mpcqp_handle *h, const double *x0, const double *
     return MPCQP_OK;
 }
 
+// Development and tests, not part of the C ABI of include/mpcqp.h (the CPU twin does not have it): the closed loop's carry inside the latency round
+// since creation / the last reset of mpcqp_get_stats -- out3 = { steps whose transition the round made itself, of those the steps handed back to the
+// kernel's begin because a constraint type changed, queue-item parts per instance of the last persistent closed-loop launch (0 = not persistent) }.
+extern "C" int mpcqp_dev_carry_stats(mpcqp_handle *h, uint64_t *out3) {
+    if (!h || !out3) return fail(MPCQP_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(out3, h->P.stats + 8, 2 * sizeof(uint64_t), hipMemcpyDefault, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    out3[2] = (uint64_t)h->loop_parts;
+    return MPCQP_OK;
+}
+
 extern "C" int mpcqp_get_stats(mpcqp_handle *h, uint64_t *out4, int reset) {
     if (!h || !out4) return fail(MPCQP_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(out4, h->P.stats, 4 * sizeof(uint64_t), hipMemcpyDefault, h->stream));
 #ifdef MPCQP_RUN_TIMING
-    { uint64_t t[4]; hipMemcpy(t, h->P.stats + 4, sizeof(t), hipMemcpyDeviceToHost); fprintf(stderr, "phase wall-clock ticks: begin %llu admm %llu check %llu\n", (unsigned long long)t[0], (unsigned long long)t[1], (unsigned long long)t[2]);
+    { uint64_t t[4]; hipMemcpy(t, h->P.stats + 4, sizeof(t), hipMemcpyDeviceToHost); fprintf(stderr, "phase wall-clock ticks: begin %llu admm %llu check %llu body %llu\n", (unsigned long long)t[0], (unsigned long long)t[1], (unsigned long long)t[2], (unsigned long long)t[3]);
       unsigned long long g[16]; hipMemcpyFromSymbol(g, HIP_SYMBOL(g_ticks), sizeof(g)); unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_ticks), z, sizeof(z));
       if (h->L.nw == 8) mpcqp_w8_ticks(g);      // (the 512-thread kernels count in their own translation unit)
       { double tot = 0; for (int i = 0; i < 7; ++i) tot += (double)g[i]; if (tot <= 0) tot = 1;
         fprintf(stderr, "iteration cycles (thread 0, summed over workgroups): rhs %.1f%% fwd %.1f%% middle %.1f%% bwd %.1f%% t4 %.1f%% t5 %.1f%% t6 %.1f%% total %.3g;  outside the iterations (same unit): t7 %.3g t8 %.3g t9 %.3g;  check: setup+tail %.3g rows %.3g vars %.3g reduce %.3g decide %.3g\n",
                 100 * g[0] / tot, 100 * g[1] / tot, 100 * g[2] / tot, 100 * g[3] / tot, 100 * g[4] / tot, 100 * g[5] / tot, 100 * g[6] / tot, tot, (double)g[7], (double)g[8], (double)g[9], (double)g[10], (double)g[11], (double)g[12], (double)g[13], (double)g[14]); } }
 #endif
-    if (reset) HIPCHK(hipMemsetAsync(h->P.stats, 0, 8 * sizeof(uint64_t), h->stream));
+    if (reset) HIPCHK(hipMemsetAsync(h->P.stats, 0, 10 * sizeof(uint64_t), h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }

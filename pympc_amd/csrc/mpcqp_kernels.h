@@ -126,7 +126,7 @@ __device__ __forceinline__ void run_instance(const int k0, const int k1) {
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         P.tstamp[(size_t)TS_STRIDE * b + 2 + TS_STEPS - 1] = ((unsigned long long)(xcc & 15) << 32) | hw;
     }
-    if (MODE >= MODE_BCRT && tid == 0) S.iflag[2] = 0;      // (the rounds' LDS-resident part of the factor is not loaded yet: admm_latw; a barrier follows in load_common)
+    if (MODE >= MODE_BCRT && tid == 0) { S.iflag[2] = 0; S.iflag[6] = 0; S.iflag[7] = 0; }      // (the rounds' LDS-resident part of the factor is not loaded yet, no carry: admm_latw; a barrier follows in load_common)
     const double *step_src = step;
     if (!LOOP && R.inl_n) {                      // update(x0, u_{-1}, xref) from the kernel arguments: into the step blob for the phases that follow (behind load_common's
         for (int i = tid; i < R.inl_n; i += NT) step[i] = R.inl[i];      // barrier), while load_common reads the very same values from the arguments -- no round trip at all
@@ -145,8 +145,15 @@ __device__ __forceinline__ void run_instance(const int k0, const int k1) {
         return;
     }
     const int nx = L.nx, nu = L.nu;
+    // The latency round carries a converged solve into the item's next step itself (admm_latw, latw_carry) where nothing but x0, u_{-1} and the
+    // bounds and q entries they enter changes from step to step: no estimator, no reference trajectory, a warm start
+    const bool carry = LOOP && MODE >= MODE_BCRT && !(A.S.tuning & MPCQP_TUNE_NO_CARRY) && R.ny == 0 && !R.xref_traj && !R.plain && A.S.warm_start && !L.raw;
+    bool stepped = false;                        // (the step's transition was made inside the round, its begin was not: latw_carry)
     for (int k = k0; k < k1; ++k) {              // (LOOP = false: [0, 1), one solve of the current data -- mpcqp_solve)
-        if (LOOP) {
+#ifdef MPCQP_RUN_TIMING
+        const unsigned long long tbody = wall_clock64();
+#endif
+        if (LOOP && !stepped) {
             // scratch in the (idle) work area: un | xn | xt | ym | inn | xu, 128 doubles each (nx + nu <= 128, ny <= 64)
             double *un = S.T, *xn = S.T + 128, *xt = S.T + 256, *ym = S.T + 384, *inn = S.T + 512, *xu = S.T + 640;
             const size_t kb = (size_t)k * R.batch + b;
@@ -201,9 +208,12 @@ __device__ __forceinline__ void run_instance(const int k0, const int k1) {
             if (R.xref_traj) for (int i = tid; i < R.xref_blk; i += NT) { const double xr = R.xref_traj[kb * R.xref_blk + i]; step[nx + nu + i] = xr; if (i < nx) S.xrs[i] = xr; }
             __syncthreads();
         }
+        stepped = false;
+        if (carry && tid == 0) { S.iflag[6] = k; S.iflag[7] = k1; }      // (begin's barriers publish them)
 #ifdef MPCQP_RUN_TIMING
 #define PHASE_CLOCK(i) { unsigned long long t_ = wall_clock64(); if (tid == 0) atomicAdd(&P.stats[4 + (i)], t_ - tphase); tphase = t_; }
         unsigned long long tphase = wall_clock64();
+        if (LOOP && tid == 0) atomicAdd(&P.stats[7], tphase - tbody);      // (the loop body: output, plant, update)
 #else
 #define PHASE_CLOCK(i)
 #endif
@@ -231,6 +241,10 @@ __device__ __forceinline__ void run_instance(const int k0, const int k1) {
                 if (tid == 0) R.pending[atomicAdd(R.npending, 1)] = b;
                 break;
             }
+        }
+        if (carry) {                             // steps the round has finished itself (their records are written)
+            k = __builtin_amdgcn_readfirstlane(S.iflag[6]);
+            if (__builtin_amdgcn_readfirstlane(S.iflag[7]) < 0) { stepped = true; --k; __syncthreads(); continue; }
         }
         if (LOOP && tid == 0) {
             R.status_traj[(size_t)k * R.batch + b] = S.iflag[4];
@@ -299,7 +313,8 @@ __global__ __launch_bounds__(NT, run_occupancy(NB, MODE)) void k_mpc_run(RunKArg
                     volatile int *done = R.vdone + (entry & PERM_INST_MASK);
                     while (*done < ka) __builtin_amdgcn_s_sleep(16);
                 }
-                R.vcur[blockIdx.x] = entry;                   // (read by this workgroup only: the barrier below orders it)
+                R.vcur[blockIdx.x] = entry;                   // (read by this workgroup only: fenced, then the barrier below orders it)
+                __threadfence();
             }
             s_item[0] = entry; s_item[1] = ka; s_item[2] = kb;
         }
@@ -313,6 +328,7 @@ __global__ __launch_bounds__(NT, run_occupancy(NB, MODE)) void k_mpc_run(RunKArg
         __builtin_amdgcn_s_dcache_inv();                       // (inst_of's load of vcur[blockIdx.x] is a scalar load in most phases)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // (... and a vector load in the others; with parts: everything the previous part wrote)
         run_instance<NB, LDSSTATE, NXT, NUT, MODE, LOOP>(ka, kb);
+        if (nparts > 1) __threadfence();                     // (every thread's stores of the item, before the barrier that precedes vdone: release)
         __syncthreads();
         if (nparts > 1 && threadIdx.x == 0) { __threadfence(); *(volatile int *)(R.vdone + (entry & PERM_INST_MASK)) = kb; }
     }

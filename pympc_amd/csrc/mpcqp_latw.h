@@ -422,6 +422,8 @@ enum { LATW_CONTINUE = 0, LATW_SOLVED = 1, LATW_GENERIC = 2 };
 template <int NXT, int NUT, int NST>
 __device__ int latw_check(double pv, double pv2, double ncq, double zA, double ysA, double omA, double zB, double ysB, double omB, double z0, double ys0, double om0,
                           double loA, double hiA, double loB, double hiB, double cc, int iter, int *frame_pin);      // (mpcqp_latw_check.h)
+template <int NXT, int NUT, int NST>
+__device__ int latw_carry(int iter, int *frame_pin);      // (mpcqp_latw_check.h)
 
 // FAST (iter0 >= 0): the round does not end with its iterations.  The termination test of OSQP (update_info + check_termination, mpcqp_phases.h:
 // check_body) is evaluated right here in the OWNER layout -- A x and A'y are the two MFMA groups of the iteration applied to x and y, P x a 16-long
@@ -632,8 +634,19 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
         { FramePin pin; verdict = latw_check<NXT, NUT, NST>(pv[0], pv2[0], ncq[0], rA[0].z, rA[0].ys, rA[0].om, rB[0].z, rB[0].ys, rB[0].om, r0.z, r0.ys, r0.om,
                                                                loA[0], hiA[0], loB[0], hiB[0], cc, iter, &pin.v); }
         verdict = __builtin_amdgcn_readfirstlane(verdict);
-        if (verdict == LATW_SOLVED) { term = 1; break; }
-        if (verdict != LATW_CONTINUE) break;
+        if (verdict == LATW_SOLVED) {
+            // the closed loop on the device: the queue item's next step -- output, plant, update, q -- without leaving this function
+            // (latw_carry), and its solve warm-started from the owner registers, as a write-back, begin and this prologue would start it
+            const int kc = __builtin_amdgcn_readfirstlane(S.iflag[6]), ke = __builtin_amdgcn_readfirstlane(S.iflag[7]);
+            if (!(R.nsteps > 0 && kc >= 0 && ke <= R.nsteps && kc + 1 < ke)) { term = 1; break; }      // (iflag[6], [7]: run_instance's)
+            int carried;
+            { FramePin pin; carried = latw_carry<NXT, NUT, NST>(iter, &pin.v); }
+            if (!__builtin_amdgcn_readfirstlane(carried)) { term = 1; break; }      // (a constraint type changed: the kernel's begin refactors)
+            // what changed in the owned coefficients -- q of stage 0's inputs, the bounds of stage 0's dynamics rows: where latw_carry left them
+            if (u0v) ncq[0] = Tc[sl[0]];
+            if (is_x && wv == 0 && (lane & 3) == 0) { loA[0] = Cc[sl[0]]; hiA[0] = loA[0]; }
+            iter = 0;
+        } else if (verdict != LATW_CONTINUE) break;
         iters = next_stop(iter, R.max_iter, R.chk, R.rho_every) - iter;
         // The next round starts from exactly the state a write-back and a reload would give it -- y leaves as ys (om / c) and comes back as c y / om:
         // the same two roundings here -- so that an instance's iterates do not depend on whether a round boundary was crossed in this function or through

@@ -145,3 +145,85 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     if (tid == 0) S.iflag[3] += 1;
     return LATW_CONTINUE;
 }
+
+// The closed loop on the device, between two steps of one queue item, without leaving the latency round (admm_latw, after latw_check has
+// returned LATW_SOLVED; Smem::iflag[6] = the step whose solve just ended, [7] = the end of the item, 0 where the carry does not apply -- the kernel
+// decides: no estimator, no reference trajectory, warm start on, not MPCQP_TUNE_NO_CARRY).  What the kernel's loop body and begin_body would do,
+// in their arithmetic and summation order: the records of step k, output (u_0 of the converged solve), plant step, update of x0 / u_{-1} / the
+// first Delta-u bounds and the step blob, and of what these enter -- q of stage 0's inputs (the only entries of q that change with a constant
+// reference), the types of stage 0's dynamics rows and the first Delta-u rows (the only bounds that move).  Every global request of the
+// function is issued before its first barrier: one memory round trip.
+// Returns 1: carried -- the caller starts step k + 1's solve from its owner registers, iflag[6] = k + 1, with the new -c q of stage 0's inputs
+// in Tc and the new bound of stage 0's dynamics rows in Cc at their owners' slots (both vectors are rewritten by the iteration before it reads
+// them).  Returns 0: a type changed -- the step's transition is done, its begin (refactorization) is not: iflag[7] = -1 tells the kernel to run
+// begin for step iflag[6] = k + 1.
+// A function of its own for the reason latw_check is one: nothing of it lives across the iterations.
+template <int NXT, int NUT, int NST>
+__device__ __noinline__ int latw_carry(int iter, int *frame_pin) {
+    PHASE_PIN_USE(frame_pin);
+#ifdef MPCQP_RUN_TIMING
+    const unsigned long long tw0_ = wall_clock64();
+#endif
+    constexpr int NB = 16, VS = LAT_VS(NST);
+    const RunKArgs &KA = run_kargs();
+    const Lay &L = KA.L; const Ptrs &P = KA.P; const RunArgs &R = KA.R;
+    RunSmem rs = run_smem<true>(L, P);
+    Smem &S = rs.S;
+    const int nx = NXT ? NXT : L.nx, nu = NUT ? NUT : L.nu;
+    const int b = inst_of(P.perm), tid = threadIdx.x;
+    double *step = P.step + (size_t)b * L.step_sz;
+    const int k = S.iflag[6], k1 = k + 1;                  // (written before the round began)
+    const size_t kb = (size_t)k1 * R.batch + b;
+    // the requests: disturbance, scaling and current type of the row this thread checks, rho and c
+    const int r = tid < nx ? tid : (tid < nx + nu ? L.rdu + (tid - nx) : -1);
+    const double v = (tid < nx && R.w) ? R.w[kb * nx + tid] : 0.0;
+    const double Er = r >= 0 ? P.E[(size_t)b * L.m + r] : 0.0;
+    const int ct = r >= 0 ? P.ctype[(size_t)b * L.m + r] : 0;
+    const double rho = P.rho[b], cc = P.c[b];
+    __syncthreads();                                       // (S.uo, S.iflag[4]: latw_check's)
+    if (tid == 0) {
+        R.status_traj[(size_t)k * R.batch + b] = S.iflag[4];
+        R.iter_traj[(size_t)k * R.batch + b] = iter;
+        if (k < TS_STEPS) P.tstamp[(size_t)TS_STRIDE * b + 2 + k] = wall_clock64();
+    }
+    // ---- output (solved: the first input), plant step, update -- mpcqp_kernels.h run_instance, ny = 0
+    const double *un = S.uo, *xt = S.x0s;
+    double xn = 0.0;
+    if (tid < nx) {
+        const double *Ap = R.Ap ? R.Ap + (size_t)b * nx * nx : S.hot + L.oAd;
+        const double *Bp = R.Bp ? R.Bp + (size_t)b * nx * nu : S.hot + L.oBd;
+        double acc = 0.0;
+        for (int j = 0; j < nx; ++j) acc += Ap[tid * nx + j] * xt[j];
+        for (int j = 0; j < nu; ++j) acc += Bp[tid * nu + j] * un[j];
+        xn = acc + v;
+        R.x_traj[kb * nx + tid] = xt[tid];
+    }
+    if (tid < nu) R.u_traj[kb * nu + tid] = un[tid];
+    __syncthreads();
+    if (tid < nx) { S.x0s[tid] = xn; step[tid] = xn; }
+    if (tid < nu) { const double u = un[tid]; S.um1s[tid] = u; step[nx + tid] = u; S.du0[tid] = S.hot[L.oDumin + tid] + u; S.du0[nu + tid] = S.hot[L.oDumax + tid] + u; }
+    __syncthreads();
+    // ---- begin_body for what moved: q of stage 0's inputs (memory, and -c q for their owners), stage 0's dynamics-row bounds for theirs, types
+    const Ctx c{L, S.hot, S.hot + L.hot_sz};              // (hot_lds > hot_sz: the caller's fast path)
+    double *Tc = S.T + NB, *Cc = Tc + VS;                  // (owner slot of stage 0's slot a: a)
+    if (tid < nu) { const double qj = q_input(c, 0, tid, S.um1s, S.hot + L.ouref); S.Qv[L.n_x + tid] = qj; Tc[nx + tid] = -cc * qj; }
+    if (tid < nx) Cc[tid] = -S.x0s[tid];
+    int changed = 0;
+    if (r >= 0) { double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi); changed = row_type(Er, lo, hi) != ct; }
+    changed = __syncthreads_or(changed);
+    if (tid == 0) {
+        S.iflag[6] = k1;
+        atomicAdd(&P.stats[8], 1ULL);                      // (mpcqp_dev_carry_stats: steps carried, and of those handed back)
+        if (changed) { S.iflag[7] = -1; atomicAdd(&P.stats[9], 1ULL); }
+        else {
+            mpcqp_info *inf = P.info + b;                  // (begin_body's record, field by field: no frame for a local copy)
+            inf->status = MPCQP_UNSOLVED; inf->iter = 0; inf->rho_updates = 0; inf->reserved = 0;
+            inf->obj_val = 0.0; inf->pri_res = 0.0; inf->dua_res = 0.0; inf->rho = rho;
+            S.iflag[1] = 0; S.iflag[3] = 0;
+        }
+    }
+#ifdef MPCQP_RUN_TIMING
+    if (tid == 0) atomicAdd(&P.stats[7], wall_clock64() - tw0_);      // (the loop body's clock: transitions inside the round count there too)
+#endif
+    return changed ? 0 : 1;
+}

@@ -18,7 +18,10 @@ struct Smem {
 };
 // Smem::iflag (ints): [0] a factorization's non-positive-pivot flag, [1] rho updates and [3] termination checks of the solve in progress (what
 // mpcqp_info reports: kept here so that a check writes the record without reading it back first), [2] the latency round's LDS copy of the top
-// inverse is valid (mpcqp_latw.h), [4] status of the solve that just ended.  Smem::uo: its first input (what output() returns), Smem::xrs: the
+// inverse is valid (mpcqp_latw.h), [4] status of the solve that just ended, [5] the iteration count the latency round reached (admm_latw),
+// [6] / [7] the closed loop's carry inside that round (run_instance, latw_carry): [6] the step whose solve is in progress, [7] the end of the queue
+// item where the round may carry a converged solve into the next step (0: no carry), -1 after a carried transition whose begin the kernel still
+// has to run (a constraint type changed).  (carve(p, 4) below: eight ints.)  Smem::uo: its first input (what output() returns), Smem::xrs: the
 // constant reference (xref_rows == 1) -- both for the next step of the closed loop on the device, which would otherwise fetch them from memory.
 __device__ __forceinline__ BorderPtrs border_ptrs(const Lay &L, const Ptrs &P, const Smem &S) {
     BorderPtrs bp; bp.red = S.red;

@@ -127,6 +127,18 @@ __device__ __forceinline__ void row_bounds(const Ctx &c, const double *x0s, cons
     hi = hi > QP_INFTY ? QP_INFTY : hi;
 }
 
+// Linear cost of input jj at stage k (mpc.py:411-452): build_q's input entries, and the first stage's alone between two steps of the closed loop
+// (latw_carry, mpcqp_latw_check.h) -- one formula, so that both give the same bits.
+__device__ __forceinline__ double q_input(const Ctx &c, int k, int jj, const double *um1, const double *uref) {
+    const Lay &L = c.L;
+    double iu = (k == L.Nc - 1) ? (double)(L.Np - L.Nc + 1) : 1.0;
+    double a = 0.0;
+    for (int l = 0; l < L.nu; ++l) a += c.Qu()[jj * L.nu + l] * uref[l];
+    double acc = iu * (-a);
+    if (k == 0) { double d = 0.0; for (int l = 0; l < L.nu; ++l) d += c.QDu()[jj * L.nu + l] * um1[l]; acc += -d; }
+    return acc;
+}
+
 // Linear cost of the x and u variables (eps part is zero): mpc.py:489-526 / 411-452.
 // um1s / xrs: LDS copies of u_{-1} and of a constant reference (load_common; xrs = nullptr: the reference is a trajectory, read from the step blob).
 __device__ __forceinline__ void build_q(const Ctx &c, const double *step, double *Qv, const double *um1s = nullptr, const double *xrs = nullptr) {
@@ -143,11 +155,7 @@ __device__ __forceinline__ void build_q(const Ctx &c, const double *step, double
             acc = -acc;
         } else {
             int cc = j - L.n_x; int k = idiv(cc, L.rnu), jj = cc - k * L.nu;
-            double iu = (k == L.Nc - 1) ? (double)(L.Np - L.Nc + 1) : 1.0;
-            double a = 0.0;
-            for (int l = 0; l < L.nu; ++l) a += c.Qu()[jj * L.nu + l] * uref[l];
-            acc = iu * (-a);
-            if (k == 0) { double d = 0.0; for (int l = 0; l < L.nu; ++l) d += c.QDu()[jj * L.nu + l] * um1[l]; acc += -d; }
+            acc = q_input(c, k, jj, um1, uref);
         }
         Qv[j] = acc;
     }

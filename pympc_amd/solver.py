@@ -433,6 +433,15 @@ class BatchProblem:
         _lib.check(self._L.mpcqp_get_stats(self._h, out, int(bool(reset))), 'mpcqp_get_stats')
         return tuple(int(v) for v in out)
 
+    def carry_stats(self):
+        """(steps the latency round carried into the next step itself, of those handed back to begin, queue-item parts per instance of the last
+        persistent closed-loop launch) -- counters since creation / the last ``stats(reset=True)``."""
+        fn = self._L.mpcqp_dev_carry_stats                 # (development export of the HIP library, outside the C ABI)
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        out = (C.c_uint64 * 3)()
+        _lib.check(fn(self._h, out), 'mpcqp_dev_carry_stats')
+        return tuple(int(v) for v in out)
+
     def stream_bytes(self):
         """(bytes per ADMM iteration, per round, per solve) one instance streams by design (mpcqp_get_stream_bytes)."""
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()

@@ -19,6 +19,15 @@ SYMBOLS = [
     'mpcqp_export_qp', 'mpcqp_get_scaling', 'mpcqp_debug_kkt_solve', 'mpcqp_get_iterate', 'mpcqp_iterate', 'mpcqp_refactor', 'mpcqp_share_factor', 'mpcqp_eq_solve',
 ]
 
+# include/mpcqp_polish.h: an extension beside mpcqp.h, bound only where the loaded library exports it (the CPU twin does not)
+POLISH_SYMBOLS = ['mpcqp_polish_default_settings', 'mpcqp_set_polish', 'mpcqp_polish', 'mpcqp_get_polish_info']
+
+
+class PolishSettings(C.Structure):
+    """mpcqp_polish_settings (include/mpcqp_polish.h)."""
+    _fields_ = [('struct_size', C.c_int32), ('polish', C.c_int32), ('delta', C.c_double),
+                ('polish_refine_iter', C.c_int32), ('reserved', C.c_int32)]
+
 
 class Settings(C.Structure):
     _fields_ = [('rho', C.c_double), ('sigma', C.c_double), ('alpha', C.c_double),
@@ -130,8 +139,22 @@ def load():
         getattr(L, name)           # AttributeError here = header and library out of sync
         if name not in ('mpcqp_default_settings', 'mpcqp_status_string', 'mpcqp_last_error', 'mpcqp_destroy'):
             getattr(L, name).restype = C.c_int
+    if has_polish(L):
+        L.mpcqp_polish_default_settings.argtypes = [C.POINTER(PolishSettings)]
+        L.mpcqp_polish_default_settings.restype = None
+        L.mpcqp_set_polish.argtypes = [H, C.POINTER(PolishSettings)]
+        L.mpcqp_polish.argtypes = [H]
+        L.mpcqp_get_polish_info.argtypes = [H, C.c_void_p]
+        for name in ('mpcqp_set_polish', 'mpcqp_polish', 'mpcqp_get_polish_info'):
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
+
+
+def has_polish(L=None):
+    """True if the library exports include/mpcqp_polish.h (libmpcqp_hip.so does; the CPU twin does not)."""
+    L = L if L is not None else load()
+    return all(hasattr(L, name) for name in POLISH_SYMBOLS)
 
 
 def check(rc, what):

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/mpcqp.h"
+#include "../../include/mpcqp_polish.h"
 
 #include "mpcqp_defs.h"
 
@@ -78,6 +79,7 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #include "mpcqp_latw.h"
 #include "mpcqp_kernels.h"
 #include "mpcqp_latw_check.h"
+#include "mpcqp_polish.h"
 #include "mpcqp_csc.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -135,6 +137,8 @@ struct mpcqp_handle {
     double *vec_buf;                     // staging of mpcqp_update_vectors' host arrays [q | l | u], allocated on first use, kept
     bool step_blank;                     // set up through mpcqp_setup_qp: the step blob holds no x0 / u_{-1} / xref yet
     int *fown_dev; unsigned *nshared_dev;   // mpcqp_share_factor: [batch] factor slot per instance (P.fown points here while sharing is on); how many share
+    mpcqp_polish_settings pol;           // mpcqp_set_polish (include/mpcqp_polish.h)
+    PolishArgs pq; Lay pol_lay; size_t smem_polish;   // the polish's buffers (pq.status null until first use), layout and LDS
 };
 
 extern "C" void mpcqp_default_settings(mpcqp_settings *s) {
@@ -221,6 +225,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     if (device < 0 || device >= ndev) return fail(MPCQP_ERR_ARG, "mpcqp_create: bad device index");
     HIPCHK(hipSetDevice(device));
     mpcqp_handle *h = new mpcqp_handle();
+    mpcqp_polish_default_settings(&h->pol);
     h->device = device; h->batch = batch; h->is_setup = false; h->u0_dev = nullptr; h->run_buf = nullptr; h->run_bytes = 0; h->perm_dev = nullptr; h->vcur_dev = nullptr; h->vdone_dev = nullptr; h->vqueue_dev = nullptr; h->qperm_dev = nullptr; h->qperm_set = false; h->solves_since_balance = 0; h->auto_balance = 1; h->ncu = 0; h->loop_parts = 0;
     h->profiling = false; h->run_ms = 0.0; h->run_launches = 0; h->ev_count = 0; h->nevents = 0; h->stream = nullptr; h->own_stream = false;
     h->warm_x_pending = false;
@@ -878,7 +883,87 @@ static int launch_solve(mpcqp_handle *h, int plain_iters) {
     return rc;
 }
 
-extern "C" int mpcqp_solve(mpcqp_handle *h) { if (!h) return fail(MPCQP_ERR_ARG, "null handle"); return launch_solve(h, 0); }
+// ---- solution polishing (include/mpcqp_polish.h, mpcqp_polish.h) --------------------------------------------------------------
+extern "C" void mpcqp_polish_default_settings(mpcqp_polish_settings *s) {
+    if (!s) return;
+    memset(s, 0, sizeof(*s));
+    s->struct_size = (int32_t)sizeof(mpcqp_polish_settings); s->polish = 0; s->delta = 1e-6; s->polish_refine_iter = 3;
+}
+extern "C" int mpcqp_set_polish(mpcqp_handle *h, const mpcqp_polish_settings *s) {
+    if (!h || !s) return fail(MPCQP_ERR_ARG, "null argument");
+    if (s->struct_size != (int32_t)sizeof(mpcqp_polish_settings)) return fail(MPCQP_ERR_ARG, "mpcqp_set_polish: struct_size is not sizeof(mpcqp_polish_settings) (take the struct from mpcqp_polish_default_settings)");
+    if ((s->polish != 0 && s->polish != 1) || !(s->delta > 0.0) || !(s->delta < 1e30) || s->polish_refine_iter < 0)
+        return fail(MPCQP_ERR_ARG, "mpcqp_set_polish: polish must be 0 or 1, delta > 0, polish_refine_iter >= 0");
+    h->pol = *s;
+    return MPCQP_OK;
+}
+// The polish's buffers, on first use: the factor of K_pol in the generic block format, its metric, the polished point, the sweep vectors,
+// the active set, the border and workspace of the factorization, status_polish.
+static int polish_alloc(mpcqp_handle *h) {
+    if (h->pq.status) return MPCQP_OK;
+    const Lay G = polish_layout(h->L);
+    const size_t smem = sizeof(double) * (size_t)smem_common_doubles(G);
+    if (smem > 160 * 1024) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_polish: problem too large for one workgroup's LDS");
+    PolishArgs Q; memset(&Q, 0, sizeof(Q));
+    const size_t B = (size_t)h->batch;
+    Q.fsz = polish_factor_doubles(G);
+    int rc = 0;
+    rc |= dalloc(h, &Q.F, B * (size_t)Q.fsz);
+    rc |= dalloc(h, &Q.om, B * G.m); rc |= dalloc(h, &Q.s, B * G.n);
+    rc |= dalloc(h, &Q.x, B * G.n); rc |= dalloc(h, &Q.z, B * G.m); rc |= dalloc(h, &Q.y, B * G.m);
+    rc |= dalloc(h, &Q.r, B * G.n); rc |= dalloc(h, &Q.d, B * G.n); rc |= dalloc(h, &Q.e, B * G.n); rc |= dalloc(h, &Q.dd, B * G.n);
+    rc |= dalloc(h, &Q.bt, B * G.m); rc |= dalloc(h, &Q.act, B * G.m);
+    if (G.border) { rc |= dalloc(h, &Q.Bb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &Q.Zb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &Q.Sig, B * (size_t)G.nu * G.nu); }
+    if (G.NB == 128) rc |= dalloc(h, &Q.gws, B * (size_t)HugeFmt::GWS);
+    int *status = nullptr;
+    rc |= dalloc(h, &status, B);
+    if (rc) return MPCQP_ERR_HIP;      // (what was allocated stays in h->allocs: freed by mpcqp_destroy)
+    Q.status = status; Q.batch = h->batch;
+    h->pq = Q; h->pol_lay = G; h->smem_polish = smem;
+    return MPCQP_OK;
+}
+// Polish the last solve of every instance (k_polish; pub: mpcqp_step_host's mapped result block and flag, else null).
+static int launch_polish(mpcqp_handle *h, double *pub = nullptr, unsigned *done = nullptr, unsigned long long seq = 0) {
+    int rc = polish_alloc(h);
+    if (rc) return rc;
+    if (flush_puts(h)) return MPCQP_ERR_HIP;
+    PolishArgs Q = h->pq;
+    Q.delta = h->pol.delta; Q.refine = h->pol.polish_refine_iter; Q.pub = pub; Q.done = done; Q.seq = seq;
+    Ptrs P = h->P; P.perm = nullptr; P.fown = nullptr;      // (workgroup b = instance b; the polish factors into its own buffers)
+    Lay G = polish_layout(h->L);                            // (the handle's Lay changes with raw-vector mode and the reference shape)
+    DISPATCH_NB(G.NB, {
+        if (set_smem(k_polish<NB>, h->smem_polish)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_polish<NB>, dim3(h->batch), dim3(NT), h->smem_polish, h->stream, G, P, Q);
+    });
+    HIPCHK(hipGetLastError());
+    return MPCQP_OK;
+}
+// After a solve: polish it (polish on), or record 'not performed' where an earlier solve left a status_polish behind.
+static int after_solve(mpcqp_handle *h) {
+    if (h->pol.polish) return launch_polish(h);
+    if (h->pq.status) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * (size_t)h->batch, h->stream));
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_polish(mpcqp_handle *h) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_polish before mpcqp_setup");
+    HIPCHK(hipSetDevice(h->device));
+    return launch_polish(h);
+}
+extern "C" int mpcqp_get_polish_info(mpcqp_handle *h, int32_t *status_polish) {
+    if (!h || !status_polish) return fail(MPCQP_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->pq.status) { HIPCHK(hipStreamSynchronize(h->stream)); memset(status_polish, 0, sizeof(int32_t) * (size_t)h->batch); return MPCQP_OK; }
+    HIPCHK(hipMemcpyAsync(status_polish, h->pq.status, sizeof(int32_t) * (size_t)h->batch, hipMemcpyDefault, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+extern "C" int mpcqp_solve(mpcqp_handle *h) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    const int rc = launch_solve(h, 0);
+    return rc ? rc : after_solve(h);
+}
 extern "C" int mpcqp_refactor(mpcqp_handle *h) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_refactor before mpcqp_setup");
@@ -950,6 +1035,7 @@ static int get(mpcqp_handle *h, void *dst, const void *src, size_t bytes) {
 extern "C" int mpcqp_mpc_loop(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
     if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop: bad argument");
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_mpc_loop before mpcqp_setup");
+    if (h->pol.polish) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_mpc_loop / mpcqp_mpc_run: solution polishing inside the device closed loop is not implemented; switch polish off (mpcqp_set_polish) or step with mpcqp_mpc_step");
     if ((io->Ap == nullptr) != (io->Bp == nullptr)) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop: give both Ap and Bp or neither");
     const int ny = io->ny;
     if (ny < 0 || ny > 64) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop: ny must be in 0..64");
@@ -1007,6 +1093,7 @@ extern "C" int mpcqp_mpc_loop(mpcqp_handle *h, int nsteps, const mpcqp_loop *io)
     R.status_traj = (int *)dev(os); R.iter_traj = (int *)dev(oi);
     int rc = launch_run(h, R, 0);
     if (rc) return rc;
+    if (h->pq.status) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * B, h->stream));      // (the last solve of the loop: not polished)
     for (int i = 0; i < np; ++i)
         if (parts[i].dst && parts[i].bytes && !parts[i].direct && get(h, parts[i].dst, dev(i), parts[i].bytes)) return MPCQP_ERR_HIP;
     const bool due = balance_due(h);
@@ -1035,6 +1122,7 @@ extern "C" int mpcqp_eq_solve(mpcqp_handle *h, int sweeps, int cold, double tol,
         hipLaunchKernelGGL(k_eq_solve<NB>, dim3(h->batch), dim3(NT), h->smem_setup, h->stream, h->L, h->P, sweeps, cold, tol, dres);
     });
     HIPCHK(hipGetLastError());
+    if (h->pq.status) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * (size_t)h->batch, h->stream));      // (the polish setting is ignored here)
     if (res) HIPCHK(hipMemcpyAsync(res, dres, sizeof(double) * 5 * (size_t)h->batch, hipMemcpyDefault, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
@@ -1073,6 +1161,7 @@ extern "C" int mpcqp_mpc_step(mpcqp_handle *h, const double *x0, const double *u
     int rc = step_upload(h, x0, uminus1, xref, xref_rows);
     if (rc) return rc;
     if ((rc = launch_solve(h, 0))) return rc;
+    if ((rc = after_solve(h))) return rc;
     const int tot = h->batch * h->L.nu;
     hipLaunchKernelGGL(k_output_u, dim3((tot + 255) / 256), dim3(256), 0, h->stream, h->L, h->P, h->u0_dev, h->batch, 1);
     HIPCHK(hipGetLastError());
@@ -1136,7 +1225,10 @@ extern "C" int mpcqp_step_host(mpcqp_handle *h, const double *x0, const double *
     R.pin_in = (!inl && (x0 || uminus1 || xref)) ? (const double *)h->pin_in_dev : nullptr;
     R.pin_stride = h->pin_stride; R.pin_mask = (x0 ? 1 : 0) | (uminus1 ? 2 : 0) | (xref ? 4 : 0); R.pin_xref = nxr;
     R.pub = (double *)h->pin_out_dev; R.done = (unsigned *)h->npending_dev + 2; R.seq = ++h->host_seq;
+    if (h->pq.status && !h->pol.polish) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * B, h->stream));
+    if (h->pol.polish) R.pub = nullptr;                        // (polishing: the second launch, k_polish, publishes the results and raises the flag)
     int rc = launch_run(h, R, 0);
+    if (!rc && h->pol.polish) rc = launch_polish(h, (double *)h->pin_out_dev, (unsigned *)h->npending_dev + 2, h->host_seq);
     if (rc) return rc;
     h->step_blank = false;                                     // the step data has been accepted (a failed launch leaves the handle demanding it again)
     volatile unsigned long long *flag = (volatile unsigned long long *)((char *)h->pin_out + sizeof(double) * B * (L.n + L.m) + sizeof(mpcqp_info) * B);

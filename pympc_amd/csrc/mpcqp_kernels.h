@@ -379,6 +379,50 @@ __global__ __launch_bounds__(NT) void k_kkt_solve(Lay L, Ptrs P, const double *r
 // res [batch][5]: |P x + q + A_e'y|_inf, max(|P x|, |A_e'y|, |q|)_inf, |A_e x - b|_inf, max(|A_e x|, |b|)_inf after the last sweep, sweeps done.
 // Plain loops over the visitors: a utility on a handful of instances, not a hot path.
 // ------------------------------------------------------------------------------------------------
+// The three passes of one such sweep over the rows of an equality-constrained subproblem, shared with the polish (mpcqp_polish.h: the active
+// set instead of the dynamics rows).  Rows 0 .. nrows-1 are visited; sel(i, b) returns true if row i belongs to the subproblem and sets its
+// target b.  g (LDS, nrows doubles): c y + omega (A x - b) of the subproblem's rows; nrm[2], nrm[3]: |A x - b|, max(|A x|, |b|) of them.
+template <class Sel>
+__device__ __forceinline__ void mm_row_residual(const Ctx &c, int nrows, Sel sel, const double *x, const double *y, const double *om, double cc,
+                                                double *g, double *nrm) {
+    for (int i = threadIdx.x; i < nrows; i += NT) {
+        double b;
+        if (!sel(i, b)) { g[i] = 0.0; continue; }
+        double ax = 0.0;
+        A_row(c, i, [&](double co, int idx) { ax += co * x[idx]; });
+        g[i] = cc * y[i] + om[i] * (ax - b);
+        nrm[2] = fmax(nrm[2], fabs(ax - b)); nrm[3] = fmax(nrm[3], fmax(fabs(ax), fabs(b)));
+    }
+    __syncthreads();
+}
+// r = -c (P x + q + A_e' y) - A_e' (omega_e . (A_e x - b)) from g; nrm[0], nrm[1]: |P x + q + A_e'y|, max(|P x|, |A_e'y|, |q|).  Rows outside
+// the subproblem must carry g = 0 and y = 0 (or lie at or beyond nrows).
+__device__ __forceinline__ void mm_var_residual(const Ctx &c, int nrows, const double *x, const double *y, const double *g, const double *Qv,
+                                                double cc, double *r, double *nrm) {
+    const Lay &L = c.L;
+    for (int j = threadIdx.x; j < L.n; j += NT) {
+        double px = 0.0, atg = 0.0, aty = 0.0;
+        P_row(c, j, [&](double co, int idx) { px += co * x[idx]; });
+        AT_row(c, j, [&](double co, int row) { if (row < nrows) { atg += co * g[row]; aty += co * y[row]; } });
+        const double qj = (j < L.oe) ? Qv[j] : 0.0;
+        r[j] = -cc * (px + qj) - atg;
+        nrm[0] = fmax(nrm[0], fabs(px + qj + aty)); nrm[1] = fmax(nrm[1], fmax(fabs(px), fmax(fabs(aty), fabs(qj))));
+    }
+    __syncthreads();
+}
+// y += (omega / c) (A x - b) on the subproblem's rows
+template <class Sel>
+__device__ __forceinline__ void mm_dual_update(const Ctx &c, int nrows, Sel sel, const double *x, const double *om, double cc, double *y) {
+    for (int i = threadIdx.x; i < nrows; i += NT) {
+        double b;
+        if (!sel(i, b)) continue;
+        double ax = 0.0;
+        A_row(c, i, [&](double co, int idx) { ax += co * x[idx]; });
+        y[i] += (om[i] / cc) * (ax - b);
+    }
+    __syncthreads();
+}
+
 template <int NB>
 __global__ __launch_bounds__(NT) void k_eq_solve(Lay L, Ptrs P, int sweeps, int cold, double tol, double *res) {
     extern __shared__ __attribute__((aligned(16))) double sh[];
@@ -399,25 +443,11 @@ __global__ __launch_bounds__(NT) void k_eq_solve(Lay L, Ptrs P, int sweeps, int 
     int done = 0;
     bool settled = false;
     bool broken = P.info[b].status == MPCQP_NON_CVX && P.info[b].iter == 0;      // (k_setup's verdict on its factorization: a non-positive pivot)
+    auto dyn = [&](int i, double &lo) { double hi; row_bounds(c, S.x0s, S.du0, i, lo, hi); return true; };      // the dynamics rows, target lo (= hi)
     for (int sw = 0; sw <= sweeps && !broken; ++sw) {
         nrm[0] = nrm[1] = nrm[2] = nrm[3] = 0.0;
-        for (int i = tid; i < L.n_x; i += NT) {
-            double ax = 0.0, lo, hi;
-            A_row(c, i, [&](double co, int idx) { ax += co * x[idx]; });
-            row_bounds(c, S.x0s, S.du0, i, lo, hi);
-            g[i] = cc * y[i] + om[i] * (ax - lo);
-            nrm[2] = fmax(nrm[2], fabs(ax - lo)); nrm[3] = fmax(nrm[3], fmax(fabs(ax), fabs(lo)));
-        }
-        __syncthreads();
-        for (int j = tid; j < L.n; j += NT) {
-            double px = 0.0, atg = 0.0, aty = 0.0;
-            P_row(c, j, [&](double co, int idx) { px += co * x[idx]; });
-            AT_row(c, j, [&](double co, int row) { if (row < L.n_x) { atg += co * g[row]; aty += co * y[row]; } });
-            const double qj = (j < L.oe) ? S.Qv[j] : 0.0;
-            r[j] = -cc * (px + qj) - atg;
-            nrm[0] = fmax(nrm[0], fabs(px + qj + aty)); nrm[1] = fmax(nrm[1], fmax(fabs(px), fmax(fabs(aty), fabs(qj))));
-        }
-        __syncthreads();
+        mm_row_residual(c, L.n_x, dyn, x, y, om, cc, g, nrm);
+        mm_var_residual(c, L.n_x, x, y, g, S.Qv, cc, r, nrm);
         if (sw == sweeps || settled) break;
         kkt_solve<NB>(c, om, sv, cc, factor_of(P, b), r, S.T + L.m, d, border_ptrs(L, P, S), S.tv);
         double mx[2] = {0.0, 0.0}, dsum[1] = {0.0};
@@ -428,13 +458,7 @@ __global__ __launch_bounds__(NT) void k_eq_solve(Lay L, Ptrs P, int sweeps, int 
         //  the plain sum of the corrections carries it, as the objective does in check_body)
         if (dsum[0] != dsum[0]) { broken = true; break; }
         settled = mx[0] <= tol * fmax(1.0, mx[1]);       // (the residuals of the settled iterate are evaluated by one more pass of the loop head)
-        for (int i = tid; i < L.n_x; i += NT) {
-            double ax = 0.0, lo, hi;
-            A_row(c, i, [&](double co, int idx) { ax += co * x[idx]; });
-            row_bounds(c, S.x0s, S.du0, i, lo, hi);
-            y[i] += (om[i] / cc) * (ax - lo);
-        }
-        __syncthreads();
+        mm_dual_update(c, L.n_x, dyn, x, om, cc, y);
     }
     block_reduce<4, 1>(nrm, dummy, S.red);
     if (tid < 4) res[(size_t)b * 5 + tid] = nrm[tid];

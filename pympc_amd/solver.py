@@ -18,8 +18,9 @@ from . import _lib
 
 _SETTING_NAMES = [f[0] for f in _lib.Settings._fields_]
 # accepted for call compatibility with osqp, without effect on this solver
-_IGNORED_SETTINGS = ('verbose', 'polish', 'linsys_solver', 'time_limit', 'scaled_termination', 'delta',
-                     'polish_refine_iter', 'adaptive_rho_fraction')
+_IGNORED_SETTINGS = ('verbose', 'linsys_solver', 'time_limit', 'scaled_termination', 'adaptive_rho_fraction')
+# osqp's solution polishing (include/mpcqp_polish.h): applied with mpcqp_set_polish, any time after the handle exists
+_POLISH_SETTINGS = ('polish', 'delta', 'polish_refine_iter')
 
 
 # fixed when the handle is created / set up: mpcqp_update_settings keeps the handle's own values (include/mpcqp.h)
@@ -78,6 +79,12 @@ class forced_settings:
         return False
 
 
+def _split_polish(kw):
+    """(settings without the polish ones, the polish ones) of a settings dict."""
+    kw = dict(kw)
+    return kw, {k: kw.pop(k) for k in _POLISH_SETTINGS if k in kw}
+
+
 def make_settings(**kw):
     L = _lib.load()
     s = _lib.Settings()
@@ -114,6 +121,7 @@ class Result:
         self.info.pri_res = float(info.pri_res)
         self.info.dua_res = float(info.dua_res)
         self.info.rho_estimate = float(info.rho)
+        self.info.status_polish = 0               # osqp's name: 1 polished, -1 polishing rejected, 0 not performed (set by the caller)
 
 
 class BatchProblem:
@@ -126,6 +134,7 @@ class BatchProblem:
             raise RuntimeError('pympc_amd needs an AMD GPU (no HIP device visible); there is no CPU fallback')
         self.batch, self.nx, self.nu, self.Np = int(batch), int(nx), int(nu), int(Np)
         self.Nc = int(Np if Nc is None else Nc)
+        settings, polish = _split_polish(settings)
         self.settings = make_settings(**settings)
         rc = self._L.mpcqp_create(C.byref(self._h), int(device), self.batch, self.nx, self.nu, self.Np, self.Nc,
                                   C.byref(self.settings))
@@ -133,6 +142,7 @@ class BatchProblem:
             raise NotImplementedError(self._L.mpcqp_last_error().decode())
         _lib.check(rc, 'mpcqp_create')
         self._finish_init(stream)
+        self._set_polish(**polish)
 
     @classmethod
     def from_matrices(cls, P, A, batch=1, device=0, stream=None, nx=None, nu=None, **settings):
@@ -145,6 +155,7 @@ class BatchProblem:
         self._L = _lib.load()
         self._h = C.c_void_p()
         self.batch = int(batch)
+        settings, polish = _split_polish(settings)
         self.settings = make_settings(**settings)
         Pc, Ac = sp.csc_matrix(P), sp.csc_matrix(A)
         Pc.sort_indices(); Ac.sort_indices()
@@ -165,6 +176,7 @@ class BatchProblem:
         _lib.check(self._L.mpcqp_get_shape(self._h, *[C.byref(v) for v in d]), 'mpcqp_get_shape')
         self.nx, self.nu, self.Np, self.Nc = (v.value for v in d)
         self._finish_init(stream)
+        self._set_polish(**polish)
         return self
 
     def setup_csc(self, P_val, A_val, q, l, u):
@@ -180,6 +192,41 @@ class BatchProblem:
         _lib.check(rc, 'mpcqp_setup_csc')
 
     _hin = None                # (step_host of a single controller: input buffer, made on first use)
+    _polish = None             # mpcqp_polish_settings of the handle (None: the library has no polishing, include/mpcqp_polish.h)
+
+    def _set_polish(self, **kw):
+        """Apply osqp's polish / delta / polish_refine_iter (mpcqp_set_polish).  Asking for polish=True of a library without
+        include/mpcqp_polish.h raises NotImplementedError; it is never ignored."""
+        if not _lib.has_polish(self._L):
+            if kw.get('polish'):
+                raise NotImplementedError('polish=True: this build of the solver library has no solution polishing (include/mpcqp_polish.h)')
+            return
+        if self._polish is None:
+            self._polish = _lib.PolishSettings()
+            self._L.mpcqp_polish_default_settings(C.byref(self._polish))
+        if not kw:
+            return
+        for k, v in kw.items():
+            setattr(self._polish, k, int(bool(v)) if k == 'polish' else v)
+        _lib.check(self._L.mpcqp_set_polish(self._h, C.byref(self._polish)), 'mpcqp_set_polish')
+
+    @property
+    def polishing(self):
+        """True if the solves of this problem are polished (polish=True)."""
+        return self._polish is not None and bool(self._polish.polish)
+
+    def polish(self):
+        """Polish the last solve of every instance now (mpcqp_polish: stream-ordered), with this problem's delta / polish_refine_iter."""
+        if not _lib.has_polish(self._L):
+            raise NotImplementedError('this build of the solver library has no solution polishing (include/mpcqp_polish.h)')
+        _lib.check(self._L.mpcqp_polish(self._h), 'mpcqp_polish')
+
+    def polish_status(self):
+        """status_polish [batch] int32 of the last solve: 1 polished, -1 rejected, 0 not performed (mpcqp_get_polish_info; synchronises)."""
+        out = np.zeros(self.batch, dtype=np.int32)
+        if _lib.has_polish(self._L):
+            _lib.check(self._L.mpcqp_get_polish_info(self._h, _ptr(out)), 'mpcqp_get_polish_info')
+        return out
 
     def _finish_init(self, stream):
         n, m, fd, nnzL = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
@@ -278,6 +325,9 @@ class BatchProblem:
             pass
 
     def update_settings(self, **kw):
+        kw, polish = _split_polish(kw)
+        if polish:
+            self._set_polish(**polish)
         for k, v in kw.items():
             if k not in _SETTING_NAMES:
                 raise TypeError('unknown solver setting %r' % k)
@@ -405,7 +455,10 @@ class BatchProblem:
         io.x_traj, io.u_traj, io.status_traj, io.iter_traj = (_ptr(o) for o in out[:4])
         if ny and len(out) >= 6:
             io.xhat_traj, io.y_traj = _ptr(out[4]), _ptr(out[5])
-        _lib.check(self._L.mpcqp_mpc_loop(self._h, K, C.byref(io)), 'mpcqp_mpc_loop')
+        rc = self._L.mpcqp_mpc_loop(self._h, K, C.byref(io))
+        if rc == -4:
+            raise NotImplementedError(self._L.mpcqp_last_error().decode())
+        _lib.check(rc, 'mpcqp_mpc_loop')
         return tuple(out)
 
     def solution(self, want_y=True):
@@ -634,7 +687,10 @@ class DeviceProblem:
         else:
             self._bp.solve_async()
             x, y, info = self._bp.solution()
-        return Result(x[0], y[0], info[0], self._bp.status_string(info[0].status))
+        res = Result(x[0], y[0], info[0], self._bp.status_string(info[0].status))
+        if self._bp.polishing:
+            res.info.status_polish = int(self._bp.polish_status()[0])
+        return res
 
     @property
     def batch_problem(self):

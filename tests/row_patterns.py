@@ -1,0 +1,168 @@
+"""Mixed constraint-row patterns for the KKT backends (tests/test_row_patterns.py on the CPU twin, tests/test_gpu_row_types.py on the device).
+
+Every constraint row has a type -- loose (RHO_MIN), equality (1e3 rho) or inequality (rho) -- decided on the scaled bounds
+(csrc/mpcqp_phases.h: row_type / row_rho), stored per instance and built into every factorization.  ``draw`` makes controllers whose state
+box, input box and Delta-u bounds mix every kind, component by component; ``flip_types`` changes a kind after setup through the raw seam.
+
+Feasibility by construction.  pyMPC's Delta-u rows couple neighbouring channels (qp_build.build_qp: row k nu + j is u_flat[k nu + j + 1] -
+u_flat[k nu + j], the last one -u_flat[-1]), so the draw is built around one feasible input sequence, the constant c in every channel and
+every stage: every input box contains c (an equality input is c itself), every Delta-u range contains 0 (and -c on the last channel, whose
+range also bounds -u_flat[-1]: c = 0 when that range is an equality), and u_{-1} = c.  State boxes are soft unless ``soft=False``.
+"""
+import numpy as np
+
+KINDS = ('two', 'lower', 'upper', 'absent', 'eq')        # 'eq': inputs and Delta-u only
+STATE_KINDS = KINDS[:4]
+
+
+def _box(kind, half, centre=0.0):
+    return {'two': (centre - half, centre + half), 'lower': (centre - half, np.inf), 'upper': (-np.inf, centre + half),
+            'absent': (-np.inf, np.inf), 'eq': (centre, centre)}[kind]
+
+
+def draw(seed, nx, nu, Np, Nc=None, soft=True):
+    """Controller kwargs of one instance (MPCController / pympc_amd.fixtures style; ``_SOFT_ON`` = False for a hard state box,
+    fixtures.split_attrs).  Each component's kind is recorded in ``_kinds`` = {'x': [...], 'u': [...], 'du': [...]} -- not a
+    constructor argument: ``ctor`` strips it."""
+    rng = np.random.default_rng([int(seed), nx, nu, Np, Nc or 0, int(soft)])
+    G = rng.standard_normal((nx, nx))
+    Ad = G * (0.95 / np.max(np.abs(np.linalg.eigvals(G))))
+    Bd = rng.standard_normal((nx, nu))
+    xk = [STATE_KINDS[i] for i in rng.integers(0, 4, nx)]
+    uk = [KINDS[i] for i in rng.integers(0, 5, nu)]
+    dk = [KINDS[i] for i in rng.integers(0, 5, nu)]
+    c = 0.0 if dk[-1] == 'eq' else float(rng.uniform(-0.3, 0.3))
+    xbox = rng.uniform(3.0, 6.0, nx) if soft else rng.uniform(6.0, 10.0, nx)
+    ubox = rng.uniform(0.5, 1.5, nu)
+    dubox = rng.uniform(0.4, 1.0, nu)
+    xmin, xmax = np.array([_box(k, h) for k, h in zip(xk, xbox)]).T
+    umin, umax = np.array([_box(k, h) if k != 'eq' else (c, c) for k, h in zip(uk, ubox)]).T
+    Dumin, Dumax = np.array([_box(k, h) for k, h in zip(dk, dubox)]).T
+    Qx = (lambda M: M @ M.T / nx + 0.05 * np.eye(nx))(rng.standard_normal((nx, nx)))       # dense, positive definite
+    QxN = Qx.copy() if rng.random() < 0.5 else 3.0 * Qx
+    Qu, QDu = np.diag(rng.uniform(0.05, 0.5, nu)), np.diag(rng.uniform(0.05, 0.5, nu))
+    w = rng.random()
+    if w < 0.25:
+        Qu = np.zeros((nu, nu))
+    elif w < 0.5:
+        QDu = np.zeros((nu, nu))
+    x0 = (0.5 if soft else 0.2) * rng.standard_normal(nx)
+    kw = dict(Ad=Ad, Bd=Bd, Np=Np, x0=x0, xref=0.2 * rng.standard_normal(nx), uref=0.1 * rng.standard_normal(nu),
+              uminus1=np.full(nu, c), Qx=Qx, QxN=QxN, Qu=Qu, QDu=QDu, xmin=xmin, xmax=xmax, umin=umin, umax=umax,
+              Dumin=Dumin, Dumax=Dumax, eps_feas=float(10.0 ** rng.integers(3, 6)), _kinds=dict(x=xk, u=uk, du=dk))
+    if Nc is not None and Nc != Np:
+        kw['Nc'] = Nc
+    if not soft:
+        kw['_SOFT_ON'] = False
+    return kw
+
+
+def ctor(kw):
+    """(constructor kwargs, attributes to set afterwards) of a draw."""
+    return {k: v for k, v in kw.items() if not k.startswith('_')}, ({'SOFT_ON': False} if kw.get('_SOFT_ON', True) is False else {})
+
+
+def kinds_present(kws):
+    """Every (class, kind) pair that occurs in a list of draws."""
+    return {(cls, k) for kw in kws for cls, ks in kw['_kinds'].items() for k in ks}
+
+
+ALL_KINDS = {('x', k) for k in STATE_KINDS} | {(c, k) for c in ('u', 'du') for k in KINDS}
+
+
+def batch_seeds(nx, nu, Np, Nc=None, soft=True, B=8):
+    """B consecutive seeds whose draws hold every kind of every class between them (searched from 0 in steps of B: the first
+    block that covers; a shape with nu = 1 needs about ten blocks)."""
+    for base in range(0, 400 * B, B):
+        seeds = list(range(base, base + B))
+        if kinds_present([draw(s, nx, nu, Np, Nc, soft) for s in seeds]) >= ALL_KINDS:
+            return seeds
+    raise AssertionError('no block of %d seeds covers every row kind for %r' % (B, (nx, nu, Np, Nc)))
+
+
+def batch(nx, nu, Np, Nc=None, soft=True, B=8):
+    return [draw(s, nx, nu, Np, Nc, soft) for s in batch_seeds(nx, nu, Np, Nc, soft, B)]
+
+
+def stack(kws, **kw):
+    """BatchMPCController kwargs for a list of draws (tests/test_gpu_parity.py: _stacked_batch)."""
+    st = lambda k: np.stack([np.asarray(d[k], dtype=float) for d in kws])
+    k0 = kws[0]
+    args = dict(Ad=st('Ad'), Bd=st('Bd'), Np=k0['Np'], Nc=k0.get('Nc'), x0=st('x0'), xref=st('xref'), uref=st('uref'), uminus1=st('uminus1'),
+                Qx=st('Qx'), QxN=st('QxN'), Qu=st('Qu'), QDu=st('QDu'), xmin=st('xmin'), xmax=st('xmax'), umin=st('umin'), umax=st('umax'),
+                Dumin=st('Dumin'), Dumax=st('Dumax'), eps_feas=np.array([[d['eps_feas']] for d in kws]), SOFT_ON=k0.get('_SOFT_ON', True))
+    args.update(kw)
+    return args
+
+
+def row_rho(E, l, u, rho):
+    """rho per row from the row-type rule of csrc/mpcqp_phases.h (row_type / row_rho) on the scaled bounds."""
+    l, u = np.clip(l, -1e30, 1e30), np.clip(u, -1e30, 1e30)
+    ls, us = E * l, E * u
+    return np.where((ls < -1e26) & (us > 1e26), 1e-6, np.where(us - ls < 1e-4, 1e3 * rho, rho))
+
+
+def reduced_kkt(bp, b, sigma=1e-6):
+    """Dense c P + diag(sigma / D^2) + A' diag(rho_i E^2) A of instance b of a BatchProblem, from what it exports now: the matrix
+    every backend's factor must solve with (tests/test_gpu_backends.py: test_kkt_solve_matches_dense)."""
+    P, _, A, l, u = (v[b] for v in bp.export_qp())
+    D, E, c, rho = (v[b] for v in bp.scaling())
+    return c * P + np.diag(sigma / D ** 2) + A.T @ np.diag(row_rho(E, l, u, rho) * E ** 2) @ A
+
+
+def bounds(kw):
+    """(l, u) of the draw's QP (qp_build.build_qp's row layout: dynamics | state box | input box | Delta-u), bounds clipped to +-1e30."""
+    nx, nu = kw['Bd'].shape
+    Np = kw['Np']
+    Nc = kw.get('Nc', Np)
+    N = Np + 1
+    leq = np.concatenate([-np.asarray(kw['x0'], dtype=float), np.zeros(Np * nx)])
+    um1 = np.asarray(kw['uminus1'], dtype=float)
+    ldu, udu = np.tile(kw['Dumin'], Nc + 1), np.tile(kw['Dumax'], Nc + 1)
+    ldu[:nu] += um1
+    udu[:nu] += um1
+    l = np.concatenate([leq, np.tile(kw['xmin'], N), np.tile(kw['umin'], Nc), ldu])
+    u = np.concatenate([leq, np.tile(kw['xmax'], N), np.tile(kw['umax'], Nc), udu])
+    return np.clip(l, -1e30, 1e30), np.clip(u, -1e30, 1e30)
+
+
+def flip_types(kw, rng):
+    """Change the row type of one component class -- one state, input or Delta-u component, in every stage (the seam stores one
+    period of the bounds: k_decode_vectors, qp_recover.check_vectors) -- by one of inequality -> equality (inputs and Delta-u),
+    finite -> loose, loose -> inequality; the constant input c of the draw stays feasible.  Returns (new draw, l, u): the
+    vectors for BatchProblem.update_vectors / the oracle's update(l=, u=); dynamics rows stay the equalities carrying x0."""
+    kw = dict(kw)
+    kinds = {k: list(v) for k, v in kw['_kinds'].items()}
+    c = float(kw['uminus1'][0])
+    nu = kw['Bd'].shape[1]
+    moves = []
+    for cls, ks in kinds.items():
+        for j, k in enumerate(ks):
+            if k in ('two', 'lower', 'upper', 'eq'):
+                moves.append((cls, j, 'absent'))
+            if k == 'two' and cls != 'x' and not (cls == 'du' and j == nu - 1 and c != 0.0):
+                moves.append((cls, j, 'eq'))
+            if k == 'absent':
+                moves.append((cls, j, 'two'))
+    cls, j, new = moves[int(rng.integers(len(moves)))]
+    lo, hi = {'x': ('xmin', 'xmax'), 'u': ('umin', 'umax'), 'du': ('Dumin', 'Dumax')}[cls]
+    kw[lo], kw[hi] = np.array(kw[lo], dtype=float), np.array(kw[hi], dtype=float)
+    if new == 'absent':
+        kw[lo][j], kw[hi][j] = -np.inf, np.inf
+    elif new == 'eq':
+        kw[lo][j] = kw[hi][j] = c if cls == 'u' else 0.0
+    else:
+        half = {'x': 8.0, 'u': 1.0 + abs(c), 'du': 0.5 + abs(c)}[cls]
+        kw[lo][j], kw[hi][j] = -half, half
+    kinds[cls][j] = new
+    kw['_kinds'] = kinds
+    kw['_flipped'] = (cls, j, new)
+    return (kw,) + bounds(kw)
+
+
+def row_types(kw, E=None):
+    """Row-type vector (-1 loose, 0 inequality, 1 equality) of a draw, on unscaled bounds unless the scaling E is given."""
+    l, u = bounds(kw)
+    E = np.ones_like(l) if E is None else E
+    r = row_rho(E, l, u, 1.0)
+    return np.where(r == 1e-6, -1, np.where(r == 1e3, 1, 0))

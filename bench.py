@@ -15,8 +15,14 @@ pyMPC/mpc.py:80), synthetic data, FP64, all inputs resident in HBM when the time
     python bench.py --workload notebook            # examples/example_inverted_pendulum_kalman.ipynb shape (4,1,150,75), one controller
     ... bench.py --gpus N --total-batch 1024       # BASELINE configs[3] read as strong scaling: the SAME 1024 instances over N GPUs
     python bench.py --dump-outputs DIR             # also write what the last timed step computed (DIR/<name>.npy) to compare two builds by
+    python bench.py --full ...                     # everything beside the headline as well (see below)
 
-Two ways through the same library, both measured, `--path` chooses which one is `value` (the other is `other_path`):
+A plain run does what the headline needs and no more: set up, warm up, time the steps, dump (--dump-outputs), print the line.
+`--full` adds the rest, after the timed steps: the other path, the parity setting (eps 1e-9), the timing of a refactorization, the
+secondary legs (strong scaling, batch 4096, cfg-5, small batches, the bandwidth kernel, one model many states, single-controller
+latency), the CPU baseline, max |u* - u*_ref| against the CPU reference and the real-OSQP pin.  The --no-* options trim a full run.
+
+Two ways through the same library, `--path` chooses which one is `value` (with --full the other is measured too: `other_path`):
   device_loop (default): the K steps run inside mpcqp_mpc_loop launches (output -> plant -> update -> solve per
                          instance on the device, SURVEY 8f-1), at most 50 steps per launch (--chunk);
   stepwise             : the reference's call pattern, update()/solve()/output() per step from the host.
@@ -757,14 +763,15 @@ def compact_line(out):
     for k, v in lat.items():
         if isinstance(v, dict) and 'update_us_median' in v:
             legs['latency_' + k] = _pick(v, ('update_us_median', 'update_us_p95', 'kernel_us', 'raw_c_abi_step_us', 'cpu_oracle_update_us_median', 'mean_admm_iters'), 4)
-    line['legs'] = legs
-    ro = out.get('real_osqp') or {}
-    line['real_osqp'] = _pick(ro, ('osqp_available', 'osqp_version', 'all_equal'))
+    if legs:                           # (a plain run has no legs and no real-OSQP pin: those come with --full)
+        line['legs'] = legs
+    if out.get('real_osqp'):
+        line['real_osqp'] = _pick(out['real_osqp'], ('osqp_available', 'osqp_version', 'all_equal'))
     line['legs_file'] = out.get('legs_file')
     # the budget is a hard one: shed detail (never the contract's keys) until the line fits
     def fits():
         return len(json.dumps(line)) <= LINE_BUDGET
-    if not fits():
+    if not fits() and legs:
         line['legs'] = {k: _pick(v, ('batch', 'value', 'frac', 'update_us_median', 'projected_8gpu_value'), 4) for k, v in legs.items()}
     for drop in ('cold', 'real_osqp', 'legs'):
         if fits():
@@ -842,9 +849,9 @@ def shared_model_leg(args, dims, B, torch, dev, steps=40, warmup=20, chunk=20):
                 definition='device loop, %d timed steps in launches of %d after %d warm-up steps; value = the bandwidth kernel with ONE shared factor (mpcqp_share_factor)' % (steps, chunk, warmup))
 
 
-def latency_leg(kind, nsim=300):
+def latency_leg(kind, nsim=300, full=True):
     """One controller through the drop-in class, `MPCController.update()` per step (pyMPC/mpc.py:338-364), median microseconds;
-    beside it the CPU oracle on the same loop.  kind = 'cfg2': examples/example_inverted_pendulum.py:10-69 (4,1,20);
+    with `full`, beside it the raw C-ABI step and the CPU oracle on the same loop.  kind = 'cfg2': examples/example_inverted_pendulum.py:10-69 (4,1,20);
     'notebook': examples/example_inverted_pendulum_kalman.ipynb cells 3/12/13/15 (4,1,Np=150,Nc=75; the notebook's own
     timing cell reports about 1.05-1.2 ms per step for its OSQP-backed controller); 'kalman_np200': the script version of that example,
     examples/example_inverted_pendulum_kalman.py:19,71-110 (Ts = 5 ms, Np = Nc = 200, eps_feas = 1e3)."""
@@ -871,6 +878,10 @@ def latency_leg(kind, nsim=300):
 
     K = MPCController(**kw)
     ts, its = loop(K)
+    out = dict(workload='%s: one cart-pole MPCController, nx=4 nu=1 Np=%d Nc=%d' % (kind, kw['Np'], kw.get('Nc', kw['Np'])),
+               update_us_median=float(np.median(ts)), update_us_p95=float(np.percentile(ts, 95)), mean_admm_iters=float(its.mean()))
+    if not full:
+        return out
     bp = K.prob.batch_problem
     bp.profile(enable=True, reset=True)
     x = np.array(K.x0_rh, dtype=float)
@@ -883,9 +894,7 @@ def latency_leg(kind, nsim=300):
     for _ in range(200):
         bp.update(x0=x[None, :]); bp.solve_async(); bp.u0()
     raw3_us = 1e6 * (time.perf_counter() - t0) / 200
-    out = dict(workload='%s: one cart-pole MPCController, nx=4 nu=1 Np=%d Nc=%d' % (kind, kw['Np'], kw.get('Nc', kw['Np'])),
-               update_us_median=float(np.median(ts)), update_us_p95=float(np.percentile(ts, 95)), mean_admm_iters=float(its.mean()),
-               raw_c_abi_step_us=raw_us, raw_c_abi_update_solve_u0_us=raw3_us, kernel_us=1e3 * ms / max(1, nl), kernel=bp.kernel_name(loop=False))
+    out.update(raw_c_abi_step_us=raw_us, raw_c_abi_update_solve_u0_us=raw3_us, kernel_us=1e3 * ms / max(1, nl), kernel=bp.kernel_name(loop=False))
     from oracle.osqp_oracle import OSQP
     Ko = MPCController(**kw); Ko.prob = OSQP()
     tso, itso = loop(Ko)
@@ -949,20 +958,22 @@ def main():
     ap.add_argument('--total-batch', type=int, default=None, help='instances in total, split evenly over the GPUs (strong scaling)')
     ap.add_argument('--eps', type=float, default=1e-3)
     ap.add_argument('--chunk', type=int, default=None, help='device loop: steps per kernel launch (default: the timed steps in equal launches of at most 50)')
+    ap.add_argument('--full', action='store_true', help='after the headline, also run everything else the benchmark measures and checks (other path, parity setting, '
+                                                        'refactorization timing, secondary legs, CPU baseline, u* against the CPU reference); the --no-* options trim it')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--shared-model', action='store_true', help='every instance (on every rank) is a copy of ONE controller -- the first instance\'s model, broadcast once -- and only the states are scattered '
                                                                 '(test_scripts/example_mpc_function.py:105-111, SURVEY 8e last paragraph); implies --no-cpu-baseline')
-    ap.add_argument('--no-shared-model-leg', action='store_true', help='skip the one-model-many-states legs (mpcqp_share_factor)')
-    ap.add_argument('--no-other-path', action='store_true', help='skip the secondary measurements (other path, parity setting, strong-scaling / HBM / latency legs)')
-    ap.add_argument('--no-refactor-timing', action='store_true', help='skip the timing of the factorization alone (profiling runs: its launches carry the solve kernel\'s name)')
+    ap.add_argument('--no-shared-model-leg', action='store_true', help='--full: skip the one-model-many-states legs (mpcqp_share_factor)')
+    ap.add_argument('--no-other-path', action='store_true', help='--full: skip the secondary measurements (other path, parity setting, strong-scaling / HBM / latency legs)')
+    ap.add_argument('--no-refactor-timing', action='store_true', help='--full: skip the timing of the factorization alone (profiling runs: its launches carry the solve kernel\'s name)')
     ap.add_argument('--path', default='device_loop', choices=['stepwise', 'device_loop'],
                     help='stepwise: update()/solve()/output() per step from the host (the reference call pattern); '
                          'device_loop: the same K steps inside mpcqp_mpc_loop (SURVEY 8f-1)')
     ap.add_argument('--workload', default='cfg3', choices=['cfg3', 'cfg5', 'cfg2', 'notebook', 'kalman_np200'],
                     help='cfg3: 1024 x (12,4,30) (headline); cfg5: 512 x (20,8,100), tight state box (SURVEY 8d); '
                          'cfg2 / notebook: single-controller latency legs only')
-    ap.add_argument('--hbm-leg-batch', type=int, default=4096, help='cfg3, 1 GPU: second leg with a working set beyond the Infinity Cache (0 = skip)')
-    ap.add_argument('--cfg5-leg-batch', type=int, default=512, help='cfg3, 1 GPU: BASELINE configs[4] (512 x (20,8,100)) as a leg of the default line (0 = skip)')
+    ap.add_argument('--hbm-leg-batch', type=int, default=4096, help='--full, cfg3, 1 GPU: second leg with a working set beyond the Infinity Cache (0 = skip)')
+    ap.add_argument('--cfg5-leg-batch', type=int, default=512, help='--full, cfg3, 1 GPU: BASELINE configs[4] (512 x (20,8,100)) as a leg of the line (0 = skip)')
     ap.add_argument('--backend', default=None, choices=['sweeps', 'dense', 'bcr8'],
                     help='force a KKT backend for the headline shard (mpcqp_settings.backend; default: the library chooses) -- profiling runs of the bandwidth kernel at the headline batch')
     ap.add_argument('--tuning', type=int, default=None, help='mpcqp_settings.tuning for the headline shard (development: switch a mechanism off, see enum mpcqp_tuning)')
@@ -976,6 +987,8 @@ def main():
         ap.error('--steps must be at least 1')
     if args.dump_outputs and args.workload not in WORKLOADS:
         ap.error('--dump-outputs: only the batch workloads (%s)' % ', '.join(WORKLOADS))
+    if not args.full:
+        args.no_cpu_baseline = args.no_other_path = args.no_refactor_timing = True      # (a plain run: the headline alone)
     if args.shared_model:
         args.no_cpu_baseline = args.no_other_path = True      # (the CPU legs and the u* references rebuild instance i's OWN model from its seed)
     self_launch_if_needed(args)
@@ -987,7 +1000,7 @@ def main():
         return dry_run(args, rank, world, dev, seen, torch, dist)
     if args.workload in ('cfg2', 'notebook', 'kalman_np200'):
         if rank == 0:
-            leg = latency_leg(args.workload)
+            leg = latency_leg(args.workload, full=args.full)
             print(json.dumps({'metric': 'MPCController.update() latency, one controller (BASELINE configs[1])', 'value': leg['update_us_median'], 'unit': 'us',
                               'n_gpus': 1, 'higher_is_better': False, 'dtype': 'f64', 'data': 'synthetic', 'config': {'workload': leg['workload']}, 'latency': leg}))
         if comm_on(world):
@@ -1017,7 +1030,7 @@ def main():
     elapsed, iters, refacts, solves = res['elapsed'], res['iters'], res['refacts'], res['solves']
     infos = prob.infos()
     n_solved = sum(1 for i in infos if i.status == 1)
-    samples = [] if args.shared_model else [dict(sh.sample_point(), eps=args.eps)]
+    samples = [dict(sh.sample_point(), eps=args.eps)] if args.full and not args.shared_model else []
     other = None
     if not args.no_other_path:
         oname = 'stepwise' if args.path == 'device_loop' else 'device_loop'
@@ -1204,6 +1217,7 @@ def main():
             'parity_setting': parity,
         }
         out.update(extra)
+    if rank == 0 and args.full:
         cpu, refs = cpu_legs(dims, args.eps, samples, want_baseline=not args.no_cpu_baseline)
         if cpu:
             out['cpu_baseline'] = cpu

@@ -84,6 +84,27 @@ def test_eight_rank_record_fits():
     assert back['legs']['strong_total1024']['value'] == 5.8e6
 
 
+FULL_ONLY = ('other_path', 'parity_setting', 'strong_scaling', 'hbm_leg', 'cfg5_leg', 'small_batch_legs', 'strong_scaling_projection',
+             'shared_model_legs', 'latency', 'cpu_baseline', 'u_err', 'real_osqp')
+
+
+def test_plain_record_line():
+    """A plain run (no --full) records the headline alone: the line carries the headline's keys and no leg, CPU baseline, u* comparison or
+    real-OSQP pin -- not even as empty objects."""
+    out = canned()
+    for k in FULL_ONLY:
+        out.pop(k, None)
+    out['legs_file'] = 'bench_legs.json'
+    line = json.loads(json.dumps(bench.compact_line(out)))
+    for k in CONTRACT:
+        if k != 'cpu_baseline':
+            assert k in line, k
+    for k in ('cpu_baseline', 'u_err', 'legs', 'real_osqp'):
+        assert k not in line, k
+    assert line['value'] == float('%.6g' % out['value']) and line['higher_is_better'] is True and line['dtype'] == out['dtype']
+    assert line['ms_per_step'] == float('%.6g' % out['ms_per_step'])
+
+
 def test_budget_sheds_detail_not_contract():
     out = canned()
     out['small_batch_legs'] = {'leg%03d' % i: dict(out['small_batch_legs']['b128']) for i in range(200)}      # far too many legs

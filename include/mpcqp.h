@@ -96,7 +96,6 @@ enum mpcqp_tuning {
     MPCQP_TUNE_NO_QUEUE = 16,   /* batches beyond the resident workgroup slots: one workgroup per instance (the hardware's dispatch) instead of persistent workgroups taking instances off a queue */
     MPCQP_TUNE_NO_PARTS = 32,   /* persistent closed-loop launches: an instance's whole loop is ONE queue item (no parts) */
     MPCQP_TUNE_QUEUE_SOLVES = 64, /* development: persistent launches for single solves (mpcqp_solve) too, not only for the closed loop */
-    MPCQP_TUNE_EVEN_PARTS = 128, /* development: persistent closed-loop launches cut an instance's steps into EQUAL parts (default: decreasing) */
     MPCQP_TUNE_ITEMS_SHIFT = 16, /* development: tuning bits 16..22 = queue items per resident workgroup slot of a persistent closed-loop launch (what its step-range parts are cut by); 0 = the library's choice */
     MPCQP_TUNE_NO_CARRY = 1 << 23, /* development: the closed loop on the device leaves the latency round after every solve (write-back, begin, prologue) instead of carrying a converged solve's iterate in registers into the next step of the queue item (A/B switch: results and launch structure are the same) */
     MPCQP_TUNE_ONE_LAUNCH_SOLVES = 1 << 29, /* development: a solve of more instances than resident slots as ONE persistent launch (instances off the queue, longest expected work first, each run to its end) instead of two launches (one round for everybody, then the unfinished ones re-dealt) */

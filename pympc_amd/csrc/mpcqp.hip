@@ -89,10 +89,6 @@ constexpr int BCR_STAGES = 31;      // the largest stage count the register-resi
 // The static schedule of mpcqp_lat.h exists for 11, 21 and 31 stages; a problem runs the smallest one that holds its N = Np + 1 stages (the rest
 // are identity padding: factor_bcr).  0: too long a horizon for this backend.
 static int bcr_schedule(int N) { return N <= 11 ? 11 : N <= 21 ? 21 : N <= BCR_STAGES ? BCR_STAGES : 0; }
-// AUTO at up to one instance per compute unit: the eight-wave kernels of mpcqp_w8.hip (measured against the four-wave ones: DESIGN.md section 5b)
-#ifndef MPCQP_AUTO_BCR8
-#define MPCQP_AUTO_BCR8 1
-#endif
 // mpcqp_w8.hip: the second translation unit (NT = 512).  kargs: this unit's RunKArgs, byte for byte the other's.
 int mpcqp_w8_launch(const void *kargs, size_t kargs_bytes, int spec12_4, int sched, int loop, int grid, size_t smem, hipStream_t stream);
 #ifdef MPCQP_RUN_TIMING
@@ -287,8 +283,8 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     h->L.bcr = bcr ? bcr_schedule(L.N) : 0;
     // What AUTO runs it on: 512-thread workgroups (two waves per SIMD) with a dense top (mpcqp_latw.h, mpcqp_w8.hip) -- 128 / 256 / 512 instances
     // 608 k / 1.03 M / 1.13 M solves/s against 506 k / 841 k / 935 k on four waves with the plain reduction (MPCQP_BACKEND_BCR, mpcqp_lat.h).
-    // MPCQP_BACKEND_BCRT: the dense-top format on four waves (533 k / 890 k: what the eight waves add on top of the format).
-    const bool bcr8 = bcr && (want == MPCQP_BACKEND_BCR8 || (want == MPCQP_BACKEND_AUTO && MPCQP_AUTO_BCR8));
+    // MPCQP_BACKEND_BCRT: the dense-top format on four waves (533 k / 890 k: what the eight waves add on top of the format).  DESIGN.md section 5b.
+    const bool bcr8 = bcr && (want == MPCQP_BACKEND_BCR8 || want == MPCQP_BACKEND_AUTO);
     const bool bcrt = bcr8 || (bcr && want == MPCQP_BACKEND_BCRT);
     h->L.bcrtop = bcrt ? BcrFmt::top_count(h->L.bcr) : 0;
     h->L.nw = bcr8 ? 8 : NWAVES;
@@ -705,8 +701,7 @@ static RunKArgs run_kernel_args(mpcqp_handle *h, const RunArgs &R0, int *grid) {
                 for (int p = 0; p < np; ++p) {
                     A.R.voff[p] = off;
                     const int left = R0.nsteps - off, pl = np - p;
-                    int len = pl == 1 ? left : std::max(1, std::min(left - (pl - 1), (2 * left + pl) / (pl + 1)));
-                    if (h->S.tuning & MPCQP_TUNE_EVEN_PARTS) len = pl == 1 ? left : (left + pl - 1) / pl;
+                    const int len = pl == 1 ? left : std::max(1, std::min(left - (pl - 1), (2 * left + pl) / (pl + 1)));
                     off += len;
                 }
                 A.R.voff[np] = R0.nsteps; A.R.vparts = np; A.R.vdone = h->vdone_dev;
@@ -1384,7 +1379,7 @@ extern "C" int mpcqp_get_work(mpcqp_handle *h, int64_t *mfma_per_iter) {
     else if (L.bcr) {
         for (int l = 0; l < (L.bcrtop ? 2 : bcr_levels(L.bcr)); ++l)
             for (int kind = 0; kind < 3; ++kind) for (int t = 0; t < lat_count(L.bcr, l, kind); ++t) mv += lat_nfr(L.bcr, l, kind, t);
-        if (!LATW_TOP_VALU) mv += (int64_t)L.bcrtop * L.bcrtop;      // dense top on the matrix cores: one mat-vec per block of the inverse (LATW_TOP_VALU: 512 nt^2 flop per iteration on the vector ALU instead, not counted here)
+        // (the dense top runs on the vector ALU: 512 nt^2 flop per iteration, not counted here)
         mv += 2 * ((L.bcr + 3) / 4);                 // G v and G'W: one group per four stages each
     } else if (L.grp) mv = 3 * (int64_t)group_count(L.N, L.grp) - 1;      // forward 1, backward 2 mat-vecs per super-stage, the middle stage
     else {

@@ -35,12 +35,12 @@ struct BcrFmt {
     // tridiagonal Schur complement of order 16 nt (112 at N = 31) whose EXPLICIT inverse is stored as nt x nt fragments behind the stage records:
     // block (r, c) at TOPOFF(N) + (r nt + c) NN.  Levels 2 .. 4 of the plain reduction are a chain of five dependent level steps that one wave
     // walks alone (2 700 of an iteration's 11 000 cycles); the inverse is nt independent block rows of nt mat-vecs each.
-    // LATW_TOP_VALU (mpcqp_latw.h: the round applies the inverse on the vector ALU): a second copy of it behind the fragments, in the row-part order the
+    // The round applies the inverse on the vector ALU (mpcqp_latw.h): a second copy of it behind the fragments, in the row-part order the
     // round keeps it in LDS in -- TOPVOFF(N) + 2 pair + {0, 1}, pairs as bcr_topv_rc enumerates them -- so that the round's LDS copy is a straight, coalesced copy.
     static constexpr int top_count(int N) { return N / 4; }
     static constexpr long long top_off(int N) { return (long long)N * REC; }
     static constexpr long long topv_off(int N) { return top_off(N) + (long long)top_count(N) * top_count(N) * NN; }
-    static constexpr long long doubles(int N, bool top) { return (long long)N * REC + (top ? (LATW_TOP_VALU ? 2LL : 1LL) * top_count(N) * top_count(N) * NN : 0); }
+    static constexpr long long doubles(int N, bool top) { return (long long)N * REC + (top ? 2LL * top_count(N) * top_count(N) * NN : 0); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -216,9 +216,7 @@ __device__ __forceinline__ int factor_bcr(const Ctx &c, const double *om, const 
         __syncthreads();
         double *rowP = W, *rowC = W + (size_t)nt * NN, *Lc = W + (size_t)2 * nt * NN, *Sc = Lc + NN;
         double *Ft = F + BcrFmt::top_off(N);
-#if LATW_TOP_VALU
         double *Fv = F + BcrFmt::topv_off(N);                 // the same in the round's row-part order
-#endif
         for (int idx = tid; idx < NN; idx += NT) rowC[(size_t)(nt - 1) * NN + idx] = SinvG[(size_t)(nt - 1) * NN + idx];
         for (int r = nt - 1; r >= 0; --r) {
             if (r < nt - 1) {
@@ -252,10 +250,8 @@ __device__ __forceinline__ int factor_bcr(const Ctx &c, const double *om, const 
                 const double v = (a >= nbr || bb >= nvar(4 * (j + 1) - 1)) ? 0.0 : rowC[(size_t)j * NN + e];
                 Ft[(size_t)(r * nt + j) * NN + frag_pos<NB>(a, bb)] = v;
                 if (j != r) Ft[(size_t)(j * nt + r) * NN + frag_pos<NB>(bb, a)] = v;
-#if LATW_TOP_VALU
                 Fv[bcr_topv_pos(nt, NB * r + a, NB * j + bb)] = v;
                 if (j != r) Fv[bcr_topv_pos(nt, NB * j + bb, NB * r + a)] = v;
-#endif
             }
             __syncthreads();
             double *sw = rowP; rowP = rowC; rowC = sw;

@@ -52,18 +52,15 @@ typedef __attribute__((address_space(1))) const d4 cgd4;
 //     the neighbour the back substitution comes from, written by the factorization (omega changes only when it runs).
 // Per stage and iteration the sweeps stream NB^2 + SINV + 2 NB doubles (16: 3.6 KB, 32: 13.4 KB) instead of the 2 NB^2 + SINV of
 // a format that also runs the back substitution from (transposed) forward matrices.
-// 32 x 32 stages use the S^-1-ONLY variant (MPCQP_SONLY32 = 1, the default): NO forward matrices -- header first, per stage
+// 32 x 32 stages use the S^-1-ONLY variant: NO forward matrices -- header first, per stage
 // [ packed S^-1 | table towards the stage above | table towards the stage below ] -- and both sweeps run through S^-1 and G:
 //     forward   w_k = S_k^-1 ( b_k - K_{k,nbr} w_nbr )        backward   x_k = w_k - S_k^-1 K_{k,nbr} x_nbr
 // 2 x 5.7 KB per stage and iteration instead of 8 + 4.7 + 0.5 KB.  Measured on cfg-5 (scripts/diag/ab_cfg5.sh): the forward
 // matrices cost 12 % throughput at 1024 instances and 7 % at the parity tolerance (the stream is the bound there), and win
-// 7 % on the 512-instance default run, where one straggling instance's critical path sets the time; MPCQP_SONLY32 = 0 builds
-// that alternative.  16 x 16 stages: the forward-matrix format wins at every batch size (+7 .. 10 % over reading S^-1 twice).
-#ifndef MPCQP_SONLY32
-#define MPCQP_SONLY32 1
-#endif
+// 7 % on the 512-instance default run, where one straggling instance's critical path sets the time.
+// 16 x 16 stages: the forward-matrix format wins at every batch size (+7 .. 10 % over reading S^-1 twice).
 template <int NB> struct FactorFmt {
-    static constexpr bool SONLY = MPCQP_SONLY32 && NB == 32;
+    static constexpr bool SONLY = NB == 32;
     static constexpr int SINV = NB == 32 ? 164 + 164 + 256 : 164;
     static constexpr int FWD = SONLY ? 0 : NB * NB;
     static constexpr int TAB = SONLY ? 4 * NB : 2 * NB;

@@ -24,12 +24,7 @@
 // prefetch ring depths of the two sweeps (stages in flight in registers: 16 VGPRs each forward, 8 backward).  Measured on the notebook shape, one
 // controller: 0.19 us per forward step, 0.11 per backward step; deeper rings (4 / 8, 5 / 8) do NOT help -- update() 461 us against 452 -- so the steps
 // are not waiting for these loads.
-#ifndef MPCQP_GRP_FWD_DEPTH
-#define MPCQP_GRP_FWD_DEPTH 3
-#endif
-#ifndef MPCQP_GRP_BWD_DEPTH
-#define MPCQP_GRP_BWD_DEPTH 4
-#endif
+constexpr int GRP_FWD_DEPTH = 3, GRP_BWD_DEPTH = 4;
 struct GroupFmt {
     static constexpr int NN = 256;
     static constexpr int OMH = 0, OMHT = NN, OSINV = 2 * NN, REC = 3 * NN;      // (the forward matrix first: chain_sweep reads a stage's record from its start)
@@ -148,10 +143,9 @@ __device__ __forceinline__ int factor_group(const Ctx &c, const double *om, cons
 // sequences in one block, which the scheduler interleaves: w rides in the latency of the chain.  Fragments of the next stages are prefetched
 // into a register ring (branch-free refills with clamped indices, like chain_sweep).
 __device__ __forceinline__ void group_fwd_sweep(const int first, const int dir, const int nsteps, const int ylast, const double *F, double *Tg) {
-    constexpr int NB = 16, DEPTH = MPCQP_GRP_FWD_DEPTH;
+    constexpr int NB = 16, DEPTH = GRP_FWD_DEPTH;
     const int lane = opaque_lane(threadIdx.x & 63);
     double *tb = Tg + vec_lane_offset(lane);
-    const bool writer = MPCQP_STORE_ALL ? true : vec_lane_writer(lane);
     auto stage_of = [&](int i) { return first + dir * (i < nsteps ? i : nsteps); };
     d4 rf[DEPTH], rs[DEPTH];                              // ring slot d: forward matrix of stage i, S^-1 of stage i - 1
     auto ring_load = [&](int i, int d) {
@@ -169,7 +163,7 @@ __device__ __forceinline__ void group_fwd_sweep(const int first, const int dir, 
         double y[1] = {own[0]}, w[1] = {0.0};
         frag_matvec<NB>(&rf[d], run, y);                          // the chain: yh_K from yh_{K-dir}
         frag_matvec<NB>(&rs[d], run, w);                          // beside it: w_{K-dir} = S^-1 yh_{K-dir}
-        vec_store<NB>(tb, K - dir, w, writer);
+        vec_store<NB>(tb, K - dir, w, true);
         run[0] = y[0];
         own[0] = nxt[0];
     };
@@ -185,18 +179,17 @@ __device__ __forceinline__ void group_fwd_sweep(const int first, const int dir, 
         const d4 sl = *(cgd4 *)(F + (size_t)K * GroupFmt::REC + GroupFmt::OSINV + lane * 4);
         double w[1] = {0.0};
         frag_matvec<NB>(&sl, run, w);
-        vec_store<NB>(tb, ylast, run, writer);
-        vec_store<NB>(tb, K, w, writer);
+        vec_store<NB>(tb, ylast, run, true);
+        vec_store<NB>(tb, K, w, true);
     }
 }
 
 // One half of the back substitution by ONE wave: for i = 1..nsteps, K = first + dir * i:   Tg[K] (= w_K) <- w_K + MhT(K - dir) Tg[K - dir]
 // (MhT(J): the transposed forward matrix stored with stage J; `extra` replaces J = first, the middle stage, where the bottom half needs -Mt_m').
 __device__ __forceinline__ void group_back_sweep(const int first, const int dir, const int nsteps, const int extra, const double *F, double *Tg) {
-    constexpr int NB = 16, DEPTH = MPCQP_GRP_BWD_DEPTH;
+    constexpr int NB = 16, DEPTH = GRP_BWD_DEPTH;
     const int lane = opaque_lane(threadIdx.x & 63);
     double *tb = Tg + vec_lane_offset(lane);
-    const bool writer = MPCQP_STORE_ALL ? true : vec_lane_writer(lane);
     if (nsteps < 1) return;
     auto stage_of = [&](int i) { return first + dir * (i < nsteps ? i : nsteps); };
     auto src_of = [&](int i) { const int J = stage_of(i) - dir; return (J == first && extra >= 0) ? extra : J; };
@@ -213,7 +206,7 @@ __device__ __forceinline__ void group_back_sweep(const int first, const int dir,
         double x[1] = {own[0]};
         frag_matvec<NB>(&rm[d], run, x);
         run[0] = x[0];
-        vec_store<NB>(tb, K, run, writer);
+        vec_store<NB>(tb, K, run, true);
         own[0] = nxt[0];
     };
     int i0 = 1;

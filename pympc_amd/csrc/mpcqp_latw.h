@@ -14,32 +14,27 @@
 //     block rows of nt mat-vecs, one row per wave, ONE barrier instead of a five-deep chain on one wave.  Its nt^2 fragments (49: 98 KB) are
 //     what the registers no longer hold: they sit in LDS for the whole launch (with the constant fragments G, G'; a refactorization says when
 //     they are stale) -- the latency kernels use 44 of the compute unit's 160 KB otherwise.  Since the second half of round 5 the top is a
-//     VECTOR-ALU mat-vec over that LDS copy (LATW_TOP_VALU below: 2 043 -> 1 214 cycles of an iteration's 8 138); the matrix-core form
-//     (fragments as [block][half][lane][2 doubles], a lane's 32 bytes two conflict-free 16-byte reads) remains as a build switch.
+//     VECTOR-ALU mat-vec over that LDS copy (latw_top_valu below: 2 043 -> 1 214 cycles of an iteration's 8 138).
 // Barriers per iteration: seven as before (G'W + right-hand side | level 0 | level 1 | top | level 1 back | level 0 back | G v + row updates) where the waves share
-// groups of stages; FIVE where every wave owns exactly one group of four stages (31 stages on eight waves: LATW_FUSE0 below) -- a wave then runs the level-0 tasks of
+// groups of stages; FIVE where every wave owns exactly one group of four stages (31 stages on eight waves: latw_fused below) -- a wave then runs the level-0 tasks of
 // its own stages straight behind its right-hand side, and both back substitutions of its own stages in one phase.
 #pragma once
 
 // ---- static schedule of levels 0 and 1 over NWAVES waves (task kinds as in mpcqp_lat.h: 0 kept stage forward, 1 eliminated stage forward, 2 back substitution)
 // kept stages (two mat-vecs each) are dealt from wave 0 up, eliminated ones (one mat-vec) from the last wave down
 constexpr int latw_owner(int /*N*/, int /*L*/, int kind, int t) { return kind == 1 ? NWAVES - 1 - t % NWAVES : t % NWAVES; }
-// LATW_FUSE0: level 0 forward WITHOUT the barrier behind the right-hand side, where every wave owns exactly one group of four stages (31 stages on
-// eight waves).  Wave w then runs the level-0 tasks of ITS stages 4w .. 4w+3 -- D^-1 of 4w and 4w+2, the kept stage 4w+1, the kept stage 4w+3 from
+// Fused schedule (latw_fused): level 0 forward WITHOUT the barrier behind the right-hand side, where every wave owns exactly one group of four stages (31
+// stages on eight waves).  Wave w then runs the level-0 tasks of ITS stages 4w .. 4w+3 -- D^-1 of 4w and 4w+2, the kept stage 4w+1, the kept stage 4w+3 from
 // its left neighbour 4w+2 -- straight from the right-hand side it has just written (a wave reads its own LDS writes in order), plus the one
 // contribution that crosses into the previous group: the right neighbour 4w of the kept stage 4w-1, left in a second vector (x2) that level 1
 // forward adds when it starts that stage's chain.  Six fragments per wave as before; one barrier and the wait in front of it less per iteration.
-// LATW_FUSE0 >= 2: the same idea on the way back -- level 1 back and level 0 back of the wave's own stages in ONE phase: x(4w+1) from the top's solution
+// The same idea on the way back -- level 1 back and level 0 back of the wave's own stages in ONE phase: x(4w+1) from the top's solution
 // at 4w-1 and 4w+3 (read where the top left it), then x(4w) and x(4w+2) from those three -- nothing another wave computes in the same phase.
 // Five barriers per iteration: right-hand side + level 0 | level 1 | top | back | owner update.  Measured (one (12,4,30) instance alone, cycles per iteration; 128 / 256
 // instances): unfused 7 407, 690 k / 1.15 M solves/s; level 0 forward fused 6 966, 724 k / 1.21 M; back substitution fused too 6 372, 773 k / 1.29 M.  Level 1 forward
 // in the same phase as well (its tasks need only b'(4w+1), the top then adds two partial inputs as it reads them; four barriers): 6 938, 724 k / 1.19 M -- nine
 // dependent mat-vecs on one wave are longer than six and three with a barrier between them, and the extra live values spill in the owner passes; not kept.
-#ifndef LATW_FUSE0
-#define LATW_FUSE0 2
-#endif
-constexpr bool latw_fused(int N) { return LATW_FUSE0 && (N + 3) / 4 == NWAVES; }
-constexpr bool latw_fused_back(int N) { return LATW_FUSE0 >= 2 && latw_fused(N); }
+constexpr bool latw_fused(int N) { return (N + 3) / 4 == NWAVES; }
 constexpr int LATW_F0 = 6;          // fragment slots of the fused level-0 forward: D^-1(4w), D^-1(4w+2), kept 4w+1 (left, right), kept 4w+3 (left), kept 4w-1 (right)
 constexpr int LATW_FB = 6;          // ... of the fused back substitution: x(4w+1) (left, right), x(4w) (left, right), x(4w+2) (left, right)
 // slot of a task's first fragment in its wave's register array: level 0 forward, level 1 forward, level 1 back, level 0 back
@@ -51,7 +46,7 @@ constexpr int latw_slot(int N, int W, int Lq, int kq, int tq) {
             for (int kind = (pass == 0 ? 0 : 2); kind < (pass == 0 ? 2 : 3); ++kind)
                 for (int t = 0; t < lat_count(N, L, kind); ++t) {
                     if (latw_fused(N) && L == 0 && kind < 2) continue;
-                    if (latw_fused_back(N) && kind == 2) continue;
+                    if (latw_fused(N) && kind == 2) continue;
                     if (L == Lq && kind == kq && t == tq) return s;
                     if (latw_owner(N, L, kind, t) == W) s += lat_nfr(N, L, kind, t);
                 }
@@ -59,21 +54,20 @@ constexpr int latw_slot(int N, int W, int Lq, int kq, int tq) {
     return s;
 }
 constexpr int latw_back_base(int N, int W) { return latw_slot(N, W, -1, -1, -1); }      // (fused back substitution: its six slots behind everything scheduled)
-constexpr int latw_slots(int N, int W) { return latw_slot(N, W, -1, -1, -1) + (latw_fused_back(N) ? LATW_FB : 0); }
+constexpr int latw_slots(int N, int W) { return latw_slot(N, W, -1, -1, -1) + (latw_fused(N) ? LATW_FB : 0); }
 constexpr int latw_max_slots(int N) { int m = 0; for (int w = 0; w < NWAVES; ++w) m = latw_slots(N, w) > m ? latw_slots(N, w) : m; return m; }
 constexpr int latw_top_stage(int r) { return 4 * (r + 1) - 1; }
 
-// The top on the VECTOR ALU (LATW_TOP_VALU; 0 = on the matrix cores, latw_top, as until the middle of round 5): a mat-vec uses one of the four
+// The top on the VECTOR ALU (on the matrix cores until the middle of round 5): a mat-vec uses one of the four
 // B columns of v_mfma_f64_4x4x4, so the 28 MFMAs a wave issues for its block row carry 64 useful products each at 17-20 cycles of the matrix
 // pipe; the same 64 products are ONE v_fma_f64 at 6.5 cycles when enough of them are independent (scripts/diag/mfma_rate.hip).  The inverse then
 // sits in LDS in row-part order instead of fragment order, the reduced right-hand sides of the top stages in a compact vector Xt behind it:
-//   1: lane (i = lane & 15, p = lane >> 4) of the wave that owns block row r: row 16 r + i times columns [4 nt p, 4 nt (p + 1)) -- 2 nt 16-byte reads
-//      of the matrix, 2 nt 16-byte broadcast reads of Xt, 4 nt FMAs on 7 independent accumulators, two cross-lane steps (p);
-//   2: lane (q = lane >> 3, p = lane & 7): rows 16 r + 2 q, 2 q + 1 times columns [2 nt p, 2 nt (p + 1)) -- half the reads of Xt, three DPP steps.
+// lane (q = lane >> 3, p = lane & 7): rows 16 r + 2 q, 2 q + 1 times columns [2 nt p, 2 nt (p + 1)) -- three DPP steps.  One row per lane
+// instead (i = lane & 15, p = lane >> 4: columns [4 nt p, 4 nt (p + 1)), 7 accumulators, two cross-lane steps) reads Xt twice as often.
 // Measured (one (12,4,30) instance alone, cycles of the top phase / of the iteration; 128 / 256 instances, driver's flags):
-//   matrix cores 2 043 / 8 138, 628 k / 1.04 M solves/s;  mode 1 (groups of 2, pipelined) 1 464 / 7 545, 654 k / 1.08 M;  mode 2 (the same) 1 214 / 7 310,
-//   682 k / 1.13 M;  larger groups (3 or 4 column pairs in flight twice) spill in the owner passes and lose more there than they gain here.
-// (LATW_TOP_VALU and the order of the inverse: mpcqp_bcr.h)
+//   matrix cores 2 043 / 8 138, 628 k / 1.04 M solves/s;  one row per lane (groups of 2, pipelined) 1 464 / 7 545, 654 k / 1.08 M;  two rows per lane
+//   (the same) 1 214 / 7 310, 682 k / 1.13 M;  larger groups (3 or 4 column pairs in flight twice) spill in the owner passes and lose more there than they gain here.
+// (The order of the inverse: mpcqp_bcr.h)
 #define LATW_TOP_LDS(N) ((BcrFmt::top_count(N) * BcrFmt::top_count(N) + 2) * BcrFmt::NN + 32 * BcrFmt::top_count(N))      /* LDS doubles of the top inverse and, behind it, of the fragments G and G', of Xt and of x2 */
 #if NT == 512
 #define LATW_DISPATCH(wv, CALL) switch (wv) { \
@@ -95,7 +89,7 @@ __device__ __forceinline__ void latw_load(const double *F, d4 *fr) {
         if constexpr (s0 + 3 < N) fr[4] = bcr_frag(F, s0 + 2, BcrFmt::OLBRT, lane);
         if constexpr (W > 0 && s0 < N) fr[5] = bcr_frag(F, s0, BcrFmt::OLBLT, lane);
     }
-    if constexpr (latw_fused_back(N)) {
+    if constexpr (latw_fused(N)) {
         constexpr int bb = latw_back_base(N, W), e1 = 4 * W + 1, ea = 4 * W, eb = 4 * W + 2;
         if constexpr (e1 < N) { if constexpr (e1 - 2 >= 0) fr[bb] = bcr_frag(F, e1, BcrFmt::OLBL, lane); if constexpr (e1 + 2 < N) fr[bb + 1] = bcr_frag(F, e1, BcrFmt::OLBR, lane); }
         if constexpr (ea < N) { if constexpr (ea - 1 >= 0) fr[bb + 2] = bcr_frag(F, ea, BcrFmt::OLBL, lane); if constexpr (ea + 1 < N) fr[bb + 3] = bcr_frag(F, ea, BcrFmt::OLBR, lane); }
@@ -114,7 +108,7 @@ __device__ __forceinline__ void latw_load(const double *F, d4 *fr) {
         static_for<0, lat_count(N, L, 1)>([&](auto tc) {
             constexpr int t = decltype(tc)::value, e = lat_stage(L, 1, t);
             if constexpr (!(latw_fused(N) && L == 0) && latw_owner(N, L, 1, t) == W) { constexpr int s1 = latw_slot(N, W, L, 1, t); fr[s1] = bcr_frag(F, e, BcrFmt::ODINV, lane); }
-            if constexpr (!latw_fused_back(N) && latw_owner(N, L, 2, t) == W) {
+            if constexpr (!latw_fused(N) && latw_owner(N, L, 2, t) == W) {
                 constexpr int s = latw_slot(N, W, L, 2, t);
                 if constexpr (e - h >= 0) fr[s] = bcr_frag(F, e, BcrFmt::OLBL, lane);
                 constexpr int s2 = s + (e - h >= 0 ? 1 : 0);
@@ -126,16 +120,10 @@ __device__ __forceinline__ void latw_load(const double *F, d4 *fr) {
 
 // LDS vectors of the round (stage-major, stride 16; mpcqp_lat.h): tb right-hand side / solution, cb c_e of the reduction -- and, at the top stages'
 // slots, the top's solution until level 1 back has copied it into tb; each seen through the lane bases of the four block rotations.
-struct LatwVecs { double *tb, *cb; const double *t1, *t2, *t3, *c1, *c2, *c3; double *xt, *x2; };      // (xt: LATW_TOP_VALU, the top's compact input, per-lane base as tb; x2: LATW_FUSE0, the top stages' contributions from the next group)
-#ifndef LATW_IN_DPP
-#define LATW_IN_DPP 0              // 1: one LDS read per input vector and three DPP block rotations instead of four reads (measured: see LAB_NOTES.md)
-#endif
+struct LatwVecs { double *tb, *cb; const double *t1, *t2, *t3, *c1, *c2, *c3; double *xt, *x2; };      // (xt: the top's compact input, per-lane base as tb; x2: fused schedule, the top stages' contributions from the next group)
+// four LDS reads per input vector (one read and three DPP block rotations instead: measured, see LAB_NOTES.md)
 template <bool FROMC>
 __device__ __forceinline__ void latw_mv_lds(const d4 a, const LatwVecs &v, int off, double &p, double &q) {
-#if LATW_IN_DPP
-    lat_mv(a, FROMC ? v.cb[off] : v.tb[off], p, q);
-    return;
-#endif
     const double i0 = FROMC ? v.cb[off] : v.tb[off], i1 = FROMC ? v.c1[off] : v.t1[off], i2 = FROMC ? v.c2[off] : v.t2[off], i3 = FROMC ? v.c3[off] : v.t3[off];
     p = __builtin_amdgcn_mfma_f64_4x4x4f64(a[0], i0, p, 0, 0, 0);
     q = __builtin_amdgcn_mfma_f64_4x4x4f64(a[2], i2, q, 0, 0, 0);
@@ -154,9 +142,9 @@ __device__ __forceinline__ void latw_fwd(const d4 *fr, const LatwVecs &v) {
             if constexpr (latw_fused(N) && L == 1) p += v.x2[((i + 1) / 4 - 1) * 16];      // (its level-0 contribution from the next group's first stage)
             latw_mv_lds<false>(fr[s], v, (i - h) * 16, p, q);
             if constexpr (i + h < N) latw_mv_lds<false>(fr[s + 1], v, (i + h) * 16, p, q);
-            // (level 1 keeps exactly the top stages 4 (r + 1) - 1: with the vector-ALU top their reduced right-hand side goes to the compact Xt --
+            // (level 1 keeps exactly the top stages 4 (r + 1) - 1: their reduced right-hand side goes to the top's compact Xt --
             //  nobody reads tb there before level 1 back has put the top's solution in its place)
-            if constexpr (LATW_TOP_VALU && L == 1) v.xt[((i + 1) / 4 - 1) * 16] = p + q;
+            if constexpr (L == 1) v.xt[((i + 1) / 4 - 1) * 16] = p + q;
             else v.tb[i * 16] = p + q;
         }
     });
@@ -170,7 +158,7 @@ __device__ __forceinline__ void latw_fwd(const d4 *fr, const LatwVecs &v) {
         }
     });
 }
-// level 0 forward of wave W's own four stages (LATW_FUSE0), called right behind the right-hand side without a barrier
+// level 0 forward of wave W's own four stages (fused schedule), called right behind the right-hand side without a barrier
 template <int N, int W>
 __device__ __forceinline__ void latw_fwd0_own(const d4 *fr, const LatwVecs &v) {
     constexpr int s0 = 4 * W;
@@ -210,7 +198,7 @@ __device__ __forceinline__ void latw_bwd1(const d4 *fr, const LatwVecs &v) {
     latw_bwd<N, W, 1, true>(fr, v);
 }
 
-// level 1 back and level 0 back of wave W's own stages in one phase (LATW_FUSE0 >= 2); the top's solution is read from cb where the neighbour is a top stage
+// level 1 back and level 0 back of wave W's own stages in one phase (fused schedule); the top's solution is read from cb where the neighbour is a top stage
 template <int N, int W>
 __device__ __forceinline__ void latw_bwd_own(const d4 *fr, const LatwVecs &v) {
     constexpr int bb = latw_back_base(N, W), e1 = 4 * W + 1, ea = 4 * W, eb = 4 * W + 2;
@@ -235,61 +223,14 @@ __device__ __forceinline__ void latw_bwd_own(const d4 *fr, const LatwVecs &v) {
     }
 }
 
-// one fragment of the top inverse from its LDS copy: [block][half][lane][2]
+// one fragment of the LDS copy behind the top inverse (G, G'): [block][half][lane][2]
 typedef double d2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ d4 latw_top_frag(const double *TopL, int blk, int lane) {
     const d2 lo = *(const d2 *)(TopL + ((blk * 2 + 0) * 64 + lane) * 2), hi = *(const d2 *)(TopL + ((blk * 2 + 1) * 64 + lane) * 2);
     return d4{lo[0], lo[1], hi[0], hi[1]};
 }
-// the top: block row r of the inverse times the reduced right-hand sides of the nt top stages (tb), into cb at stage i_r.
-// Measured on the way (cycles of this phase for one (12,4,30) instance alone, 8 waves; scripts/lat_phase.py with a -DMPCQP_RUN_TIMING build):
-//   * left to itself the compiler requests a row's fragments one or two at a time, each right in front of the MFMAs that need it (it has ~ 30
-//     free registers), and the wave sits through an LDS round trip per block: 2 115 - 2 340;
-//   * all fragments of the row up front, inputs read once and rotated by DPP moves: 2 320 -- the 42 moves alone cost 600 (without them 1 810),
-//     the MFMAs alone 1 120 (28 per wave, two waves per SIMD: 20 cycles each, the matrix pipe's rate), the fragment reads alone 980;
-//   * independent accumulators per column instead of two pairs of chains: 2 380; the chains of two columns interleaved MFMA by MFMA: 2 200;
-//   * inputs as four 8-byte LDS reads through the rotated lane bases, the row in groups of LATW_TOP_HALF columns whose fragments and inputs
-//     are requested together and whose chains are interleaved: 2 columns 1 975 (kept), 4: 2 206, all 7: 2 270 and spills in other phases.
-// The phase is at twice its matrix-pipe time; what is left is LDS delivery (98 KB of fragments per iteration) not overlapping with it.
-#ifndef LATW_TOP_HALF
-#define LATW_TOP_HALF 2
-#endif
-template <int N, int W>
-__device__ __forceinline__ void latw_top(const double *TopL, const LatwVecs &v, int lane) {
-    constexpr int NTOP = BcrFmt::top_count(N), H = LATW_TOP_HALF;
-    static_for<0, NTOP>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        if constexpr (r % NWAVES == W) {
-            double p0 = 0.0, q0 = 0.0, p1 = 0.0, q1 = 0.0;
-            static_for<0, (NTOP + H - 1) / H>([&](auto hc) {
-                constexpr int c0 = decltype(hc)::value * H, c1 = c0 + H < NTOP ? c0 + H : NTOP, n = c1 - c0;
-                d4 a[H]; double x[H][4];
-                static_for<0, n>([&](auto cc_) {
-                    constexpr int j = decltype(cc_)::value, off = latw_top_stage(c0 + j) * 16;
-                    a[j] = latw_top_frag(TopL, r * NTOP + c0 + j, lane);
-                    x[j][0] = v.tb[off]; x[j][1] = v.t1[off]; x[j][2] = v.t2[off]; x[j][3] = v.t3[off];
-                });
-                __builtin_amdgcn_sched_barrier(0);
-                static_for<0, (n + 1) / 2>([&](auto pc) {
-                    constexpr int j = 2 * decltype(pc)::value;
-                    if constexpr (j + 1 < n) {
-                        p0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j][0], x[j][0], p0, 0, 0, 0); p1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j + 1][0], x[j + 1][0], p1, 0, 0, 0);
-                        q0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j][2], x[j][2], q0, 0, 0, 0); q1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j + 1][2], x[j + 1][2], q1, 0, 0, 0);
-                        p0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j][1], x[j][1], p0, 0, 0, 0); p1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j + 1][1], x[j + 1][1], p1, 0, 0, 0);
-                        q0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j][3], x[j][3], q0, 0, 0, 0); q1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j + 1][3], x[j + 1][3], q1, 0, 0, 0);
-                    } else {
-                        p0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j][0], x[j][0], p0, 0, 0, 0); q0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j][2], x[j][2], q0, 0, 0, 0);
-                        p0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j][1], x[j][1], p0, 0, 0, 0); q0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a[j][3], x[j][3], q0, 0, 0, 0);
-                    }
-                });
-                __builtin_amdgcn_sched_barrier(0);
-            });
-            v.cb[latw_top_stage(r) * 16] = (p0 + q0) + (p1 + q1);
-        }
-    });
-}
 
-// ---- the top on the vector ALU (LATW_TOP_VALU; order of the inverse in LDS and in memory: bcr_topv_rc, mpcqp_bcr.h) ----------------------------------------
+// ---- the top on the vector ALU (order of the inverse in LDS and in memory: bcr_topv_rc, mpcqp_bcr.h) ----------------------------------------
 template <int CTRL>
 __device__ __forceinline__ double latw_dpp(double x) {
     const long long xi = __builtin_bit_cast(long long, x);
@@ -297,24 +238,17 @@ __device__ __forceinline__ double latw_dpp(double x) {
     return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
 }
 // Left to itself the compiler requests one or two 16-byte reads at a time and waits for each (an LDS round trip per pair of FMAs: it has ~ 30
-// free registers here), so the reads are issued in groups of LATW_TOPV_GRP column pairs behind scheduling fences; LATW_TOPV_PIPE: the next
+// free registers here), so the reads are issued in groups of H = 2 column pairs behind scheduling fences, and the next
 // group's reads are issued before the current group's FMAs (two groups of registers in flight).  (Requesting a wave's first group of matrix
 // pairs on the other side of the barrier, at the start of level 1 forward -- they depend on nothing the iteration computes -- took 80 cycles off
 // this phase and, through 16 more live registers, added 300 to the owner passes: 7 572 against 7 352 cycles per iteration; not kept.)
-#ifndef LATW_TOPV_GRP
-#define LATW_TOPV_GRP 2
-#endif
-#ifndef LATW_TOPV_PIPE
-#define LATW_TOPV_PIPE 1
-#endif
 template <int N, int W>
 __device__ __forceinline__ void latw_top_valu(const double *TopL, const double *Xt, double *Cc, int lane) {
-    constexpr int NTOP = BcrFmt::top_count(N), H = LATW_TOPV_GRP;
+    constexpr int NTOP = BcrFmt::top_count(N), H = 2;
     static_for<0, NTOP>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
         if constexpr (r % NWAVES == W) {
             const d2 *tm = (const d2 *)TopL + (size_t)(r * 2 * NTOP) * 64 + lane;
-#if LATW_TOP_VALU == 2
             constexpr int KQ = NTOP, NA = NTOP < 4 ? NTOP : 4, NG = (KQ + H - 1) / H;
             const d2 *xv = (const d2 *)(Xt + 2 * NTOP * (lane & 7));
             double a0[NA], a1[NA];
@@ -333,36 +267,16 @@ __device__ __forceinline__ void latw_top_valu(const double *TopL, const double *
                     a0[q] = fma(t0[1], x[1], a0[q]); a1[q] = fma(t1[1], x[1], a1[q]);
                 });
             };
-#else
-            constexpr int KQ = 2 * NTOP, NA = KQ < 7 ? KQ : 7, NG = (KQ + H - 1) / H;
-            const d2 *xv = (const d2 *)(Xt + 4 * NTOP * (lane >> 4));
-            double a[NA];
-            d2 bx[2][H], b0[2][H];
-            auto load = [&](auto gc) {
-                constexpr int g = decltype(gc)::value, k0 = g * H, n = (k0 + H < KQ ? k0 + H : KQ) - k0;
-                static_for<0, n>([&](auto jc) { constexpr int j = decltype(jc)::value, k = k0 + j; bx[g & 1][j] = xv[k]; b0[g & 1][j] = tm[k * 64]; });
-            };
-            auto compute = [&](auto gc) {
-                constexpr int g = decltype(gc)::value, k0 = g * H, n = (k0 + H < KQ ? k0 + H : KQ) - k0;
-                static_for<0, n>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value, k = k0 + j, q = k % NA;
-                    const d2 x = bx[g & 1][j], t = b0[g & 1][j];
-                    if constexpr (k < NA) a[q] = t[0] * x[0]; else a[q] = fma(t[0], x[0], a[q]);
-                    a[q] = fma(t[1], x[1], a[q]);
-                });
-            };
-#endif
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (LATW_TOPV_PIPE) { load(std::integral_constant<int, 0>{}); __builtin_amdgcn_sched_barrier(0); }
+            load(std::integral_constant<int, 0>{});
+            __builtin_amdgcn_sched_barrier(0);
             static_for<0, NG>([&](auto gc) {
                 constexpr int g = decltype(gc)::value;
-                if constexpr (LATW_TOPV_PIPE) { if constexpr (g + 1 < NG) load(std::integral_constant<int, g + 1>{}); }
-                else load(gc);
+                if constexpr (g + 1 < NG) load(std::integral_constant<int, g + 1>{});
                 __builtin_amdgcn_sched_barrier(0);
                 compute(gc);
                 __builtin_amdgcn_sched_barrier(0);
             });
-#if LATW_TOP_VALU == 2
             double s0 = a0[0], s1 = a1[0];
             if constexpr (NA == 4) { s0 = (a0[0] + a0[1]) + (a0[2] + a0[3]); s1 = (a1[0] + a1[1]) + (a1[2] + a1[3]); }
             else { static_for<1, NA>([&](auto jc) { constexpr int j = decltype(jc)::value; s0 += a0[j]; s1 += a1[j]; }); }
@@ -372,14 +286,6 @@ __device__ __forceinline__ void latw_top_valu(const double *TopL, const double *
             s0 += latw_dpp<0x4E>(s0); s1 += latw_dpp<0x4E>(s1);
             s0 += latw_dpp<0x141>(s0); s1 += latw_dpp<0x141>(s1);
             if ((lane & 7) == 0) *(d2 *)(Cc + latw_top_stage(r) * 16 + 2 * (lane >> 3)) = d2{s0, s1};
-#else
-            double s = a[0];
-            if constexpr (NA == 7) s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + a[6]);
-            else { static_for<1, NA>([&](auto jc) { s += a[decltype(jc)::value]; }); }
-            s += lane_permute(s, 4 * (lane ^ 16));
-            s += lane_permute(s, 4 * (lane ^ 32));
-            if (lane < 16) Cc[latw_top_stage(r) * 16 + lane] = s;
-#endif
         }
     });
 }
@@ -397,16 +303,12 @@ __device__ __forceinline__ void latw_solve(const d4 *fr, const double *TopL, con
     LATW_DISPATCH(wv, (latw_fwd<N, W, 1>(fr, v)))
     __syncthreads();
     TICK(2)
-#if LATW_TOP_VALU
     LATW_DISPATCH(wv, (latw_top_valu<N, W>(TopL, TopL + LATW_TOP_LDS(N) - 32 * NTOP, Cc, lane)))
-#else
-    LATW_DISPATCH(wv, (latw_top<N, W>(TopL, v, lane)))
-#endif
     __syncthreads();
     TICK(3)
     // level 1 back reads the top's solution from cb; on the way every top row's owner moves its stage into tb, where level 0 back (and the
     // owner passes) look for it -- nobody reads tb at a top stage during this phase
-    if constexpr (latw_fused_back(N)) {
+    if constexpr (latw_fused(N)) {
         LATW_DISPATCH(wv, (latw_bwd_own<N, W>(fr, v)))
         TICK(4)
     } else {
@@ -443,10 +345,7 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
 #ifdef MPCQP_RUN_TIMING
     const unsigned long long tf0_ = clock64();            // (development: the whole function on thread 0's clock, slot 11)
 #endif
-#ifndef LATW_FAST
-#define LATW_FAST 1                // development: 0 = the in-function termination test compiled in but never taken; 2 = taken, but a converged solve is finished by the generic check
-#endif
-    const bool fast = LATW_FAST && iter0 >= 0 && L.hot_lds > L.hot_sz;      // (the check reads the weight matrices from their LDS copy)
+    const bool fast = iter0 >= 0 && L.hot_lds > L.hot_sz;      // (the check reads the weight matrices from their LDS copy)
     static_assert(NXT + NUT <= NB, "16 x 16 stages");
     const int nx = NXT ? NXT : L.nx, nu = NUT ? NUT : L.nu, NR = L.N;
     const int b = inst_of(P.perm), tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -472,8 +371,6 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
     constexpr int NTOP = BcrFmt::top_count(N);
     if (S.iflag[2] == 0) {
         typedef __attribute__((address_space(1))) const d2 cgd2;
-        cgd2 *Ft = (cgd2 *)(Fb + BcrFmt::top_off(N));
-#if LATW_TOP_VALU
         cgd2 *Fv = (cgd2 *)(Fb + BcrFmt::topv_off(N));                      // (the copy factor_bcr left in this very order: 16 bytes per thread and trip, coalesced)
         {   // every trip's load requested before the first store: the stores go through a generic pointer, behind which the compiler keeps the next load --
             // thirteen dependent memory round trips (~ 12 us per kernel prologue, i.e. per queue item and per stepwise solve) instead of one
@@ -484,13 +381,6 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
 #pragma unroll
             for (int t = 0; t < TRIPS; ++t) { const int idx = tid + t * NT; if (idx < PAIRS) *(d2 *)(TopL + 2 * idx) = buf[t]; }
         }
-        (void)Ft;
-#else
-        for (int idx = tid; idx < NTOP * NTOP * 128; idx += NT) {           // (16 bytes per thread and trip: fragment element pairs (lane, j = 0,1 | 2,3))
-            const int blk = idx >> 7, r = idx & 127, ln = r >> 1, hf = r & 1;
-            *(d2 *)(TopL + ((blk * 2 + hf) * 64 + ln) * 2) = Ft[idx];
-        }
-#endif
         const double *Ad = hot + L.oAd, *Bd = hot + L.oBd;
         auto gent = [&](int r, int c) { return r < nx ? (c < nx ? Ad[r * nx + c] : (c < nx + nu ? Bd[r * nu + (c - nx)] : 0.0)) : 0.0; };
         if (wv == 0) {

@@ -644,10 +644,7 @@ __device__ __forceinline__ int check_body(const Lay &L, const Ptrs &P, const mpc
 }
 
 // ---- hot-loop pieces.  NXT/NUT: compile-time nx/nu (0 = take them from the layout at run time).
-#ifndef MPCQP_HOT_U
-#define MPCQP_HOT_U 4
-#endif
-constexpr int HOT_U = MPCQP_HOT_U;                   // global-memory iterate: elements per thread whose loads are issued together
+constexpr int HOT_U = 4;                            // global-memory iterate: elements per thread whose loads are issued together
 template <int NXT> __device__ __forceinline__ int hx(const Lay &L) { return NXT ? NXT : L.nx; }
 template <int NUT> __device__ __forceinline__ int hu(const Lay &L) { return NUT ? NUT : L.nu; }
 template <int NXT> __device__ __forceinline__ int divx(const Lay &L, int v) { return NXT ? v / NXT : idiv(v, L.rnx); }
@@ -1101,9 +1098,7 @@ __device__ __forceinline__ void admm_round_global(const Lay &L, const HotPtrs &P
     gdouble *dxg = (gdouble *)(P.dx + (size_t)b * L.n), *dyg = (gdouble *)(P.dy + (size_t)b * L.m);
     const double *F = factor_of(P, b);
     const double cc = P.c[b];
-#ifndef MPCQP_ABL_NOPAR
     gown_rows_w<NB, INL>(L, gom, cc, Z, Y, W, Tc);
-#endif
     TICK_RESET
     const int pace = INL ? 0 : __builtin_amdgcn_readfirstlane(pace_of(P.perm));
     for (int it = 1; it <= iters; ++it) {
@@ -1112,23 +1107,17 @@ __device__ __forceinline__ void admm_round_global(const Lay &L, const HotPtrs &P
         //  idles here, leaving its share of the memory system to the stragglers -- rebalance() in mpcqp.hip sets the pace, results do not depend on it)
         for (int p = 0; p < pace; ++p) __builtin_amdgcn_s_sleep(127);
         TICK_START
-#ifndef MPCQP_ABL_NOPAR
         gown_rhs<NB, NXT, NUT, INL>(L, S.hot, gom, gsv, gqv, cc, X, W, Tc, S.tv);
-#endif
         TICK(0)
         if (BORDER) border_pre<NB>(L, Bb, Zb, Sg, Tc, S.tv, S.red);
         TICK(4)
         kkt_core<NB, NB == 16 && (NXT == 0 || NXT == 4)>(core_args(L, opaque_ptr(F), opaque_ptr((const double *)P.omega + (size_t)b * L.m)), Tc);
         if (BORDER) border_post(L, NB, Tc, S.tv);
-#ifndef MPCQP_ABL_NOPAR
         gown_update<NB, NXT, NUT, INL>(L, S.hot, S.x0s, S.du0, gom, gsv, cc, alpha, X, Z, Y, W, Tc, keep_delta, dxg, dyg);
-#endif
         TICK(5)
     }
     TICK_FLUSH
-#ifndef MPCQP_ABL_NOPAR
     gown_finish<INL>(L, gom, cc, Y);
-#endif
     if constexpr (INL) {
         for (int j = tid; j < L.n; j += NT) gx[j] = X[j];
         for (int r = tid; r < L.m; r += NT) { gz[r] = Z[r]; gy[r] = Y[r]; }
@@ -1159,16 +1148,12 @@ __device__ __forceinline__ void admm_body(const Lay &L, const HotPtrs &P, Smem &
     constexpr bool BORDER = MODE == MODE_BORDER;
     OwnRegs hr;
     own_load<NB, NXT, NUT>(L, gom, gsv, gqv, cc, hr);
-#ifndef MPCQP_ABL_NOPAR
     own_rows_w<NB>(L, hr, cc, Z, Y, W, Tc);
-#endif
     TICK_RESET
     for (int it = 1; it <= iters; ++it) {
         const bool keep_delta = it == iters;         // the increments feed the infeasibility certificates of the check
         TICK_START
-#ifndef MPCQP_ABL_NOPAR
         own_rhs<NB, NXT, NUT>(L, S.hot, hr, cc, X, W, Tc, S.tv);
-#endif
         TICK(0)
         BorderPtrs bp; bp.red = S.red;
         if (BORDER) {
@@ -1178,15 +1163,11 @@ __device__ __forceinline__ void admm_body(const Lay &L, const HotPtrs &P, Smem &
         if (BORDER) border_pre<NB>(L, bp.Bb, bp.Zb, bp.Sig, Tc, S.tv, S.red);
         kkt_core<NB, NB == 16 && (NXT == 0 || NXT == 4)>(core_args(L, opaque_ptr(F), opaque_ptr((const double *)P.omega + (size_t)b * L.m)), Tc);
         if (BORDER) border_post(L, NB, Tc, S.tv);
-#ifndef MPCQP_ABL_NOPAR
         own_update<NB, NXT, NUT>(L, S.hot, S.x0s, S.du0, hr, cc, alpha, X, Z, Y, W, Tc, keep_delta, dxg, dyg);
-#endif
         TICK(5)
     }
     TICK_FLUSH
-#ifndef MPCQP_ABL_NOPAR
     own_finish(L, hr, cc, Y);
-#endif
     for (int j = tid; j < L.n; j += NT) gx[j] = X[j];
     for (int r = tid; r < L.m; r += NT) { gz[r] = Z[r]; gy[r] = Y[r]; }
 }

@@ -22,10 +22,7 @@ __device__ __forceinline__ void vec_store(double *tb, int k, const double *v, bo
 // per-lane base of a stage vector in Tc: lane 16k + 4b + j holds element 4b + k
 __device__ __forceinline__ int vec_lane_offset(int lane) { return 4 * ((lane >> 2) & 3) + (lane >> 4); }
 // A stage vector is replicated over the four lanes j of a row position; one of them writes it back -- or, inside the sweeps,
-// all four (MPCQP_STORE_ALL: the same value to the same address, no exec-mask juggling and no extra basic block per stage).
-#ifndef MPCQP_STORE_ALL
-#define MPCQP_STORE_ALL 1
-#endif
+// all four (the same value to the same address, no exec-mask juggling and no extra basic block per stage).
 __device__ __forceinline__ bool vec_lane_writer(int lane) { return (lane & 3) == 0; }
 
 // rotate every 16-lane row by 4*sft lanes: lane (k, b, j) receives the value of lane (k, (b+sft)%4, j)
@@ -46,49 +43,32 @@ __device__ __forceinline__ double rot_blocks(double x) {
 // out[bi] += sum_bj A(bi,bj) * in[bj]   with A given as fragments (one d4 per block per lane)
 // The four MFMAs of a block are issued as TWO dependent pairs whose partial sums are added on the vector ALU: a stage of a
 // sweep is a latency chain, and a dependent f64 4x4x4 MFMA costs ~44 cycles -- two in a row plus one add instead of four.
-#ifndef MPCQP_MFMA_PAIRS
-#define MPCQP_MFMA_PAIRS 1
-#endif
 template <int NB>
 __device__ __forceinline__ void frag_matvec(const d4 *A, const double *in, double *out) {
     constexpr int NBLK = NB / 16;
-#if MPCQP_MFMA_PAIRS
     double side[NBLK];
 #pragma unroll
     for (int bi = 0; bi < NBLK; ++bi) side[bi] = 0.0;
-#endif
 #pragma unroll
     for (int bj = 0; bj < NBLK; ++bj) {
         const double r0 = in[bj], r1 = rot_blocks<1>(in[bj]), r2 = rot_blocks<2>(in[bj]), r3 = rot_blocks<3>(in[bj]);
 #pragma unroll
         for (int bi = 0; bi < NBLK; ++bi) {
             const d4 a = A[bi * NBLK + bj];
-#if MPCQP_MFMA_PAIRS
             out[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[0], r0, out[bi], 0, 0, 0);
             side[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[2], r2, side[bi], 0, 0, 0);
             out[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[1], r1, out[bi], 0, 0, 0);
             side[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[3], r3, side[bi], 0, 0, 0);
-#else
-            out[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[0], r0, out[bi], 0, 0, 0);
-            out[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[1], r1, out[bi], 0, 0, 0);
-            out[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[2], r2, out[bi], 0, 0, 0);
-            out[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[3], r3, out[bi], 0, 0, 0);
-#endif
         }
     }
-#if MPCQP_MFMA_PAIRS
 #pragma unroll
     for (int bi = 0; bi < NBLK; ++bi) out[bi] += side[bi];
-#endif
 }
 
 // The 32 x 32 sweeps read the factor stream through BUFFER loads: resource = the instance's factor, scalar offset = the stage,
 // vector offset = the lane's constant byte offset inside a stage record -- the address of a load needs no vector arithmetic at
 // all (a global load takes a 64-bit per-lane address, formed with one or two VALU instructions per load and stage: ten of the
 // ~150 instructions of a stage).  cfg-5 +1 %; at 16 x 16 (three loads per stage) it measured -0.7 %, so those keep global loads.
-#ifndef MPCQP_BUFFER_LOADS
-#define MPCQP_BUFFER_LOADS 1
-#endif
 typedef unsigned int bu4 __attribute__((ext_vector_type(4)));
 typedef unsigned int bu2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t factor_rsrc(const double *F) {
@@ -118,13 +98,7 @@ __device__ __forceinline__ double lane_permute(double x, int byte_addr) {
 }
 template <int NB> struct SweepCfg {
     static constexpr int NF = (NB / 16) * (NB / 16);
-#ifndef MPCQP_DEPTH
-#define MPCQP_DEPTH 4
-#endif
-#ifndef MPCQP_DEPTH32
-#define MPCQP_DEPTH32 4
-#endif
-    static constexpr int DEPTH = NB == 32 ? MPCQP_DEPTH32 : MPCQP_DEPTH;   // factor stages kept in flight in registers (8 VGPRs each at NB = 16, 32 at NB = 32)
+    static constexpr int DEPTH = 4;                                       // factor stages kept in flight in registers (8 VGPRs each at NB = 16, 32 at NB = 32)
 };
 
 // The sweeping waves are dependent MFMA chains: two of them on one SIMD share its matrix pipe and slow each other
@@ -132,11 +106,7 @@ template <int NB> struct SweepCfg {
 // which of their waves does what, so that the sweepers of the four co-resident workgroups spread over the four
 // SIMDs.  Purely a speed matter: any placement gives the same results.
 __device__ __forceinline__ int logical_wave() {
-#ifdef MPCQP_NO_WAVE_ROTATION
-    return threadIdx.x >> 6;
-#else
     return ((threadIdx.x >> 6) - (blockIdx.x >> 8)) & (NWAVES - 1);
-#endif
 }
 
 // Forward elimination of one half-chain by ONE wave: for i = 1..nsteps, k = first + dir*i:   Tc[k] <- Tc[k] + Fwd(k) * Tc[k - dir]
@@ -147,7 +117,6 @@ __device__ __forceinline__ void chain_sweep(const int first, const int dir, cons
     constexpr int NBLK = NB / 16, NF = SweepCfg<NB>::NF, DEPTH = SweepCfg<NB>::DEPTH;
     const int lane = opaque_lane(threadIdx.x & 63);
     double *tb = Tc + vec_lane_offset(lane);
-    const bool writer = MPCQP_STORE_ALL ? true : vec_lane_writer(lane);
     auto stage_of = [&](int i) { return first + dir * i; };
     auto frag_of = [&](int i) { return F + (size_t)stage_of(i) * fstage; };
     // The group loop below is branch-free on purpose: with conditionals around the refills the compiler can no longer
@@ -173,7 +142,7 @@ __device__ __forceinline__ void chain_sweep(const int first, const int dir, cons
 #pragma unroll
         for (int bi = 0; bi < NBLK; ++bi) dst[bi] = own[bi];
         frag_matvec<NB>(ring[d], src, dst);
-        vec_store<NB>(tb, k, dst, writer);
+        vec_store<NB>(tb, k, dst, true);
     };
     int i0 = 1;
     for (; i0 + DEPTH - 1 <= nsteps; i0 += DEPTH) {
@@ -214,13 +183,7 @@ __device__ __forceinline__ CoreArgs core_args(const Lay &L, const double *F, con
 template <int NB> struct SoCfg {
     static constexpr int NBLK = NB / 16, NF = NBLK * NBLK;
     static constexpr int NS = NB == 16 ? 1 : 3;               // streamed d4 per lane and stage: sym(S) | sym(S00), sym(S11), S01
-#ifndef MPCQP_SO_DEPTH16
-#define MPCQP_SO_DEPTH16 3
-#endif
-#ifndef MPCQP_SO_DEPTH32
-#define MPCQP_SO_DEPTH32 2
-#endif
-    static constexpr int DEPTH = NB == 32 ? MPCQP_SO_DEPTH32 : MPCQP_SO_DEPTH16;      // stages in flight (12 VGPRs each at NB = 16, 40 at NB = 32)
+    static constexpr int DEPTH = NB == 32 ? 2 : 3;            // stages in flight (12 VGPRs each at NB = 16, 40 at NB = 32)
 };
 __device__ __forceinline__ d4 sym_window(const double *Fm, int lane) {
     const int R = (lane >> 2) & 3;
@@ -409,7 +372,6 @@ __device__ __forceinline__ void so_sweep(const CoreArgs &a, double *Tc, const in
     constexpr int NBLK = NB / 16, DEPTH = SoCfg<NB>::DEPTH;
     const int lane = opaque_lane(threadIdx.x & 63);
     double *tb = Tc + vec_lane_offset(lane);
-    const bool writer = MPCQP_STORE_ALL ? true : vec_lane_writer(lane);
     const SoLaneK lc = so_lane_consts<NB, UP>(lane);
     d4 Gf[SoCfg<NB>::NF];
     frag_load<NB>(a.G + (UP ? 0 : NB * NB), lane, Gf);
@@ -417,7 +379,7 @@ __device__ __forceinline__ void so_sweep(const CoreArgs &a, double *Tc, const in
     auto clamp_i = [&](int i) { return i < nsteps ? i : nsteps; };       // (branch-free refills, see chain_sweep)
     const __amdgpu_buffer_rsrc_t rs = factor_rsrc(a.F);
     auto load = [&](int i, SoSlot<NB> &s) {
-        if constexpr (MPCQP_BUFFER_LOADS && NB == 32) so_slot_load<NB>(rs, (unsigned)(stage_of(i) * a.fstage) * 8u, lc, s);
+        if constexpr (NB == 32) so_slot_load<NB>(rs, (unsigned)(stage_of(i) * a.fstage) * 8u, lc, s);
         else so_slot_load<NB>((const char *)(a.F + (size_t)stage_of(i) * a.fstage), lc, s);
     };
     if (nsteps < ibegin) return;
@@ -487,7 +449,7 @@ __device__ __forceinline__ void so_sweep(const CoreArgs &a, double *Tc, const in
         // (6)
 #pragma unroll
         for (int bi = 0; bi < NBLK; ++bi) { run[bi] = SOLVE ? xp[bi] + xq[bi] : (xp[bi] + xq[bi]) + own[bi]; own[bi] = own_next[bi]; }
-        if (writer && valid) {
+        if (valid) {
 #pragma unroll
             for (int bi = 0; bi < NBLK; ++bi) tb[k * NB + bi * 16] = run[bi];
         }
@@ -582,13 +544,9 @@ __device__ __forceinline__ void kkt_core_group(const CoreArgs &, double *);     
 // (GROUPABLE = false: an instantiation that can never meet grouped stages -- compile-time nx + nu = 16 -- does not carry that path)
 template <int NB, bool GROUPABLE = (NB == 16)>
 __device__ __forceinline__ void kkt_core(const CoreArgs &a, double *Tc) {
-#ifndef MPCQP_ABL_NOCHAIN
     if constexpr (NB == 16 && GROUPABLE) { if (a.grp > 1) { kkt_core_group(a, Tc); return; } }
     if constexpr (FactorFmt<NB>::SONLY) kkt_core_so<NB>(a, Tc);
     else kkt_core_fwd<NB>(a, Tc);                 // (each of them ends with a barrier)
-#else
-    __syncthreads();
-#endif
 }
 template <> __device__ __forceinline__ void kkt_core<64, false>(const CoreArgs &, double *);      // mpcqp_wide.h (stages wider than 32)
 template <> __device__ __forceinline__ void kkt_core<128, false>(const CoreArgs &, double *);     // mpcqp_huge.h (stages wider than 64)

@@ -1,10 +1,10 @@
-"""Time K plain ADMM iterations on the cfg-3 batch with the library named by MPCQP_LIB (ablation builds)."""
+"""Time K plain ADMM iterations on the cfg-3 batch with the library named by MPCQP_LIB (e.g. a -DMPCQP_RUN_TIMING build)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import bench
 from pympc_amd import _lib
-if os.environ.get('MPCQP_LIB'):            # ablation build: point the loader at it BEFORE the first load (scripts only)
+if os.environ.get('MPCQP_LIB'):            # another build: point the loader at it BEFORE the first load (scripts only)
     _lib.LIB_PATH = os.environ['MPCQP_LIB']
 from pympc_amd.solver import BatchProblem
 B = int(os.environ.get('B', 1024)); iters = int(os.environ.get('ITERS', 100))

@@ -1,11 +1,9 @@
 """The order the dense top of the cyclic reduction is stored in for the round's vector-ALU mat-vec (pympc_amd/csrc/mpcqp_topv.h): factor_bcr writes the inverse
 entry by entry through bcr_topv_pos, the round's LDS copy is read pair by pair as bcr_topv_rc enumerates them -- the two maps must be inverse to each other
-for every top size the schedules produce (2, 5, 7 stages) and both lane layouts.  Plain host functions: compiled here with g++ (no GPU)."""
+for every top size the schedules produce (2, 5, 7 stages).  Plain host functions: compiled here with g++ (no GPU)."""
 import os
 import subprocess
 import tempfile
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = r'''
@@ -32,11 +30,10 @@ int main() {
 '''
 
 
-@pytest.mark.parametrize('mode', [1, 2])
-def test_position_map_inverts_the_pair_enumeration(mode):
+def test_position_map_inverts_the_pair_enumeration():
     with tempfile.TemporaryDirectory() as d:
         src, exe = os.path.join(d, 't.cpp'), os.path.join(d, 't')
         open(src, 'w').write(SRC)
-        subprocess.check_call(['g++', '-std=c++17', '-O1', '-DLATW_TOP_VALU=%d' % mode, '-I', os.path.join(ROOT, 'pympc_amd', 'csrc'), src, '-o', exe])
+        subprocess.check_call(['g++', '-std=c++17', '-O1', '-I', os.path.join(ROOT, 'pympc_amd', 'csrc'), src, '-o', exe])
         out = subprocess.run([exe], capture_output=True, text=True)
         assert out.returncode == 0 and out.stdout.strip() == '0', out.stdout

@@ -22,6 +22,9 @@ SYMBOLS = [
 # include/mpcqp_polish.h: an extension beside mpcqp.h, bound only where the loaded library exports it (the CPU twin does not)
 POLISH_SYMBOLS = ['mpcqp_polish_default_settings', 'mpcqp_set_polish', 'mpcqp_polish', 'mpcqp_get_polish_info']
 
+# include/mpcqp_model.h: likewise -- a new model under a handle that is in use, and a schedule of models for the device loop
+MODEL_SYMBOLS = ['mpcqp_update_model', 'mpcqp_mpc_loop_tv']
+
 
 class PolishSettings(C.Structure):
     """mpcqp_polish_settings (include/mpcqp_polish.h)."""
@@ -68,6 +71,12 @@ class Loop(C.Structure):
                 ('C', C.c_void_p), ('Lgain', C.c_void_p), ('v', C.c_void_p), ('x_true', C.c_void_p),
                 ('x_traj', C.c_void_p), ('xhat_traj', C.c_void_p), ('y_traj', C.c_void_p), ('u_traj', C.c_void_p),
                 ('status_traj', C.c_void_p), ('iter_traj', C.c_void_p)]
+
+
+class ModelTraj(C.Structure):
+    """mpcqp_model_traj (include/mpcqp_model.h): entry e of Ad / Bd is in force during steps e * hold .. e * hold + hold - 1."""
+    _fields_ = [('struct_size', C.c_int32), ('hold', C.c_int32), ('nmodels', C.c_int32), ('reserved', C.c_int32),
+                ('Ad', C.c_void_p), ('Bd', C.c_void_p)]
 
 
 _lib = None
@@ -147,6 +156,11 @@ def load():
         L.mpcqp_get_polish_info.argtypes = [H, C.c_void_p]
         for name in ('mpcqp_set_polish', 'mpcqp_polish', 'mpcqp_get_polish_info'):
             getattr(L, name).restype = C.c_int
+    if has_model_update(L):
+        L.mpcqp_update_model.argtypes = [H, C.POINTER(Model)]
+        L.mpcqp_mpc_loop_tv.argtypes = [H, C.c_int, C.POINTER(Loop), C.POINTER(ModelTraj)]
+        for name in MODEL_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -155,6 +169,12 @@ def has_polish(L=None):
     """True if the library exports include/mpcqp_polish.h (libmpcqp_hip.so does; the CPU twin does not)."""
     L = L if L is not None else load()
     return all(hasattr(L, name) for name in POLISH_SYMBOLS)
+
+
+def has_model_update(L=None):
+    """True if the library exports include/mpcqp_model.h (libmpcqp_hip.so does; the CPU twin does not)."""
+    L = L if L is not None else load()
+    return all(hasattr(L, name) for name in MODEL_SYMBOLS)
 
 
 def check(rc, what):

@@ -92,6 +92,32 @@ class BatchMPCController:
         ``update()`` afterwards.  Results do not change; returns how many instances share (0 on the register-resident backends)."""
         return self.prob.share_factor()
 
+    def update_model(self, solve=True, **fields):
+        """New model data for the batch in use (``BatchProblem.update_model``): any of Ad, Bd, Qx, QxN, Qu, QDu, xmin, xmax, umin, umax, Dumin,
+        Dumax, uref, eps_feas, broadcast to the batch like the constructor's arguments; what is not given keeps its value.  The device
+        re-equilibrates, refactors and keeps every instance's iterate; ``solve=True`` then warm-solves like ``update``."""
+        if self.prob is None:
+            raise RuntimeError('update_model() needs a controller that has been set up; before setup() assign the attributes')
+        shapes = self.prob._model_shapes()
+        new = {}
+        for k, v in fields.items():
+            if k not in shapes:
+                raise TypeError('unknown model field %r' % k)
+            if v is not None:
+                new[k] = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=float), shapes[k]))      # (ValueError if it does not fit, like the constructor)
+        if not new:
+            raise ValueError('update_model needs at least one model field')
+        for k, v in new.items():
+            setattr(self, k, v)
+        if 'uref' in new:
+            self.u_failure = self.uref
+        if not self._um1_on_device:               # output() moved u_{-1} on: the rho vector is built from the bounds as update() would leave them
+            self.prob.update(None, self.uminus1_rh, None)
+            self._um1_on_device = True
+        self.prob.update_model(**new)
+        if solve:
+            self.solve()
+
     def update(self, x, u=None, xref=None, solve=True):
         self.x0_rh = x
         if u is not None:
@@ -123,19 +149,29 @@ class BatchMPCController:
         self._u_last = None
         return uMPC
 
-    def run(self, nsteps, w=None, Ap=None, Bp=None, xref_traj=None, estimator=None):
+    def run(self, nsteps, w=None, Ap=None, Bp=None, xref_traj=None, estimator=None, model_traj=None):
         """``nsteps`` closed-loop steps on the device, equivalent to
         ``for k in range(nsteps): u = K.output(); x = Ap @ x + Bp @ u + w[k]; K.update(x, u, xref_traj[k])``
         (the loop of examples/example_point_mass.py:88-101 with a linear plant; default plant = (Ad, Bd)), or, with
         ``estimator = BatchLinearStateEstimator`` (pympc_amd.kalman), to the output-feedback loop of
         examples/example_inverted_pendulum_kalman.py:135-174 -- the estimator object supplies C, L, the measurement noise
         ``estimator.v`` [nsteps,B,ny] (optional) and the true plant state ``estimator.x_true`` [B,nx], advanced in place.
+        ``model_traj = (Ad [nmodels,B,nx,nx] or None, Bd [nmodels,B,nx,nu] or None, hold)``: a schedule of models -- entry ``k // hold`` replaces
+        Ad / Bd at the start of step k (mpcqp_mpc_loop_tv: ``update_model`` between closed-loop launches, no host round trip); the controller is
+        left with the last entry used.  Not with an estimator.
         Returns ``dict(x=[nsteps+1,B,nx], u=[nsteps,B,nu], status=[nsteps,B] (OSQP status values), iter=[nsteps,B])``
         plus ``xhat`` and ``y`` with an estimator."""
         est = None
         if estimator is not None:
             est = dict(C=estimator.C, L=estimator.L, x_true=estimator.x_true, v=getattr(estimator, 'v', None))
-        out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=est)
+        out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=est, model_traj=model_traj)
+        if model_traj is not None:
+            last = (int(nsteps) - 1) // int(model_traj[2])
+            host = lambda a: np.array(a[last].cpu() if hasattr(a, 'data_ptr') else a[last], dtype=float).reshape((self.B,) + tuple(a.shape[-2:]))
+            if model_traj[0] is not None:
+                self.Ad = host(model_traj[0])
+            if model_traj[1] is not None:
+                self.Bd = host(model_traj[1])
         xt, ut, st, it = out[:4]
         res = dict(x=xt, u=ut, status=st, iter=it)
         if estimator is not None:

@@ -223,6 +223,71 @@ class MPCController:
         elif hasattr(self.prob, 'flush'):
             self.prob.flush()                 # (the device solver sends the step data with the solve; without one, now)
 
+    def update_model(self, Ad=None, Bd=None, Qx=None, QxN=None, Qu=None, QDu=None,
+                     xmin=None, xmax=None, umin=None, umax=None, Dumin=None, Dumax=None,
+                     uref=None, eps_feas=None, solve=True):
+        """New controller data for a controller that is in use -- a relinearised plant, scheduled weights or bounds; an addition to the
+        reference's class, which can only be constructed again.  Every argument left at None keeps its value (QxN included: it does not
+        follow a new Qx).  The arguments are checked like the constructor's, with its messages; dimensions cannot change.  The public
+        attributes and P, q, A, l, u are rebuilt for the current x0 / u_{-1} / xref, and the solver takes the new problem WITHOUT losing
+        its iterate: ``prob.update_model`` where the solver has it (the device re-equilibrates, refactors and keeps x, y), otherwise a fresh
+        ``type(prob)()`` set up with the new matrices and warm-started from ``res.x, res.y``.  Before ``setup()`` only the attributes change."""
+        nx, nu = self.nx, self.nu
+        new = {}
+        if Ad is not None:
+            if not (_matrix_like(Ad) and Ad.shape[0] == Ad.shape[1] and Ad.shape[0] == nx):
+                raise ValueError("Ad should be a square matrix of dimension (nx,nx)!")
+            new['Ad'] = Ad
+        if Bd is not None:
+            if not (_matrix_like(Bd) and Bd.shape[0] == nx and Bd.shape[1] == nu):
+                raise ValueError("Bd should be a matrix of dimension (nx, nu)!")
+            new['Bd'] = Bd
+        for name, val, size in (('Qx', Qx, nx), ('Qu', Qu, nu), ('QDu', QDu, nu)):
+            if val is not None:
+                if not (_matrix_like(val) and val.shape[0] == size and val.shape[1] == size):
+                    raise ValueError(_ERR[name])
+                new[name] = val
+        if QxN is not None:
+            if not (_matrix_like(QxN) and QxN.shape[0] == nx and QxN.shape[1] == nx):
+                raise ValueError(_ERR['QxN'])
+            new['QxN'] = QxN
+        for name, val, size, ravel in (('xmin', xmin, nx, True), ('xmax', xmax, nx, False), ('umin', umin, nu, False), ('umax', umax, nu, False),
+                                       ('Dumin', Dumin, nu, False), ('Dumax', Dumax, nu, False), ('uref', uref, nu, True)):
+            if val is not None:
+                if not (_vector_like(val) and val.size == size):
+                    raise ValueError(_ERR[name])
+                new[name] = val.ravel() if ravel else val
+        if eps_feas is not None:
+            new['eps_feas'] = eps_feas
+        if not new:
+            raise ValueError("update_model needs at least one of Ad, Bd, Qx, QxN, Qu, QDu, xmin, xmax, umin, umax, Dumin, Dumax, uref, eps_feas!")
+        for k, v in new.items():
+            setattr(self, k, v)
+        if 'eps_feas' in new:
+            self.Qeps = eps_feas * sparse.eye(nx)
+        if 'uref' in new:
+            self.u_failure = self.uref
+        if self.prob is None or self.P is None:          # not set up yet: setup() builds from the attributes
+            return
+        self._stale = False
+        self._compute_QP_matrices_()                     # (from x0, uminus1 like setup(); then for the step data in force, like update())
+        self.q, self.J_CNST = qp_build.refresh_vectors(self)
+        if hasattr(self.prob, 'update_model') and getattr(self.prob, 'supports_update_model', True):
+            md = self._model_data()
+            # (the weights as the debug switches JX_ON / JU_ON / JDU_ON leave them; the step data as this call sees it: output() may have moved u_{-1} on)
+            self.prob.update(mpc_step=(np.array(md['x0'], dtype=float).reshape(1, -1), np.array(md['uminus1'], dtype=float).reshape(1, -1),
+                                       np.array(md['xref'], dtype=float).reshape(1, -1)))
+            self.prob.update_model(**{k: md[k] for k in new})
+        else:
+            prob = type(self.prob)()
+            prob.setup(self.P, self.q, self.A, self.l, self.u, warm_start=True, verbose=False,
+                       eps_abs=self.eps_rel, eps_rel=self.eps_abs, mpc=self._model_data(), **self.solver_settings)
+            if self.res is not None:
+                prob.warm_start(x=self.res.x, y=self.res.y)
+            self.prob = prob
+        if solve:
+            self.solve()
+
     def solve(self):
         """Warm-started solve (mpc.py:366-375)."""
         self.res = self.prob.solve()

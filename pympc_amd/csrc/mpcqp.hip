@@ -43,6 +43,7 @@
 
 #include "../../include/mpcqp.h"
 #include "../../include/mpcqp_polish.h"
+#include "../../include/mpcqp_model.h"
 
 #include "mpcqp_defs.h"
 
@@ -476,7 +477,8 @@ static int step_upload(mpcqp_handle *h, const double *x0, const double *um1, con
 
 static int share_factor_async(mpcqp_handle *h);
 // setup's two launches (mpcqp_phases.h): equilibration, rho vector and cold start with a lean LDS block; then the first factorization
-static int launch_setup(mpcqp_handle *h) {
+// keep: no cold start -- the iterate, the reported solution and the last mpcqp_info stay (mpcqp_update_model)
+static int launch_setup(mpcqp_handle *h, bool keep = false) {
     const Lay &L = h->L;
     h->P.fown = nullptr;                            // (every instance factors into its own slot: sharing is off until mpcqp_share_factor is asked again)
     if (flush_puts(h)) return MPCQP_ERR_HIP;
@@ -484,7 +486,7 @@ static int launch_setup(mpcqp_handle *h) {
     const size_t de = sizeof(double) * (size_t)(L.n + L.m);
     const int lds_de = lean + de <= 96 * 1024 ? 1 : 0;      // (cfg-5: 91 KB -- one workgroup per compute unit, still well ahead of two walking memory)
     if (set_smem(k_setup, lean + (lds_de ? de : 0))) return MPCQP_ERR_HIP;
-    hipLaunchKernelGGL(k_setup, dim3(h->batch), dim3(NT), lean + (lds_de ? de : 0), h->stream, h->L, h->P, h->S, lds_de);
+    hipLaunchKernelGGL(k_setup, dim3(h->batch), dim3(NT), lean + (lds_de ? de : 0), h->stream, h->L, h->P, h->S, lds_de, keep ? 1 : 0);
     // the cyclic reduction's factorization at 256 threads uses the work area only as far as BcrFmt::lds_doubles says (three workgroups per compute unit at (12,4,30)
     // where the solve kernel's block -- iterate, top inverse -- would allow one); everything else factors in the block it solves in
     if (L.NB == 16 && L.bcr) {
@@ -524,6 +526,34 @@ extern "C" int mpcqp_setup(mpcqp_handle *h, const mpcqp_model *M, const double *
     if ((rc = step_upload(h, x0, um1, xref, xref_rows))) return rc;
     if ((rc = launch_setup(h))) return rc;
     h->is_setup = true;
+    return MPCQP_OK;
+}
+
+// ---- include/mpcqp_model.h: a new model under a handle that is in use
+// The given fields into the model blob (device sources through put's pack list: one k_pack_rows launch for all of them).
+static int merge_model(mpcqp_handle *h, const mpcqp_model *M) {
+    const Lay &L = h->L; const int nx = L.nx, nu = L.nu, ms = L.model_sz;
+    const struct { const double *src; int off, w; } f[14] = {
+        {M->Ad, L.oAd, nx * nx}, {M->Bd, L.oBd, nx * nu}, {M->xmin, L.oxmin, nx}, {M->xmax, L.oxmax, nx}, {M->umin, L.oumin, nu}, {M->umax, L.oumax, nu},
+        {M->Dumin, L.oDumin, nu}, {M->Dumax, L.oDumax, nu}, {M->uref, L.ouref, nu}, {M->eps_feas, L.oeps, 1},
+        {M->Qx, L.oQx, nx * nx}, {M->QxN, L.oQxN, nx * nx}, {M->Qu, L.oQu, nu * nu}, {M->QDu, L.oQDu, nu * nu}};
+    h->pack.n = 0;                                  // (nothing left over from a call that failed half-way)
+    for (int i = 0; i < 14; ++i)
+        if (f[i].src && put(h, h->P.model, ms, f[i].off, f[i].src, f[i].w)) return MPCQP_ERR_HIP;
+    return MPCQP_OK;
+}
+static bool model_is_empty(const mpcqp_model *M) {
+    return !M->Ad && !M->Bd && !M->Qx && !M->QxN && !M->Qu && !M->QDu && !M->xmin && !M->xmax && !M->umin && !M->umax && !M->Dumin && !M->Dumax && !M->uref && !M->eps_feas;
+}
+extern "C" int mpcqp_update_model(mpcqp_handle *h, const mpcqp_model *M) {
+    if (!h || !M) return fail(MPCQP_ERR_ARG, "mpcqp_update_model: null argument");
+    if (model_is_empty(M)) return fail(MPCQP_ERR_ARG, "mpcqp_update_model: no model field given");
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_update_model before mpcqp_setup");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = merge_model(h, M);
+    if (rc) return rc;
+    if ((rc = launch_setup(h, true))) return rc;   // (flushes the pack list first)
+    h->warm_x_pending = true;                       // the next solve begins from z = A_new x
     return MPCQP_OK;
 }
 
@@ -1027,7 +1057,8 @@ static int get(mpcqp_handle *h, void *dst, const void *src, size_t bytes) {
     return 0;
 }
 
-extern "C" int mpcqp_mpc_loop(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
+// what mpcqp_mpc_loop refuses (before anything is launched or changed)
+static int loop_check(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
     if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop: bad argument");
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_mpc_loop before mpcqp_setup");
     if (h->pol.polish) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_mpc_loop / mpcqp_mpc_run: solution polishing inside the device closed loop is not implemented; switch polish off (mpcqp_set_polish) or step with mpcqp_mpc_step");
@@ -1039,6 +1070,12 @@ extern "C" int mpcqp_mpc_loop(mpcqp_handle *h, int nsteps, const mpcqp_loop *io)
         return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop: xref_rows must be 0 (as last uploaded), 1 or Np+1");
     HIPCHK(hipSetDevice(h->device));
     if (h->L.raw) return fail(MPCQP_ERR_STATE, "mpcqp_mpc_loop: the handle holds raw q, l, u (mpcqp_update_vectors); call mpcqp_update first");
+    return MPCQP_OK;
+}
+// balance: the call may end with a wait for the stream and a rebuild of the workgroup -> instance map when one is due (not between the segments of
+// mpcqp_mpc_loop_tv, which does it once at its end)
+static int loop_run(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, bool balance) {
+    const int ny = io->ny;
     if (io->xref_traj && io->xref_rows) h->L.xref_rows = io->xref_rows;     // update(x, u, xref_k) with this reference shape
     const Lay &L = h->L;
     const size_t B = (size_t)h->batch, K = (size_t)nsteps, nx = L.nx, nu = L.nu;
@@ -1091,10 +1128,47 @@ extern "C" int mpcqp_mpc_loop(mpcqp_handle *h, int nsteps, const mpcqp_loop *io)
     if (h->pq.status) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * B, h->stream));      // (the last solve of the loop: not polished)
     for (int i = 0; i < np; ++i)
         if (parts[i].dst && parts[i].bytes && !parts[i].direct && get(h, parts[i].dst, dev(i), parts[i].bytes)) return MPCQP_ERR_HIP;
-    const bool due = balance_due(h);
+    const bool due = balance && balance_due(h);
     if (!due && !any_host) return MPCQP_OK;                   // every buffer is device memory: stream-ordered, nothing to wait for
     HIPCHK(hipStreamSynchronize(h->stream));
     return due ? rebalance(h) : MPCQP_OK;
+}
+extern "C" int mpcqp_mpc_loop(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
+    const int rc = loop_check(h, nsteps, io);
+    return rc ? rc : loop_run(h, nsteps, io, true);
+}
+
+// The device loop under a schedule of models (include/mpcqp_model.h): per entry, mpcqp_update_model and one closed-loop launch of the steps it holds for.
+extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt) {
+    if (!mt) return mpcqp_mpc_loop(h, nsteps, io);
+    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: bad argument");
+    if (mt->struct_size != (int32_t)sizeof(mpcqp_model_traj)) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: struct_size is not sizeof(mpcqp_model_traj)");
+    if (mt->hold < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: hold must be >= 1");
+    const int nseg = (nsteps + mt->hold - 1) / mt->hold;
+    if (mt->nmodels < nseg) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: fewer than ceil(nsteps / hold) model entries");
+    if (!mt->Ad && !mt->Bd) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: give Ad, Bd or both");
+    if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_mpc_loop_tv: output feedback with a model schedule is not implemented");
+    int rc = loop_check(h, nsteps, io);
+    if (rc) return rc;
+    const Lay &L = h->L;
+    const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu;
+    const size_t xblk = (size_t)(io->xref_traj && io->xref_rows ? io->xref_rows : L.xref_rows) * nx;
+    for (int s = 0; s < nseg; ++s) {
+        const size_t k0 = (size_t)s * mt->hold;
+        mpcqp_model M; memset(&M, 0, sizeof(M));
+        if (mt->Ad) M.Ad = mt->Ad + (size_t)s * B * nx * nx;
+        if (mt->Bd) M.Bd = mt->Bd + (size_t)s * B * nx * nu;
+        if ((rc = mpcqp_update_model(h, &M))) return rc;
+        mpcqp_loop seg = *io;                       // the trajectory buffers, advanced to step k0
+        if (seg.w) seg.w += k0 * B * nx;
+        if (seg.xref_traj) seg.xref_traj += k0 * B * xblk;
+        if (seg.x_traj) seg.x_traj += k0 * B * nx;  // (its row k0 is written again: the state the last segment ended in)
+        if (seg.u_traj) seg.u_traj += k0 * B * nu;
+        if (seg.status_traj) seg.status_traj += k0 * B;
+        if (seg.iter_traj) seg.iter_traj += k0 * B;
+        if ((rc = loop_run(h, std::min(mt->hold, nsteps - (int)k0), &seg, s == nseg - 1))) return rc;
+    }
+    return MPCQP_OK;
 }
 
 extern "C" int mpcqp_mpc_run(mpcqp_handle *h, int nsteps, const double *w, const double *Ap, const double *Bp,

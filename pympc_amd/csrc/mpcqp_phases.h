@@ -75,7 +75,9 @@ __device__ __forceinline__ void load_common(const Lay &L, const double *model, c
 // 219 registers and, for the cyclic reduction with a dense top, 142 KB of LDS held the equilibration passes to two / one workgroup per compute unit.)
 // lds_de: the scaling vectors D, E live in LDS during the passes (where the work area T would start; the launch provides n + m doubles there) -- every term of
 // every row norm reads one of them, through a visitor the compiler cannot hoist the loads out of: a memory round trip per term otherwise.
-__global__ __launch_bounds__(NT) void k_setup(Lay L, Ptrs P, mpcqp_settings S_, int lds_de) {
+// keep: mpcqp_update_model (include/mpcqp_model.h) -- the model blob has changed under a handle that is in use: everything above is redone, but the
+// iterate x, z, y, the reported solution xo, yo and the last mpcqp_info stay as they are (no cold start).
+__global__ __launch_bounds__(NT) void k_setup(Lay L, Ptrs P, mpcqp_settings S_, int lds_de, int keep) {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     double *p = sh; Smem S; smem_common(L, P, p, S);
     const int b = inst_of(P.perm), tid = threadIdx.x;
@@ -137,6 +139,11 @@ __global__ __launch_bounds__(NT) void k_setup(Lay L, Ptrs P, mpcqp_settings S_, 
     for (int j = tid; j < L.n; j += NT) sv[j] = S_.sigma / (D[j] * D[j]);
     if (tid == 0) { P.c[b] = cc; P.rho[b] = rho; }
     __syncthreads();
+    if (keep) {
+        // (the verdict of an EARLIER factorization must not outlive it: the one that follows writes its own)
+        if (tid == 0 && P.info[b].status == MPCQP_NON_CVX && P.info[b].iter == 0) P.info[b].status = MPCQP_UNSOLVED;
+        return;
+    }
     // cold start
     for (int j = tid; j < L.n; j += NT) { P.x[(size_t)b * L.n + j] = 0.0; P.xo[(size_t)b * L.n + j] = 0.0; }
     for (int r = tid; r < L.m; r += NT) { P.z[(size_t)b * L.m + r] = 0.0; P.y[(size_t)b * L.m + r] = 0.0; P.yo[(size_t)b * L.m + r] = 0.0; }
@@ -161,7 +168,7 @@ __global__ __launch_bounds__(NT) void k_setup_factor(Lay L, Ptrs P) {
     const int bad = NB == 16 && L.grp > 1 ? factor_grouped(c, om, sv, cc, P.F + (size_t)b * P.fsz, S.T, S.iflag, border_ptrs(L, P, S))
                   : NB == 16 && L.dense ? factor_dense(c, om, sv, cc, P.F + (size_t)b * P.fsz, S.T, S.iflag)
                             : factor_all<NB>(c, om, sv, cc, P.F + (size_t)b * P.fsz, S.T, S.iflag, border_ptrs(L, P, S));
-    if (bad && threadIdx.x == 0) P.info[b].status = MPCQP_NON_CVX;
+    if (bad && threadIdx.x == 0) { P.info[b].status = MPCQP_NON_CVX; P.info[b].iter = 0; }      // (iter: 0 already after k_setup's cold start; after mpcqp_update_model the last solve's)
 }
 
 // ... of the cyclic reduction (a kernel of its own: 130 registers and 47 KB of LDS at (12,4,30) -- three workgroups per compute unit)
@@ -173,7 +180,7 @@ __global__ __launch_bounds__(NT) void k_setup_factor_bcr(Lay L, Ptrs P) {
     load_common(L, model, P.step + (size_t)b * L.step_sz, S);
     Ctx c{L, S.hot, model + L.hot_sz};
     const int bad = factor_bcr(c, P.omega + (size_t)b * L.m, P.s + (size_t)b * L.n, P.c[b], P.F + (size_t)b * P.fsz, P.bws + (size_t)b * L.bcr * BcrFmt::WSTAGE, S.T, S.iflag);
-    if (bad && threadIdx.x == 0) P.info[b].status = MPCQP_NON_CVX;
+    if (bad && threadIdx.x == 0) { P.info[b].status = MPCQP_NON_CVX; P.info[b].iter = 0; }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -291,6 +291,31 @@ class BatchProblem:
     def _bound(self, v, name):
         return None if v is None else _prep(v, (self.batch, self.m), name)
 
+    def _model_shapes(self):
+        B, nx, nu = self.batch, self.nx, self.nu
+        return dict(Ad=(B, nx, nx), Bd=(B, nx, nu), Qx=(B, nx, nx), QxN=(B, nx, nx), Qu=(B, nu, nu), QDu=(B, nu, nu),
+                    xmin=(B, nx), xmax=(B, nx), umin=(B, nu), umax=(B, nu), Dumin=(B, nu), Dumax=(B, nu), uref=(B, nu), eps_feas=(B, 1))
+
+    def update_model(self, **fields):
+        """A new model under a problem that is in use (mpcqp_update_model, include/mpcqp_model.h): the given fields -- names and shapes as in
+        ``setup``, numpy arrays or torch device tensors, None = unchanged -- replace the problem's, the device re-equilibrates, rebuilds the rho
+        vector, refactors and keeps the iterate: the next solve warm-starts from it exactly as setup + warm_start(x, y) would.  Stream-ordered
+        (no wait) when every field is device memory."""
+        if not _lib.has_model_update(self._L):
+            raise NotImplementedError('this build of the solver library has no in-place model update (include/mpcqp_model.h)')
+        shapes = self._model_shapes()
+        for k in fields:
+            if k not in shapes:
+                raise TypeError('unknown model field %r' % k)
+        arrs = {k: _prep(v, shapes[k], k) for k, v in fields.items() if v is not None}
+        if not arrs:
+            raise ValueError('update_model: give at least one model field')
+        model = _lib.Model()
+        for k, v in arrs.items():
+            setattr(model, k, C.cast(_ptr(v), C.POINTER(C.c_double)))
+        self._keep = [arrs]                    # (device tensors: alive until the stream has read them -- at least until the next call)
+        _lib.check(self._L.mpcqp_update_model(self._h, C.byref(model)), 'mpcqp_update_model')
+
     def update_vectors(self, q=None, l=None, u=None):
         """osqp's update(q=, l=, u=) (mpc.py:454) with caller-built vectors.  q may be None (unchanged); l and u go together --
         both or neither: the equality rows l[:nx] == u[:nx] carry x0 (the library refuses one without the other)."""
@@ -405,7 +430,7 @@ class BatchProblem:
         buf = np.frombuffer(cb, dtype=np.float64)
         return buf[:n].reshape(1, n), buf[n:].reshape(1, m), info
 
-    def mpc_run(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None):
+    def mpc_run(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None):
         """Device-side receding-horizon loop (mpcqp_mpc_loop): ``nsteps`` closed-loop steps
         ``u = output(); x = Ap x + Bp u + w[k]; update(x)`` of every instance without host round trips.
 
@@ -413,6 +438,8 @@ class BatchProblem:
         ``xref_traj`` [nsteps, batch, rows*nx] gives the reference of the solve after step k (rows as last uploaded).
         ``estimator = dict(C=[B,ny,nx], L=[B,nx,ny], x_true=[B,nx], v=[nsteps,B,ny] or None)`` switches output feedback on
         (pyMPC/kalman.py:109-134): the controller is updated with the estimate, ``x_true`` is advanced in place.
+        ``model_traj = (Ad [nmodels,B,nx,nx] or None, Bd [nmodels,B,nx,nu] or None, hold)`` schedules the model (mpcqp_mpc_loop_tv): entry
+        ``k // hold`` replaces Ad / Bd at the start of step k (``update_model``), for the controller and, without ``Ap``/``Bp``, the plant.
         Returns ``(x_traj [nsteps+1,B,nx], u_traj [nsteps,B,nu], status [nsteps,B] int32, iters [nsteps,B] int32)`` as
         numpy arrays (plus ``xhat_traj, y_traj`` with an estimator), or fills the arrays/tensors given in ``out``."""
         K, B, nx, nu = int(nsteps), self.batch, self.nx, self.nu
@@ -455,10 +482,29 @@ class BatchProblem:
         io.x_traj, io.u_traj, io.status_traj, io.iter_traj = (_ptr(o) for o in out[:4])
         if ny and len(out) >= 6:
             io.xhat_traj, io.y_traj = _ptr(out[4]), _ptr(out[5])
-        rc = self._L.mpcqp_mpc_loop(self._h, K, C.byref(io))
+        if model_traj is not None:
+            if not _lib.has_model_update(self._L):
+                raise NotImplementedError('this build of the solver library has no model schedule for the device loop (include/mpcqp_model.h)')
+            Adt, Bdt, hold = model_traj
+            hold = int(hold)
+            if hold < 1:
+                raise ValueError('model_traj: hold must be >= 1')
+            given = [a for a in (Adt, Bdt) if a is not None]
+            if not given:
+                raise ValueError('model_traj: give Ad, Bd or both')
+            nm = int(tuple(given[0].shape)[0])
+            mt = _lib.ModelTraj()
+            mt.struct_size, mt.hold, mt.nmodels = C.sizeof(_lib.ModelTraj), hold, nm
+            mt.Ad = inp(Adt, (nm, B, nx, nx), 'model_traj Ad'); mt.Bd = inp(Bdt, (nm, B, nx, nu), 'model_traj Bd')
+            rc = self._L.mpcqp_mpc_loop_tv(self._h, K, C.byref(io), C.byref(mt))
+            what = 'mpcqp_mpc_loop_tv'
+        else:
+            rc = self._L.mpcqp_mpc_loop(self._h, K, C.byref(io))
+            what = 'mpcqp_mpc_loop'
         if rc == -4:
             raise NotImplementedError(self._L.mpcqp_last_error().decode())
-        _lib.check(rc, 'mpcqp_mpc_loop')
+        _lib.check(rc, what)
+        self._keep = [keep]                    # (device inputs of a stream-ordered run: alive at least until the next call)
         return tuple(out)
 
     def solution(self, want_y=True):
@@ -675,6 +721,18 @@ class DeviceProblem:
 
     def update_settings(self, **kw):
         self._bp.update_settings(**kw)
+
+    @property
+    def supports_update_model(self):
+        """True if the loaded solver library has mpcqp_update_model (include/mpcqp_model.h)."""
+        return _lib.has_model_update()
+
+    def update_model(self, **fields):
+        """New controller data under the problem in use (``BatchProblem.update_model`` for the one instance): Ad, Bd, Qx, QxN, Qu, QDu, xmin, xmax,
+        umin, umax, Dumin, Dumax, uref, eps_feas -- None or absent = unchanged.  The iterate is kept; the next ``solve()`` warm-starts from it."""
+        self.flush()
+        one = lambda k, v: np.array([[float(v)]]) if k == 'eps_feas' else np.asarray(v, dtype=float)[None]
+        self._bp.update_model(**{k: one(k, v) for k, v in fields.items() if v is not None})
 
     def warm_start(self, x=None, y=None):
         self.flush()

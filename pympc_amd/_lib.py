@@ -25,11 +25,27 @@ POLISH_SYMBOLS = ['mpcqp_polish_default_settings', 'mpcqp_set_polish', 'mpcqp_po
 # include/mpcqp_model.h: likewise -- a new model under a handle that is in use, and a schedule of models for the device loop
 MODEL_SYMBOLS = ['mpcqp_update_model', 'mpcqp_mpc_loop_tv']
 
+# include/mpcqp_adjoint.h: likewise -- adjoint derivatives of the solution and the gains of the constrained control law
+ADJOINT_SYMBOLS = ['mpcqp_adjoint_default_settings', 'mpcqp_set_adjoint', 'mpcqp_adjoint', 'mpcqp_gains', 'mpcqp_get_adjoint_info']
+
 
 class PolishSettings(C.Structure):
     """mpcqp_polish_settings (include/mpcqp_polish.h)."""
     _fields_ = [('struct_size', C.c_int32), ('polish', C.c_int32), ('delta', C.c_double),
                 ('polish_refine_iter', C.c_int32), ('reserved', C.c_int32)]
+
+
+class AdjointSettings(C.Structure):
+    """mpcqp_adjoint_settings (include/mpcqp_adjoint.h)."""
+    _fields_ = [('struct_size', C.c_int32), ('refine_iter', C.c_int32), ('delta', C.c_double), ('weak_tol', C.c_double),
+                ('extra_iter', C.c_int32), ('reserved', C.c_int32)]
+
+
+class AdjointIO(C.Structure):
+    """mpcqp_adjoint_io (include/mpcqp_adjoint.h): seeds in, gradients out; host or device pointers, None = not given / not wanted."""
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('g_w', C.c_void_p), ('g_u0', C.c_void_p),
+                ('d_x0', C.c_void_p), ('d_uminus1', C.c_void_p), ('d_xref', C.c_void_p), ('d_uref', C.c_void_p),
+                ('d_q', C.c_void_p), ('d_l', C.c_void_p), ('d_u', C.c_void_p)]
 
 
 class Settings(C.Structure):
@@ -161,6 +177,15 @@ def load():
         L.mpcqp_mpc_loop_tv.argtypes = [H, C.c_int, C.POINTER(Loop), C.POINTER(ModelTraj)]
         for name in MODEL_SYMBOLS:
             getattr(L, name).restype = C.c_int
+    if has_adjoint(L):
+        L.mpcqp_adjoint_default_settings.argtypes = [C.POINTER(AdjointSettings)]
+        L.mpcqp_adjoint_default_settings.restype = None
+        L.mpcqp_set_adjoint.argtypes = [H, C.POINTER(AdjointSettings)]
+        L.mpcqp_adjoint.argtypes = [H, C.POINTER(AdjointIO)]
+        L.mpcqp_gains.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mpcqp_get_adjoint_info.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ADJOINT_SYMBOLS[1:]:
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -175,6 +200,12 @@ def has_model_update(L=None):
     """True if the library exports include/mpcqp_model.h (libmpcqp_hip.so does; the CPU twin does not)."""
     L = L if L is not None else load()
     return all(hasattr(L, name) for name in MODEL_SYMBOLS)
+
+
+def has_adjoint(L=None):
+    """True if the library exports include/mpcqp_adjoint.h (libmpcqp_hip.so does; the CPU twin does not)."""
+    L = L if L is not None else load()
+    return all(hasattr(L, name) for name in ADJOINT_SYMBOLS)
 
 
 def check(rc, what):

@@ -71,6 +71,7 @@ class BatchMPCController:
         # does the device copy of u_{-1} equal self.uminus1_rh?  output() moves the host value on (mpc.py:330) without
         # touching the device; setup()/update() upload it, step()/run() leave the applied input on the device themselves
         self._um1_on_device = False
+        self.solve_count = 0                      # solves launched so far (pympc_amd.torch_layer: has the solution moved on since a forward?)
 
     def setup(self, solve=True):
         self.x0_rh = self.x0.copy()
@@ -131,11 +132,12 @@ class BatchMPCController:
 
     def solve(self):
         self.prob.solve_async()
+        self.solve_count += 1
         self._u_last = None
 
-    def step(self, x, u=None, xref=None):
+    def step(self, x, u=None, xref=None, out=None):
         """``u = K(x, u_{-1})``: ``update(x, u, xref)`` followed by ``output()`` in one library call
-        (MPCController.__controller_function__, mpc.py:377-384)."""
+        (MPCController.__controller_function__, mpc.py:377-384).  ``out``: an array or torch device tensor [B,nu] to write the inputs into."""
         self.x0_rh = x
         if u is not None:
             self.uminus1_rh = u
@@ -143,7 +145,8 @@ class BatchMPCController:
             self.xref = xref
         if u is None and not self._um1_on_device:
             u = self.uminus1_rh                   # update(x, u=None) uses the input of the last output() (mpc.py:330,357-359)
-        uMPC = self.prob.mpc_step(x, u, xref)
+        uMPC = self.prob.mpc_step(x, u, xref, out=out)
+        self.solve_count += 1
         self.uminus1_rh = uMPC
         self._um1_on_device = True                # mpcqp_mpc_step stored it as the next u_{-1}
         self._u_last = None
@@ -164,6 +167,7 @@ class BatchMPCController:
         est = None
         if estimator is not None:
             est = dict(C=estimator.C, L=estimator.L, x_true=estimator.x_true, v=getattr(estimator, 'v', None))
+        self.solve_count += int(nsteps)
         out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=est, model_traj=model_traj)
         if model_traj is not None:
             last = (int(nsteps) - 1) // int(model_traj[2])
@@ -185,6 +189,25 @@ class BatchMPCController:
         self.uminus1_rh = ut[-1].copy()
         self._um1_on_device = True
         self._u_last = None
+        return res
+
+    def gains(self, like=None):
+        """Local gains of the constrained control law of every instance at its last solve (mpcqp_gains, include/mpcqp_adjoint.h):
+        ``dict(K_x0 [B,nu,nx], K_um1 [B,nu,nu], K_xref [B,nu,rows*nx], K_uref [B,nu,nu], n_weak [B], status [B])`` -- the Jacobians of u_0
+        for the active set the iterate implies; the key names follow ``pympc_amd.unconstrained``.  ``like``: a torch device tensor to get
+        device tensors back.  ``n_weak > 0``: a kink of the law, one-sided gains; ``status`` 1 computed, 0 not solved (zeros), -1 broken
+        factorization (zeros)."""
+        g = self.prob.gains(like=like)
+        _, n_weak, status = self.prob.adjoint_info()
+        return dict(K_x0=g['x0'], K_um1=g['uminus1'], K_xref=g['xref'], K_uref=g['uref'], n_weak=n_weak, status=status)
+
+    def adjoint(self, g_u0=None, g_w=None):
+        """Vector-Jacobian products of the last solve (mpcqp_adjoint): for ``g_u0`` [B,nu] = dL/du_0 and / or ``g_w`` [B,n] = dL/dw returns
+        ``dict(x0 [B,nx], uminus1 [B,nu], xref [B,rows*nx], uref [B,nu], n_weak [B], status [B])`` = dL/d(x0, u_{-1}, xref, uref).  numpy in,
+        numpy out; torch device tensors in, device tensors out."""
+        res = self.prob.adjoint(g_w=g_w, g_u0=g_u0)
+        _, n_weak, status = self.prob.adjoint_info()
+        res.update(n_weak=n_weak, status=status)
         return res
 
     def status(self):

@@ -312,6 +312,20 @@ class MPCController:
             gs = self._gain_solver = GainSolver(self.nx, self.nu, self.Np, self.Nc, tol=tol)      # (kept: a second call allocates nothing)
         return unconstrained_gains(d(self.Ad), d(self.Bd), self.Np, self.Nc, Qx=d(self.Qx), QxN=d(self.QxN), Qu=d(self.Qu), QDu=d(self.QDu), tol=tol, solver=gs)
 
+    def gains(self):
+        """Local gains of the CONSTRAINED control law at the last solve: ``dict(K_x0 [nu, nx], K_um1 [nu, nu], K_xref [nu, rows*nx],
+        K_uref [nu, nu], n_weak, status)`` -- du_0/dx0, du_0/du_{-1}, du_0/dxref, du_0/duref of the active set the iterate implies
+        (mpcqp_gains, include/mpcqp_adjoint.h: one factorization on the device, nu adjoint solves).  With no inequality active they are the
+        first nu rows of ``unconstrained_gains()``.  ``n_weak > 0``: the state sits on a kink of the piecewise affine law and the gains
+        are one-sided; ``status`` 1 computed, 0 the last solve did not end 'solved' (zeros).  Solve tightly, or with ``polish=True``, where
+        the active set must be the true one.  An addition to the reference's class."""
+        bp = getattr(self.prob, 'batch_problem', None)
+        if bp is None or not hasattr(bp, 'gains'):
+            raise NotImplementedError('gains() needs the device solver behind prob (pympc_amd.solver.DeviceProblem)')
+        g = bp.gains()
+        _, n_weak, status = bp.adjoint_info()
+        return dict(K_x0=g['x0'][0], K_um1=g['uminus1'][0], K_xref=g['xref'][0], K_uref=g['uref'][0], n_weak=int(n_weak[0]), status=int(status[0]))
+
     # ------------------------------------------------------------------------------------
     # q, l, u, J_CNST are public attributes of the reference (mpc.py:598-606).  The device solver rebuilds them itself from
     # (x0, u_{-1}, xref), so after update() the host copies are refreshed only when somebody reads them.

@@ -44,6 +44,7 @@
 #include "../../include/mpcqp.h"
 #include "../../include/mpcqp_polish.h"
 #include "../../include/mpcqp_model.h"
+#include "../../include/mpcqp_adjoint.h"
 
 #include "mpcqp_defs.h"
 
@@ -81,6 +82,7 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #include "mpcqp_kernels.h"
 #include "mpcqp_latw_check.h"
 #include "mpcqp_polish.h"
+#include "mpcqp_adjoint.h"
 #include "mpcqp_csc.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -136,6 +138,10 @@ struct mpcqp_handle {
     int *fown_dev; unsigned *nshared_dev;   // mpcqp_share_factor: [batch] factor slot per instance (P.fown points here while sharing is on); how many share
     mpcqp_polish_settings pol;           // mpcqp_set_polish (include/mpcqp_polish.h)
     PolishArgs pq; Lay pol_lay; size_t smem_polish;   // the polish's buffers (pq.status null until first use), layout and LDS
+    mpcqp_adjoint_settings adj;          // mpcqp_set_adjoint (include/mpcqp_adjoint.h)
+    AdjointArgs aq; size_t smem_adjoint; // the adjoint's buffers (aq.status null until first use) and LDS
+    double *adj_gw, *adj_gu0;            // staging of the caller's seeds [batch][n], [batch][nu]
+    bool has_solve;                      // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
 
 extern "C" void mpcqp_default_settings(mpcqp_settings *s) {
@@ -223,6 +229,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     HIPCHK(hipSetDevice(device));
     mpcqp_handle *h = new mpcqp_handle();
     mpcqp_polish_default_settings(&h->pol);
+    mpcqp_adjoint_default_settings(&h->adj);
     h->device = device; h->batch = batch; h->is_setup = false; h->u0_dev = nullptr; h->run_buf = nullptr; h->run_bytes = 0; h->perm_dev = nullptr; h->vcur_dev = nullptr; h->vdone_dev = nullptr; h->vqueue_dev = nullptr; h->qperm_dev = nullptr; h->qperm_set = false; h->solves_since_balance = 0; h->auto_balance = 1; h->ncu = 0; h->loop_parts = 0;
     h->profiling = false; h->run_ms = 0.0; h->run_launches = 0; h->ev_count = 0; h->nevents = 0; h->stream = nullptr; h->own_stream = false;
     h->warm_x_pending = false;
@@ -465,6 +472,7 @@ static int set_smem(K kernel, size_t bytes) {
 
 static int step_upload(mpcqp_handle *h, const double *x0, const double *um1, const double *xref, int xref_rows) {
     const Lay &L = h->L;
+    h->has_solve = false;                           // (the bounds and the linear cost no longer belong to the iterate: mpcqp_adjoint waits for the next solve)
     if (x0 && put(h, h->P.step, L.step_sz, 0, x0, L.nx)) return MPCQP_ERR_HIP;
     if (um1 && put(h, h->P.step, L.step_sz, L.nx, um1, L.nu)) return MPCQP_ERR_HIP;
     if (xref) {
@@ -481,6 +489,7 @@ static int share_factor_async(mpcqp_handle *h);
 static int launch_setup(mpcqp_handle *h, bool keep = false) {
     const Lay &L = h->L;
     h->P.fown = nullptr;                            // (every instance factors into its own slot: sharing is off until mpcqp_share_factor is asked again)
+    h->has_solve = false;                           // (a cold start or a new model: nothing to differentiate until the next solve, include/mpcqp_adjoint.h)
     if (flush_puts(h)) return MPCQP_ERR_HIP;
     const size_t lean = sizeof(double) * (size_t)(smem_common_doubles(L) - L.tsz);      // (the work area T is carved last and not touched by k_setup)
     const size_t de = sizeof(double) * (size_t)(L.n + L.m);
@@ -593,6 +602,7 @@ extern "C" int mpcqp_update_vectors(mpcqp_handle *h, const double *q, const doub
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_update_vectors before setup");
     if ((l == nullptr) != (u == nullptr)) return fail(MPCQP_ERR_ARG, "mpcqp_update_vectors: give l and u together (the equality rows l[:nx] == u[:nx] carry x0)");
     HIPCHK(hipSetDevice(h->device));
+    h->has_solve = false;                           // (as in step_upload)
     if (!h->L.raw) {
         // entering raw mode: the vectors that are NOT given now must keep describing the current problem, so the
         // tables behind them are materialised once from the controller data (q from (xref, uref, u_{-1}); du0 from u_{-1})
@@ -825,6 +835,7 @@ static int launch_run(mpcqp_handle *h, RunArgs R, int plain_iters) {
     const Lay &L = h->L; const mpcqp_settings &S = h->S;
     R.plain = plain_iters > 0;
     R.warm_x = (h->warm_x_pending && R.part != 2 && R.part != 3) ? 1 : 0;
+    if (R.part != 3) h->has_solve = true;
     if (R.part == 0 || R.part == 2) h->warm_x_pending = false;      // (a two-launch solve begins in its first launch only; mpcqp_refactor, part 3, is not a solve)
     R.max_iter = R.plain ? plain_iters : S.max_iter;
     R.chk = R.plain ? 0 : S.check_termination;
@@ -1057,6 +1068,141 @@ static int get(mpcqp_handle *h, void *dst, const void *src, size_t bytes) {
     return 0;
 }
 
+// ---- adjoint derivatives (include/mpcqp_adjoint.h, mpcqp_adjoint.h) ------------------------------------------------------------
+extern "C" void mpcqp_adjoint_default_settings(mpcqp_adjoint_settings *s) {
+    if (!s) return;
+    memset(s, 0, sizeof(*s));
+    s->struct_size = (int32_t)sizeof(mpcqp_adjoint_settings); s->refine_iter = 3; s->delta = 1e-6; s->weak_tol = 1e-6; s->extra_iter = 12;
+}
+extern "C" int mpcqp_set_adjoint(mpcqp_handle *h, const mpcqp_adjoint_settings *s) {
+    if (!h || !s) return fail(MPCQP_ERR_ARG, "null argument");
+    if (s->struct_size != (int32_t)sizeof(mpcqp_adjoint_settings)) return fail(MPCQP_ERR_ARG, "mpcqp_set_adjoint: struct_size is not sizeof(mpcqp_adjoint_settings) (take the struct from mpcqp_adjoint_default_settings)");
+    if (!(s->delta > 0.0) || !(s->delta < 1e30) || s->refine_iter < 0 || !(s->weak_tol >= 0.0) || s->extra_iter < 0)
+        return fail(MPCQP_ERR_ARG, "mpcqp_set_adjoint: delta > 0, refine_iter >= 0, weak_tol >= 0, extra_iter >= 0");
+    h->adj = *s;
+    return MPCQP_OK;
+}
+// The adjoint's buffers, on first use: the factor of K_pol and its metric, r_w / r_y and the sweep vectors, the seed, the active set, the
+// border and workspace of the factorization, the staged seeds, the outputs for up to nu seeds, the three info vectors.
+static int adjoint_alloc(mpcqp_handle *h) {
+    if (h->aq.status) return MPCQP_OK;
+    const Lay G = polish_layout(h->L);
+    const size_t smem = sizeof(double) * (size_t)smem_common_doubles(G);
+    if (smem > 160 * 1024) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_adjoint: problem too large for one workgroup's LDS");
+    AdjointArgs Q; memset(&Q, 0, sizeof(Q));
+    const size_t B = (size_t)h->batch, S = (size_t)G.nu;
+    Q.fsz = polish_factor_doubles(G);
+    int rc = 0;
+    rc |= dalloc(h, &Q.F, B * (size_t)Q.fsz);
+    rc |= dalloc(h, &Q.om, B * G.m); rc |= dalloc(h, &Q.s, B * G.n);
+    const size_t C = ADJOINT_COLS;      // (the vectors of a seed in progress: one per column of a solve)
+    rc |= dalloc(h, &Q.x, B * C * G.n); rc |= dalloc(h, &Q.y, B * C * G.m); rc |= dalloc(h, &Q.g, B * C * G.n);
+    rc |= dalloc(h, &Q.r, B * C * G.n); rc |= dalloc(h, &Q.d, B * C * G.n); rc |= dalloc(h, &Q.e, B * C * G.n); rc |= dalloc(h, &Q.dd, B * C * G.n);
+    rc |= dalloc(h, &Q.act, B * G.m); rc |= dalloc(h, &Q.gt, B * C * G.m);
+    if (G.border) { rc |= dalloc(h, &Q.Bb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &Q.Zb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &Q.Sig, B * (size_t)G.nu * G.nu); }
+    if (G.NB == 128) rc |= dalloc(h, &Q.gws, B * (size_t)HugeFmt::GWS);
+    rc |= dalloc(h, &h->adj_gw, B * G.n); rc |= dalloc(h, &h->adj_gu0, B * G.nu);
+    rc |= dalloc(h, &Q.ox0, B * S * G.nx); rc |= dalloc(h, &Q.oum1, B * S * G.nu); rc |= dalloc(h, &Q.ouref, B * S * G.nu);
+    rc |= dalloc(h, &Q.oxref, B * S * (size_t)G.N * G.nx);
+    rc |= dalloc(h, &Q.oq, B * G.n); rc |= dalloc(h, &Q.ol, B * G.m); rc |= dalloc(h, &Q.ou, B * G.m);
+    int *status = nullptr;
+    rc |= dalloc(h, &Q.nact, B); rc |= dalloc(h, &Q.nweak, B); rc |= dalloc(h, &status, B);
+    if (rc) return MPCQP_ERR_HIP;      // (what was allocated stays in h->allocs: freed by mpcqp_destroy)
+    Q.status = status;
+    h->aq = Q; h->smem_adjoint = smem;
+    return MPCQP_OK;
+}
+// One launch of k_adjoint: nseeds seeds per instance against one factorization (gw / gu0: the staged seeds of mpcqp_adjoint; both null: the
+// unit seeds of mpcqp_gains); raw: the d_q, d_l, d_u outputs are wanted.
+static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const double *gu0, bool raw_out) {
+    if (flush_puts(h)) return MPCQP_ERR_HIP;
+    AdjointArgs Q = h->aq;
+    Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
+    Q.nseeds = nseeds; Q.gw = gw; Q.gu0 = gu0; Q.chain = h->L.raw ? 0 : 1;
+    if (!raw_out) { Q.oq = nullptr; Q.ol = nullptr; Q.ou = nullptr; }
+    Ptrs P = h->P; P.perm = nullptr; P.fown = nullptr;      // (workgroup b = instance b; the adjoint factors into its own buffers)
+    Lay G = polish_layout(h->L);                            // (the handle's Lay changes with raw-vector mode and the reference shape)
+    // Several seeds against stages of at most 32 go four to a solve (kkt_core_cols): the work area then holds four row vectors and four stage-major
+    // vectors, these two doubles further apart than their length so that the four lanes of a row position do not all meet in one LDS bank.  Where that does
+    // not fit a workgroup's LDS the kernel loops over the seeds one at a time.
+    size_t smem = h->smem_adjoint;
+    Q.ncol = 1; Q.cs = 0;
+    if (nseeds > 1 && G.NB <= 32) {
+        const int cs = G.N * G.NB + 2;
+        Lay W = G; W.tsz = std::max(G.tsz, ADJOINT_COLS * (G.m + cs));      // (the row scratch of the passes around the solves, then the columns)
+        const size_t wide = sizeof(double) * (size_t)smem_common_doubles(W);
+        if (wide <= 160 * 1024) { G = W; smem = wide; Q.ncol = ADJOINT_COLS; Q.cs = cs; }
+    }
+    DISPATCH_NB(G.NB, {
+        if (set_smem(k_adjoint<NB>, smem)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_adjoint<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, P, Q);
+    });
+    HIPCHK(hipGetLastError());
+    return MPCQP_OK;
+}
+static int adjoint_ready(mpcqp_handle *h, const char *what, bool chain) {
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, std::string(what) + " before mpcqp_setup");
+    if (!h->has_solve) return fail(MPCQP_ERR_STATE, std::string(what) + ": no solve since the last setup, update, model update or warm start: there is no solution of the current problem to differentiate");
+    if (chain && h->L.raw) return fail(MPCQP_ERR_STATE, std::string(what) + ": the handle works from raw q, l, u (mpcqp_setup_qp / mpcqp_update_vectors), where only d_q, d_l, d_u are defined");
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_adjoint(mpcqp_handle *h, const mpcqp_adjoint_io *io) {
+    if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
+    if (io->struct_size != (int32_t)sizeof(mpcqp_adjoint_io)) return fail(MPCQP_ERR_ARG, "mpcqp_adjoint: struct_size is not sizeof(mpcqp_adjoint_io)");
+    if (!io->g_w && !io->g_u0) return fail(MPCQP_ERR_ARG, "mpcqp_adjoint: give g_w, g_u0 or both");
+    if ((io->d_l == nullptr) != (io->d_u == nullptr)) return fail(MPCQP_ERR_ARG, "mpcqp_adjoint: d_l and d_u go together");
+    const bool chain = io->d_x0 || io->d_uminus1 || io->d_xref || io->d_uref;
+    int rc = adjoint_ready(h, "mpcqp_adjoint", chain);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = adjoint_alloc(h))) return rc;
+    const Lay &L = h->L; const size_t B = (size_t)h->batch, db = sizeof(double);
+    if (io->g_w) HIPCHK(hipMemcpyAsync(h->adj_gw, io->g_w, B * L.n * db, hipMemcpyDefault, h->stream));
+    if (io->g_u0) HIPCHK(hipMemcpyAsync(h->adj_gu0, io->g_u0, B * L.nu * db, hipMemcpyDefault, h->stream));
+    if ((rc = launch_adjoint(h, 1, io->g_w ? h->adj_gw : nullptr, io->g_u0 ? h->adj_gu0 : nullptr, io->d_q || io->d_l))) return rc;
+    const AdjointArgs &Q = h->aq;
+    if (get(h, io->d_x0, Q.ox0, B * L.nx * db) || get(h, io->d_uminus1, Q.oum1, B * L.nu * db) || get(h, io->d_uref, Q.ouref, B * L.nu * db) ||
+        get(h, io->d_xref, Q.oxref, B * (size_t)L.xref_rows * L.nx * db) || get(h, io->d_q, Q.oq, B * L.n * db) ||
+        get(h, io->d_l, Q.ol, B * L.m * db) || get(h, io->d_u, Q.ou, B * L.m * db)) return MPCQP_ERR_HIP;
+    const void *all[] = {io->g_w, io->g_u0, io->d_x0, io->d_uminus1, io->d_xref, io->d_uref, io->d_q, io->d_l, io->d_u};
+    bool dev = true;
+    for (const void *q : all) if (q && !is_device_ptr(q)) dev = false;
+    if (!dev) HIPCHK(hipStreamSynchronize(h->stream));      // (device buffers throughout: stream-ordered, no need to wait)
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_gains(mpcqp_handle *h, double *K_x0, double *K_uminus1, double *K_xref, double *K_uref) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    int rc = adjoint_ready(h, "mpcqp_gains", true);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = adjoint_alloc(h))) return rc;
+    const Lay &L = h->L; const size_t B = (size_t)h->batch, db = sizeof(double), S = (size_t)L.nu;
+    if ((rc = launch_adjoint(h, L.nu, nullptr, nullptr, false))) return rc;
+    const AdjointArgs &Q = h->aq;
+    if (get(h, K_x0, Q.ox0, B * S * L.nx * db) || get(h, K_uminus1, Q.oum1, B * S * L.nu * db) || get(h, K_uref, Q.ouref, B * S * L.nu * db) ||
+        get(h, K_xref, Q.oxref, B * S * (size_t)L.xref_rows * L.nx * db)) return MPCQP_ERR_HIP;
+    const void *all[] = {K_x0, K_uminus1, K_xref, K_uref};
+    bool dev = true;
+    for (const void *q : all) if (q && !is_device_ptr(q)) dev = false;
+    if (!dev) HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_get_adjoint_info(mpcqp_handle *h, int32_t *n_active, int32_t *n_weak, int32_t *status) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t bytes = sizeof(int32_t) * (size_t)h->batch;
+    int32_t *dst[3] = {n_active, n_weak, status};
+    const int *src[3] = {h->aq.nact, h->aq.nweak, h->aq.status};
+    for (int i = 0; i < 3; ++i) {
+        if (!dst[i]) continue;
+        if (h->aq.status) HIPCHK(hipMemcpyAsync(dst[i], src[i], bytes, hipMemcpyDefault, h->stream));
+        else if (is_device_ptr(dst[i])) HIPCHK(hipMemsetAsync(dst[i], 0, bytes, h->stream));      // (no adjoint call yet)
+        else memset(dst[i], 0, bytes);
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
 // what mpcqp_mpc_loop refuses (before anything is launched or changed)
 static int loop_check(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
     if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop: bad argument");
@@ -1192,6 +1338,7 @@ extern "C" int mpcqp_eq_solve(mpcqp_handle *h, int sweeps, int cold, double tol,
     });
     HIPCHK(hipGetLastError());
     if (h->pq.status) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * (size_t)h->batch, h->stream));      // (the polish setting is ignored here)
+    h->has_solve = true;
     if (res) HIPCHK(hipMemcpyAsync(res, dres, sizeof(double) * 5 * (size_t)h->batch, hipMemcpyDefault, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
@@ -1498,6 +1645,7 @@ extern "C" int mpcqp_warm_start(mpcqp_handle *h, const double *x, const double *
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "warm_start before setup");
     HIPCHK(hipSetDevice(h->device));
     size_t B = (size_t)h->batch;
+    if (x || y) h->has_solve = false;               // (the iterate mpcqp_adjoint takes its active set from is replaced)
     if (x) { HIPCHK(hipMemcpyAsync(h->P.x, x, B * h->L.n * sizeof(double), hipMemcpyDefault, h->stream)); h->warm_x_pending = true; }
     if (y) { HIPCHK(hipMemcpyAsync(h->P.y, y, B * h->L.m * sizeof(double), hipMemcpyDefault, h->stream)); }
     return MPCQP_OK;

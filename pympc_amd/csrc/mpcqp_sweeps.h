@@ -24,6 +24,13 @@ __device__ __forceinline__ int vec_lane_offset(int lane) { return 4 * ((lane >> 
 // A stage vector is replicated over the four lanes j of a row position; one of them writes it back -- or, inside the sweeps,
 // all four (the same value to the same address, no exec-mask juggling and no extra basic block per stage).
 __device__ __forceinline__ bool vec_lane_writer(int lane) { return (lane & 3) == 0; }
+// Several right-hand sides in one solve (MC, used by k_adjoint): where the single-vector solve replicates its stage vector over the four
+// lanes j -- three of the four columns of every matrix instruction repeat the first -- lane j works on a vector of its own, column j of
+// the work area at Tc + j * cs.  The factor fragments, the rotations and everything per element are the same for all j; what differs is the
+// lane's base address, that every lane stores, and the one broadcast of an element (so_element_col).  Four solves for the
+// matrix-instruction chain of one.
+template <bool MC>
+__device__ __forceinline__ int vec_col_offset(int lane, int cs) { if constexpr (MC) return (lane & 3) * cs; else return 0; }
 
 // rotate every 16-lane row by 4*sft lanes: lane (k, b, j) receives the value of lane (k, (b+sft)%4, j)
 // (`old` operand of the DPP move: with row_ror every lane receives a value, so what the destination held before is
@@ -112,11 +119,12 @@ __device__ __forceinline__ int logical_wave() {
 // Forward elimination of one half-chain by ONE wave: for i = 1..nsteps, k = first + dir*i:   Tc[k] <- Tc[k] + Fwd(k) * Tc[k - dir]
 // (Fwd(k) = the forward-matrix slot of stage k, which holds the negated factor block).  The factor fragments of the next DEPTH
 // stages are prefetched into a register ring; the running vector ping-pongs between two register sets (no copies between MFMAs).
-template <int NB>
-__device__ __forceinline__ void chain_sweep(const int first, const int dir, const int nsteps, const int fstage, const double *F, double *Tc) {
+template <int NB, bool MC = false>
+__device__ __forceinline__ void chain_sweep(const int first, const int dir, const int nsteps, const int fstage, const double *F, double *Tc, const int cs = 0) {
     constexpr int NBLK = NB / 16, NF = SweepCfg<NB>::NF, DEPTH = SweepCfg<NB>::DEPTH;
     const int lane = opaque_lane(threadIdx.x & 63);
     double *tb = Tc + vec_lane_offset(lane);
+    if constexpr (MC) tb += vec_col_offset<MC>(lane, cs);
     auto stage_of = [&](int i) { return first + dir * i; };
     auto frag_of = [&](int i) { return F + (size_t)stage_of(i) * fstage; };
     // The group loop below is branch-free on purpose: with conditionals around the refills the compiler can no longer
@@ -240,17 +248,25 @@ __device__ __forceinline__ double so_element(const double *v, int E) {
     if constexpr (NB == 16) return lane_bcast(v[0], src);
     else { const double a0 = lane_bcast(v[0], src), a1 = lane_bcast(v[1], src); return (E >> 4) ? a1 : a0; }
 }
+// the same per column: lane (k, b, j) receives element E of column j
+template <int NB>
+__device__ __forceinline__ double so_element_col(const double *v, int E, int lane) {
+    const int l = E & 15, addr = 4 * (16 * (l & 3) + 4 * (l >> 2) + (lane & 3));
+    if constexpr (NB == 16) return lane_permute(v[0], addr);
+    else { const double a0 = lane_permute(v[0], addr), a1 = lane_permute(v[1], addr); return (E >> 4) ? a1 : a0; }
+}
 // t = -K_{k,nbr} v   (UP: nbr = k-1, uses G; else nbr = k+1, uses G').  sc = om of stage max(k,nbr) on x lanes (1 elsewhere).
-template <int NB, bool UP>
+template <int NB, bool UP, bool MC = false>
 __device__ __forceinline__ void so_offdiag(const CoreArgs &a, const SoLane<NB> &q, const d4 *Gf, int k, const double *v,
-                                           const double *sc, double wd, double *t) {
+                                           const double *sc, double wd, double *t, const int lane = 0) {
     constexpr int NBLK = NB / 16;
     double in[NBLK], out[NBLK];
 #pragma unroll
     for (int bi = 0; bi < NBLK; ++bi) { in[bi] = UP ? v[bi] : sc[bi] * v[bi]; out[bi] = 0.0; }
     frag_matvec<NB>(Gf, in, out);
     const int Esrc = UP ? a.nx + a.nu - 1 : a.nx, Edst = UP ? a.nx : a.nx + a.nu - 1;
-    const double cpl = wd * so_element<NB>(v, Esrc);
+    double cpl;
+    if constexpr (MC) cpl = wd * so_element_col<NB>(v, Esrc, lane); else cpl = wd * so_element<NB>(v, Esrc);
     const bool has_u = k < a.NcT;
 #pragma unroll
     for (int bi = 0; bi < NBLK; ++bi) {
@@ -367,11 +383,12 @@ __device__ __forceinline__ void so_expand_finish(SoSlot<NB> &s, const SoLaneK &c
     s.S[0] = sel(s.S[0], t.s0);
     if constexpr (NB == 32) { s.S[3] = sel(s.S[3], t.s1); s.S[2] = d4{t.tr[0], t.tr[1], t.tr[2], t.tr[3]}; }
 }
-template <int NB, bool SOLVE, bool UP>
-__device__ __forceinline__ void so_sweep(const CoreArgs &a, double *Tc, const int first, const int dir, const int ibegin, const int nsteps) {
+template <int NB, bool SOLVE, bool UP, bool MC = false>
+__device__ __forceinline__ void so_sweep(const CoreArgs &a, double *Tc, const int first, const int dir, const int ibegin, const int nsteps, const int cs = 0) {
     constexpr int NBLK = NB / 16, DEPTH = SoCfg<NB>::DEPTH;
     const int lane = opaque_lane(threadIdx.x & 63);
     double *tb = Tc + vec_lane_offset(lane);
+    if constexpr (MC) tb += vec_col_offset<MC>(lane, cs);
     const SoLaneK lc = so_lane_consts<NB, UP>(lane);
     d4 Gf[SoCfg<NB>::NF];
     frag_load<NB>(a.G + (UP ? 0 : NB * NB), lane, Gf);
@@ -414,7 +431,8 @@ __device__ __forceinline__ void so_sweep(const CoreArgs &a, double *Tc, const in
                 q[bi] = __builtin_amdgcn_mfma_f64_4x4x4f64(g[3], r3, q[bi], 0, 0, 0);
             }
         }
-        const double nsrc = so_element<NB>(run, Esrc);
+        double nsrc;
+        if constexpr (MC) nsrc = so_element_col<NB>(run, Esrc, lane); else nsrc = so_element<NB>(run, Esrc);
 #pragma unroll
         for (int bi = 0; bi < NBLK; ++bi) { base[bi] = SOLVE ? fma(slot.tab[bi][1], nsrc, own[bi]) : slot.tab[bi][1] * nsrc; pin_here(base[bi]); }
         __builtin_amdgcn_sched_barrier(0);
@@ -460,18 +478,19 @@ __device__ __forceinline__ void so_sweep(const CoreArgs &a, double *Tc, const in
     }
 }
 
-template <int NB>
-__device__ __forceinline__ void kkt_core_so(const CoreArgs &a, double *Tc) {
+template <int NB, bool MC = false>
+__device__ __forceinline__ void kkt_core_so(const CoreArgs &a, double *Tc, const int cs = 0) {
     constexpr int NBLK = NB / 16, NF = SoCfg<NB>::NF;
     const int N = a.N, mid = N / 2, wv = logical_wave(), lane = opaque_lane(threadIdx.x & 63);
     TICK_START
-    if (wv == 0) so_sweep<NB, true, true>(a, Tc, 0, +1, 0, mid - 1);                     // w_0 .. w_{mid-1}
-    else if (wv == 1) so_sweep<NB, true, false>(a, Tc, N - 1, -1, 0, N - 2 - mid);       // w_{N-1} .. w_{mid+1}
+    if (wv == 0) so_sweep<NB, true, true, MC>(a, Tc, 0, +1, 0, mid - 1, cs);                     // w_0 .. w_{mid-1}
+    else if (wv == 1) so_sweep<NB, true, false, MC>(a, Tc, N - 1, -1, 0, N - 2 - mid, cs);       // w_{N-1} .. w_{mid+1}
     __syncthreads();
     TICK(1)
     if (wv == 0) {                                                                       // the middle stage sees both halves
         const SoLane<NB> q = so_lane<NB>(a, lane);
         double *tb = Tc + vec_lane_offset(lane);
+        if constexpr (MC) tb += vec_col_offset<MC>(lane, cs);
         SoStep<NB> su, sd;
         so_step_load<NB>(a, q, lane, mid, mid - 1, su);
         so_step_load<NB>(a, q, lane, mid, mid + 1, sd);
@@ -482,19 +501,19 @@ __device__ __forceinline__ void kkt_core_so(const CoreArgs &a, double *Tc) {
         double scu[NBLK], scd[NBLK], wdu, wdd;
         so_step_fix<NB>(a, q, mid, mid - 1, su, scu, wdu);
         so_step_fix<NB>(a, q, mid, mid + 1, sd, scd, wdd);
-        so_offdiag<NB, true>(a, q, Gf, mid, vu, scu, wdu, tu);
+        so_offdiag<NB, true, MC>(a, q, Gf, mid, vu, scu, wdu, tu, lane);
         frag_load<NB>(a.G + NB * NB, lane, Gf);
-        so_offdiag<NB, false>(a, q, Gf, mid, vd, scd, wdd, td);
+        so_offdiag<NB, false, MC>(a, q, Gf, mid, vd, scd, wdd, td, lane);
         so_expand<NB>(su.S, lane, Sf);
 #pragma unroll
         for (int bi = 0; bi < NBLK; ++bi) { tu[bi] += own[bi] + td[bi]; out[bi] = 0.0; }
         frag_matvec<NB>(Sf, tu, out);
-        vec_store<NB>(tb, mid, out, vec_lane_writer(lane));
+        vec_store<NB>(tb, mid, out, MC || vec_lane_writer(lane));
     }
     __syncthreads();
     TICK(2)
-    if (wv == 0) so_sweep<NB, false, false>(a, Tc, mid, -1, 1, mid);                     // x_{mid-1} .. x_0       (neighbour below)
-    else if (wv == 1) so_sweep<NB, false, true>(a, Tc, mid, +1, 1, N - 1 - mid);         // x_{mid+1} .. x_{N-1}   (neighbour above)
+    if (wv == 0) so_sweep<NB, false, false, MC>(a, Tc, mid, -1, 1, mid, cs);                     // x_{mid-1} .. x_0       (neighbour below)
+    else if (wv == 1) so_sweep<NB, false, true, MC>(a, Tc, mid, +1, 1, N - 1 - mid, cs);         // x_{mid+1} .. x_{N-1}   (neighbour above)
     __syncthreads();
     TICK(3)
 }
@@ -502,18 +521,19 @@ __device__ __forceinline__ void kkt_core_so(const CoreArgs &a, double *Tc) {
 // Forward-matrix format: forward elimination from the forward matrices (chain_sweep), the middle stage, then back substitution
 //     x_k = S_k^-1 ( yh_k - K_{k,nbr} x_nbr )
 // outwards from the middle with the off-diagonal blocks applied matrix-free -- S^-1 is read once, the forward matrices once.
-template <int NB>
-__device__ __forceinline__ void kkt_core_fwd(const CoreArgs &a, double *Tc) {
+template <int NB, bool MC = false>
+__device__ __forceinline__ void kkt_core_fwd(const CoreArgs &a, double *Tc, const int cs = 0) {
     constexpr int NBLK = NB / 16, NF = SoCfg<NB>::NF;
     const int N = a.N, fstage = a.fstage, mid = N / 2, wv = logical_wave(), lane = opaque_lane(threadIdx.x & 63);
     const double *F = a.F;
     TICK_START
-    if (wv == 0) chain_sweep<NB>(0, +1, mid - 1, fstage, F, Tc);                          // yh_1 .. yh_{mid-1}
-    else if (wv == 1) chain_sweep<NB>(N - 1, -1, N - 2 - mid, fstage, F, Tc);             // yh_{N-2} .. yh_{mid+1}
+    if (wv == 0) chain_sweep<NB, MC>(0, +1, mid - 1, fstage, F, Tc, cs);                          // yh_1 .. yh_{mid-1}
+    else if (wv == 1) chain_sweep<NB, MC>(N - 1, -1, N - 2 - mid, fstage, F, Tc, cs);             // yh_{N-2} .. yh_{mid+1}
     __syncthreads();
     TICK(1)
     if (wv == 0) {                                   // yh_mid = b_mid - Mh_mid yh_{mid-1} - Mt_mid yh_{mid+1};  x_mid = S_mid^-1 yh_mid
         double *tb = Tc + vec_lane_offset(lane);
+        if constexpr (MC) tb += vec_col_offset<MC>(lane, cs);
         d4 A0[NF], A2[NF], Am[SoCfg<NB>::NS], Sf[NF];
         frag_load<NB>(F + (size_t)mid * fstage, lane, A0);
         frag_load<NB>(F, lane, A2);                  // the middle's second forward matrix (kept in stage 0's slot)
@@ -526,12 +546,12 @@ __device__ __forceinline__ void kkt_core_fwd(const CoreArgs &a, double *Tc) {
 #pragma unroll
         for (int bi = 0; bi < NBLK; ++bi) out[bi] = 0.0;
         frag_matvec<NB>(Sf, acc, out);
-        vec_store<NB>(tb, mid, out, vec_lane_writer(lane));
+        vec_store<NB>(tb, mid, out, MC || vec_lane_writer(lane));
     }
     __syncthreads();
     TICK(2)
-    if (wv == 0) so_sweep<NB, true, false>(a, Tc, mid, -1, 1, mid);                        // x_{mid-1} .. x_0       (neighbour below)
-    else if (wv == 1) so_sweep<NB, true, true>(a, Tc, mid, +1, 1, N - 1 - mid);            // x_{mid+1} .. x_{N-1}   (neighbour above)
+    if (wv == 0) so_sweep<NB, true, false, MC>(a, Tc, mid, -1, 1, mid, cs);                        // x_{mid-1} .. x_0       (neighbour below)
+    else if (wv == 1) so_sweep<NB, true, true, MC>(a, Tc, mid, +1, 1, N - 1 - mid, cs);            // x_{mid+1} .. x_{N-1}   (neighbour above)
     __syncthreads();
     TICK(3)
 }
@@ -547,6 +567,13 @@ __device__ __forceinline__ void kkt_core(const CoreArgs &a, double *Tc) {
     if constexpr (NB == 16 && GROUPABLE) { if (a.grp > 1) { kkt_core_group(a, Tc); return; } }
     if constexpr (FactorFmt<NB>::SONLY) kkt_core_so<NB>(a, Tc);
     else kkt_core_fwd<NB>(a, Tc);                 // (each of them ends with a barrier)
+}
+// Four right-hand sides at once, columns cs doubles apart (stages of at most 32, never grouped: the adjoint's layout)
+template <int NB>
+__device__ __forceinline__ void kkt_core_cols(const CoreArgs &a, double *Tc, const int cs) {
+    static_assert(NB == 16 || NB == 32, "the wide formats keep their stage vectors in another layout");
+    if constexpr (FactorFmt<NB>::SONLY) kkt_core_so<NB, true>(a, Tc, cs);
+    else kkt_core_fwd<NB, true>(a, Tc, cs);
 }
 template <> __device__ __forceinline__ void kkt_core<64, false>(const CoreArgs &, double *);      // mpcqp_wide.h (stages wider than 32)
 template <> __device__ __forceinline__ void kkt_core<128, false>(const CoreArgs &, double *);     // mpcqp_huge.h (stages wider than 64)

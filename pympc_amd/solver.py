@@ -37,6 +37,20 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def _prep_out(a, shape, name):
+    """An array / tensor the library writes ``shape`` doubles into: it must be float64, C-contiguous and hold exactly that many (the C ABI
+    carries no sizes); returned as it is."""
+    size = int(np.prod(shape))
+    if hasattr(a, 'data_ptr'):
+        import torch
+        ok = a.dtype == torch.float64 and a.is_contiguous() and a.numel() == size
+    else:
+        ok = type(a) is np.ndarray and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable and a.size == size
+    if not ok:
+        raise ValueError('%s must be a writable C-contiguous float64 array or tensor of %d values (shape %s)' % (name, size, (shape,)))
+    return a
+
+
 def _prep(a, shape, name):
     """float64, C-contiguous, exact shape; returns an object that keeps the memory alive."""
     if a is None:
@@ -228,6 +242,93 @@ class BatchProblem:
             _lib.check(self._L.mpcqp_get_polish_info(self._h, _ptr(out)), 'mpcqp_get_polish_info')
         return out
 
+    # -- adjoint derivatives (include/mpcqp_adjoint.h) --------------------------------------------
+    _adjoint = None            # mpcqp_adjoint_settings of the handle, once changed
+
+    def _need_adjoint(self):
+        if not _lib.has_adjoint(self._L):
+            raise NotImplementedError('this build of the solver library has no adjoint derivatives (include/mpcqp_adjoint.h)')
+
+    def set_adjoint(self, **kw):
+        """The adjoint's own delta / refine_iter / extra_iter / weak_tol (mpcqp_set_adjoint); the polish settings are separate."""
+        self._need_adjoint()
+        if self._adjoint is None:
+            self._adjoint = _lib.AdjointSettings()
+            self._L.mpcqp_adjoint_default_settings(C.byref(self._adjoint))
+        for k, v in kw.items():
+            if k not in ('delta', 'refine_iter', 'weak_tol', 'extra_iter'):
+                raise TypeError('unknown adjoint setting %r' % k)
+            setattr(self._adjoint, k, v)
+        _lib.check(self._L.mpcqp_set_adjoint(self._h, C.byref(self._adjoint)), 'mpcqp_set_adjoint')
+
+    # rows of the last reference upload the library ACCEPTED (1 or Np+1): the shape d_xref / K_xref come back in.  It sizes the buffers the
+    # library writes into, so it is only ever assigned after the uploading call has returned without an error.
+    _xref_rows_last = 1
+
+    def _out(self, like, shape):
+        """An output array of the kind the inputs are: a torch tensor on ``like``'s device, else numpy."""
+        if like is not None and hasattr(like, 'data_ptr'):
+            import torch
+            return torch.empty(shape, dtype=torch.float64, device=like.device)
+        return np.empty(shape)
+
+    def adjoint(self, g_w=None, g_u0=None, want=('x0', 'uminus1', 'xref', 'uref'), out=None):
+        """Adjoint derivatives of the current solution (mpcqp_adjoint): for the seed ``g_w`` [B, n] = dL/dw and / or ``g_u0`` [B, nu] = dL/du_0
+        returns a dict with the gradients named in ``want`` -- any of 'x0' [B, nx], 'uminus1' [B, nu], 'xref' [B, rows*nx] (shape of the
+        last upload), 'uref' [B, nu], 'q' [B, n], 'l', 'u' [B, m].  Seeds may be numpy arrays or torch device tensors; the results are of the
+        same kind (device tensors: stream-ordered, no wait), or are written into the arrays / tensors given in ``out`` (a dict by the same
+        names).  The gradients are those of the active set the iterate implies; ``adjoint_info()`` reports weakly active rows."""
+        self._need_adjoint()
+        if g_w is None and g_u0 is None:
+            raise ValueError('adjoint: give g_w, g_u0 or both')
+        B = self.batch
+        like = g_w if g_w is not None else g_u0
+        gw = _prep(g_w, (B, self.n), 'g_w') if g_w is not None else None
+        gu = _prep(g_u0, (B, self.nu), 'g_u0') if g_u0 is not None else None
+        shapes = dict(x0=(B, self.nx), uminus1=(B, self.nu), xref=(B, self._xref_rows_last * self.nx), uref=(B, self.nu),
+                      q=(B, self.n), l=(B, self.m), u=(B, self.m))
+        want = list(want)
+        if ('l' in want) != ('u' in want):
+            want += ['l' if 'u' in want else 'u']
+        res = {}
+        io = _lib.AdjointIO()
+        io.struct_size = C.sizeof(_lib.AdjointIO)
+        io.g_w, io.g_u0 = _ptr(gw), _ptr(gu)
+        for k in want:
+            if k not in shapes:
+                raise TypeError('unknown gradient %r' % k)
+            if out is not None and k in out:
+                a = _prep_out(out[k], shapes[k], 'out[%r]' % k)
+            else:
+                a = self._out(like, shapes[k])
+            res[k] = a
+            setattr(io, 'd_' + k, _ptr(a))
+        self._keep = [gw, gu, res]
+        rc = self._L.mpcqp_adjoint(self._h, C.byref(io))
+        _lib.check(rc, 'mpcqp_adjoint')
+        return res
+
+    def gains(self, want=('x0', 'uminus1', 'xref', 'uref'), like=None):
+        """Jacobians of the first input u_0 of the current solution (mpcqp_gains: one factorization, nu seeds): dict with 'x0' [B, nu, nx],
+        'uminus1' [B, nu, nu], 'xref' [B, nu, rows*nx], 'uref' [B, nu, nu] as named in ``want``; numpy, or torch tensors on the device
+        of ``like``."""
+        self._need_adjoint()
+        B, nu = self.batch, self.nu
+        shapes = dict(x0=(B, nu, self.nx), uminus1=(B, nu, nu), xref=(B, nu, self._xref_rows_last * self.nx), uref=(B, nu, nu))
+        res = {k: self._out(like, shapes[k]) for k in want}
+        self._keep = [res]
+        _lib.check(self._L.mpcqp_gains(self._h, *[_ptr(res.get(k)) for k in ('x0', 'uminus1', 'xref', 'uref')]), 'mpcqp_gains')
+        return res
+
+    def adjoint_info(self):
+        """(n_active, n_weak, status) [batch] int32 of the last adjoint() / gains() (mpcqp_get_adjoint_info; synchronises): status 1 computed,
+        0 the instance's solve did not end 'solved', -1 the factorization broke (outputs zero in both cases); n_weak > 0: rows on a bound
+        with a zero multiplier -- the control law has a kink there and the result is a one-sided derivative."""
+        self._need_adjoint()
+        out = [np.zeros(self.batch, dtype=np.int32) for _ in range(3)]
+        _lib.check(self._L.mpcqp_get_adjoint_info(self._h, *[_ptr(o) for o in out]), 'mpcqp_get_adjoint_info')
+        return tuple(out)
+
     def _finish_init(self, stream):
         n, m, fd, nnzL = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
         _lib.check(self._L.mpcqp_get_dims(self._h, C.byref(n), C.byref(m), C.byref(fd), C.byref(nnzL)), 'mpcqp_get_dims')
@@ -268,6 +369,7 @@ class BatchProblem:
         xra = _prep(xref, (B, xref_rows * nx), 'xref')
         self._keep = [arrs, x0a, uma, xra]
         _lib.check(self._L.mpcqp_setup(self._h, C.byref(model), _ptr(x0a), _ptr(uma), _ptr(xra), xref_rows), 'mpcqp_setup')
+        self._xref_rows_last = xref_rows
         _lib.check(self._L.mpcqp_synchronize(self._h), 'mpcqp_synchronize')
         self._keep = []
 
@@ -345,6 +447,8 @@ class BatchProblem:
             c = _prep(xref, (B, rows * nx), 'xref')
         self._keep = [a, b, c]
         _lib.check(self._L.mpcqp_update(self._h, _ptr(a), _ptr(b), _ptr(c), rows), 'mpcqp_update')
+        if xref is not None:
+            self._xref_rows_last = rows
         if any(hasattr(v, 'ctypes') for v in self._keep if v is not None):
             # pageable host memory: the async copy has completed or been staged when the call returns
             pass
@@ -386,6 +490,8 @@ class BatchProblem:
         if out is None:
             out = np.empty((B, nu))
         _lib.check(self._L.mpcqp_mpc_step(self._h, _ptr(a), _ptr(b), _ptr(c), rows, _ptr(out)), 'mpcqp_mpc_step')
+        if xref is not None:
+            self._xref_rows_last = rows
         return out
 
     def step_host(self, x0=None, uminus1=None, xref=None):
@@ -405,6 +511,8 @@ class BatchProblem:
         x, y = np.empty((B, self.n)), np.empty((B, self.m))
         info = (_lib.Info * B)()
         _lib.check(self._L.mpcqp_step_host(self._h, _ptr(a), _ptr(b), _ptr(c), rows, _ptr(x), _ptr(y), C.cast(info, C.c_void_p)), 'mpcqp_step_host')
+        if xref is not None:
+            self._xref_rows_last = rows
         return x, y, info
 
     def _step_host_one(self, x0, uminus1, xref):
@@ -427,6 +535,7 @@ class BatchProblem:
         info = (_lib.Info * 1)()
         a, b, c = self._hin_p
         _lib.check(self._L.mpcqp_step_host(self._h, a, b, c, nxr // nx, cb, C.addressof(cb) + 8 * n, info), 'mpcqp_step_host')
+        self._xref_rows_last = nxr // nx
         buf = np.frombuffer(cb, dtype=np.float64)
         return buf[:n].reshape(1, n), buf[n:].reshape(1, m), info
 
@@ -504,6 +613,8 @@ class BatchProblem:
         if rc == -4:
             raise NotImplementedError(self._L.mpcqp_last_error().decode())
         _lib.check(rc, what)
+        if xref_traj is not None:
+            self._xref_rows_last = int(io.xref_rows)
         self._keep = [keep]                    # (device inputs of a stream-ordered run: alive at least until the next call)
         return tuple(out)
 

@@ -41,8 +41,9 @@ typedef struct {
     double delta;                 /* regularization of the active-set KKT system, > 0 (default 1e-6) */
     double weak_tol;              /* a row counts as weakly active below this, >= 0 (default 1e-6; see mpcqp_get_adjoint_info) */
     int32_t extra_iter;           /* where the last of the refine_iter sweeps still moved the answer the kernel goes on, at most this many
-                                     sweeps more, >= 0 (default 12), until the correction is negligible (1e-12 of r_w, 1e-10 of r_y) or stops
-                                     halving.  0: exactly refine_iter sweeps, the cost of a seed is then bounded by the setting alone */
+                                     sweeps more, >= 0 (default 60), until the correction is negligible (1e-12 of the solution, 1e-10 of r_y) or
+                                     no longer shrinks by a tenth (rows held by a slack variable contract by about 0.5 a sweep and take some
+                                     30).  0: exactly refine_iter sweeps, the cost of a seed is then bounded by the setting alone */
     int32_t reserved;             /* 0 */
 } mpcqp_adjoint_settings;
 
@@ -63,7 +64,7 @@ typedef struct {
                                      with respect to its common value in d_l and 0 in d_u, an inactive row 0 in both */
 } mpcqp_adjoint_io;
 
-/* Defaults: struct_size set, delta = 1e-6, refine_iter = 3, weak_tol = 1e-6, extra_iter = 12.  The adjoint's own settings: mpcqp_set_polish does not
+/* Defaults: struct_size set, delta = 1e-6, refine_iter = 3, weak_tol = 1e-6, extra_iter = 60.  The adjoint's own settings: mpcqp_set_polish does not
  * change them and they do not change polishing. */
 void mpcqp_adjoint_default_settings(mpcqp_adjoint_settings *s);
 /* Any time after mpcqp_create / mpcqp_create_csc.  The adjoint's buffers are allocated on first use. */

@@ -1072,7 +1072,7 @@ static int get(mpcqp_handle *h, void *dst, const void *src, size_t bytes) {
 extern "C" void mpcqp_adjoint_default_settings(mpcqp_adjoint_settings *s) {
     if (!s) return;
     memset(s, 0, sizeof(*s));
-    s->struct_size = (int32_t)sizeof(mpcqp_adjoint_settings); s->refine_iter = 3; s->delta = 1e-6; s->weak_tol = 1e-6; s->extra_iter = 12;
+    s->struct_size = (int32_t)sizeof(mpcqp_adjoint_settings); s->refine_iter = 3; s->delta = 1e-6; s->weak_tol = 1e-6; s->extra_iter = 60;
 }
 extern "C" int mpcqp_set_adjoint(mpcqp_handle *h, const mpcqp_adjoint_settings *s) {
     if (!h || !s) return fail(MPCQP_ERR_ARG, "null argument");

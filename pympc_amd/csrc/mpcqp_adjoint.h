@@ -9,7 +9,8 @@
 //                system (the multiplier sweep of k_eq_solve / k_polish with q = -g and every target 0), each KKT solve refined against K_pol
 //                itself, applied matrix-free, until its correction stalls (polish_kmul: K_pol is conditioned 1e9 .. 1e12).  Where the
 //                last of them still moved the answer (nearly dependent active rows: three sweeps left r_y 2e-6 off on random_5_3_8, 5e-7
-//                on the 200-step cart pole) up to extra_iter more follow, until the correction is negligible or stops shrinking;
+//                on the 200-step cart pole; rows held by a slack variable contract by about 0.5 a sweep) up to extra_iter more follow,
+//                until the correction is negligible or stops shrinking;
 //   results      dL/dq = -r_w, dL/db = r_y, and the chain rule into x0, u_{-1}, xref, uref (build_q / row_bounds read backwards): reductions
 //                over the stage blocks with Qx, QxN, Qu, QDu from the model blob.
 // mpcqp_gains runs the nu unit seeds of the u_0 block against the one factor.  For stages of at most 32 (NB = 16, 32) they go FOUR TO A SOLVE:
@@ -312,14 +313,17 @@ __global__ __launch_bounds__(NT) void k_adjoint(Lay L, Ptrs P, AdjointArgs Q) {
                     }
                     if constexpr (C == 1) block_reduce<4, 1>(cm, dsum, S.red);
                     else { double none[1] = {0.0}; block_reduce<8, C>(cm, dsum, S.red); block_reduce<4 * C - 8, 1>(cm + 8, none, S.red); }
-                    // refine_iter sweeps at least; then on while the correction is neither negligible (1e-12 of r_w, 1e-10 of r_y) nor stalled --
-                    // nearly dependent active rows contract r_y by only 1e-2 .. 1e-1 a sweep.  A column that is done keeps what it has.
+                    // refine_iter sweeps at least; then on while the correction is neither negligible (1e-12 of the solution, 1e-10 of r_y) nor stalled --
+                    // nearly dependent active rows contract r_y by only 1e-2 .. 1e-1 a sweep, rows held by a slack variable (a violated soft state box:
+                    // eps_feas against delta) by about 0.5: "stalled" is a correction that no longer shrinks by a tenth, not one that fails to halve.
+                    // r_w's correction is measured against the whole solution (|r_w|, c |r_y|, both scaled): where the seed's input sits on a bound r_w is
+                    // zero but for rounding and its own relative change says nothing.  A column that is done keeps what it has.
 #pragma unroll
                     for (int col = 0; col < C; ++col) {
                         if (!((live >> col) & 1u)) continue;
                         if (dsum[col] != dsum[col]) bad = true;        // (a NaN correction: a broken factor)
-                        const double rel = fmax(cm[4 * col] / fmax(cm[4 * col + 1], 1e-300), 1e-2 * cm[4 * col + 2] / fmax(cm[4 * col + 3], 1e-300));
-                        if (sw >= Q.refine && (rel <= 1e-12 || rel > 0.5 * lastrel[col])) live &= ~(1u << col);
+                        const double rel = fmax(cm[4 * col] / fmax(fmax(cm[4 * col + 1], cc * cm[4 * col + 3]), 1e-300), 1e-2 * cm[4 * col + 2] / fmax(cm[4 * col + 3], 1e-300));
+                        if (sw >= Q.refine && (rel <= 1e-12 || rel > 0.9 * lastrel[col])) live &= ~(1u << col);
                         lastrel[col] = rel;
                     }
                 }

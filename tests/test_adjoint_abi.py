@@ -71,7 +71,7 @@ def test_adjoint_defaults():
     s = _lib.AdjointSettings()
     L.mpcqp_adjoint_default_settings(C.byref(s))
     assert s.struct_size == C.sizeof(_lib.AdjointSettings)
-    assert (s.delta, s.refine_iter, s.weak_tol, s.extra_iter, s.reserved) == (1e-6, 3, 1e-6, 12, 0)
+    assert (s.delta, s.refine_iter, s.weak_tol, s.extra_iter, s.reserved) == (1e-6, 3, 1e-6, 60, 0)
 
 
 def test_the_older_headers_are_unchanged():

@@ -82,3 +82,14 @@ def test_scratch_of_the_hot_kernels_stays_where_it_was():
             assert int(v['ScratchSize']) <= 320, (n, v)
         if n.startswith('_ZN2w89k_mpc_runILi16ELb0ELi4ELi1E'):
             assert int(v['ScratchSize']) <= 128, (n, v)
+
+
+def test_the_adjoint_kernels():
+    """k_adjoint<16> holds the one-seed and the four-column code at the full register budget of one workgroup per CU without scratch
+    (DESIGN.md section 5f); the wider instantiations exist and are resident."""
+    ks = _kernels()
+    ad = {int(m.group(1)): v for n, v in ks.items() for m in [re.match(r'_Z9k_adjointILi(\d+)EE', n)] if m}
+    assert sorted(ad) == [16, 32, 64, 128], sorted(ad)
+    assert int(ad[16]['ScratchSize']) == 0 and int(ad[16]['VGPRs']) == 256 and int(ad[16]['Occupancy']) >= 1, ad[16]
+    for nb in (32, 64, 128):
+        assert int(ad[nb]['Occupancy']) >= 1, (nb, ad[nb])

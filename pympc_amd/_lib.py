@@ -28,6 +28,10 @@ MODEL_SYMBOLS = ['mpcqp_update_model', 'mpcqp_mpc_loop_tv']
 # include/mpcqp_adjoint.h: likewise -- adjoint derivatives of the solution and the gains of the constrained control law
 ADJOINT_SYMBOLS = ['mpcqp_adjoint_default_settings', 'mpcqp_set_adjoint', 'mpcqp_adjoint', 'mpcqp_gains', 'mpcqp_get_adjoint_info']
 
+# include/mpcqp_adjoint_model.h: likewise -- the matrix half of the adjoint: gradients for Ad, Bd, Qx, QxN, Qu, QDu, eps_feas
+ADJOINT_MODEL_SYMBOLS = ['mpcqp_adjoint_model']
+ADJOINT_MODEL_NAMES = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu', 'eps_feas')      # the outputs of mpcqp_adjoint_model_io, in its order
+
 
 class PolishSettings(C.Structure):
     """mpcqp_polish_settings (include/mpcqp_polish.h)."""
@@ -46,6 +50,12 @@ class AdjointIO(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('g_w', C.c_void_p), ('g_u0', C.c_void_p),
                 ('d_x0', C.c_void_p), ('d_uminus1', C.c_void_p), ('d_xref', C.c_void_p), ('d_uref', C.c_void_p),
                 ('d_q', C.c_void_p), ('d_l', C.c_void_p), ('d_u', C.c_void_p)]
+
+
+class AdjointModelIO(C.Structure):
+    """mpcqp_adjoint_model_io (include/mpcqp_adjoint_model.h): model gradients out; host or device pointers, None = not wanted."""
+    _fields_ = [('struct_size', C.c_int32), ('batch_sum', C.c_int32), ('d_Ad', C.c_void_p), ('d_Bd', C.c_void_p), ('d_Qx', C.c_void_p),
+                ('d_QxN', C.c_void_p), ('d_Qu', C.c_void_p), ('d_QDu', C.c_void_p), ('d_eps_feas', C.c_void_p)]
 
 
 class Settings(C.Structure):
@@ -186,6 +196,9 @@ def load():
         L.mpcqp_get_adjoint_info.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ADJOINT_SYMBOLS[1:]:
             getattr(L, name).restype = C.c_int
+    if has_adjoint_model(L):
+        L.mpcqp_adjoint_model.argtypes = [H, C.POINTER(AdjointIO), C.POINTER(AdjointModelIO)]
+        L.mpcqp_adjoint_model.restype = C.c_int
     _lib = L
     return L
 
@@ -206,6 +219,12 @@ def has_adjoint(L=None):
     """True if the library exports include/mpcqp_adjoint.h (libmpcqp_hip.so does; the CPU twin does not)."""
     L = L if L is not None else load()
     return all(hasattr(L, name) for name in ADJOINT_SYMBOLS)
+
+
+def has_adjoint_model(L=None):
+    """True if the library exports include/mpcqp_adjoint_model.h (libmpcqp_hip.so does; the CPU twin does not)."""
+    L = L if L is not None else load()
+    return all(hasattr(L, name) for name in ADJOINT_MODEL_SYMBOLS)
 
 
 def check(rc, what):

@@ -71,7 +71,21 @@ class BatchMPCController:
         # does the device copy of u_{-1} equal self.uminus1_rh?  output() moves the host value on (mpc.py:330) without
         # touching the device; setup()/update() upload it, step()/run() leave the applied input on the device themselves
         self._um1_on_device = False
+        self._on_device = {}                      # model fields update_model() got as device tensors and nobody has read on the host since
         self.solve_count = 0                      # solves launched so far (pympc_amd.torch_layer: has the solution moved on since a forward?)
+
+    def __getattr__(self, name):
+        """A model field last given to ``update_model`` as a device tensor: its host copy is made on the first read, not per update."""
+        dev = self.__dict__.get('_on_device', {})
+        if name == 'u_failure' and 'uref' in dev:
+            return self.uref
+        if name in dev:
+            v = np.ascontiguousarray(dev.pop(name).cpu().numpy(), dtype=float)
+            setattr(self, name, v)
+            if name == 'uref':
+                self.u_failure = v
+            return v
+        raise AttributeError(name)
 
     def setup(self, solve=True):
         self.x0_rh = self.x0.copy()
@@ -95,7 +109,9 @@ class BatchMPCController:
 
     def update_model(self, solve=True, **fields):
         """New model data for the batch in use (``BatchProblem.update_model``): any of Ad, Bd, Qx, QxN, Qu, QDu, xmin, xmax, umin, umax, Dumin,
-        Dumax, uref, eps_feas, broadcast to the batch like the constructor's arguments; what is not given keeps its value.  The device
+        Dumax, uref, eps_feas, broadcast to the batch like the constructor's arguments (numpy, or torch device tensors, which go down without a
+        round trip through the host; the attributes stay numpy arrays, copied back when they are next read);
+        what is not given keeps its value.  The device
         re-equilibrates, refactors and keeps every instance's iterate; ``solve=True`` then warm-solves like ``update``."""
         if self.prob is None:
             raise RuntimeError('update_model() needs a controller that has been set up; before setup() assign the attributes')
@@ -104,14 +120,23 @@ class BatchMPCController:
         for k, v in fields.items():
             if k not in shapes:
                 raise TypeError('unknown model field %r' % k)
-            if v is not None:
+            if v is not None and hasattr(v, 'data_ptr') and v.is_cuda:
+                new[k] = v.detach().expand(shapes[k])     # (a torch device tensor goes down as it is, without a round trip through the host)
+            elif v is not None:
                 new[k] = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=float), shapes[k]))      # (ValueError if it does not fit, like the constructor)
         if not new:
             raise ValueError('update_model needs at least one model field')
         for k, v in new.items():
-            setattr(self, k, v)
+            if hasattr(v, 'data_ptr'):            # the host attribute stays a numpy array: copied from the device when somebody reads it (__getattr__)
+                self.__dict__.pop(k, None)
+                self._on_device[k] = v
+            else:
+                self._on_device.pop(k, None)
+                setattr(self, k, v)
         if 'uref' in new:
-            self.u_failure = self.uref
+            self.__dict__.pop('u_failure', None)  # (read through __getattr__: it is uref)
+            if 'uref' not in self._on_device:
+                self.u_failure = self.uref
         if not self._um1_on_device:               # output() moved u_{-1} on: the rho vector is built from the bounds as update() would leave them
             self.prob.update(None, self.uminus1_rh, None)
             self._um1_on_device = True
@@ -201,11 +226,13 @@ class BatchMPCController:
         _, n_weak, status = self.prob.adjoint_info()
         return dict(K_x0=g['x0'], K_um1=g['uminus1'], K_xref=g['xref'], K_uref=g['uref'], n_weak=n_weak, status=status)
 
-    def adjoint(self, g_u0=None, g_w=None):
+    def adjoint(self, g_u0=None, g_w=None, want=('x0', 'uminus1', 'xref', 'uref'), batch_sum=False):
         """Vector-Jacobian products of the last solve (mpcqp_adjoint): for ``g_u0`` [B,nu] = dL/du_0 and / or ``g_w`` [B,n] = dL/dw returns
-        ``dict(x0 [B,nx], uminus1 [B,nu], xref [B,rows*nx], uref [B,nu], n_weak [B], status [B])`` = dL/d(x0, u_{-1}, xref, uref).  numpy in,
-        numpy out; torch device tensors in, device tensors out."""
-        res = self.prob.adjoint(g_w=g_w, g_u0=g_u0)
+        ``dict(x0 [B,nx], uminus1 [B,nu], xref [B,rows*nx], uref [B,nu], n_weak [B], status [B])`` = dL/d(x0, u_{-1}, xref, uref).  ``want`` may
+        also name the model gradients 'Ad' [B,nx,nx], 'Bd' [B,nx,nu], 'Qx', 'QxN' [B,nx,nx], 'Qu', 'QDu' [B,nu,nu], 'eps_feas' [B]
+        (mpcqp_adjoint_model; ``batch_sum``: summed over the batch, leading dimension 1 -- see ``BatchProblem.adjoint``).  numpy in, numpy
+        out; torch device tensors in, device tensors out."""
+        res = self.prob.adjoint(g_w=g_w, g_u0=g_u0, want=want, batch_sum=batch_sum)
         _, n_weak, status = self.prob.adjoint_info()
         res.update(n_weak=n_weak, status=status)
         return res

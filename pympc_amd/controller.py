@@ -326,6 +326,26 @@ class MPCController:
         _, n_weak, status = bp.adjoint_info()
         return dict(K_x0=g['x0'][0], K_um1=g['uminus1'][0], K_xref=g['xref'][0], K_uref=g['uref'][0], n_weak=int(n_weak[0]), status=int(status[0]))
 
+    def adjoint(self, g_u0=None, g_w=None, want=('x0', 'uminus1', 'xref', 'uref')):
+        """Vector-Jacobian products of the last solve for the seed ``g_u0`` [nu] = dL/du_0 and / or ``g_w`` [n] = dL/dw (mpcqp_adjoint,
+        mpcqp_adjoint_model): a dict with the gradients named in ``want`` -- 'x0', 'uminus1', 'xref', 'uref', 'q', 'l', 'u' and the model
+        gradients 'Ad' [nx, nx], 'Bd' [nx, nu], 'Qx', 'QxN' [nx, nx], 'Qu', 'QDu' [nu, nu], 'eps_feas' (weights: with respect to a symmetric
+        perturbation) -- plus ``n_weak`` and ``status`` as in ``gains()``.  A weight whose cost term this controller runs without (the
+        switches JX_ON, JU_ON, JDU_ON) gets zero.  An addition to the reference's class."""
+        bp = getattr(self.prob, 'batch_problem', None)
+        if bp is None or not hasattr(bp, 'adjoint'):
+            raise NotImplementedError('adjoint() needs the device solver behind prob (pympc_amd.solver.DeviceProblem)')
+        one = lambda a: None if a is None else np.asarray(a, dtype=float).reshape(1, -1)
+        res = bp.adjoint(g_w=one(g_w), g_u0=one(g_u0), want=want)
+        _, n_weak, status = bp.adjoint_info()
+        res = {k: v[0] for k, v in res.items()}
+        off = {'Qx': self.JX_ON, 'QxN': self.JX_ON, 'Qu': self.JU_ON, 'QDu': self.JDU_ON}
+        for k, on in off.items():
+            if k in res and not on:
+                res[k] = np.zeros_like(res[k])
+        res.update(n_weak=int(n_weak[0]), status=int(status[0]))
+        return res
+
     # ------------------------------------------------------------------------------------
     # q, l, u, J_CNST are public attributes of the reference (mpc.py:598-606).  The device solver rebuilds them itself from
     # (x0, u_{-1}, xref), so after update() the host copies are refreshed only when somebody reads them.

@@ -45,6 +45,7 @@
 #include "../../include/mpcqp_polish.h"
 #include "../../include/mpcqp_model.h"
 #include "../../include/mpcqp_adjoint.h"
+#include "../../include/mpcqp_adjoint_model.h"
 
 #include "mpcqp_defs.h"
 
@@ -83,6 +84,7 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #include "mpcqp_latw_check.h"
 #include "mpcqp_polish.h"
 #include "mpcqp_adjoint.h"
+#include "mpcqp_adjoint_model.h"
 #include "mpcqp_csc.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -141,6 +143,9 @@ struct mpcqp_handle {
     mpcqp_adjoint_settings adj;          // mpcqp_set_adjoint (include/mpcqp_adjoint.h)
     AdjointArgs aq; size_t smem_adjoint; // the adjoint's buffers (aq.status null until first use) and LDS
     double *adj_gw, *adj_gu0;            // staging of the caller's seeds [batch][n], [batch][nu]
+    double *um1_used; bool um1_moved;    // mpcqp_mpc_step: the u_{-1} its solve was made with, [batch][nu]; true while the step data hold the applied input instead
+    double *adj_step;                    // the adjoint's copy of the step data with that u_{-1} put back [batch][step_sz] (null until first needed)
+    double *adjm_out, *adjm_sum;         // mpcqp_adjoint_model: the per-instance model gradients (field-major, AdjointModelArgs::out) and their batch sum; null until first use
     bool has_solve;                      // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
 
@@ -234,6 +239,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     h->profiling = false; h->run_ms = 0.0; h->run_launches = 0; h->ev_count = 0; h->nevents = 0; h->stream = nullptr; h->own_stream = false;
     h->warm_x_pending = false;
     h->csc = nullptr; h->vec_buf = nullptr; h->step_blank = false;
+    h->adjm_out = nullptr; h->adjm_sum = nullptr; h->um1_used = nullptr; h->um1_moved = false; h->adj_step = nullptr;
     h->pin_in = h->pin_out = nullptr; h->pin_in_dev = h->pin_out_dev = nullptr; h->done_dev = nullptr; h->host_seq = 0; h->pin_stride = 0; h->pin_tried = false;
     if (s) h->S = *s; else mpcqp_default_settings(&h->S);
     h->L = make_layout(nx, nu, Np, Nc, h->S.soft_constraints);
@@ -323,7 +329,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     if (L.border) { rc |= dalloc(h, &P.Bb, B * (size_t)L.nu * L.N * L.NB); rc |= dalloc(h, &P.Zb, B * (size_t)L.nu * L.N * L.NB); rc |= dalloc(h, &P.Sig, B * (size_t)L.nu * L.nu); }
     rc |= dalloc(h, &P.Dt, B * L.n); rc |= dalloc(h, &P.Et, B * L.m);
     rc |= dalloc(h, &P.ctype, B * L.m); rc |= dalloc(h, &P.info, B); rc |= dalloc(h, &P.stats, 10);
-        rc |= dalloc(h, &h->u0_dev, B * L.nu);
+        rc |= dalloc(h, &h->u0_dev, B * L.nu); rc |= dalloc(h, &h->um1_used, B * L.nu);
     rc |= dalloc(h, &P.work, B); rc |= dalloc(h, &h->perm_dev, B);
     rc |= dalloc(h, &h->vcur_dev, (size_t)std::max(4 * h->ncu, 1)); rc |= dalloc(h, &h->vqueue_dev, 4); rc |= dalloc(h, &h->vdone_dev, B); rc |= dalloc(h, &h->qperm_dev, B);
     rc |= dalloc(h, &P.tstamp, (size_t)TS_STRIDE * B);
@@ -835,7 +841,7 @@ static int launch_run(mpcqp_handle *h, RunArgs R, int plain_iters) {
     const Lay &L = h->L; const mpcqp_settings &S = h->S;
     R.plain = plain_iters > 0;
     R.warm_x = (h->warm_x_pending && R.part != 2 && R.part != 3) ? 1 : 0;
-    if (R.part != 3) h->has_solve = true;
+    if (R.part != 3) { h->has_solve = true; h->um1_moved = false; }
     if (R.part == 0 || R.part == 2) h->warm_x_pending = false;      // (a two-launch solve begins in its first launch only; mpcqp_refactor, part 3, is not a solve)
     R.max_iter = R.plain ? plain_iters : S.max_iter;
     R.chk = R.plain ? 0 : S.check_termination;
@@ -1114,13 +1120,29 @@ static int adjoint_alloc(mpcqp_handle *h) {
 }
 // One launch of k_adjoint: nseeds seeds per instance against one factorization (gw / gu0: the staged seeds of mpcqp_adjoint; both null: the
 // unit seeds of mpcqp_gains); raw: the d_q, d_l, d_u outputs are wanted.
+// dst = the step data with u_{-1} replaced by the one the last solve was made with
+__global__ __launch_bounds__(256) void k_adjoint_step(Lay L, const double *step, const double *um1_used, double *dst, int batch) {
+    const size_t total = (size_t)batch * L.step_sz;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const int b = (int)(idx / L.step_sz), i = (int)(idx - (size_t)b * L.step_sz);
+        dst[idx] = (i >= L.nx && i < L.nx + L.nu) ? um1_used[(size_t)b * L.nu + (i - L.nx)] : step[idx];
+    }
+}
 static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const double *gu0, bool raw_out) {
     if (flush_puts(h)) return MPCQP_ERR_HIP;
+    // mpcqp_mpc_step has left the applied input in the step data as the NEXT u_{-1}, while the iterate belongs to the one before (um1_used):
+    // the bounds of the first Delta-u rows (the active set) and the QDu gradient need that one, so the kernels read a copy with it put back.
+    if (h->um1_moved) {
+        const size_t total = (size_t)h->batch * h->L.step_sz;
+        if (!h->adj_step && dalloc(h, &h->adj_step, total)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_adjoint_step, dim3((unsigned)std::min<size_t>(1024, (total + 255) / 256)), dim3(256), 0, h->stream, h->L, h->P.step, h->um1_used, h->adj_step, h->batch);
+    }
     AdjointArgs Q = h->aq;
     Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
     Q.nseeds = nseeds; Q.gw = gw; Q.gu0 = gu0; Q.chain = h->L.raw ? 0 : 1;
     if (!raw_out) { Q.oq = nullptr; Q.ol = nullptr; Q.ou = nullptr; }
     Ptrs P = h->P; P.perm = nullptr; P.fown = nullptr;      // (workgroup b = instance b; the adjoint factors into its own buffers)
+    if (h->um1_moved) P.step = h->adj_step;
     Lay G = polish_layout(h->L);                            // (the handle's Lay changes with raw-vector mode and the reference shape)
     // Several seeds against stages of at most 32 go four to a solve (kkt_core_cols): the work area then holds four row vectors and four stage-major
     // vectors, these two doubles further apart than their length so that the four lanes of a row position do not all meet in one LDS bank.  Where that does
@@ -1146,13 +1168,49 @@ static int adjoint_ready(mpcqp_handle *h, const char *what, bool chain) {
     if (chain && h->L.raw) return fail(MPCQP_ERR_STATE, std::string(what) + ": the handle works from raw q, l, u (mpcqp_setup_qp / mpcqp_update_vectors), where only d_q, d_l, d_u are defined");
     return MPCQP_OK;
 }
-extern "C" int mpcqp_adjoint(mpcqp_handle *h, const mpcqp_adjoint_io *io) {
-    if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
-    if (io->struct_size != (int32_t)sizeof(mpcqp_adjoint_io)) return fail(MPCQP_ERR_ARG, "mpcqp_adjoint: struct_size is not sizeof(mpcqp_adjoint_io)");
-    if (!io->g_w && !io->g_u0) return fail(MPCQP_ERR_ARG, "mpcqp_adjoint: give g_w, g_u0 or both");
-    if ((io->d_l == nullptr) != (io->d_u == nullptr)) return fail(MPCQP_ERR_ARG, "mpcqp_adjoint: d_l and d_u go together");
+// Entries of the model gradients of one instance, field by field (Ad, Bd, Qx, QxN, Qu, QDu, eps_feas), as prefix sums.
+static void adjoint_model_offsets(const Lay &L, int *off) {
+    const int sz[ADJM_FIELDS] = {L.nx * L.nx, L.nx * L.nu, L.nx * L.nx, L.nx * L.nx, L.nu * L.nu, L.nu * L.nu, 1};
+    off[0] = 0;
+    for (int f = 0; f < ADJM_FIELDS; ++f) off[f + 1] = off[f] + sz[f];
+}
+// k_adjoint_model behind the k_adjoint launch of the same call, k_adjoint_model_sum behind it where the batch sum is wanted.
+static int launch_adjoint_model(mpcqp_handle *h, bool batch_sum) {
+    const Lay G = polish_layout(h->L);
+    AdjointModelArgs M; memset(&M, 0, sizeof(M));
+    adjoint_model_offsets(G, M.off);
+    const size_t E = (size_t)M.off[ADJM_FIELDS];
+    if (!h->adjm_out) {                                      // on first use, like the adjoint's other buffers
+        if (dalloc(h, &h->adjm_out, (size_t)h->batch * E) || dalloc(h, &h->adjm_sum, E)) return MPCQP_ERR_HIP;
+    }
+    M.rw = h->aq.x; M.ry = h->aq.y; M.w = h->P.x; M.y = h->P.y; M.model = h->P.model; M.step = h->um1_moved ? h->adj_step : h->P.step; M.status = h->aq.status;      // (the step data k_adjoint just read)
+    M.out = h->adjm_out; M.batch = h->batch;
+    const size_t staged = sizeof(double) * ((size_t)NT + 2 * (size_t)G.n + 2 * (size_t)G.n_x);
+    M.staged = staged <= 64 * 1024 ? 1 : 0;                  // (beyond that the vectors are read where they are)
+    const size_t smem = M.staged ? staged : sizeof(double) * (size_t)NT;
+    if (set_smem(k_adjoint_model, smem)) return MPCQP_ERR_HIP;
+    hipLaunchKernelGGL(k_adjoint_model, dim3(h->batch), dim3(NT), smem, h->stream, G, M);
+    if (batch_sum) hipLaunchKernelGGL(k_adjoint_model_sum, dim3((unsigned)((E + 15) / 16)), dim3(256), 0, h->stream, M, h->adjm_sum);
+    HIPCHK(hipGetLastError());
+    return MPCQP_OK;
+}
+// mpcqp_adjoint (mo null) and mpcqp_adjoint_model: one k_adjoint launch, the model kernels behind it where mo asks for anything.
+static int adjoint_call(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp_adjoint_model_io *mo, const char *what) {
+    const std::string w(what);
+    if (io->struct_size != (int32_t)sizeof(mpcqp_adjoint_io)) return fail(MPCQP_ERR_ARG, w + ": struct_size is not sizeof(mpcqp_adjoint_io)");
+    if (mo && mo->struct_size != (int32_t)sizeof(mpcqp_adjoint_model_io)) return fail(MPCQP_ERR_ARG, w + ": struct_size is not sizeof(mpcqp_adjoint_model_io)");
+    if (!io->g_w && !io->g_u0) return fail(MPCQP_ERR_ARG, w + ": give g_w, g_u0 or both");
+    if ((io->d_l == nullptr) != (io->d_u == nullptr)) return fail(MPCQP_ERR_ARG, w + ": d_l and d_u go together");
+    double *const mout[ADJM_FIELDS] = {mo ? mo->d_Ad : nullptr, mo ? mo->d_Bd : nullptr, mo ? mo->d_Qx : nullptr, mo ? mo->d_QxN : nullptr,
+                                       mo ? mo->d_Qu : nullptr, mo ? mo->d_QDu : nullptr, mo ? mo->d_eps_feas : nullptr};
+    bool model = false;
+    for (double *q : mout) if (q) model = true;
     const bool chain = io->d_x0 || io->d_uminus1 || io->d_xref || io->d_uref;
-    int rc = adjoint_ready(h, "mpcqp_adjoint", chain);
+    if (mo) {
+        if (mo->batch_sum != 0 && mo->batch_sum != 1) return fail(MPCQP_ERR_ARG, w + ": batch_sum is 0 or 1");
+        if (!model && !chain && !io->d_q && !io->d_l) return fail(MPCQP_ERR_ARG, w + ": no output asked for");
+    }
+    int rc = adjoint_ready(h, what, chain || model);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
     if ((rc = adjoint_alloc(h))) return rc;
@@ -1160,15 +1218,33 @@ extern "C" int mpcqp_adjoint(mpcqp_handle *h, const mpcqp_adjoint_io *io) {
     if (io->g_w) HIPCHK(hipMemcpyAsync(h->adj_gw, io->g_w, B * L.n * db, hipMemcpyDefault, h->stream));
     if (io->g_u0) HIPCHK(hipMemcpyAsync(h->adj_gu0, io->g_u0, B * L.nu * db, hipMemcpyDefault, h->stream));
     if ((rc = launch_adjoint(h, 1, io->g_w ? h->adj_gw : nullptr, io->g_u0 ? h->adj_gu0 : nullptr, io->d_q || io->d_l))) return rc;
+    if (model && (rc = launch_adjoint_model(h, mo->batch_sum != 0))) return rc;
     const AdjointArgs &Q = h->aq;
     if (get(h, io->d_x0, Q.ox0, B * L.nx * db) || get(h, io->d_uminus1, Q.oum1, B * L.nu * db) || get(h, io->d_uref, Q.ouref, B * L.nu * db) ||
         get(h, io->d_xref, Q.oxref, B * (size_t)L.xref_rows * L.nx * db) || get(h, io->d_q, Q.oq, B * L.n * db) ||
         get(h, io->d_l, Q.ol, B * L.m * db) || get(h, io->d_u, Q.ou, B * L.m * db)) return MPCQP_ERR_HIP;
-    const void *all[] = {io->g_w, io->g_u0, io->d_x0, io->d_uminus1, io->d_xref, io->d_uref, io->d_q, io->d_l, io->d_u};
+    if (model) {
+        int off[ADJM_FIELDS + 1]; adjoint_model_offsets(L, off);
+        for (int f = 0; f < ADJM_FIELDS; ++f) {
+            const size_t sz = (size_t)(off[f + 1] - off[f]);
+            const double *src = mo->batch_sum ? h->adjm_sum + off[f] : h->adjm_out + B * (size_t)off[f];
+            if (get(h, mout[f], src, (mo->batch_sum ? 1 : B) * sz * db)) return MPCQP_ERR_HIP;
+        }
+    }
+    const void *all[] = {io->g_w, io->g_u0, io->d_x0, io->d_uminus1, io->d_xref, io->d_uref, io->d_q, io->d_l, io->d_u,
+                         mout[0], mout[1], mout[2], mout[3], mout[4], mout[5], mout[6]};
     bool dev = true;
     for (const void *q : all) if (q && !is_device_ptr(q)) dev = false;
     if (!dev) HIPCHK(hipStreamSynchronize(h->stream));      // (device buffers throughout: stream-ordered, no need to wait)
     return MPCQP_OK;
+}
+extern "C" int mpcqp_adjoint(mpcqp_handle *h, const mpcqp_adjoint_io *io) {
+    if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
+    return adjoint_call(h, io, nullptr, "mpcqp_adjoint");
+}
+extern "C" int mpcqp_adjoint_model(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
+    if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
+    return adjoint_call(h, io, mo, mo ? "mpcqp_adjoint_model" : "mpcqp_adjoint");
 }
 extern "C" int mpcqp_gains(mpcqp_handle *h, double *K_x0, double *K_uminus1, double *K_xref, double *K_uref) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
@@ -1338,7 +1414,7 @@ extern "C" int mpcqp_eq_solve(mpcqp_handle *h, int sweeps, int cold, double tol,
     });
     HIPCHK(hipGetLastError());
     if (h->pq.status) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * (size_t)h->batch, h->stream));      // (the polish setting is ignored here)
-    h->has_solve = true;
+    h->has_solve = true; h->um1_moved = false;
     if (res) HIPCHK(hipMemcpyAsync(res, dres, sizeof(double) * 5 * (size_t)h->batch, hipMemcpyDefault, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
@@ -1379,8 +1455,9 @@ extern "C" int mpcqp_mpc_step(mpcqp_handle *h, const double *x0, const double *u
     if ((rc = launch_solve(h, 0))) return rc;
     if ((rc = after_solve(h))) return rc;
     const int tot = h->batch * h->L.nu;
-    hipLaunchKernelGGL(k_output_u, dim3((tot + 255) / 256), dim3(256), 0, h->stream, h->L, h->P, h->u0_dev, h->batch, 1);
+    hipLaunchKernelGGL(k_output_u, dim3((tot + 255) / 256), dim3(256), 0, h->stream, h->L, h->P, h->u0_dev, h->batch, 1, h->um1_used);
     HIPCHK(hipGetLastError());
+    h->um1_moved = true;                            // (the step data now hold the NEXT u_{-1}; this solve's is in um1_used)
     if (get(h, u_out, h->u0_dev, sizeof(double) * (size_t)tot)) return MPCQP_ERR_HIP;
     const bool due = balance_due(h);
     if (!due && is_device_ptr(u_out)) return MPCQP_OK;

@@ -519,12 +519,13 @@ __global__ void k_keep_du0(Lay L, Ptrs P, int batch) {
 
 // output() of mpc.py:271-336 for the whole batch: u = first input of the solution if the status is 'solved', else
 // u_failure (= uref); optionally also becomes u_{-1} of the next update (output() sets uminus1_rh).
-__global__ void k_output_u(Lay L, Ptrs P, double *u_out, int batch, int store_um1) {
+// um1_used: where the u_{-1} this solve was made with is kept when the step data move on to the next one (what the adjoint's QDu gradient reads)
+__global__ void k_output_u(Lay L, Ptrs P, double *u_out, int batch, int store_um1, double *um1_used) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < batch * L.nu) {
         const int b = i / L.nu, j = i - b * L.nu;
         const double u = P.info[b].status == MPCQP_SOLVED ? P.xo[(size_t)b * L.n + L.ou + j] : P.model[(size_t)b * L.model_sz + L.ouref + j];
         u_out[i] = u;
-        if (store_um1) P.step[(size_t)b * L.step_sz + L.nx + j] = u;
+        if (store_um1) { double *um1 = P.step + (size_t)b * L.step_sz + L.nx + j; um1_used[i] = *um1; *um1 = u; }
     }
 }

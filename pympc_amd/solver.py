@@ -272,40 +272,54 @@ class BatchProblem:
             return torch.empty(shape, dtype=torch.float64, device=like.device)
         return np.empty(shape)
 
-    def adjoint(self, g_w=None, g_u0=None, want=('x0', 'uminus1', 'xref', 'uref'), out=None):
+    def adjoint(self, g_w=None, g_u0=None, want=('x0', 'uminus1', 'xref', 'uref'), out=None, batch_sum=False):
         """Adjoint derivatives of the current solution (mpcqp_adjoint): for the seed ``g_w`` [B, n] = dL/dw and / or ``g_u0`` [B, nu] = dL/du_0
         returns a dict with the gradients named in ``want`` -- any of 'x0' [B, nx], 'uminus1' [B, nu], 'xref' [B, rows*nx] (shape of the
-        last upload), 'uref' [B, nu], 'q' [B, n], 'l', 'u' [B, m].  Seeds may be numpy arrays or torch device tensors; the results are of the
-        same kind (device tensors: stream-ordered, no wait), or are written into the arrays / tensors given in ``out`` (a dict by the same
-        names).  The gradients are those of the active set the iterate implies; ``adjoint_info()`` reports weakly active rows."""
+        last upload), 'uref' [B, nu], 'q' [B, n], 'l', 'u' [B, m], and of the model gradients 'Ad' [B, nx, nx], 'Bd' [B, nx, nu], 'Qx', 'QxN'
+        [B, nx, nx], 'Qu', 'QDu' [B, nu, nu], 'eps_feas' [B] (mpcqp_adjoint_model, include/mpcqp_adjoint_model.h: the same call, the same
+        single factorization; the weight gradients are those of a symmetric perturbation).  ``batch_sum``: the model gradients come summed
+        over the batch, with a leading dimension of 1 -- one model shared by many states; the sum is formed on the device in a fixed order.
+        Seeds may be numpy arrays or torch device tensors; the results are of the same kind (device tensors: stream-ordered, no wait), or
+        are written into the arrays / tensors given in ``out`` (a dict by the same names).  The gradients are those of the active set the
+        iterate implies; ``adjoint_info()`` reports weakly active rows."""
         self._need_adjoint()
         if g_w is None and g_u0 is None:
             raise ValueError('adjoint: give g_w, g_u0 or both')
-        B = self.batch
+        B, nx, nu = self.batch, self.nx, self.nu
         like = g_w if g_w is not None else g_u0
         gw = _prep(g_w, (B, self.n), 'g_w') if g_w is not None else None
         gu = _prep(g_u0, (B, self.nu), 'g_u0') if g_u0 is not None else None
         shapes = dict(x0=(B, self.nx), uminus1=(B, self.nu), xref=(B, self._xref_rows_last * self.nx), uref=(B, self.nu),
                       q=(B, self.n), l=(B, self.m), u=(B, self.m))
+        Bm = 1 if batch_sum else B
+        mshapes = dict(Ad=(Bm, nx, nx), Bd=(Bm, nx, nu), Qx=(Bm, nx, nx), QxN=(Bm, nx, nx), Qu=(Bm, nu, nu), QDu=(Bm, nu, nu), eps_feas=(Bm,))
         want = list(want)
         if ('l' in want) != ('u' in want):
             want += ['l' if 'u' in want else 'u']
+        model = any(k in mshapes for k in want)
+        if model and not _lib.has_adjoint_model(self._L):
+            raise NotImplementedError('this build of the solver library has no model gradients (include/mpcqp_adjoint_model.h)')
         res = {}
         io = _lib.AdjointIO()
         io.struct_size = C.sizeof(_lib.AdjointIO)
         io.g_w, io.g_u0 = _ptr(gw), _ptr(gu)
+        mo = _lib.AdjointModelIO()
+        mo.struct_size, mo.batch_sum = C.sizeof(_lib.AdjointModelIO), int(bool(batch_sum))
         for k in want:
-            if k not in shapes:
+            if k not in shapes and k not in mshapes:
                 raise TypeError('unknown gradient %r' % k)
+            shape = shapes[k] if k in shapes else mshapes[k]
             if out is not None and k in out:
-                a = _prep_out(out[k], shapes[k], 'out[%r]' % k)
+                a = _prep_out(out[k], shape, 'out[%r]' % k)
             else:
-                a = self._out(like, shapes[k])
+                a = self._out(like, shape)
             res[k] = a
-            setattr(io, 'd_' + k, _ptr(a))
+            setattr(mo if k in mshapes else io, 'd_' + k, _ptr(a))
         self._keep = [gw, gu, res]
-        rc = self._L.mpcqp_adjoint(self._h, C.byref(io))
-        _lib.check(rc, 'mpcqp_adjoint')
+        if model:
+            _lib.check(self._L.mpcqp_adjoint_model(self._h, C.byref(io), C.byref(mo)), 'mpcqp_adjoint_model')
+        else:                                     # (without a model gradient: the call as it always was)
+            _lib.check(self._L.mpcqp_adjoint(self._h, C.byref(io)), 'mpcqp_adjoint')
         return res
 
     def gains(self, want=('x0', 'uminus1', 'xref', 'uref'), like=None):

@@ -14,6 +14,12 @@ is the container of the device buffers and the owner of the graph; no torch oper
   examples/differentiable_mpc.py).  The library refuses on its own account where the controller's step data, model or iterate were replaced
   without a solve (``update(..., solve=False)``, ``update_model(solve=False)``, ``warm_start``): mpcqp_adjoint answers MPCQP_ERR_STATE
   until the next solve.
+* ``params``: the model itself as an input of the layer -- a dict of device tensors under the names Ad, Bd, Qx, QxN, Qu, QDu, each
+  [B, ...] (one per instance) or unbatched [...] (one model shared by the batch).  Forward puts them under the controller with
+  ``update_model(solve=False, ...)`` (mpcqp_update_model: re-equilibrate, refactor, keep the iterate) and steps; backward asks ONE
+  ``mpcqp_adjoint_model`` call (include/mpcqp_adjoint_model.h) for exactly the gradients torch needs, an unbatched parameter's as the sum
+  over the batch formed on the device (``batch_sum``).  The weight gradients are those of a symmetric perturbation: a weight that is
+  parametrized symmetric (Q = L L', a diagonal) gets its true gradient.
 """
 import torch
 
@@ -23,15 +29,20 @@ def _sync_needed(K):
     return K.stream is None or int(K.stream) != int(torch.cuda.current_stream().cuda_stream)
 
 
+MODEL_PARAMS = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu')
+
+
 class _MPCStep(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, K, x, u_prev, xref):
+    def forward(ctx, K, x, u_prev, xref, names, *params):
         if not x.is_cuda:
             raise ValueError('mpc_step works on device tensors (x is on %s)' % x.device)
         sync = _sync_needed(K)
         if sync:
             torch.cuda.current_stream().synchronize()
         det = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
+        if names:
+            K.update_model(solve=False, **{n: det(p) for n, p in zip(names, params)})
         u = torch.empty((K.B, K.nu), dtype=torch.float64, device=x.device)
         xr = det(xref)
         K.step(det(x), det(u_prev), None if xr is None else xr.reshape(K.B, -1), out=u)
@@ -39,6 +50,7 @@ class _MPCStep(torch.autograd.Function):
             K.prob.synchronize()
         ctx.K, ctx.count = K, K.solve_count
         ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (x, u_prev, xref))
+        ctx.names, ctx.pshapes = names, tuple(tuple(p.shape) for p in params)
         return u
 
     @staticmethod
@@ -49,22 +61,43 @@ class _MPCStep(torch.autograd.Function):
                                'its solution is no longer the one to differentiate.  Use one controller per step of a rollout.'
                                % (ctx.count, K.solve_count))
         names = ('x0', 'uminus1', 'xref')
-        want = [n for n, need, shp in zip(names, ctx.needs_input_grad[1:], ctx.shapes) if need and shp is not None]
-        if not want:
-            return None, None, None, None
+        want = [n for n, need, shp in zip(names, ctx.needs_input_grad[1:4], ctx.shapes) if need and shp is not None]
+        pneed = [n for n, need in zip(ctx.names, ctx.needs_input_grad[5:]) if need]
+        none = (None,) * (5 + len(ctx.names))
+        if not want and not pneed:
+            return none
+        # one model for the whole batch: the device adds the instances' gradients up (a mixture of shared and per-instance parameters
+        # takes them per instance and adds the shared ones' here)
+        shared = {n: len(shp) == 2 for n, shp in zip(ctx.names, ctx.pshapes)}
+        batch_sum = bool(pneed) and all(shared[n] for n in pneed)
         sync = _sync_needed(K)
         if sync:
             torch.cuda.current_stream().synchronize()
-        res = K.prob.adjoint(g_u0=grad_u.to(torch.float64).contiguous(), want=want)
+        res = K.prob.adjoint(g_u0=grad_u.to(torch.float64).contiguous(), want=want + pneed, batch_sum=batch_sum)
         if sync:
             K.prob.synchronize()
         grads = [res[n].reshape(shp) if n in res else None for n, shp in zip(names, ctx.shapes)]
-        return (None,) + tuple(grads)
+        pgrads = []
+        for n, shp in zip(ctx.names, ctx.pshapes):
+            g = res.get(n)
+            if g is not None:
+                g = (g[0] if batch_sum else g.sum(dim=0)) if shared[n] else g
+                g = g.reshape(shp)
+            pgrads.append(g)
+        return (None,) + tuple(grads) + (None,) + tuple(pgrads)
 
 
-def mpc_step(controller, x, u_prev=None, xref=None):
+def mpc_step(controller, x, u_prev=None, xref=None, params=None):
     """``u [B,nu] = K(x [B,nx], u_prev [B,nu], xref [B,nx] or [B,Np+1,nx])`` of a set-up ``BatchMPCController``, differentiable with
-    respect to the three tensors (float64 device tensors; ``u_prev`` / ``xref`` None: the controller's own, no gradient)."""
+    respect to the three tensors (float64 device tensors; ``u_prev`` / ``xref`` None: the controller's own, no gradient) and, with
+    ``params`` -- a dict of device tensors under any of the names Ad, Bd, Qx, QxN, Qu, QDu, each [B, ...] or unbatched [...] -- with respect
+    to the model the step is made with: the controller's model is replaced by them first (``update_model``)."""
     if controller.prob is None:
         raise RuntimeError('mpc_step needs a controller that has been set up')
-    return _MPCStep.apply(controller, x, u_prev, xref)
+    names = tuple(params) if params else ()
+    for n in names:
+        if n not in MODEL_PARAMS:
+            raise TypeError('mpc_step: unknown model parameter %r (one of %s)' % (n, ', '.join(MODEL_PARAMS)))
+        if not hasattr(params[n], 'data_ptr') or not params[n].is_cuda or params[n].dim() not in (2, 3):
+            raise ValueError('mpc_step: params[%r] must be a device tensor [B, ., .] or [., .]' % n)
+    return _MPCStep.apply(controller, x, u_prev, xref, names, *[params[n] for n in names])

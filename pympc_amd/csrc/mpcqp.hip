@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -82,6 +83,7 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #include "mpcqp_latw.h"
 #include "mpcqp_kernels.h"
 #include "mpcqp_latw_check.h"
+#include "mpcqp_kpol.h"
 #include "mpcqp_polish.h"
 #include "mpcqp_adjoint.h"
 #include "mpcqp_adjoint_model.h"
@@ -139,9 +141,9 @@ struct mpcqp_handle {
     bool step_blank;                     // set up through mpcqp_setup_qp: the step blob holds no x0 / u_{-1} / xref yet
     int *fown_dev; unsigned *nshared_dev;   // mpcqp_share_factor: [batch] factor slot per instance (P.fown points here while sharing is on); how many share
     mpcqp_polish_settings pol;           // mpcqp_set_polish (include/mpcqp_polish.h)
-    PolishArgs pq; Lay pol_lay; size_t smem_polish;   // the polish's buffers (pq.status null until first use), layout and LDS
+    PolishArgs pq;                       // the polish's buffers (pq.status null until first use)
     mpcqp_adjoint_settings adj;          // mpcqp_set_adjoint (include/mpcqp_adjoint.h)
-    AdjointArgs aq; size_t smem_adjoint; // the adjoint's buffers (aq.status null until first use) and LDS
+    AdjointArgs aq;                      // the adjoint's buffers (aq.status null until first use)
     double *adj_gw, *adj_gu0;            // staging of the caller's seeds [batch][n], [batch][nu]
     double *um1_used; bool um1_moved;    // mpcqp_mpc_step: the u_{-1} its solve was made with, [batch][nu]; true while the step data hold the applied input instead
     double *adj_step;                    // the adjoint's copy of the step data with that u_{-1} put back [batch][step_sz] (null until first needed)
@@ -939,29 +941,44 @@ extern "C" int mpcqp_set_polish(mpcqp_handle *h, const mpcqp_polish_settings *s)
     h->pol = *s;
     return MPCQP_OK;
 }
-// The polish's buffers, on first use: the factor of K_pol in the generic block format, its metric, the polished point, the sweep vectors,
-// the active set, the border and workspace of the factorization, status_polish.
+// What a K_pol kernel (k_polish, k_adjoint) is launched with: the layout of mpcqp_kpol.h (taken from the handle's Lay at every launch:
+// it changes with raw-vector mode and the reference shape), workgroup b = instance b, a factor of the kernel's own, and the LDS of that layout.
+struct KpolLaunch { Lay G; Ptrs P; size_t smem; };
+static KpolLaunch kpol_launch(const mpcqp_handle *h) {
+    KpolLaunch v{polish_layout(h->L), h->P, 0};
+    v.P.perm = nullptr; v.P.fown = nullptr;
+    v.smem = sizeof(double) * (size_t)smem_common_doubles(v.G);
+    return v;
+}
+// The buffers of K_pol: the factor in the generic block format, the metric, the active set, the border and workspace of the factorization.
+static int kpol_alloc(mpcqp_handle *h, KpolBufs *K, const char *what) {
+    const KpolLaunch v = kpol_launch(h);
+    const Lay &G = v.G;
+    if (v.smem > 160 * 1024) return fail(MPCQP_ERR_UNSUPPORTED, std::string(what) + ": problem too large for one workgroup's LDS");
+    const size_t B = (size_t)h->batch;
+    K->fsz = polish_factor_doubles(G);
+    int rc = 0;
+    rc |= dalloc(h, &K->F, B * (size_t)K->fsz);
+    rc |= dalloc(h, &K->om, B * G.m); rc |= dalloc(h, &K->s, B * G.n); rc |= dalloc(h, &K->act, B * G.m);
+    if (G.border) { rc |= dalloc(h, &K->Bb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &K->Zb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &K->Sig, B * (size_t)G.nu * G.nu); }
+    if (G.NB == 128) rc |= dalloc(h, &K->gws, B * (size_t)HugeFmt::GWS);
+    return rc ? MPCQP_ERR_HIP : MPCQP_OK;      // (what was allocated stays in h->allocs: freed by mpcqp_destroy)
+}
+// The polish's buffers, on first use: K_pol, the polished point, the sweep vectors, the targets of the active rows, status_polish.
 static int polish_alloc(mpcqp_handle *h) {
     if (h->pq.status) return MPCQP_OK;
-    const Lay G = polish_layout(h->L);
-    const size_t smem = sizeof(double) * (size_t)smem_common_doubles(G);
-    if (smem > 160 * 1024) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_polish: problem too large for one workgroup's LDS");
     PolishArgs Q; memset(&Q, 0, sizeof(Q));
-    const size_t B = (size_t)h->batch;
-    Q.fsz = polish_factor_doubles(G);
-    int rc = 0;
-    rc |= dalloc(h, &Q.F, B * (size_t)Q.fsz);
-    rc |= dalloc(h, &Q.om, B * G.m); rc |= dalloc(h, &Q.s, B * G.n);
-    rc |= dalloc(h, &Q.x, B * G.n); rc |= dalloc(h, &Q.z, B * G.m); rc |= dalloc(h, &Q.y, B * G.m);
-    rc |= dalloc(h, &Q.r, B * G.n); rc |= dalloc(h, &Q.d, B * G.n); rc |= dalloc(h, &Q.e, B * G.n); rc |= dalloc(h, &Q.dd, B * G.n);
-    rc |= dalloc(h, &Q.bt, B * G.m); rc |= dalloc(h, &Q.act, B * G.m);
-    if (G.border) { rc |= dalloc(h, &Q.Bb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &Q.Zb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &Q.Sig, B * (size_t)G.nu * G.nu); }
-    if (G.NB == 128) rc |= dalloc(h, &Q.gws, B * (size_t)HugeFmt::GWS);
+    int rc = kpol_alloc(h, &Q.K, "mpcqp_polish");
+    if (rc) return rc;
+    const Lay &L = h->L; const size_t B = (size_t)h->batch;
+    rc |= dalloc(h, &Q.x, B * L.n); rc |= dalloc(h, &Q.z, B * L.m); rc |= dalloc(h, &Q.y, B * L.m);
+    rc |= dalloc(h, &Q.r, B * L.n); rc |= dalloc(h, &Q.d, B * L.n); rc |= dalloc(h, &Q.e, B * L.n); rc |= dalloc(h, &Q.dd, B * L.n);
+    rc |= dalloc(h, &Q.bt, B * L.m);
     int *status = nullptr;
     rc |= dalloc(h, &status, B);
-    if (rc) return MPCQP_ERR_HIP;      // (what was allocated stays in h->allocs: freed by mpcqp_destroy)
+    if (rc) return MPCQP_ERR_HIP;
     Q.status = status; Q.batch = h->batch;
-    h->pq = Q; h->pol_lay = G; h->smem_polish = smem;
+    h->pq = Q;
     return MPCQP_OK;
 }
 // Polish the last solve of every instance (k_polish; pub: mpcqp_step_host's mapped result block and flag, else null).
@@ -971,11 +988,10 @@ static int launch_polish(mpcqp_handle *h, double *pub = nullptr, unsigned *done 
     if (flush_puts(h)) return MPCQP_ERR_HIP;
     PolishArgs Q = h->pq;
     Q.delta = h->pol.delta; Q.refine = h->pol.polish_refine_iter; Q.pub = pub; Q.done = done; Q.seq = seq;
-    Ptrs P = h->P; P.perm = nullptr; P.fown = nullptr;      // (workgroup b = instance b; the polish factors into its own buffers)
-    Lay G = polish_layout(h->L);                            // (the handle's Lay changes with raw-vector mode and the reference shape)
-    DISPATCH_NB(G.NB, {
-        if (set_smem(k_polish<NB>, h->smem_polish)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL(k_polish<NB>, dim3(h->batch), dim3(NT), h->smem_polish, h->stream, G, P, Q);
+    const KpolLaunch v = kpol_launch(h);
+    DISPATCH_NB(v.G.NB, {
+        if (set_smem(k_polish<NB>, v.smem)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_polish<NB>, dim3(h->batch), dim3(NT), v.smem, h->stream, v.G, v.P, Q);
     });
     HIPCHK(hipGetLastError());
     return MPCQP_OK;
@@ -1088,34 +1104,27 @@ extern "C" int mpcqp_set_adjoint(mpcqp_handle *h, const mpcqp_adjoint_settings *
     h->adj = *s;
     return MPCQP_OK;
 }
-// The adjoint's buffers, on first use: the factor of K_pol and its metric, r_w / r_y and the sweep vectors, the seed, the active set, the
-// border and workspace of the factorization, the staged seeds, the outputs for up to nu seeds, the three info vectors.
+// The adjoint's buffers, on first use: K_pol, r_w / r_y and the sweep vectors, the seed, the staged seeds, the outputs for up to nu seeds,
+// the three info vectors.
 static int adjoint_alloc(mpcqp_handle *h) {
     if (h->aq.status) return MPCQP_OK;
-    const Lay G = polish_layout(h->L);
-    const size_t smem = sizeof(double) * (size_t)smem_common_doubles(G);
-    if (smem > 160 * 1024) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_adjoint: problem too large for one workgroup's LDS");
     AdjointArgs Q; memset(&Q, 0, sizeof(Q));
-    const size_t B = (size_t)h->batch, S = (size_t)G.nu;
-    Q.fsz = polish_factor_doubles(G);
-    int rc = 0;
-    rc |= dalloc(h, &Q.F, B * (size_t)Q.fsz);
-    rc |= dalloc(h, &Q.om, B * G.m); rc |= dalloc(h, &Q.s, B * G.n);
+    int rc = kpol_alloc(h, &Q.K, "mpcqp_adjoint");
+    if (rc) return rc;
+    const Lay &L = h->L; const size_t B = (size_t)h->batch, S = (size_t)L.nu;
     const size_t C = ADJOINT_COLS;      // (the vectors of a seed in progress: one per column of a solve)
-    rc |= dalloc(h, &Q.x, B * C * G.n); rc |= dalloc(h, &Q.y, B * C * G.m); rc |= dalloc(h, &Q.g, B * C * G.n);
-    rc |= dalloc(h, &Q.r, B * C * G.n); rc |= dalloc(h, &Q.d, B * C * G.n); rc |= dalloc(h, &Q.e, B * C * G.n); rc |= dalloc(h, &Q.dd, B * C * G.n);
-    rc |= dalloc(h, &Q.act, B * G.m); rc |= dalloc(h, &Q.gt, B * C * G.m);
-    if (G.border) { rc |= dalloc(h, &Q.Bb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &Q.Zb, B * (size_t)G.nu * G.N * G.NB); rc |= dalloc(h, &Q.Sig, B * (size_t)G.nu * G.nu); }
-    if (G.NB == 128) rc |= dalloc(h, &Q.gws, B * (size_t)HugeFmt::GWS);
-    rc |= dalloc(h, &h->adj_gw, B * G.n); rc |= dalloc(h, &h->adj_gu0, B * G.nu);
-    rc |= dalloc(h, &Q.ox0, B * S * G.nx); rc |= dalloc(h, &Q.oum1, B * S * G.nu); rc |= dalloc(h, &Q.ouref, B * S * G.nu);
-    rc |= dalloc(h, &Q.oxref, B * S * (size_t)G.N * G.nx);
-    rc |= dalloc(h, &Q.oq, B * G.n); rc |= dalloc(h, &Q.ol, B * G.m); rc |= dalloc(h, &Q.ou, B * G.m);
+    rc |= dalloc(h, &Q.x, B * C * L.n); rc |= dalloc(h, &Q.y, B * C * L.m); rc |= dalloc(h, &Q.g, B * C * L.n);
+    rc |= dalloc(h, &Q.r, B * C * L.n); rc |= dalloc(h, &Q.d, B * C * L.n); rc |= dalloc(h, &Q.e, B * C * L.n); rc |= dalloc(h, &Q.dd, B * C * L.n);
+    rc |= dalloc(h, &Q.gt, B * C * L.m);
+    rc |= dalloc(h, &h->adj_gw, B * L.n); rc |= dalloc(h, &h->adj_gu0, B * L.nu);
+    rc |= dalloc(h, &Q.ox0, B * S * L.nx); rc |= dalloc(h, &Q.oum1, B * S * L.nu); rc |= dalloc(h, &Q.ouref, B * S * L.nu);
+    rc |= dalloc(h, &Q.oxref, B * S * (size_t)L.N * L.nx);
+    rc |= dalloc(h, &Q.oq, B * L.n); rc |= dalloc(h, &Q.ol, B * L.m); rc |= dalloc(h, &Q.ou, B * L.m);
     int *status = nullptr;
     rc |= dalloc(h, &Q.nact, B); rc |= dalloc(h, &Q.nweak, B); rc |= dalloc(h, &status, B);
-    if (rc) return MPCQP_ERR_HIP;      // (what was allocated stays in h->allocs: freed by mpcqp_destroy)
+    if (rc) return MPCQP_ERR_HIP;
     Q.status = status;
-    h->aq = Q; h->smem_adjoint = smem;
+    h->aq = Q;
     return MPCQP_OK;
 }
 // One launch of k_adjoint: nseeds seeds per instance against one factorization (gw / gu0: the staged seeds of mpcqp_adjoint; both null: the
@@ -1141,25 +1150,30 @@ static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const d
     Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
     Q.nseeds = nseeds; Q.gw = gw; Q.gu0 = gu0; Q.chain = h->L.raw ? 0 : 1;
     if (!raw_out) { Q.oq = nullptr; Q.ol = nullptr; Q.ou = nullptr; }
-    Ptrs P = h->P; P.perm = nullptr; P.fown = nullptr;      // (workgroup b = instance b; the adjoint factors into its own buffers)
-    if (h->um1_moved) P.step = h->adj_step;
-    Lay G = polish_layout(h->L);                            // (the handle's Lay changes with raw-vector mode and the reference shape)
+    KpolLaunch v = kpol_launch(h);
+    Lay &G = v.G;
+    if (h->um1_moved) v.P.step = h->adj_step;
     // Several seeds against stages of at most 32 go four to a solve (kkt_core_cols): the work area then holds four row vectors and four stage-major
     // vectors, these two doubles further apart than their length so that the four lanes of a row position do not all meet in one LDS bank.  Where that does
     // not fit a workgroup's LDS the kernel loops over the seeds one at a time.
-    size_t smem = h->smem_adjoint;
     Q.ncol = 1; Q.cs = 0;
     if (nseeds > 1 && G.NB <= 32) {
         const int cs = G.N * G.NB + 2;
         Lay W = G; W.tsz = std::max(G.tsz, ADJOINT_COLS * (G.m + cs));      // (the row scratch of the passes around the solves, then the columns)
         const size_t wide = sizeof(double) * (size_t)smem_common_doubles(W);
-        if (wide <= 160 * 1024) { G = W; smem = wide; Q.ncol = ADJOINT_COLS; Q.cs = cs; }
+        if (wide <= 160 * 1024) { G = W; v.smem = wide; Q.ncol = ADJOINT_COLS; Q.cs = cs; }
     }
     DISPATCH_NB(G.NB, {
-        if (set_smem(k_adjoint<NB>, smem)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL(k_adjoint<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, P, Q);
+        if (set_smem(k_adjoint<NB>, v.smem)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_adjoint<NB>, dim3(h->batch), dim3(NT), v.smem, h->stream, G, v.P, Q);
     });
     HIPCHK(hipGetLastError());
+    return MPCQP_OK;
+}
+// The end of a call that copies to or from the caller's arrays (null: not given): wait, unless every one is a device pointer -- then the
+// call is stream-ordered throughout and there is nothing to wait for.
+static int sync_unless_all_device(mpcqp_handle *h, std::initializer_list<const void *> ptrs) {
+    for (const void *q : ptrs) if (q && !is_device_ptr(q)) { HIPCHK(hipStreamSynchronize(h->stream)); break; }
     return MPCQP_OK;
 }
 static int adjoint_ready(mpcqp_handle *h, const char *what, bool chain) {
@@ -1231,12 +1245,8 @@ static int adjoint_call(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp
             if (get(h, mout[f], src, (mo->batch_sum ? 1 : B) * sz * db)) return MPCQP_ERR_HIP;
         }
     }
-    const void *all[] = {io->g_w, io->g_u0, io->d_x0, io->d_uminus1, io->d_xref, io->d_uref, io->d_q, io->d_l, io->d_u,
-                         mout[0], mout[1], mout[2], mout[3], mout[4], mout[5], mout[6]};
-    bool dev = true;
-    for (const void *q : all) if (q && !is_device_ptr(q)) dev = false;
-    if (!dev) HIPCHK(hipStreamSynchronize(h->stream));      // (device buffers throughout: stream-ordered, no need to wait)
-    return MPCQP_OK;
+    return sync_unless_all_device(h, {io->g_w, io->g_u0, io->d_x0, io->d_uminus1, io->d_xref, io->d_uref, io->d_q, io->d_l, io->d_u,
+                                      mout[0], mout[1], mout[2], mout[3], mout[4], mout[5], mout[6]});
 }
 extern "C" int mpcqp_adjoint(mpcqp_handle *h, const mpcqp_adjoint_io *io) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
@@ -1257,11 +1267,7 @@ extern "C" int mpcqp_gains(mpcqp_handle *h, double *K_x0, double *K_uminus1, dou
     const AdjointArgs &Q = h->aq;
     if (get(h, K_x0, Q.ox0, B * S * L.nx * db) || get(h, K_uminus1, Q.oum1, B * S * L.nu * db) || get(h, K_uref, Q.ouref, B * S * L.nu * db) ||
         get(h, K_xref, Q.oxref, B * S * (size_t)L.xref_rows * L.nx * db)) return MPCQP_ERR_HIP;
-    const void *all[] = {K_x0, K_uminus1, K_xref, K_uref};
-    bool dev = true;
-    for (const void *q : all) if (q && !is_device_ptr(q)) dev = false;
-    if (!dev) HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    return sync_unless_all_device(h, {K_x0, K_uminus1, K_xref, K_uref});
 }
 extern "C" int mpcqp_get_adjoint_info(mpcqp_handle *h, int32_t *n_active, int32_t *n_weak, int32_t *status) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");

@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""Everything k_polish and k_adjoint compute, on the smallest cases that reach each of their code paths, written into one npz -- to compare
+two builds of the library bit for bit (a refactoring of mpcqp_kpol.h / mpcqp_polish.h / mpcqp_adjoint.h must not move a single bit):
+
+    python scripts/with_lib.py <parent.so> scripts/kpol_dump.py a.npz
+    python scripts/kpol_dump.py b.npz
+    python scripts/kpol_dump.py --compare a.npz b.npz        # exit status 1 if any array differs (float64 compared as uint64)
+
+Per case: after polish() the polished x, y, the iterate x, z, y, status_polish, obj_val / pri_res / dua_res; every output of
+adjoint(g_u0=..., want = all fourteen names) with and without batch_sum; every matrix of gains(); adjoint_info().  Cases: six golden
+fixtures, the first seed of six shapes of tests/adjoint_cases.py, a batch with an unsolved instance, a raw-vector handle (want q, l, u),
+an MPCController with polish=True stepped through update() (mpcqp_step_host), adjoint() right after BatchMPCController.step()."""
+import os
+import sys
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+
+EPS = 1e-9
+GOLDEN = ('cart_pole', 'cart_pole_nc1', 'point_mass_hard', 'small_mimo', 'random_5_3_8', 'quadcopter_nodu')
+SHAPES = ('nb16_nu6', 'nb16_nu7_hard', 'nb32_nu9_held', 'nb64_nu10_held', 'nb128_nu5', 'long200_nu2')
+CHAINED = ('x0', 'uminus1', 'xref', 'uref')
+RAW = ('q', 'l', 'u')
+MODEL = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu', 'eps_feas')
+
+
+def compare(a, b):
+    A, B = np.load(a), np.load(b)
+    bad = sorted(set(A.files) ^ set(B.files))
+    for k in sorted(set(A.files) & set(B.files)):
+        x, y = A[k], B[k]
+        same = x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x.view(np.uint64) if x.dtype == np.float64 else x,
+                                                                          y.view(np.uint64) if y.dtype == np.float64 else y)
+        if not same:
+            bad.append(k)
+    print('KPOL_COMPARE %d arrays, %d differ%s' % (len(A.files), len(bad), ': ' + ' '.join(bad) if bad else ''))
+    print('KPOL_ARRAYS ' + ' '.join(sorted(A.files)))
+    return 1 if bad else 0
+
+
+def dump_polish(out, tag, bp):
+    """polish() on the handle's last solve: the polished point, the iterate it replaces, its status and figures."""
+    bp.polish()
+    st = bp.polish_status()
+    x, y = bp.solution()[:2]
+    xi, zi, yi = bp.iterate_state()[:3]
+    infos = bp.infos()
+    out.update({tag + '/pol_x': np.array(x), tag + '/pol_y': np.array(y), tag + '/it_x': np.array(xi), tag + '/it_z': np.array(zi),
+                tag + '/it_y': np.array(yi), tag + '/status_polish': np.array(st),
+                tag + '/obj_pri_dua': np.array([[i.obj_val, i.pri_res, i.dua_res] for i in infos])})
+
+
+def dump_adjoint(out, tag, bp, want=CHAINED + RAW + MODEL, gains=True):
+    g = np.random.default_rng(3).standard_normal((bp.batch, bp.nu))
+    for bs in (False, True) if any(k in MODEL for k in want) else (False,):
+        res = bp.adjoint(g_u0=g, want=want, batch_sum=bs)
+        out.update({'%s/adj%d_%s' % (tag, bs, k): np.array(v) for k, v in res.items()})
+        out['%s/adj%d_info' % (tag, bs)] = np.stack(bp.adjoint_info())
+    if gains:
+        out.update({'%s/K_%s' % (tag, k): np.array(v) for k, v in bp.gains().items()})
+        out[tag + '/K_info'] = np.stack(bp.adjoint_info())
+
+
+def main():
+    if len(sys.argv) == 4 and sys.argv[1] == '--compare':
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) != 2 or sys.argv[1].startswith('-'):
+        sys.exit('usage: kpol_dump.py <out.npz> | kpol_dump.py --compare <a.npz> <b.npz>')
+    import adjoint_cases as ac
+    import adjoint_model_ref as am
+    from util import golden_kwargs, load_golden, apply_attrs, KW
+    from pympc_amd import MPCController, BatchMPCController
+    out = {}
+
+    def controller(kw, **settings):
+        attrs = getattr(kw, 'attrs', {})
+        kw = KW(kw); kw.attrs = attrs
+        kw.update(eps_abs=EPS, eps_rel=EPS)
+        K = apply_attrs(MPCController(**kw), kw)
+        K.solver_settings = dict(max_iter=400000, **settings)
+        K.setup()
+        return K
+
+    def batch(name, seeds):
+        K = BatchMPCController(**ac.batch_kwargs(name, seeds, eps_abs=EPS, eps_rel=EPS, max_iter=400000))
+        K.setup()
+        return K
+
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        for name in GOLDEN:                       # the adjoint first: it differentiates the solve, polish() then replaces the iterate
+            bp = controller(golden_kwargs(load_golden(name))).prob.batch_problem
+            dump_adjoint(out, name, bp)
+            dump_polish(out, name, bp)
+        for name in SHAPES:
+            bp = batch(name, ac.CASES[name]['seeds'][:1]).prob
+            dump_adjoint(out, name, bp)
+            dump_polish(out, name, bp)
+        name, bad = ac.INFEASIBLE                 # an unsolved instance among the columns: the "not computed" path
+        s = ac.CASES[name]['seeds']
+        K = batch(name, (s[0], s[1], bad, s[2]))
+        assert K.status()[2] == 'primal infeasible', K.status()
+        dump_adjoint(out, 'mixed', K.prob)
+        dump_polish(out, 'mixed', K.prob)
+        # raw-vector mode (chain = 0): only q, l, u
+        from pympc_amd.solver import DeviceProblem
+        from polish_ref import golden_qp
+        P, q, A, l, u = golden_qp(load_golden('random_12_4_30_b'))
+        prob = DeviceProblem()
+        prob.setup(P, q, A, l, u, eps_abs=EPS, eps_rel=EPS, max_iter=400000)
+        assert prob.solve().info.status == 'solved'
+        bp = prob.batch_problem
+        res = bp.adjoint(g_w=np.random.default_rng(5).standard_normal((1, bp.n)), want=RAW)
+        out.update({'raw/adj_' + k: np.array(v) for k, v in res.items()})
+        out['raw/adj_info'] = np.stack(bp.adjoint_info())
+        dump_polish(out, 'raw', bp)
+        # MPCController with polish=True through update(): k_polish's pub / done path under mpcqp_step_host
+        kw = golden_kwargs(load_golden('cart_pole'))
+        K = controller(kw, polish=True)
+        kw = am.full_kwargs(kw)
+        x = np.array(kw['x0'], dtype=float)
+        us, sp = [], []
+        for _ in range(4):
+            u = K.output()
+            x = np.asarray(kw['Ad']) @ x + np.asarray(kw['Bd']) @ u
+            K.update(x, u)
+            us.append(np.array(K.output(), dtype=float)); sp.append(int(K.res.info.status_polish))
+        out['step_host/u'] = np.array(us); out['step_host/status_polish'] = np.array(sp)
+        out['step_host/x'] = np.array(K.res.x, dtype=float); out['step_host/y'] = np.array(K.res.y, dtype=float)
+        # adjoint() right after BatchMPCController.step(): the step data hold the applied input, the kernels read the copy with u_{-1} put back
+        kw = am.full_kwargs(golden_kwargs(load_golden('small_mimo')))
+        B = 3
+        st = lambda k: np.stack([np.asarray(kw[k], dtype=float)] * B)
+        K = BatchMPCController(st('Ad'), st('Bd'), Np=kw['Np'], Nc=kw.get('Nc'), x0=st('x0'), xref=st('xref'), uref=st('uref'), uminus1=st('uminus1'),
+                               Qx=st('Qx'), QxN=st('QxN'), Qu=st('Qu'), QDu=st('QDu'), xmin=st('xmin'), xmax=st('xmax'), umin=st('umin'),
+                               umax=st('umax'), Dumin=st('Dumin'), Dumax=st('Dumax'), eps_feas=kw.get('eps_feas', 1e6), eps_abs=EPS, eps_rel=EPS,
+                               max_iter=400000)
+        K.setup(solve=False)
+        rng = np.random.default_rng(11)
+        out['after_step/u'] = np.array(K.step(st('x0') + 0.01 * rng.standard_normal((B, st('x0').shape[1])),
+                                              st('uminus1') + 0.01 * rng.standard_normal((B, st('uminus1').shape[1]))))
+        dump_adjoint(out, 'after_step', K.prob)
+    np.savez(sys.argv[1], **out)
+    print('KPOL_DUMP %d arrays -> %s' % (len(out), sys.argv[1]))
+
+
+if __name__ == '__main__':
+    main()

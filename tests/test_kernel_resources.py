@@ -93,3 +93,14 @@ def test_the_adjoint_kernels():
     assert int(ad[16]['ScratchSize']) == 0 and int(ad[16]['VGPRs']) == 256 and int(ad[16]['Occupancy']) >= 1, ad[16]
     for nb in (32, 64, 128):
         assert int(ad[nb]['Occupancy']) >= 1, (nb, ad[nb])
+
+
+def test_the_polish_kernels():
+    """k_polish<16> shares K_pol's factorization and refined solve with k_adjoint (mpcqp_kpol.h, every helper force-inlined) and, like it,
+    runs one workgroup per CU at the full register budget; the wider instantiations exist and are resident; none has scratch."""
+    ks = _kernels()
+    po = {int(m.group(1)): v for n, v in ks.items() for m in [re.match(r'_Z8k_polishILi(\d+)EE', n)] if m}
+    assert sorted(po) == [16, 32, 64, 128], sorted(po)
+    assert int(po[16]['VGPRs']) == 256, po[16]
+    for nb in (16, 32, 64, 128):
+        assert int(po[nb]['ScratchSize']) == 0 and int(po[nb]['Occupancy']) >= 1, (nb, po[nb])

@@ -32,6 +32,10 @@ ADJOINT_SYMBOLS = ['mpcqp_adjoint_default_settings', 'mpcqp_set_adjoint', 'mpcqp
 ADJOINT_MODEL_SYMBOLS = ['mpcqp_adjoint_model']
 ADJOINT_MODEL_NAMES = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu', 'eps_feas')      # the outputs of mpcqp_adjoint_model_io, in its order
 
+# include/mpcqp_rollout.h: likewise -- the device loop with a tape, and its derivative in one reverse sweep
+ROLLOUT_SYMBOLS = ['mpcqp_rollout', 'mpcqp_rollout_tape_bytes', 'mpcqp_rollout_release', 'mpcqp_rollout_adjoint', 'mpcqp_get_rollout_info',
+                   'mpcqp_rollout_get_tape']
+
 
 class PolishSettings(C.Structure):
     """mpcqp_polish_settings (include/mpcqp_polish.h)."""
@@ -56,6 +60,13 @@ class AdjointModelIO(C.Structure):
     """mpcqp_adjoint_model_io (include/mpcqp_adjoint_model.h): model gradients out; host or device pointers, None = not wanted."""
     _fields_ = [('struct_size', C.c_int32), ('batch_sum', C.c_int32), ('d_Ad', C.c_void_p), ('d_Bd', C.c_void_p), ('d_Qx', C.c_void_p),
                 ('d_QxN', C.c_void_p), ('d_Qu', C.c_void_p), ('d_QDu', C.c_void_p), ('d_eps_feas', C.c_void_p)]
+
+
+class RolloutAdjointIO(C.Structure):
+    """mpcqp_rollout_adjoint_io (include/mpcqp_rollout.h): trajectory seeds in, gradients out; host or device pointers, None = not given / not wanted."""
+    _fields_ = [('struct_size', C.c_int32), ('no_reuse', C.c_int32), ('G_x', C.c_void_p), ('G_u', C.c_void_p),
+                ('lam', C.c_void_p), ('d_uminus1', C.c_void_p), ('d_uref', C.c_void_p), ('d_xref', C.c_void_p),
+                ('d_Ap', C.c_void_p), ('d_Bp', C.c_void_p)]
 
 
 class Settings(C.Structure):
@@ -199,6 +210,15 @@ def load():
     if has_adjoint_model(L):
         L.mpcqp_adjoint_model.argtypes = [H, C.POINTER(AdjointIO), C.POINTER(AdjointModelIO)]
         L.mpcqp_adjoint_model.restype = C.c_int
+    if has_rollout(L):
+        L.mpcqp_rollout.argtypes = [H, C.c_int, C.POINTER(Loop)]
+        L.mpcqp_rollout_tape_bytes.argtypes = [H, C.c_int, C.POINTER(C.c_int64)]
+        L.mpcqp_rollout_release.argtypes = [H]
+        L.mpcqp_rollout_adjoint.argtypes = [H, C.POINTER(RolloutAdjointIO), C.POINTER(AdjointModelIO)]
+        L.mpcqp_get_rollout_info.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mpcqp_rollout_get_tape.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ROLLOUT_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -225,6 +245,12 @@ def has_adjoint_model(L=None):
     """True if the library exports include/mpcqp_adjoint_model.h (libmpcqp_hip.so does; the CPU twin does not)."""
     L = L if L is not None else load()
     return all(hasattr(L, name) for name in ADJOINT_MODEL_SYMBOLS)
+
+
+def has_rollout(L=None):
+    """True if the library exports include/mpcqp_rollout.h (libmpcqp_hip.so does; the CPU twin does not)."""
+    L = L if L is not None else load()
+    return all(hasattr(L, name) for name in ROLLOUT_SYMBOLS)
 
 
 def check(rc, what):

@@ -216,6 +216,32 @@ class BatchMPCController:
         self._u_last = None
         return res
 
+    def rollout(self, nsteps, w=None, Ap=None, Bp=None, xref_traj=None):
+        """``run`` that keeps a tape (mpcqp_rollout, include/mpcqp_rollout.h): the same loop, the same dict, one closed-loop launch per
+        step -- and afterwards ``rollout_adjoint`` differentiates a loss on the whole trajectory in one reverse sweep on the device.  No
+        estimator and no model schedule in a taped rollout."""
+        xt, ut, st, it = self.prob.rollout(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)[:4]
+        self.solve_count += int(nsteps)
+        self.x0_rh = xt[-1].copy()
+        if xref_traj is not None:
+            self.xref = np.asarray(xref_traj)[-1].reshape(self.B, -1)
+        self.uminus1_rh = ut[-1].copy()
+        self._um1_on_device = True
+        self._u_last = None
+        return dict(x=xt, u=ut, status=st, iter=it)
+
+    def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), batch_sum=False, no_reuse=False):
+        """Push a loss on the trajectory of the last ``rollout`` back through the closed loop (mpcqp_rollout_adjoint): ``g_x`` [K+1,B,nx] =
+        dL/dx_k, ``g_u`` [K,B,nu] = dL/du_k.  Returns the gradients named in ``want`` -- 'lam' [K+1,B,nx] (lam[0] = dL/dx0, lam[k+1] =
+        dL/dw[k]), 'uminus1', 'uref' [B,nu], 'xref' [K,B,rows*nx], 'Ap' [B,nx,nx], 'Bp' [B,nx,nu] (the plant path alone: with the
+        controller's own model as the plant, add them to 'Ad', 'Bd'), and 'Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu', 'eps_feas' summed over the
+        steps (``batch_sum``: and over the batch) -- plus ``n_weak`` [K,B], ``status`` [K,B] per step and ``n_factor`` [B], the
+        factorizations the sweep made.  numpy in, numpy out; torch device tensors in, device tensors out."""
+        res = self.prob.rollout_adjoint(g_x=g_x, g_u=g_u, want=want, batch_sum=batch_sum, no_reuse=no_reuse)
+        _, n_weak, status, n_factor = self.prob.rollout_info()
+        res.update(n_weak=n_weak, status=status, n_factor=n_factor)
+        return res
+
     def gains(self, like=None):
         """Local gains of the constrained control law of every instance at its last solve (mpcqp_gains, include/mpcqp_adjoint.h):
         ``dict(K_x0 [B,nu,nx], K_um1 [B,nu,nu], K_xref [B,nu,rows*nx], K_uref [B,nu,nu], n_weak [B], status [B])`` -- the Jacobians of u_0

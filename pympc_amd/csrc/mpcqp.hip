@@ -47,6 +47,7 @@
 #include "../../include/mpcqp_model.h"
 #include "../../include/mpcqp_adjoint.h"
 #include "../../include/mpcqp_adjoint_model.h"
+#include "../../include/mpcqp_rollout.h"
 
 #include "mpcqp_defs.h"
 
@@ -87,6 +88,7 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #include "mpcqp_polish.h"
 #include "mpcqp_adjoint.h"
 #include "mpcqp_adjoint_model.h"
+#include "mpcqp_rollout.h"
 #include "mpcqp_csc.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -148,6 +150,8 @@ struct mpcqp_handle {
     double *um1_used; bool um1_moved;    // mpcqp_mpc_step: the u_{-1} its solve was made with, [batch][nu]; true while the step data hold the applied input instead
     double *adj_step;                    // the adjoint's copy of the step data with that u_{-1} put back [batch][step_sz] (null until first needed)
     double *adjm_out, *adjm_sum;         // mpcqp_adjoint_model: the per-instance model gradients (field-major, AdjointModelArgs::out) and their batch sum; null until first use
+    RolloutTape tape; void *tape_buf; size_t tape_bytes;      // mpcqp_rollout (include/mpcqp_rollout.h): the tape, one device block (null until the first rollout)
+    int tape_xref_rows; bool tape_valid;                       // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
     bool has_solve;                      // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
 
@@ -241,6 +245,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     h->profiling = false; h->run_ms = 0.0; h->run_launches = 0; h->ev_count = 0; h->nevents = 0; h->stream = nullptr; h->own_stream = false;
     h->warm_x_pending = false;
     h->csc = nullptr; h->vec_buf = nullptr; h->step_blank = false;
+    memset(&h->tape, 0, sizeof(h->tape)); h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_xref_rows = 1; h->tape_valid = false;
     h->adjm_out = nullptr; h->adjm_sum = nullptr; h->um1_used = nullptr; h->um1_moved = false; h->adj_step = nullptr;
     h->pin_in = h->pin_out = nullptr; h->pin_in_dev = h->pin_out_dev = nullptr; h->done_dev = nullptr; h->host_seq = 0; h->pin_stride = 0; h->pin_tried = false;
     if (s) h->S = *s; else mpcqp_default_settings(&h->S);
@@ -389,6 +394,7 @@ extern "C" void mpcqp_destroy(mpcqp_handle *h) {
     if (h->stream) hipStreamSynchronize(h->stream);
     for (void *p : h->allocs) hipFree(p);
     if (h->run_buf) hipFree(h->run_buf);
+    if (h->tape_buf) hipFree(h->tape_buf);
     delete h->csc;
     if (h->vec_buf) hipFree(h->vec_buf);
     if (h->pin_in) hipHostFree(h->pin_in);
@@ -498,6 +504,7 @@ static int launch_setup(mpcqp_handle *h, bool keep = false) {
     const Lay &L = h->L;
     h->P.fown = nullptr;                            // (every instance factors into its own slot: sharing is off until mpcqp_share_factor is asked again)
     h->has_solve = false;                           // (a cold start or a new model: nothing to differentiate until the next solve, include/mpcqp_adjoint.h)
+    h->tape_valid = false;                          // (the model blob and the scaling a rollout's tape was made under are about to be replaced, include/mpcqp_rollout.h)
     if (flush_puts(h)) return MPCQP_ERR_HIP;
     const size_t lean = sizeof(double) * (size_t)(smem_common_doubles(L) - L.tsz);      // (the work area T is carved last and not touched by k_setup)
     const size_t de = sizeof(double) * (size_t)(L.n + L.m);
@@ -611,6 +618,7 @@ extern "C" int mpcqp_update_vectors(mpcqp_handle *h, const double *q, const doub
     if ((l == nullptr) != (u == nullptr)) return fail(MPCQP_ERR_ARG, "mpcqp_update_vectors: give l and u together (the equality rows l[:nx] == u[:nx] carry x0)");
     HIPCHK(hipSetDevice(h->device));
     h->has_solve = false;                           // (as in step_upload)
+    if (l) h->tape_valid = false;                   // (k_decode_vectors writes the boxes of l, u into the model blob, which a rollout's reverse sweep reads from the handle)
     if (!h->L.raw) {
         // entering raw mode: the vectors that are NOT given now must keep describing the current problem, so the
         // tables behind them are materialised once from the controller data (q from (xref, uref, u_{-1}); du0 from u_{-1})
@@ -1398,6 +1406,177 @@ extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *
     }
     return MPCQP_OK;
 }
+
+// ---- a rollout with a tape and its reverse sweep (include/mpcqp_rollout.h, mpcqp_rollout.h) ------------------------------------
+// The tape and the sweep's staging are ONE device block: a rollout that cannot get it changes nothing, and releasing it is one call.
+// base null: sizes only.  Returns the bytes of the block.
+static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, char *base, RolloutTape *T) {
+    const size_t B = (size_t)batch, K = (size_t)nsteps, nx = L.nx, nu = L.nu, xw = (size_t)xref_rows * nx, db = sizeof(double);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~size_t(255); return q; };
+    RolloutTape t; memset(&t, 0, sizeof(t));
+    t.x = (double *)take(K * B * L.n * db); t.z = (double *)take(K * B * L.m * db); t.y = (double *)take(K * B * L.m * db);
+    t.step = (double *)take(K * B * L.step_sz * db); t.u = (double *)take(K * B * nu * db); t.status = (int *)take(K * B * sizeof(int));
+    t.Ap = (double *)take(B * nx * nx * db); t.Bp = (double *)take(B * nx * nu * db);
+    t.gx = (double *)take((K + 1) * B * nx * db); t.gu = (double *)take(K * B * nu * db); t.lam = (double *)take((K + 1) * B * nx * db);
+    t.dxref = (double *)take(K * B * xw * db); t.dum1 = (double *)take(B * nu * db); t.duref = (double *)take(B * nu * db);
+    t.dAp = (double *)take(B * nx * nx * db); t.dBp = (double *)take(B * nx * nu * db);
+    t.carry = (double *)take(B * (size_t)rollout_carry_doubles(L) * db);
+    t.nact = (int *)take((3 * K * B + B) * sizeof(int)); t.nweak = t.nact + K * B; t.st = t.nweak + K * B; t.nfactor = t.st + K * B;
+    t.nsteps = nsteps; t.batch = batch;
+    if (T) *T = t;
+    return off;
+}
+extern "C" int mpcqp_rollout_tape_bytes(mpcqp_handle *h, int nsteps, int64_t *bytes) {
+    if (!h || !bytes || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tape_bytes: bad argument");
+    *bytes = (int64_t)tape_carve(h->L, h->batch, nsteps, h->L.xref_rows, nullptr, nullptr);
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_rollout_release(mpcqp_handle *h) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->tape_buf) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->tape_buf); }
+    h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_valid = false;
+    memset(&h->tape, 0, sizeof(h->tape));
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_rollout(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
+    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout: bad argument");
+    if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout: output feedback in a taped rollout is not implemented");
+    int rc = loop_check(h, nsteps, io);
+    if (rc) return rc;
+    if (!h->has_solve) return fail(MPCQP_ERR_STATE, "mpcqp_rollout: no solve since the last setup, update, model update or warm start: the iterate does not belong to the step data of tape entry 0");
+    if (io->xref_traj && io->xref_rows && io->xref_rows != h->L.xref_rows)
+        return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout: xref_traj must have the reference shape of the last upload (the entries of a tape have one shape)");
+    const Lay &L = h->L;
+    const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu, db = sizeof(double);
+    const size_t bytes = tape_carve(L, h->batch, nsteps, L.xref_rows, nullptr, nullptr);
+    if (!h->tape_buf || bytes > h->tape_bytes) {
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MPCQP_ERR_HIP, "mpcqp_rollout: the tape could not be allocated (mpcqp_rollout_tape_bytes says how much it takes)"); }
+        if (h->tape_buf) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->tape_buf); }
+        h->tape_buf = q; h->tape_bytes = bytes;
+    }
+    h->tape_valid = false;
+    RolloutTape T;
+    tape_carve(L, h->batch, nsteps, L.xref_rows, (char *)h->tape_buf, &T);
+    if (io->Ap) {
+        HIPCHK(hipMemcpyAsync(T.Ap, io->Ap, B * nx * nx * db, hipMemcpyDefault, h->stream));
+        HIPCHK(hipMemcpyAsync(T.Bp, io->Bp, B * nx * nu * db, hipMemcpyDefault, h->stream));
+    } else { T.Ap = nullptr; T.Bp = nullptr; }
+    HIPCHK(hipMemsetAsync(T.nact, 0, (3 * (size_t)nsteps * B + B) * sizeof(int), h->stream));      // (mpcqp_get_rollout_info before a sweep: all zero)
+    h->tape = T; h->tape_xref_rows = L.xref_rows;
+    const size_t xblk = (size_t)L.xref_rows * nx;
+    const size_t per = (size_t)L.n + 2 * (size_t)L.m + L.step_sz + nu + 1;
+    const unsigned grid = (unsigned)std::min<size_t>(1024, (B * per + 255) / 256);
+    for (int k = 0; k < nsteps; ++k) {
+        hipLaunchKernelGGL(k_rollout_tape, dim3(grid), dim3(256), 0, h->stream, h->L, h->P, T, k, (const double *)(h->um1_moved ? h->um1_used : nullptr));
+        HIPCHK(hipGetLastError());
+        mpcqp_loop seg = *io;                       // the trajectory buffers, advanced to step k (as mpcqp_mpc_loop_tv advances them per entry)
+        const size_t k0 = (size_t)k;
+        if (seg.w) seg.w += k0 * B * nx;
+        if (seg.xref_traj) seg.xref_traj += k0 * B * xblk;
+        if (seg.x_traj) seg.x_traj += k0 * B * nx;
+        if (seg.u_traj) seg.u_traj += k0 * B * nu;
+        if (seg.status_traj) seg.status_traj += k0 * B;
+        if (seg.iter_traj) seg.iter_traj += k0 * B;
+        if ((rc = loop_run(h, 1, &seg, k == nsteps - 1))) return rc;
+    }
+    h->tape_valid = true;
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
+    if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
+    if (io->struct_size != (int32_t)sizeof(mpcqp_rollout_adjoint_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: struct_size is not sizeof(mpcqp_rollout_adjoint_io)");
+    if (mo && mo->struct_size != (int32_t)sizeof(mpcqp_adjoint_model_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: struct_size is not sizeof(mpcqp_adjoint_model_io)");
+    if (!io->G_x && !io->G_u) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: give G_x, G_u or both");
+    if (io->no_reuse != 0 && io->no_reuse != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: no_reuse is 0 or 1");
+    if (mo && mo->batch_sum != 0 && mo->batch_sum != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: batch_sum is 0 or 1");
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint before mpcqp_setup");
+    if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the handle holds no tape (call mpcqp_rollout first)");
+    if (!h->tape_valid) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the model or the scaling the tape was made under has been replaced (mpcqp_setup*, mpcqp_update_model, mpcqp_update_vectors with l, u) or its rollout failed: roll out again");
+    double *const mout[ADJM_FIELDS] = {mo ? mo->d_Ad : nullptr, mo ? mo->d_Bd : nullptr, mo ? mo->d_Qx : nullptr, mo ? mo->d_QxN : nullptr,
+                                       mo ? mo->d_Qu : nullptr, mo ? mo->d_QDu : nullptr, mo ? mo->d_eps_feas : nullptr};
+    bool model = false;
+    for (double *q : mout) if (q) model = true;
+    HIPCHK(hipSetDevice(h->device));
+    int rc = adjoint_alloc(h);
+    if (rc) return rc;
+    const RolloutTape &T = h->tape;
+    KpolLaunch v = kpol_launch(h);
+    Lay &G = v.G;
+    G.raw = 0; G.xref_rows = h->tape_xref_rows;     // (the tape's entries, whatever the handle has been given since)
+    RolloutSweep W; memset(&W, 0, sizeof(W));
+    adjoint_model_offsets(G, W.off);
+    const size_t E = (size_t)W.off[ADJM_FIELDS], B = (size_t)h->batch, K = (size_t)T.nsteps, nx = G.nx, nu = G.nu, db = sizeof(double);
+    if (!h->adjm_out) {                                      // on first use, like the adjoint's other buffers
+        if (dalloc(h, &h->adjm_out, B * E) || dalloc(h, &h->adjm_sum, E)) return MPCQP_ERR_HIP;
+    }
+    if (io->G_x) HIPCHK(hipMemcpyAsync(T.gx, io->G_x, (K + 1) * B * nx * db, hipMemcpyDefault, h->stream));
+    else HIPCHK(hipMemsetAsync(T.gx, 0, (K + 1) * B * nx * db, h->stream));
+    if (io->G_u) HIPCHK(hipMemcpyAsync(T.gu, io->G_u, K * B * nu * db, hipMemcpyDefault, h->stream));
+    else HIPCHK(hipMemsetAsync(T.gu, 0, K * B * nu * db, h->stream));
+    AdjointArgs Q = h->aq;
+    Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
+    Q.nseeds = 1; Q.gw = nullptr; Q.gu0 = nullptr; Q.chain = 1; Q.ncol = 1; Q.cs = 0;
+    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = model ? 1 : 0;
+    const size_t with_carry = v.smem + db * (size_t)rollout_carry_doubles(G);
+    W.carry_lds = with_carry <= 160 * 1024 ? 1 : 0;         // (lam, mu, g behind the common block, or in the tape's few doubles of global memory)
+    const size_t smem = W.carry_lds ? with_carry : v.smem;
+    DISPATCH_NB(G.NB, {
+        if (set_smem(k_rollout_adjoint<NB>, smem)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_rollout_adjoint<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
+    });
+    HIPCHK(hipGetLastError());
+    const size_t xw = (size_t)G.xref_rows * nx;
+    if (get(h, io->lam, T.lam, (K + 1) * B * nx * db) || get(h, io->d_uminus1, T.dum1, B * nu * db) || get(h, io->d_uref, T.duref, B * nu * db) ||
+        get(h, io->d_xref, T.dxref, K * B * xw * db) || get(h, io->d_Ap, T.dAp, B * nx * nx * db) || get(h, io->d_Bp, T.dBp, B * nx * nu * db)) return MPCQP_ERR_HIP;
+    if (model) {
+        if (mo->batch_sum) {
+            AdjointModelArgs M; memset(&M, 0, sizeof(M));
+            adjoint_model_offsets(G, M.off);
+            M.out = h->adjm_out; M.batch = h->batch;
+            hipLaunchKernelGGL(k_adjoint_model_sum, dim3((unsigned)((E + 15) / 16)), dim3(256), 0, h->stream, M, h->adjm_sum);
+            HIPCHK(hipGetLastError());
+        }
+        for (int f = 0; f < ADJM_FIELDS; ++f) {
+            const size_t sz = (size_t)(W.off[f + 1] - W.off[f]);
+            const double *src = mo->batch_sum ? h->adjm_sum + W.off[f] : h->adjm_out + B * (size_t)W.off[f];
+            if (get(h, mout[f], src, (mo->batch_sum ? 1 : B) * sz * db)) return MPCQP_ERR_HIP;
+        }
+    }
+    return sync_unless_all_device(h, {io->G_x, io->G_u, io->lam, io->d_uminus1, io->d_uref, io->d_xref, io->d_Ap, io->d_Bp,
+                                      mout[0], mout[1], mout[2], mout[3], mout[4], mout[5], mout[6]});
+}
+extern "C" int mpcqp_get_rollout_info(mpcqp_handle *h, int32_t *n_active, int32_t *n_weak, int32_t *status, int32_t *n_factor) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_get_rollout_info: the handle holds no tape (call mpcqp_rollout first)");
+    HIPCHK(hipSetDevice(h->device));
+    const RolloutTape &T = h->tape;
+    const size_t kb = sizeof(int32_t) * (size_t)T.nsteps * (size_t)h->batch;
+    if (get(h, n_active, T.nact, kb) || get(h, n_weak, T.nweak, kb) || get(h, status, T.st, kb) ||
+        get(h, n_factor, T.nfactor, sizeof(int32_t) * (size_t)h->batch)) return MPCQP_ERR_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_rollout_get_tape(mpcqp_handle *h, int k, double *x, double *z, double *y, double *step, int32_t *status) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_get_tape: the handle holds no tape (call mpcqp_rollout first)");
+    const RolloutTape &T = h->tape;
+    if (k < 0 || k >= T.nsteps) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_get_tape: k must be in 0 .. nsteps - 1");
+    HIPCHK(hipSetDevice(h->device));
+    const Lay &L = h->L;
+    const size_t B = (size_t)h->batch, kB = (size_t)k * B, db = sizeof(double);
+    if (get(h, x, T.x + kB * L.n, B * L.n * db) || get(h, z, T.z + kB * L.m, B * L.m * db) || get(h, y, T.y + kB * L.m, B * L.m * db) ||
+        get(h, status, T.status + kB, B * sizeof(int32_t))) return MPCQP_ERR_HIP;
+    if (step) {
+        const size_t w = db * (size_t)(L.nx + L.nu + h->tape_xref_rows * L.nx);
+        HIPCHK(hipMemcpy2DAsync(step, w, T.step + kB * L.step_sz, db * (size_t)L.step_sz, w, B, hipMemcpyDefault, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
 
 extern "C" int mpcqp_mpc_run(mpcqp_handle *h, int nsteps, const double *w, const double *Ap, const double *Bp,
                              double *x_traj, double *u_traj, int32_t *status_traj, int32_t *iter_traj) {

@@ -1,0 +1,179 @@
+// mpcqp_rollout.h -- part of libmpcqp_hip (included by mpcqp.hip, one translation unit; C ABI in include/mpcqp_rollout.h).
+// A closed-loop rollout with a tape, and its derivative in one reverse sweep.
+//   forward   mpcqp_rollout runs the device loop one step per launch and puts k_rollout_tape in front of each: a grid-stride copy of what
+//             the handle holds at that moment -- the ADMM iterate, the step data (entry 0: with the u_{-1} its solve was made with, where
+//             mpcqp_mpc_step has already stored the next), the status, and the input output() is about to apply -- into tape entry k.
+//   reverse   k_rollout_adjoint<NB>: ONE launch, one 256-thread workgroup per instance walking its tape from entry K-1 down to 0.  Per entry it
+//             is k_adjoint (mpcqp_adjoint.h) with the pointers aimed at the tape -- kpol_row, kpol_factor, one seed through adjoint_residual /
+//             kpol_solve / adjoint_update, adjoint_outputs -- followed by the sums of adjoint_model_entry (mpcqp_adjoint_model.h), with the
+//             recursion of include/mpcqp_rollout.h around it.  lam, mu and g are carried in LDS behind the common block, or in a few doubles
+//             of global memory where that block already fills the workgroup's LDS.  The model gradients accumulate in the per-instance
+//             buffer k_adjoint_model writes (field-major: k_adjoint_model_sum adds it over the batch), the plant gradients in one of the tape's.
+//   reuse     the metric of K_pol is s = delta / D^2 (fixed) and omega = E^2 / delta on the active rows: it follows from the active set alone.
+//             The rows whose state differs from the one in place are counted while the set is written; where there is none and a factor
+//             is in place, kpol_factor is skipped.  The factorization is deterministic: the same bits either way.
+// Every sum over the steps is formed by the thread that owns the entry, in the order K-1 .. 0: no atomics, the same bits every time.
+#pragma once
+
+struct RolloutTape {
+    double *x, *z, *y;            // [K][batch][n], [K][batch][m] x2 the iterate of entry k (unscaled)
+    double *step;                 // [K][batch][step_sz] the step data its solve was made with
+    double *u;                    // [K][batch][nu] the input applied at step k
+    int *status;                  // [K][batch] mpcqp_info.status of entry k
+    double *Ap, *Bp;              // [batch][nx nx], [batch][nx nu] the plant, or null (the controller's Ad, Bd)
+    // the sweep's staging: seeds in, results out
+    double *gx, *gu;              // [K+1][batch][nx], [K][batch][nu]
+    double *lam;                  // [K+1][batch][nx]
+    double *dxref;                // [K][batch][xref_rows nx]
+    double *dum1, *duref;         // [batch][nu] x2
+    double *dAp, *dBp;            // [batch][nx nx], [batch][nx nu]
+    double *carry;                // [batch][rollout_carry_doubles] lam, mu, g where LDS has no room for them
+    int *nact, *nweak, *st;       // [K][batch]
+    int *nfactor;                 // [batch]
+    int nsteps, batch;
+};
+struct RolloutSweep {
+    double *mout;                 // the model gradients, field f of instance b: mout + batch off[f] + b (off[f + 1] - off[f])  (AdjointModelArgs::out)
+    int off[ADJM_FIELDS + 1];
+    int no_reuse, carry_lds, want_model;
+};
+
+// lam | lam as the plant alone gives it | d_x0 of the step | g | mu | d_uref of the step | d_uref so far
+__host__ __device__ inline int rollout_carry_doubles(const Lay &L) { return 3 * L.nx + 4 * L.nu; }
+
+// Entry k of the tape from what the handle holds now.  um1: the u_{-1} the current solve was made with where the step data no longer have it, else null.
+__global__ __launch_bounds__(256) void k_rollout_tape(Lay L, Ptrs P, RolloutTape T, int k, const double *um1) {
+    const size_t B = (size_t)T.batch, n = L.n, m = L.m, ss = L.step_sz, nu = L.nu;
+    const size_t per = n + 2 * m + ss + nu + 1, total = B * per;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t b = idx / per, kb = (size_t)k * B + b;
+        size_t i = idx - b * per;
+        if (i < n) { T.x[kb * n + i] = P.x[b * n + i]; continue; }
+        i -= n;
+        if (i < m) { T.z[kb * m + i] = P.z[b * m + i]; continue; }
+        i -= m;
+        if (i < m) { T.y[kb * m + i] = P.y[b * m + i]; continue; }
+        i -= m;
+        if (i < ss) { T.step[kb * ss + i] = (um1 && i >= (size_t)L.nx && i < (size_t)(L.nx + L.nu)) ? um1[b * nu + (i - L.nx)] : P.step[b * ss + i]; continue; }
+        i -= ss;
+        const int status = P.info[b].status;
+        if (i < nu) T.u[kb * nu + i] = status == MPCQP_SOLVED ? P.xo[b * n + L.ou + i] : P.model[b * L.model_sz + L.ouref + i];      // (output(), as k_mpc_run applies it)
+        else T.status[kb] = status;
+    }
+}
+
+template <int NB>
+__global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) {
+    extern __shared__ __attribute__((aligned(16))) double sh[];
+    double *p = sh; Smem S; smem_common(L, P, p, S);       // (P.perm is null: workgroup b works on instance b)
+    const int b = blockIdx.x, tid = threadIdx.x, B = T.batch, K = T.nsteps;
+    const int nx = L.nx, nu = L.nu, xw = L.xref_rows * L.nx, EN = W.off[ADJM_FIELDS];
+    double *lam = W.carry_lds ? p : T.carry + (size_t)b * rollout_carry_doubles(L);
+    double *lamn = lam + nx, *dx0 = lamn + nx, *g = dx0 + nx, *mu = g + nu, *durk = mu + nu, *dur = durk + nu;
+    const double *model = P.model + (size_t)b * L.model_sz;
+    const double *D = P.D + (size_t)b * L.n, *E = P.E + (size_t)b * L.m;
+    const double cc = P.c[b], delta = Q.delta;
+    double *om = Q.K.om + (size_t)b * L.m, *sv = Q.K.s + (size_t)b * L.n;
+    int *act = Q.K.act + (size_t)b * L.m;
+    const size_t vn = (size_t)b * ADJOINT_COLS * L.n, vm = (size_t)b * ADJOINT_COLS * L.m;      // (column 0 of the adjoint's work area)
+    double *xs = Q.x + vn, *ys = Q.y + vm, *gs = Q.g + vn, *gts = Q.gt + vm;
+    double *rs = Q.r + vn, *ds = Q.d + vn, *es = Q.e + vn, *dds = Q.dd + vn;
+    double *dAp = T.dAp + (size_t)b * nx * nx, *dBp = T.dBp + (size_t)b * nx * nu;
+    AdjointModelArgs M;                                  // (adjoint_model_entry reads the field offsets only)
+#pragma unroll
+    for (int f = 0; f <= ADJM_FIELDS; ++f) M.off[f] = W.off[f];
+    auto mdst = [&](int e) -> double & {
+        int f = 0;
+        while (e >= W.off[f + 1]) ++f;
+        return W.mout[(size_t)B * W.off[f] + (size_t)b * (W.off[f + 1] - W.off[f]) + (e - W.off[f])];
+    };
+    // lam_K = G_x[K], mu = 0, every sum 0; the fixed half of K_pol's metric
+    for (int i = tid; i < nx; i += NT) { const double v = T.gx[((size_t)K * B + b) * nx + i]; lam[i] = v; T.lam[((size_t)K * B + b) * nx + i] = v; }
+    for (int j = tid; j < nu; j += NT) { mu[j] = 0.0; dur[j] = 0.0; }
+    for (int e = tid; e < EN; e += NT) mdst(e) = 0.0;
+    for (int e = tid; e < nx * nx; e += NT) dAp[e] = 0.0;
+    for (int e = tid; e < nx * nu; e += NT) dBp[e] = 0.0;
+    for (int j = tid; j < L.n; j += NT) sv[j] = delta / (D[j] * D[j]);
+    __syncthreads();
+    Kpol kp = {};
+    bool have = false;                                   // a factor of the active set in act[] is in place
+    int nfac = 0;
+    for (int k = K - 1; k >= 0; --k) {
+        const size_t kb = (size_t)k * B + b;
+        const double *step = T.step + kb * L.step_sz;
+        load_common(L, model, step, S);                  // (x_k, u_{-1} and the first Delta-u bounds of this entry; ends with a barrier)
+        {   // g = G_u[k] + Bp' lam_{k+1} + mu;  lam_k = G_x[k] + Ap' lam_{k+1} (+ d_x0 below);  d_Ap += lam_{k+1} x_k',  d_Bp += lam_{k+1} u_k'
+            const double *Ap = T.Ap ? T.Ap + (size_t)b * nx * nx : S.hot + L.oAd, *Bp = T.Bp ? T.Bp + (size_t)b * nx * nu : S.hot + L.oBd;
+            const double *uk = T.u + kb * nu;
+            for (int j = tid; j < nu; j += NT) {
+                double a = T.gu[kb * nu + j] + mu[j];
+                for (int i = 0; i < nx; ++i) a += Bp[i * nu + j] * lam[i];
+                g[j] = a;
+            }
+            for (int i = tid; i < nx; i += NT) {
+                double a = T.gx[kb * nx + i];
+                for (int r = 0; r < nx; ++r) a += Ap[r * nx + i] * lam[r];
+                lamn[i] = a;
+            }
+            for (int e = tid; e < nx * nx; e += NT) { const int r = e / nx; dAp[e] += lam[r] * S.x0s[e - r * nx]; }
+            for (int e = tid; e < nx * nu; e += NT) { const int r = e / nu; dBp[e] += lam[r] * uk[e - r * nu]; }
+        }
+        __syncthreads();
+        int st = 0, nact = 0, nweak = 0;
+        if (T.status[kb] == MPCQP_SOLVED) {
+            Ctx c{L, S.hot, model + L.hot_sz};
+            const double *wa = T.x + kb * L.n, *za = T.z + kb * L.m, *ya = T.y + kb * L.m;
+            // 1. the active set of this entry (k_adjoint's step 1), and how many rows differ from the set in place
+            double ymx[1] = {0.0}, cnt[3] = {0.0, 0.0, 0.0};
+            for (int i = tid; i < L.m; i += NT) ymx[0] = fmax(ymx[0], fabs(ya[i]));
+            block_reduce<1, 3>(ymx, cnt, S.red);
+            const double ytol = Q.weak_tol * fmax(1.0, ymx[0]);
+            for (int i = tid; i < L.m; i += NT) {
+                double lo, hi; row_bounds(c, S.x0s, S.du0, i, lo, hi);
+                const double zv = za[i], yv = ya[i];
+                const int a = kpol_row(E[i], zv, yv, lo, hi, cc, delta, true, om[i]);
+                if (a != act[i]) cnt[2] += 1.0;
+                act[i] = a;
+                if (a) cnt[0] += 1.0;
+                if (lo != hi && fmin(zv - lo, hi - zv) <= Q.weak_tol * fmax(1.0, fabs(zv)) && fabs(yv) <= ytol) cnt[1] += 1.0;
+            }
+            block_reduce<1, 3>(ymx, cnt, S.red);             // (ends with a barrier: act, om are visible)
+            nact = (int)cnt[0]; nweak = (int)cnt[1];
+            // 2. factor K_pol, unless the factor in place belongs to this very set
+            bool bad = false;
+            if (!have || cnt[2] != 0.0 || W.no_reuse) { bad = !kpol_factor<NB>(c, Q.K, b, om, sv, cc, S, kp); ++nfac; }
+            // 3. the seed g on the u_0 block: one solve from zero, then the refinement sweeps against the unregularized system
+            if (!bad) {
+                adjoint_seeds<1>(L, nullptr, g, 0, gs, xs, ys);
+                double lastrel[1] = {0.0};
+                unsigned live = 1u;
+                for (int sw = 0; sw <= Q.refine + Q.extra && live && !bad; ++sw) {
+                    adjoint_residual<1>(c, act, om, cc, live, xs, ys, gs, S.T, gts, rs);
+                    kpol_solve<NB, 1>(c, kp, cc, live, rs, ds, es, dds, S, 0);
+                    live = adjoint_update<1>(c, act, om, cc, live, sw >= Q.refine, xs, ys, ds, gts, S.red, lastrel, bad);
+                }
+            }
+            have = !bad;
+            if (!bad) {
+                // 4. the chain rule into x_k, u_{-1}, xref, uref; 5. the model gradients of this entry onto the sums
+                const AdjointOut o{dx0, mu, T.dxref + kb * xw, durk, nullptr, nullptr, nullptr};
+                adjoint_outputs(c, act, xs, ys, 0, 1, o);
+                if (W.want_model) for (int e = tid; e < EN; e += NT) mdst(e) += adjoint_model_entry(L, M, wa, xs, ya, ys, model, step, e, 0, 1);
+                __syncthreads();
+                for (int i = tid; i < nx; i += NT) lam[i] = lamn[i] + dx0[i];
+                for (int j = tid; j < nu; j += NT) dur[j] += durk[j];
+            }
+            st = bad ? -1 : 1;
+        }
+        if (st != 1) {                                   // u_failure = uref was applied (not solved), or nothing can be said (a broken factor)
+            for (int i = tid; i < nx; i += NT) lam[i] = lamn[i];
+            for (int j = tid; j < nu; j += NT) { if (st == 0) dur[j] += g[j]; mu[j] = 0.0; }
+            for (int i = tid; i < xw; i += NT) T.dxref[kb * xw + i] = 0.0;
+        }
+        for (int i = tid; i < nx; i += NT) T.lam[kb * nx + i] = lam[i];      // (the thread that wrote lam[i])
+        if (tid == 0) { T.st[kb] = st; T.nact[kb] = nact; T.nweak[kb] = nweak; }
+        __syncthreads();
+    }
+    for (int j = tid; j < nu; j += NT) { T.dum1[(size_t)b * nu + j] = mu[j]; T.duref[(size_t)b * nu + j] = dur[j]; }
+    if (tid == 0) T.nfactor[b] = nfac;
+}

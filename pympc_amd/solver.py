@@ -343,6 +343,99 @@ class BatchProblem:
         _lib.check(self._L.mpcqp_get_adjoint_info(self._h, *[_ptr(o) for o in out]), 'mpcqp_get_adjoint_info')
         return tuple(out)
 
+    # -- a rollout with a tape and its reverse sweep (include/mpcqp_rollout.h) ---------------------
+    _rollout_shape = None      # (nsteps, xref rows) of the tape the handle holds
+    rollout_count = 0          # rollouts made so far (pympc_amd.torch_layer: is the tape still the one of a forward?)
+
+    def _need_rollout(self):
+        if not _lib.has_rollout(self._L):
+            raise NotImplementedError('this build of the solver library has no taped rollout (include/mpcqp_rollout.h)')
+
+    def rollout(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
+        """``mpc_run`` that keeps a tape (mpcqp_rollout): the same arguments and results, one closed-loop launch per step, and afterwards
+        ``rollout_adjoint`` can push a loss on the trajectory back through the loop.  No estimator, no model schedule."""
+        self._need_rollout()
+        res = self.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, _taped=True)
+        self._rollout_shape = (int(nsteps), self._xref_rows_last)
+        self.rollout_count += 1
+        return res
+
+    def rollout_tape_bytes(self, nsteps):
+        """Device memory a tape of ``nsteps`` steps takes (mpcqp_rollout_tape_bytes)."""
+        self._need_rollout()
+        v = C.c_int64()
+        _lib.check(self._L.mpcqp_rollout_tape_bytes(self._h, int(nsteps), C.byref(v)), 'mpcqp_rollout_tape_bytes')
+        return v.value
+
+    def rollout_release(self):
+        """Free the tape (mpcqp_rollout_release)."""
+        self._need_rollout()
+        _lib.check(self._L.mpcqp_rollout_release(self._h), 'mpcqp_rollout_release')
+        self._rollout_shape = None
+
+    def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), out=None, batch_sum=False, no_reuse=False):
+        """The reverse sweep over the tape of the last ``rollout`` (mpcqp_rollout_adjoint): for ``g_x`` [K+1, B, nx] = dL/dx_k and / or
+        ``g_u`` [K, B, nu] = dL/du_k returns a dict with the gradients named in ``want`` -- 'lam' [K+1, B, nx] (lam[0] = dL/dx0,
+        lam[k+1] = dL/dw[k]), 'uminus1' [B, nu], 'uref' [B, nu], 'xref' [K, B, rows*nx] (entry k: the reference step k was solved with),
+        'Ap' [B, nx, nx], 'Bp' [B, nx, nu] (the plant path alone) and the model gradients of ``adjoint`` ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu',
+        'eps_feas'; ``batch_sum`` as there), summed over the steps.  ``no_reuse``: factor at every step (the same bits, for measurements).
+        numpy in, numpy out; torch device tensors in, device tensors out (stream-ordered, no wait)."""
+        self._need_rollout()
+        if g_x is None and g_u is None:
+            raise ValueError('rollout_adjoint: give g_x, g_u or both')
+        if self._rollout_shape is None:
+            raise RuntimeError('rollout_adjoint: no rollout has been made (mpcqp_rollout)')
+        K, rows = self._rollout_shape
+        B, nx, nu = self.batch, self.nx, self.nu
+        like = g_x if g_x is not None else g_u
+        gx = _prep(g_x, (K + 1, B, nx), 'g_x') if g_x is not None else None
+        gu = _prep(g_u, (K, B, nu), 'g_u') if g_u is not None else None
+        shapes = dict(lam=(K + 1, B, nx), uminus1=(B, nu), uref=(B, nu), xref=(K, B, rows * nx), Ap=(B, nx, nx), Bp=(B, nx, nu))
+        Bm = 1 if batch_sum else B
+        mshapes = dict(Ad=(Bm, nx, nx), Bd=(Bm, nx, nu), Qx=(Bm, nx, nx), QxN=(Bm, nx, nx), Qu=(Bm, nu, nu), QDu=(Bm, nu, nu), eps_feas=(Bm,))
+        io = _lib.RolloutAdjointIO()
+        io.struct_size, io.no_reuse = C.sizeof(_lib.RolloutAdjointIO), int(bool(no_reuse))
+        io.G_x, io.G_u = _ptr(gx), _ptr(gu)
+        mo = _lib.AdjointModelIO()
+        mo.struct_size, mo.batch_sum = C.sizeof(_lib.AdjointModelIO), int(bool(batch_sum))
+        res = {}
+        for k in want:
+            if k not in shapes and k not in mshapes:
+                raise TypeError('unknown gradient %r' % k)
+            shape = shapes[k] if k in shapes else mshapes[k]
+            a = _prep_out(out[k], shape, 'out[%r]' % k) if out is not None and k in out else self._out(like, shape)
+            res[k] = a
+            if k in mshapes:
+                setattr(mo, 'd_' + k, _ptr(a))
+            else:
+                setattr(io, k if k == 'lam' else 'd_' + k, _ptr(a))
+        self._keep = [gx, gu, res]
+        _lib.check(self._L.mpcqp_rollout_adjoint(self._h, C.byref(io), C.byref(mo)), 'mpcqp_rollout_adjoint')
+        return res
+
+    def rollout_info(self):
+        """(n_active [K, B], n_weak [K, B], status [K, B], n_factor [B]) int32 of the last ``rollout_adjoint`` (mpcqp_get_rollout_info;
+        synchronises): per tape entry as ``adjoint_info``; n_factor: the factorizations the sweep made."""
+        self._need_rollout()
+        if self._rollout_shape is None:
+            raise RuntimeError('rollout_info: no rollout has been made (mpcqp_rollout)')
+        K = self._rollout_shape[0]
+        out = [np.zeros((K, self.batch), dtype=np.int32) for _ in range(3)] + [np.zeros(self.batch, dtype=np.int32)]
+        _lib.check(self._L.mpcqp_get_rollout_info(self._h, *[_ptr(o) for o in out]), 'mpcqp_get_rollout_info')
+        return tuple(out)
+
+    def rollout_tape(self, k):
+        """Tape entry k (mpcqp_rollout_get_tape; verification): dict(x [B, n], z, y [B, m], step [B, nx + nu + rows*nx] = (x_k | the u_{-1}
+        the solve was made with | xref), status [B])."""
+        self._need_rollout()
+        if self._rollout_shape is None:
+            raise RuntimeError('rollout_tape: no rollout has been made (mpcqp_rollout)')
+        B, rows = self.batch, self._rollout_shape[1]
+        r = dict(x=np.empty((B, self.n)), z=np.empty((B, self.m)), y=np.empty((B, self.m)),
+                 step=np.empty((B, self.nx + self.nu + rows * self.nx)), status=np.zeros(B, dtype=np.int32))
+        _lib.check(self._L.mpcqp_rollout_get_tape(self._h, int(k), *[_ptr(r[n]) for n in ('x', 'z', 'y', 'step', 'status')]), 'mpcqp_rollout_get_tape')
+        return r
+
     def _finish_init(self, stream):
         n, m, fd, nnzL = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
         _lib.check(self._L.mpcqp_get_dims(self._h, C.byref(n), C.byref(m), C.byref(fd), C.byref(nnzL)), 'mpcqp_get_dims')
@@ -553,7 +646,7 @@ class BatchProblem:
         buf = np.frombuffer(cb, dtype=np.float64)
         return buf[:n].reshape(1, n), buf[n:].reshape(1, m), info
 
-    def mpc_run(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None):
+    def mpc_run(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None, _taped=False):
         """Device-side receding-horizon loop (mpcqp_mpc_loop): ``nsteps`` closed-loop steps
         ``u = output(); x = Ap x + Bp u + w[k]; update(x)`` of every instance without host round trips.
 
@@ -621,6 +714,9 @@ class BatchProblem:
             mt.Ad = inp(Adt, (nm, B, nx, nx), 'model_traj Ad'); mt.Bd = inp(Bdt, (nm, B, nx, nu), 'model_traj Bd')
             rc = self._L.mpcqp_mpc_loop_tv(self._h, K, C.byref(io), C.byref(mt))
             what = 'mpcqp_mpc_loop_tv'
+        elif _taped:                              # (rollout(): the same loop, and a tape of it)
+            rc = self._L.mpcqp_rollout(self._h, K, C.byref(io))
+            what = 'mpcqp_rollout'
         else:
             rc = self._L.mpcqp_mpc_loop(self._h, K, C.byref(io))
             what = 'mpcqp_mpc_loop'

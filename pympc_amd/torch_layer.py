@@ -101,3 +101,99 @@ def mpc_step(controller, x, u_prev=None, xref=None, params=None):
         if not hasattr(params[n], 'data_ptr') or not params[n].is_cuda or params[n].dim() not in (2, 3):
             raise ValueError('mpc_step: params[%r] must be a device tensor [B, ., .] or [., .]' % n)
     return _MPCStep.apply(controller, x, u_prev, xref, names, *[params[n] for n in names])
+
+
+# ---- a closed-loop rollout as one differentiable operation (include/mpcqp_rollout.h) ---------------------------------------------------
+class _MPCRollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, K, nsteps, x0, u_prev, xref, w, Ap, Bp, names, *params):
+        if not x0.is_cuda:
+            raise ValueError('mpc_rollout works on device tensors (x0 is on %s)' % x0.device)
+        sync = _sync_needed(K)
+        if sync:
+            torch.cuda.current_stream().synchronize()
+        det = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
+        if names:
+            K.update_model(solve=False, **{n: det(p) for n, p in zip(names, params)})
+        xr = det(xref)
+        K.update(det(x0), det(u_prev), None if xr is None else xr.reshape(K.B, -1))      # (and the solve for x_0: tape entry 0)
+        kw = dict(dtype=torch.float64, device=x0.device)
+        X, U = torch.empty((nsteps + 1, K.B, K.nx), **kw), torch.empty((nsteps, K.B, K.nu), **kw)
+        st, it = (torch.empty((nsteps, K.B), dtype=torch.int32, device=x0.device) for _ in range(2))
+        bc = lambda t, shape: None if t is None else det(t).expand(shape).contiguous()
+        K.prob.rollout(nsteps, w=det(w), Ap=bc(Ap, (K.B, K.nx, K.nx)), Bp=bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it])
+        K.solve_count += nsteps
+        K.x0_rh, K.uminus1_rh, K._um1_on_device, K._u_last = X[-1], U[-1], True, None
+        if sync:
+            K.prob.synchronize()
+        ctx.K, ctx.count = K, K.prob.rollout_count
+        ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (x0, u_prev, xref, w, Ap, Bp))
+        ctx.names, ctx.pshapes = names, tuple(tuple(p.shape) for p in params)
+        ctx.status, ctx.iters = st, it
+        return X, U
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_U):
+        K = ctx.K
+        if K.prob.rollout_count != ctx.count:
+            raise RuntimeError('mpc_rollout: the controller has been rolled out again since this forward (rollout %d then, %d now); '
+                               'its tape is no longer the one to differentiate.' % (ctx.count, K.prob.rollout_count))
+        need = dict(zip(('x0', 'u_prev', 'xref', 'w', 'Ap', 'Bp'), ctx.needs_input_grad[2:8]))
+        need = {n: v and shp is not None for (n, v), shp in zip(need.items(), ctx.shapes)}
+        pneed = [n for n, v in zip(ctx.names, ctx.needs_input_grad[9:]) if v]
+        if not any(need.values()) and not pneed:
+            return (None,) * (9 + len(ctx.names))
+        own_plant = ctx.shapes[4] is not None
+        # the controller's own model as the plant: Ad, Bd are then one parameter with two paths, and the plant's comes back on its own
+        plant = [n for n, m in (('Ap', 'Ad'), ('Bp', 'Bd')) if (need[n] if own_plant else m in pneed)]
+        want = ([n for n, k in (('lam', 'x0'), ('uminus1', 'u_prev'), ('xref', 'xref')) if need[k]] + (['lam'] if need['w'] and not need['x0'] else [])
+                + plant + pneed)
+        shared = {n: len(shp) == 2 for n, shp in zip(ctx.names, ctx.pshapes)}
+        batch_sum = bool(pneed) and all(shared[n] for n in pneed)
+        sync = _sync_needed(K)
+        if sync:
+            torch.cuda.current_stream().synchronize()
+        res = K.prob.rollout_adjoint(g_x=grad_X.to(torch.float64).contiguous(), g_u=grad_U.to(torch.float64).contiguous(), want=want, batch_sum=batch_sum)
+        if sync:
+            K.prob.synchronize()
+        g = lambda v, shp: None if v is None else v.reshape(shp)
+        grads = [g(res['lam'][0] if need['x0'] else None, ctx.shapes[0]), g(res.get('uminus1'), ctx.shapes[1]),
+                 g(res['xref'].sum(dim=0) if need['xref'] else None, ctx.shapes[2]), g(res['lam'][1:] if need['w'] else None, ctx.shapes[3])]
+        for n, shp in (('Ap', ctx.shapes[4]), ('Bp', ctx.shapes[5])):
+            v = res.get(n) if own_plant and need[n] else None
+            grads.append(None if v is None else (v.sum(dim=0) if len(shp) == 2 else v).reshape(shp))
+        pgrads = []
+        for n, shp in zip(ctx.names, ctx.pshapes):
+            v = res.get(n) if n in pneed else None
+            if v is not None:
+                v = (v[0] if batch_sum else v.sum(dim=0)) if shared[n] else v
+                if not own_plant and n in ('Ad', 'Bd'):
+                    p = res['Ap' if n == 'Ad' else 'Bp']
+                    v = v + (p.sum(dim=0) if shared[n] else p)
+                v = v.reshape(shp)
+            pgrads.append(v)
+        return (None, None) + tuple(grads) + (None,) + tuple(pgrads)
+
+
+def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None):
+    """``(X [K+1,B,nx], U [K,B,nu])`` of ``nsteps`` = K closed-loop steps of a set-up ``BatchMPCController`` from ``x0`` [B,nx] against the
+    plant x_{k+1} = Ap x_k + Bp u_k + w[k] (``Ap`` / ``Bp`` None: the controller's own Ad, Bd; ``w`` [K,B,nx] or None), on ONE controller:
+    forward is ``update_model(solve=False, **params)`` where given, ``update(x0, u_prev, xref)`` with its solve, then
+    ``BatchMPCController.rollout``'s device loop with a tape (mpcqp_rollout); backward is ONE ``mpcqp_rollout_adjoint`` call with
+    ``G_x = grad_X``, ``G_u = grad_U`` -- one reverse sweep over the tape on the device, which factors the active-set system of a step only
+    where its active set differs from the step's behind it.  Differentiable with respect to ``x0``, ``u_prev``, ``xref`` (constant over
+    the rollout), ``w``, ``Ap``, ``Bp`` ([B, ., .] or unbatched) and ``params`` (as in ``mpc_step``; with ``Ap`` / ``Bp`` None the gradients
+    of ``params['Ad']`` / ``['Bd']`` include the plant path).  A step whose solve does not end 'solved' applies ``u_failure`` = uref and
+    passes the gradient through the plant alone.  The tape is a copy: stepping or solving the controller between forward and backward is
+    fine, another rollout is not -- the backward then raises."""
+    if controller.prob is None:
+        raise RuntimeError('mpc_rollout needs a controller that has been set up')
+    names = tuple(params) if params else ()
+    for n in names:
+        if n not in MODEL_PARAMS:
+            raise TypeError('mpc_rollout: unknown model parameter %r (one of %s)' % (n, ', '.join(MODEL_PARAMS)))
+        if not hasattr(params[n], 'data_ptr') or not params[n].is_cuda or params[n].dim() not in (2, 3):
+            raise ValueError('mpc_rollout: params[%r] must be a device tensor [B, ., .] or [., .]' % n)
+    if (Ap is None) != (Bp is None):
+        raise ValueError('mpc_rollout: give both Ap and Bp or neither')
+    return _MPCRollout.apply(controller, int(nsteps), x0, u_prev, xref, w, Ap, Bp, names, *[params[n] for n in names])

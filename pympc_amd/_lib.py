@@ -36,6 +36,9 @@ ADJOINT_MODEL_NAMES = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu', 'eps_feas')      # 
 ROLLOUT_SYMBOLS = ['mpcqp_rollout', 'mpcqp_rollout_tape_bytes', 'mpcqp_rollout_release', 'mpcqp_rollout_adjoint', 'mpcqp_get_rollout_info',
                    'mpcqp_rollout_get_tape']
 
+# include/mpcqp_rollout_est.h: likewise -- the taped rollout of the output-feedback loop, differentiated through the estimator
+ROLLOUT_EST_SYMBOLS = ['mpcqp_rollout_est', 'mpcqp_rollout_est_tape_bytes', 'mpcqp_rollout_adjoint_est', 'mpcqp_rollout_get_tape_est']
+
 
 class PolishSettings(C.Structure):
     """mpcqp_polish_settings (include/mpcqp_polish.h)."""
@@ -67,6 +70,12 @@ class RolloutAdjointIO(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('no_reuse', C.c_int32), ('G_x', C.c_void_p), ('G_u', C.c_void_p),
                 ('lam', C.c_void_p), ('d_uminus1', C.c_void_p), ('d_uref', C.c_void_p), ('d_xref', C.c_void_p),
                 ('d_Ap', C.c_void_p), ('d_Bp', C.c_void_p)]
+
+
+class RolloutEstIO(C.Structure):
+    """mpcqp_rollout_est_io (include/mpcqp_rollout_est.h): the estimator's seeds in, gradients out; host or device pointers, None = not given / not wanted."""
+    _fields_ = [('struct_size', C.c_int32), ('G_xhat', C.c_void_p), ('G_y', C.c_void_p), ('eta', C.c_void_p), ('d_C', C.c_void_p),
+                ('d_L', C.c_void_p), ('d_v', C.c_void_p), ('d_Ae', C.c_void_p), ('d_Be', C.c_void_p)]
 
 
 class Settings(C.Structure):
@@ -219,6 +228,13 @@ def load():
         L.mpcqp_rollout_get_tape.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ROLLOUT_SYMBOLS:
             getattr(L, name).restype = C.c_int
+    if has_rollout_est(L):
+        L.mpcqp_rollout_est.argtypes = [H, C.c_int, C.POINTER(Loop)]
+        L.mpcqp_rollout_est_tape_bytes.argtypes = [H, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        L.mpcqp_rollout_adjoint_est.argtypes = [H, C.POINTER(RolloutAdjointIO), C.POINTER(RolloutEstIO), C.POINTER(AdjointModelIO)]
+        L.mpcqp_rollout_get_tape_est.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p]
+        for name in ROLLOUT_EST_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -251,6 +267,12 @@ def has_rollout(L=None):
     """True if the library exports include/mpcqp_rollout.h (libmpcqp_hip.so does; the CPU twin does not)."""
     L = L if L is not None else load()
     return all(hasattr(L, name) for name in ROLLOUT_SYMBOLS)
+
+
+def has_rollout_est(L=None):
+    """True if the library exports include/mpcqp_rollout_est.h (libmpcqp_hip.so does; the CPU twin does not)."""
+    L = L if L is not None else load()
+    return all(hasattr(L, name) for name in ROLLOUT_EST_SYMBOLS)
 
 
 def check(rc, what):

@@ -230,14 +230,33 @@ class BatchMPCController:
         self._u_last = None
         return dict(x=xt, u=ut, status=st, iter=it)
 
-    def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), batch_sum=False, no_reuse=False):
+    def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None):
+        """``run(estimator=...)`` that keeps a tape (mpcqp_rollout_est, include/mpcqp_rollout_est.h): the output-feedback loop with a
+        ``BatchLinearStateEstimator`` -- the same dict (``x, u, status, iter, xhat, y``), ``estimator.x_true`` advanced in place -- and afterwards
+        ``rollout_adjoint`` differentiates a loss on states, estimates, inputs and measurements through controller, plant and estimator."""
+        est = dict(C=estimator.C, L=estimator.L, x_true=estimator.x_true, v=getattr(estimator, 'v', None))
+        out = self.prob.rollout_est(nsteps, est, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
+        self.solve_count += int(nsteps)
+        xt, ut, st, it, xh, ym = out[:6]
+        self.x0_rh = xh[-1].copy()
+        estimator.x = xh[-1].copy()
+        if xref_traj is not None:
+            self.xref = np.asarray(xref_traj)[-1].reshape(self.B, -1)
+        self.uminus1_rh = ut[-1].copy()
+        self._um1_on_device = True
+        self._u_last = None
+        return dict(x=xt, u=ut, status=st, iter=it, xhat=xh, y=ym)
+
+    def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), batch_sum=False, no_reuse=False, g_xhat=None, g_y=None):
         """Push a loss on the trajectory of the last ``rollout`` back through the closed loop (mpcqp_rollout_adjoint): ``g_x`` [K+1,B,nx] =
         dL/dx_k, ``g_u`` [K,B,nu] = dL/du_k.  Returns the gradients named in ``want`` -- 'lam' [K+1,B,nx] (lam[0] = dL/dx0, lam[k+1] =
         dL/dw[k]), 'uminus1', 'uref' [B,nu], 'xref' [K,B,rows*nx], 'Ap' [B,nx,nx], 'Bp' [B,nx,nu] (the plant path alone: with the
         controller's own model as the plant, add them to 'Ad', 'Bd'), and 'Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu', 'eps_feas' summed over the
         steps (``batch_sum``: and over the batch) -- plus ``n_weak`` [K,B], ``status`` [K,B] per step and ``n_factor`` [B], the
-        factorizations the sweep made.  numpy in, numpy out; torch device tensors in, device tensors out."""
-        res = self.prob.rollout_adjoint(g_x=g_x, g_u=g_u, want=want, batch_sum=batch_sum, no_reuse=no_reuse)
+        factorizations the sweep made.  numpy in, numpy out; torch device tensors in, device tensors out.  After ``rollout_est``: ``g_xhat``
+        [K+1,B,nx] = dL/dxhat_k and ``g_y`` [K,B,ny] = dL/dy_k seed the sweep too, and ``want`` may name 'eta' [K+1,B,nx] (eta[0] = dL/dxhat_0),
+        'C' [B,ny,nx], 'L' [B,nx,ny], 'v' [K,B,ny] and 'Ae' [B,nx,nx], 'Be' [B,nx,nu], the estimator path alone (add them to 'Ad', 'Bd')."""
+        res = self.prob.rollout_adjoint(g_x=g_x, g_u=g_u, want=want, batch_sum=batch_sum, no_reuse=no_reuse, g_xhat=g_xhat, g_y=g_y)
         _, n_weak, status, n_factor = self.prob.rollout_info()
         res.update(n_weak=n_weak, status=status, n_factor=n_factor)
         return res

@@ -48,6 +48,7 @@
 #include "../../include/mpcqp_adjoint.h"
 #include "../../include/mpcqp_adjoint_model.h"
 #include "../../include/mpcqp_rollout.h"
+#include "../../include/mpcqp_rollout_est.h"
 
 #include "mpcqp_defs.h"
 
@@ -151,6 +152,7 @@ struct mpcqp_handle {
     double *adj_step;                    // the adjoint's copy of the step data with that u_{-1} put back [batch][step_sz] (null until first needed)
     double *adjm_out, *adjm_sum;         // mpcqp_adjoint_model: the per-instance model gradients (field-major, AdjointModelArgs::out) and their batch sum; null until first use
     RolloutTape tape; void *tape_buf; size_t tape_bytes;      // mpcqp_rollout (include/mpcqp_rollout.h): the tape, one device block (null until the first rollout)
+    int tape_ny;                                               // > 0: the tape is one of the output-feedback loop (mpcqp_rollout_est, include/mpcqp_rollout_est.h)
     int tape_xref_rows; bool tape_valid;                       // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
     bool has_solve;                      // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
@@ -245,7 +247,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     h->profiling = false; h->run_ms = 0.0; h->run_launches = 0; h->ev_count = 0; h->nevents = 0; h->stream = nullptr; h->own_stream = false;
     h->warm_x_pending = false;
     h->csc = nullptr; h->vec_buf = nullptr; h->step_blank = false;
-    memset(&h->tape, 0, sizeof(h->tape)); h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_xref_rows = 1; h->tape_valid = false;
+    memset(&h->tape, 0, sizeof(h->tape)); h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_xref_rows = 1; h->tape_valid = false; h->tape_ny = 0;
     h->adjm_out = nullptr; h->adjm_sum = nullptr; h->um1_used = nullptr; h->um1_moved = false; h->adj_step = nullptr;
     h->pin_in = h->pin_out = nullptr; h->pin_in_dev = h->pin_out_dev = nullptr; h->done_dev = nullptr; h->host_seq = 0; h->pin_stride = 0; h->pin_tried = false;
     if (s) h->S = *s; else mpcqp_default_settings(&h->S);
@@ -1410,7 +1412,8 @@ extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *
 // ---- a rollout with a tape and its reverse sweep (include/mpcqp_rollout.h, mpcqp_rollout.h) ------------------------------------
 // The tape and the sweep's staging are ONE device block: a rollout that cannot get it changes nothing, and releasing it is one call.
 // base null: sizes only.  Returns the bytes of the block.
-static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, char *base, RolloutTape *T) {
+// ny > 0: a tape of the output-feedback loop -- the plant states, measurements, C, L and the estimator's seeds and gradients behind the rest.
+static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int ny, char *base, RolloutTape *T) {
     const size_t B = (size_t)batch, K = (size_t)nsteps, nx = L.nx, nu = L.nu, xw = (size_t)xref_rows * nx, db = sizeof(double);
     size_t off = 0;
     auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~size_t(255); return q; };
@@ -1421,51 +1424,67 @@ static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, cha
     t.gx = (double *)take((K + 1) * B * nx * db); t.gu = (double *)take(K * B * nu * db); t.lam = (double *)take((K + 1) * B * nx * db);
     t.dxref = (double *)take(K * B * xw * db); t.dum1 = (double *)take(B * nu * db); t.duref = (double *)take(B * nu * db);
     t.dAp = (double *)take(B * nx * nx * db); t.dBp = (double *)take(B * nx * nu * db);
-    t.carry = (double *)take(B * (size_t)rollout_carry_doubles(L) * db);
+    t.carry = (double *)take(B * (size_t)rollout_carry_doubles(L, ny) * db);
     t.nact = (int *)take((3 * K * B + B) * sizeof(int)); t.nweak = t.nact + K * B; t.st = t.nweak + K * B; t.nfactor = t.st + K * B;
     t.nsteps = nsteps; t.batch = batch;
+    if (ny > 0) {
+        const size_t q = (size_t)ny;
+        t.ny = ny;
+        t.xp = (double *)take((K + 1) * B * nx * db); t.ym = (double *)take(K * B * q * db);
+        t.C = (double *)take(B * q * nx * db); t.Lg = (double *)take(B * nx * q * db); t.xt = (double *)take(B * nx * db);
+        t.gxh = (double *)take((K + 1) * B * nx * db); t.gy = (double *)take(K * B * q * db);
+        t.eta = (double *)take((K + 1) * B * nx * db); t.dv = (double *)take(K * B * q * db);
+        t.dC = (double *)take(B * q * nx * db); t.dL = (double *)take(B * nx * q * db);
+        t.dAe = (double *)take(B * nx * nx * db); t.dBe = (double *)take(B * nx * nu * db);
+    }
     if (T) *T = t;
     return off;
 }
 extern "C" int mpcqp_rollout_tape_bytes(mpcqp_handle *h, int nsteps, int64_t *bytes) {
     if (!h || !bytes || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tape_bytes: bad argument");
-    *bytes = (int64_t)tape_carve(h->L, h->batch, nsteps, h->L.xref_rows, nullptr, nullptr);
+    *bytes = (int64_t)tape_carve(h->L, h->batch, nsteps, h->L.xref_rows, 0, nullptr, nullptr);
     return MPCQP_OK;
 }
 extern "C" int mpcqp_rollout_release(mpcqp_handle *h) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
     HIPCHK(hipSetDevice(h->device));
     if (h->tape_buf) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->tape_buf); }
-    h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_valid = false;
+    h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_valid = false; h->tape_ny = 0;
     memset(&h->tape, 0, sizeof(h->tape));
     return MPCQP_OK;
 }
-extern "C" int mpcqp_rollout(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
-    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout: bad argument");
-    if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout: output feedback in a taped rollout is not implemented");
+// The taped loop behind mpcqp_rollout (io->ny == 0) and mpcqp_rollout_est (io->ny > 0): the refusals, the tape's one allocation and its
+// invalidation, k_rollout_tape and one closed-loop launch per step with the trajectory buffers advanced to that step.  With an estimator C, L,
+// the plant and x_true are read from the tape's copies, and x_k, x_{k+1}, y_k are written straight onto the tape (x_traj, y_traj of the step).
+static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const std::string &what) {
     int rc = loop_check(h, nsteps, io);
     if (rc) return rc;
-    if (!h->has_solve) return fail(MPCQP_ERR_STATE, "mpcqp_rollout: no solve since the last setup, update, model update or warm start: the iterate does not belong to the step data of tape entry 0");
+    if (!h->has_solve) return fail(MPCQP_ERR_STATE, what + ": no solve since the last setup, update, model update or warm start: the iterate does not belong to the step data of tape entry 0");
     if (io->xref_traj && io->xref_rows && io->xref_rows != h->L.xref_rows)
-        return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout: xref_traj must have the reference shape of the last upload (the entries of a tape have one shape)");
+        return fail(MPCQP_ERR_UNSUPPORTED, what + ": xref_traj must have the reference shape of the last upload (the entries of a tape have one shape)");
     const Lay &L = h->L;
-    const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu, db = sizeof(double);
-    const size_t bytes = tape_carve(L, h->batch, nsteps, L.xref_rows, nullptr, nullptr);
+    const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu, ny = (size_t)io->ny, db = sizeof(double);
+    const size_t bytes = tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, nullptr, nullptr);
     if (!h->tape_buf || bytes > h->tape_bytes) {
         void *q = nullptr;
-        if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MPCQP_ERR_HIP, "mpcqp_rollout: the tape could not be allocated (mpcqp_rollout_tape_bytes says how much it takes)"); }
+        if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MPCQP_ERR_HIP, what + ": the tape could not be allocated (" + what + "_tape_bytes says how much it takes)"); }
         if (h->tape_buf) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->tape_buf); }
         h->tape_buf = q; h->tape_bytes = bytes;
     }
     h->tape_valid = false;
     RolloutTape T;
-    tape_carve(L, h->batch, nsteps, L.xref_rows, (char *)h->tape_buf, &T);
+    tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, (char *)h->tape_buf, &T);
     if (io->Ap) {
         HIPCHK(hipMemcpyAsync(T.Ap, io->Ap, B * nx * nx * db, hipMemcpyDefault, h->stream));
         HIPCHK(hipMemcpyAsync(T.Bp, io->Bp, B * nx * nu * db, hipMemcpyDefault, h->stream));
     } else { T.Ap = nullptr; T.Bp = nullptr; }
+    if (ny) {                                       // (a host x_true makes one round trip per call, not per step)
+        HIPCHK(hipMemcpyAsync(T.C, io->C, B * ny * nx * db, hipMemcpyDefault, h->stream));
+        HIPCHK(hipMemcpyAsync(T.Lg, io->Lgain, B * nx * ny * db, hipMemcpyDefault, h->stream));
+        HIPCHK(hipMemcpyAsync(T.xt, io->x_true, B * nx * db, hipMemcpyDefault, h->stream));
+    }
     HIPCHK(hipMemsetAsync(T.nact, 0, (3 * (size_t)nsteps * B + B) * sizeof(int), h->stream));      // (mpcqp_get_rollout_info before a sweep: all zero)
-    h->tape = T; h->tape_xref_rows = L.xref_rows;
+    h->tape = T; h->tape_xref_rows = L.xref_rows; h->tape_ny = io->ny;
     const size_t xblk = (size_t)L.xref_rows * nx;
     const size_t per = (size_t)L.n + 2 * (size_t)L.m + L.step_sz + nu + 1;
     const unsigned grid = (unsigned)std::min<size_t>(1024, (B * per + 255) / 256);
@@ -1476,25 +1495,64 @@ extern "C" int mpcqp_rollout(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) 
         const size_t k0 = (size_t)k;
         if (seg.w) seg.w += k0 * B * nx;
         if (seg.xref_traj) seg.xref_traj += k0 * B * xblk;
-        if (seg.x_traj) seg.x_traj += k0 * B * nx;
         if (seg.u_traj) seg.u_traj += k0 * B * nu;
         if (seg.status_traj) seg.status_traj += k0 * B;
         if (seg.iter_traj) seg.iter_traj += k0 * B;
+        if (ny) {
+            seg.Ap = T.Ap; seg.Bp = T.Bp; seg.C = T.C; seg.Lgain = T.Lg; seg.x_true = T.xt;
+            seg.x_traj = T.xp + k0 * B * nx; seg.y_traj = T.ym + k0 * B * ny;
+            if (seg.v) seg.v += k0 * B * ny;
+            if (seg.xhat_traj) seg.xhat_traj += k0 * B * nx;
+        } else if (seg.x_traj) seg.x_traj += k0 * B * nx;
         if ((rc = loop_run(h, 1, &seg, k == nsteps - 1))) return rc;
     }
+    if (ny && (get(h, io->x_traj, T.xp, ((size_t)nsteps + 1) * B * nx * db) || get(h, io->y_traj, T.ym, (size_t)nsteps * B * ny * db) ||
+               get(h, io->x_true, T.xt, B * nx * db))) return MPCQP_ERR_HIP;
     h->tape_valid = true;
+    return ny ? sync_unless_all_device(h, {io->x_traj, io->y_traj, io->x_true, io->C, io->Lgain, io->Ap, io->Bp}) : MPCQP_OK;
+}
+extern "C" int mpcqp_rollout(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
+    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout: bad argument");
+    if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout: output feedback in a taped rollout is mpcqp_rollout_est (include/mpcqp_rollout_est.h)");
+    return rollout_forward(h, nsteps, io, "mpcqp_rollout");
+}
+// ---- the taped rollout of the output-feedback loop (include/mpcqp_rollout_est.h) ---------------------------------------------------
+extern "C" int mpcqp_rollout_est_tape_bytes(mpcqp_handle *h, int nsteps, int ny, int64_t *bytes) {
+    if (!h || !bytes || nsteps < 1 || ny < 1 || ny > 64) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_est_tape_bytes: bad argument");
+    *bytes = (int64_t)tape_carve(h->L, h->batch, nsteps, h->L.xref_rows, ny, nullptr, nullptr);
     return MPCQP_OK;
 }
-extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
+extern "C" int mpcqp_rollout_est(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
+    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_est: bad argument");
+    if (io->ny == 0) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_est: ny must be > 0 (mpcqp_rollout is the taped loop without an estimator)");
+    return rollout_forward(h, nsteps, io, "mpcqp_rollout_est");
+}
+extern "C" int mpcqp_rollout_get_tape_est(mpcqp_handle *h, int k, double *x_plant, double *y_meas) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_get_tape_est: the handle holds no tape (call mpcqp_rollout_est first)");
+    if (h->tape_ny == 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_get_tape_est: the tape is one of mpcqp_rollout (no estimator)");
+    const RolloutTape &T = h->tape;
+    if (k < 0 || k >= T.nsteps) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_get_tape_est: k must be in 0 .. nsteps - 1");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = (size_t)h->batch, kB = (size_t)k * B, db = sizeof(double);
+    if (get(h, x_plant, T.xp + kB * h->L.nx, B * h->L.nx * db) || get(h, y_meas, T.ym + kB * (size_t)h->tape_ny, B * (size_t)h->tape_ny * db)) return MPCQP_ERR_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+// eo: the estimator's seeds and gradients (mpcqp_rollout_adjoint_est), or null.  est: the call is mpcqp_rollout_adjoint_est.
+static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo, bool est) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
     if (io->struct_size != (int32_t)sizeof(mpcqp_rollout_adjoint_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: struct_size is not sizeof(mpcqp_rollout_adjoint_io)");
     if (mo && mo->struct_size != (int32_t)sizeof(mpcqp_adjoint_model_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: struct_size is not sizeof(mpcqp_adjoint_model_io)");
-    if (!io->G_x && !io->G_u) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: give G_x, G_u or both");
+    if (eo && eo->struct_size != (int32_t)sizeof(mpcqp_rollout_est_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_est: struct_size is not sizeof(mpcqp_rollout_est_io)");
+    if (!est && !io->G_x && !io->G_u) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: give G_x, G_u or both");
+    if (est && !io->G_x && !io->G_u && !(eo && (eo->G_xhat || eo->G_y))) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_est: give at least one of G_x, G_u, G_xhat, G_y");
     if (io->no_reuse != 0 && io->no_reuse != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: no_reuse is 0 or 1");
     if (mo && mo->batch_sum != 0 && mo->batch_sum != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: batch_sum is 0 or 1");
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint before mpcqp_setup");
     if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the handle holds no tape (call mpcqp_rollout first)");
     if (!h->tape_valid) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the model or the scaling the tape was made under has been replaced (mpcqp_setup*, mpcqp_update_model, mpcqp_update_vectors with l, u) or its rollout failed: roll out again");
+    if (est && h->tape_ny == 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_est: the tape is one of mpcqp_rollout (no estimator); use mpcqp_rollout_adjoint");
     double *const mout[ADJM_FIELDS] = {mo ? mo->d_Ad : nullptr, mo ? mo->d_Bd : nullptr, mo ? mo->d_Qx : nullptr, mo ? mo->d_QxN : nullptr,
                                        mo ? mo->d_Qu : nullptr, mo ? mo->d_QDu : nullptr, mo ? mo->d_eps_feas : nullptr};
     bool model = false;
@@ -1516,21 +1574,37 @@ extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoin
     else HIPCHK(hipMemsetAsync(T.gx, 0, (K + 1) * B * nx * db, h->stream));
     if (io->G_u) HIPCHK(hipMemcpyAsync(T.gu, io->G_u, K * B * nu * db, hipMemcpyDefault, h->stream));
     else HIPCHK(hipMemsetAsync(T.gu, 0, K * B * nu * db, h->stream));
+    const size_t ny = (size_t)h->tape_ny;
+    if (ny) {
+        if (eo && eo->G_xhat) HIPCHK(hipMemcpyAsync(T.gxh, eo->G_xhat, (K + 1) * B * nx * db, hipMemcpyDefault, h->stream));
+        else HIPCHK(hipMemsetAsync(T.gxh, 0, (K + 1) * B * nx * db, h->stream));
+        if (eo && eo->G_y) HIPCHK(hipMemcpyAsync(T.gy, eo->G_y, K * B * ny * db, hipMemcpyDefault, h->stream));
+        else HIPCHK(hipMemsetAsync(T.gy, 0, K * B * ny * db, h->stream));
+    }
     AdjointArgs Q = h->aq;
     Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
     Q.nseeds = 1; Q.gw = nullptr; Q.gu0 = nullptr; Q.chain = 1; Q.ncol = 1; Q.cs = 0;
     W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = model ? 1 : 0;
-    const size_t with_carry = v.smem + db * (size_t)rollout_carry_doubles(G);
+    const size_t with_carry = v.smem + db * (size_t)rollout_carry_doubles(G, (int)ny);
     W.carry_lds = with_carry <= 160 * 1024 ? 1 : 0;         // (lam, mu, g behind the common block, or in the tape's few doubles of global memory)
     const size_t smem = W.carry_lds ? with_carry : v.smem;
-    DISPATCH_NB(G.NB, {
-        if (set_smem(k_rollout_adjoint<NB>, smem)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL(k_rollout_adjoint<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
-    });
+    if (ny) {
+        DISPATCH_NB(G.NB, {
+            if (set_smem(k_rollout_adjoint_est<NB>, smem)) return MPCQP_ERR_HIP;
+            hipLaunchKernelGGL(k_rollout_adjoint_est<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
+        });
+    } else {
+        DISPATCH_NB(G.NB, {
+            if (set_smem(k_rollout_adjoint<NB>, smem)) return MPCQP_ERR_HIP;
+            hipLaunchKernelGGL(k_rollout_adjoint<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
+        });
+    }
     HIPCHK(hipGetLastError());
     const size_t xw = (size_t)G.xref_rows * nx;
     if (get(h, io->lam, T.lam, (K + 1) * B * nx * db) || get(h, io->d_uminus1, T.dum1, B * nu * db) || get(h, io->d_uref, T.duref, B * nu * db) ||
         get(h, io->d_xref, T.dxref, K * B * xw * db) || get(h, io->d_Ap, T.dAp, B * nx * nx * db) || get(h, io->d_Bp, T.dBp, B * nx * nu * db)) return MPCQP_ERR_HIP;
+    if (ny && eo && (get(h, eo->eta, T.eta, (K + 1) * B * nx * db) || get(h, eo->d_v, T.dv, K * B * ny * db) || get(h, eo->d_C, T.dC, B * ny * nx * db) ||
+                     get(h, eo->d_L, T.dL, B * nx * ny * db) || get(h, eo->d_Ae, T.dAe, B * nx * nx * db) || get(h, eo->d_Be, T.dBe, B * nx * nu * db))) return MPCQP_ERR_HIP;
     if (model) {
         if (mo->batch_sum) {
             AdjointModelArgs M; memset(&M, 0, sizeof(M));
@@ -1546,7 +1620,15 @@ extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoin
         }
     }
     return sync_unless_all_device(h, {io->G_x, io->G_u, io->lam, io->d_uminus1, io->d_uref, io->d_xref, io->d_Ap, io->d_Bp,
-                                      mout[0], mout[1], mout[2], mout[3], mout[4], mout[5], mout[6]});
+                                      mout[0], mout[1], mout[2], mout[3], mout[4], mout[5], mout[6],
+                                      eo ? eo->G_xhat : nullptr, eo ? eo->G_y : nullptr, eo ? eo->eta : nullptr, eo ? eo->d_C : nullptr, eo ? eo->d_L : nullptr,
+                                      eo ? eo->d_v : nullptr, eo ? eo->d_Ae : nullptr, eo ? eo->d_Be : nullptr});
+}
+extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
+    return rollout_sweep(h, io, nullptr, mo, false);
+}
+extern "C" int mpcqp_rollout_adjoint_est(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo) {
+    return rollout_sweep(h, io, eo, mo, true);
 }
 extern "C" int mpcqp_get_rollout_info(mpcqp_handle *h, int32_t *n_active, int32_t *n_weak, int32_t *status, int32_t *n_factor) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");

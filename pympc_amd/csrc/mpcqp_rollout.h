@@ -12,6 +12,10 @@
 //   reuse     the metric of K_pol is s = delta / D^2 (fixed) and omega = E^2 / delta on the active rows: it follows from the active set alone.
 //             The rows whose state differs from the one in place are counted while the set is written; where there is none and a factor
 //             is in place, kpol_factor is skipped.  The factorization is deterministic: the same bits either way.
+//   estimator EST = true (k_rollout_adjoint_est<NB>, include/mpcqp_rollout_est.h): the loop ran output feedback, the entry's x0 is the estimate
+//             xh_k and the tape holds the plant state x_k, the measurement y_k, C and L beside it.  The step prologue then carries eta
+//             (the gradient at xh) beside lam and forms s = Ad' eta, t = L' s, r = G_y + t in three more barrier-separated phases; the
+//             step's d_x0 lands on eta instead of lam.  EST = false compiles to the code without any of it.
 // Every sum over the steps is formed by the thread that owns the entry, in the order K-1 .. 0: no atomics, the same bits every time.
 #pragma once
 
@@ -31,6 +35,14 @@ struct RolloutTape {
     int *nact, *nweak, *st;       // [K][batch]
     int *nfactor;                 // [batch]
     int nsteps, batch;
+    // output feedback (mpcqp_rollout_est; ny = 0 and null otherwise)
+    int ny;
+    double *xp, *ym;              // [K+1][batch][nx] the plant states, [K][batch][ny] the measurements
+    double *C, *Lg;               // [batch][ny nx], [batch][nx ny]
+    double *xt;                   // [batch][nx] x_true during the forward loop
+    double *gxh, *gy;             // [K+1][batch][nx], [K][batch][ny] seeds
+    double *eta, *dv;             // [K+1][batch][nx], [K][batch][ny]
+    double *dC, *dL, *dAe, *dBe;  // [batch][ny nx], [batch][nx ny], [batch][nx nx], [batch][nx nu]
 };
 struct RolloutSweep {
     double *mout;                 // the model gradients, field f of instance b: mout + batch off[f] + b (off[f + 1] - off[f])  (AdjointModelArgs::out)
@@ -39,7 +51,8 @@ struct RolloutSweep {
 };
 
 // lam | lam as the plant alone gives it | d_x0 of the step | g | mu | d_uref of the step | d_uref so far
-__host__ __device__ inline int rollout_carry_doubles(const Lay &L) { return 3 * L.nx + 4 * L.nu; }
+// with an estimator (ny > 0), behind them: eta | eta before d_x0 | s | xhat[k|k] | t | r | innovation
+__host__ __device__ inline int rollout_carry_doubles(const Lay &L, int ny = 0) { return 3 * L.nx + 4 * L.nu + (ny > 0 ? 4 * L.nx + 3 * ny : 0); }
 
 // Entry k of the tape from what the handle holds now.  um1: the u_{-1} the current solve was made with where the step data no longer have it, else null.
 __global__ __launch_bounds__(256) void k_rollout_tape(Lay L, Ptrs P, RolloutTape T, int k, const double *um1) {
@@ -62,14 +75,22 @@ __global__ __launch_bounds__(256) void k_rollout_tape(Lay L, Ptrs P, RolloutTape
     }
 }
 
-template <int NB>
-__global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) {
+// The sweep's body.  The estimator is a template parameter of this force-inlined function and not of the kernel: k_rollout_adjoint<NB> keeps the
+// name and the one template argument it had (the build's resource remarks are read by that name, tests/test_rollout_resources.py), and is the
+// EST = false instantiation; k_rollout_adjoint_est<NB> is the EST = true one.
+template <int NB, bool EST>
+__device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P, const AdjointArgs &Q, const RolloutTape &T, const RolloutSweep &W) {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     double *p = sh; Smem S; smem_common(L, P, p, S);       // (P.perm is null: workgroup b works on instance b)
     const int b = blockIdx.x, tid = threadIdx.x, B = T.batch, K = T.nsteps;
     const int nx = L.nx, nu = L.nu, xw = L.xref_rows * L.nx, EN = W.off[ADJM_FIELDS];
-    double *lam = W.carry_lds ? p : T.carry + (size_t)b * rollout_carry_doubles(L);
+    const int ny = EST ? T.ny : 0;
+    double *lam = W.carry_lds ? p : T.carry + (size_t)b * rollout_carry_doubles(L, ny);
     double *lamn = lam + nx, *dx0 = lamn + nx, *g = dx0 + nx, *mu = g + nu, *durk = mu + nu, *dur = durk + nu;
+    double *eta = dur + nu, *etan = eta + nx, *sv_e = etan + nx, *xu = sv_e + nx, *tv = xu + nx, *rv = tv + ny, *inn = rv + ny;      // (EST only)
+    const double *Cm = EST ? T.C + (size_t)b * ny * nx : nullptr, *Lg = EST ? T.Lg + (size_t)b * nx * ny : nullptr;
+    double *dC = EST ? T.dC + (size_t)b * ny * nx : nullptr, *dL = EST ? T.dL + (size_t)b * nx * ny : nullptr;
+    double *dAe = EST ? T.dAe + (size_t)b * nx * nx : nullptr, *dBe = EST ? T.dBe + (size_t)b * nx * nu : nullptr;
     const double *model = P.model + (size_t)b * L.model_sz;
     const double *D = P.D + (size_t)b * L.n, *E = P.E + (size_t)b * L.m;
     const double cc = P.c[b], delta = Q.delta;
@@ -93,6 +114,12 @@ __global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointAr
     for (int e = tid; e < EN; e += NT) mdst(e) = 0.0;
     for (int e = tid; e < nx * nx; e += NT) dAp[e] = 0.0;
     for (int e = tid; e < nx * nu; e += NT) dBp[e] = 0.0;
+    if (EST) {                                           // eta_K = G_xh[K]
+        for (int i = tid; i < nx; i += NT) { const double v = T.gxh[((size_t)K * B + b) * nx + i]; eta[i] = v; T.eta[((size_t)K * B + b) * nx + i] = v; }
+        for (int e = tid; e < nx * nx; e += NT) dAe[e] = 0.0;
+        for (int e = tid; e < nx * nu; e += NT) dBe[e] = 0.0;
+        for (int e = tid; e < nx * ny; e += NT) { dC[e] = 0.0; dL[e] = 0.0; }
+    }
     for (int j = tid; j < L.n; j += NT) sv[j] = delta / (D[j] * D[j]);
     __syncthreads();
     Kpol kp = {};
@@ -105,9 +132,11 @@ __global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointAr
         {   // g = G_u[k] + Bp' lam_{k+1} + mu;  lam_k = G_x[k] + Ap' lam_{k+1} (+ d_x0 below);  d_Ap += lam_{k+1} x_k',  d_Bp += lam_{k+1} u_k'
             const double *Ap = T.Ap ? T.Ap + (size_t)b * nx * nx : S.hot + L.oAd, *Bp = T.Bp ? T.Bp + (size_t)b * nx * nu : S.hot + L.oBd;
             const double *uk = T.u + kb * nu;
+            const double *xk = EST ? T.xp + kb * nx : S.x0s;      // (the plant state; with an estimator the entry's x0 is the estimate)
             for (int j = tid; j < nu; j += NT) {
                 double a = T.gu[kb * nu + j] + mu[j];
                 for (int i = 0; i < nx; ++i) a += Bp[i * nu + j] * lam[i];
+                if (EST) { const double *Bd = S.hot + L.oBd; for (int i = 0; i < nx; ++i) a += Bd[i * nu + j] * eta[i]; }
                 g[j] = a;
             }
             for (int i = tid; i < nx; i += NT) {
@@ -115,8 +144,42 @@ __global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointAr
                 for (int r = 0; r < nx; ++r) a += Ap[r * nx + i] * lam[r];
                 lamn[i] = a;
             }
-            for (int e = tid; e < nx * nx; e += NT) { const int r = e / nx; dAp[e] += lam[r] * S.x0s[e - r * nx]; }
+            for (int e = tid; e < nx * nx; e += NT) { const int r = e / nx; dAp[e] += lam[r] * xk[e - r * nx]; }
             for (int e = tid; e < nx * nu; e += NT) { const int r = e / nu; dBp[e] += lam[r] * uk[e - r * nu]; }
+            if (EST) {
+                // s = Ad' eta_{k+1};  d_Be += eta_{k+1} u_k'
+                const double *Ad = S.hot + L.oAd, *yk = T.ym + kb * ny;
+                for (int i = tid; i < nx; i += NT) {
+                    double a = 0.0;
+                    for (int r = 0; r < nx; ++r) a += Ad[r * nx + i] * eta[r];
+                    sv_e[i] = a;
+                }
+                for (int e = tid; e < nx * nu; e += NT) { const int r = e / nu; dBe[e] += eta[r] * uk[e - r * nu]; }
+                __syncthreads();
+                // t = L' s;  r = G_y[k] + t = d_v[k];  the innovation y_k - C xh_k
+                for (int j = tid; j < ny; j += NT) {
+                    double a = 0.0, yh = 0.0;
+                    for (int i = 0; i < nx; ++i) { a += Lg[i * ny + j] * sv_e[i]; yh += Cm[j * nx + i] * S.x0s[i]; }
+                    const double rr = T.gy[kb * ny + j] + a;
+                    tv[j] = a; rv[j] = rr; inn[j] = yk[j] - yh;
+                    T.dv[kb * ny + j] = rr;
+                }
+                __syncthreads();
+                // lam_k += C' r;  eta_k = G_xh[k] + s - C' t (+ d_x0 below);  xhat[k|k];  d_L += s inn',  d_C += r x_k' - t xh_k'
+                for (int i = tid; i < nx; i += NT) {
+                    double a = lamn[i], c = T.gxh[kb * nx + i] + sv_e[i], x = S.x0s[i];
+                    for (int j = 0; j < ny; ++j) { a += Cm[j * nx + i] * rv[j]; c -= Cm[j * nx + i] * tv[j]; x += Lg[i * ny + j] * inn[j]; }
+                    lamn[i] = a; etan[i] = c; xu[i] = x;
+                }
+                for (int e = tid; e < nx * ny; e += NT) {
+                    const int i = e / ny, j = e / nx;              // dL is [nx][ny], dC is [ny][nx]
+                    dL[e] += sv_e[i] * inn[e - i * ny];
+                    dC[e] += rv[j] * xk[e - j * nx] - tv[j] * S.x0s[e - j * nx];
+                }
+                __syncthreads();
+                // d_Ae += eta_{k+1} xhat[k|k]'
+                for (int e = tid; e < nx * nx; e += NT) { const int r = e / nx; dAe[e] += eta[r] * xu[e - r * nx]; }
+            }
         }
         __syncthreads();
         int st = 0, nact = 0, nweak = 0;
@@ -160,20 +223,28 @@ __global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointAr
                 adjoint_outputs(c, act, xs, ys, 0, 1, o);
                 if (W.want_model) for (int e = tid; e < EN; e += NT) mdst(e) += adjoint_model_entry(L, M, wa, xs, ya, ys, model, step, e, 0, 1);
                 __syncthreads();
-                for (int i = tid; i < nx; i += NT) lam[i] = lamn[i] + dx0[i];
+                if (EST) for (int i = tid; i < nx; i += NT) { lam[i] = lamn[i]; eta[i] = etan[i] + dx0[i]; }
+                else for (int i = tid; i < nx; i += NT) lam[i] = lamn[i] + dx0[i];
                 for (int j = tid; j < nu; j += NT) dur[j] += durk[j];
             }
             st = bad ? -1 : 1;
         }
         if (st != 1) {                                   // u_failure = uref was applied (not solved), or nothing can be said (a broken factor)
-            for (int i = tid; i < nx; i += NT) lam[i] = lamn[i];
+            for (int i = tid; i < nx; i += NT) { lam[i] = lamn[i]; if (EST) eta[i] = etan[i]; }
             for (int j = tid; j < nu; j += NT) { if (st == 0) dur[j] += g[j]; mu[j] = 0.0; }
             for (int i = tid; i < xw; i += NT) T.dxref[kb * xw + i] = 0.0;
         }
         for (int i = tid; i < nx; i += NT) T.lam[kb * nx + i] = lam[i];      // (the thread that wrote lam[i])
+        if (EST) for (int i = tid; i < nx; i += NT) T.eta[kb * nx + i] = eta[i];
         if (tid == 0) { T.st[kb] = st; T.nact[kb] = nact; T.nweak[kb] = nweak; }
         __syncthreads();
     }
     for (int j = tid; j < nu; j += NT) { T.dum1[(size_t)b * nu + j] = mu[j]; T.duref[(size_t)b * nu + j] = dur[j]; }
     if (tid == 0) T.nfactor[b] = nfac;
 }
+
+template <int NB>
+__global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, false>(L, P, Q, T, W); }
+// the same sweep over a tape of the output-feedback loop (mpcqp_rollout_est)
+template <int NB>
+__global__ __launch_bounds__(NT) void k_rollout_adjoint_est(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, true>(L, P, Q, T, W); }

@@ -345,6 +345,7 @@ class BatchProblem:
 
     # -- a rollout with a tape and its reverse sweep (include/mpcqp_rollout.h) ---------------------
     _rollout_shape = None      # (nsteps, xref rows) of the tape the handle holds
+    _rollout_ny = 0            # > 0: the tape is one of the output-feedback loop (rollout_est)
     rollout_count = 0          # rollouts made so far (pympc_amd.torch_layer: is the tape still the one of a forward?)
 
     def _need_rollout(self):
@@ -357,13 +358,35 @@ class BatchProblem:
         self._need_rollout()
         res = self.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, _taped=True)
         self._rollout_shape = (int(nsteps), self._xref_rows_last)
+        self._rollout_ny = 0
         self.rollout_count += 1
         return res
 
-    def rollout_tape_bytes(self, nsteps):
-        """Device memory a tape of ``nsteps`` steps takes (mpcqp_rollout_tape_bytes)."""
+    def _need_rollout_est(self):
+        if not _lib.has_rollout_est(self._L):
+            raise NotImplementedError('this build of the solver library has no taped output-feedback rollout (include/mpcqp_rollout_est.h)')
+
+    def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None, out=None):
+        """``mpc_run(estimator=dict(C=, L=, x_true=, v=))`` that keeps a tape (mpcqp_rollout_est): the same arguments and results
+        (``x, u, status, iter, xhat, y``), and afterwards ``rollout_adjoint`` -- with ``g_xhat``, ``g_y`` and the gradients 'eta', 'C', 'L', 'v',
+        'Ae', 'Be' on top -- pushes a loss on the trajectory back through controller, plant and estimator."""
+        self._need_rollout_est()
+        if estimator is None:
+            raise ValueError('rollout_est: an estimator dict(C=, L=, x_true=, v=) is needed (rollout is the taped loop without one)')
+        res = self.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, _taped='est')
+        self._rollout_shape = (int(nsteps), self._xref_rows_last)
+        self._rollout_ny = int(tuple(estimator['C'].shape)[-2])
+        self.rollout_count += 1
+        return res
+
+    def rollout_tape_bytes(self, nsteps, ny=0):
+        """Device memory a tape of ``nsteps`` steps takes (mpcqp_rollout_tape_bytes; with ``ny`` outputs: mpcqp_rollout_est_tape_bytes)."""
         self._need_rollout()
         v = C.c_int64()
+        if ny:
+            self._need_rollout_est()
+            _lib.check(self._L.mpcqp_rollout_est_tape_bytes(self._h, int(nsteps), int(ny), C.byref(v)), 'mpcqp_rollout_est_tape_bytes')
+            return v.value
         _lib.check(self._L.mpcqp_rollout_tape_bytes(self._h, int(nsteps), C.byref(v)), 'mpcqp_rollout_tape_bytes')
         return v.value
 
@@ -372,25 +395,39 @@ class BatchProblem:
         self._need_rollout()
         _lib.check(self._L.mpcqp_rollout_release(self._h), 'mpcqp_rollout_release')
         self._rollout_shape = None
+        self._rollout_ny = 0
 
-    def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), out=None, batch_sum=False, no_reuse=False):
+    def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), out=None, batch_sum=False, no_reuse=False, g_xhat=None, g_y=None):
         """The reverse sweep over the tape of the last ``rollout`` (mpcqp_rollout_adjoint): for ``g_x`` [K+1, B, nx] = dL/dx_k and / or
         ``g_u`` [K, B, nu] = dL/du_k returns a dict with the gradients named in ``want`` -- 'lam' [K+1, B, nx] (lam[0] = dL/dx0,
         lam[k+1] = dL/dw[k]), 'uminus1' [B, nu], 'uref' [B, nu], 'xref' [K, B, rows*nx] (entry k: the reference step k was solved with),
         'Ap' [B, nx, nx], 'Bp' [B, nx, nu] (the plant path alone) and the model gradients of ``adjoint`` ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu',
         'eps_feas'; ``batch_sum`` as there), summed over the steps.  ``no_reuse``: factor at every step (the same bits, for measurements).
-        numpy in, numpy out; torch device tensors in, device tensors out (stream-ordered, no wait)."""
+        numpy in, numpy out; torch device tensors in, device tensors out (stream-ordered, no wait).
+        On the tape of a ``rollout_est`` (mpcqp_rollout_adjoint_est): ``g_xhat`` [K+1, B, nx] = dL/dxhat_k and ``g_y`` [K, B, ny] = dL/dy_k are
+        seeds too (any one of the four is enough), and ``want`` may name 'eta' [K+1, B, nx] (eta[0] = dL/dxhat_0), 'C' [B, ny, nx],
+        'L' [B, nx, ny], 'v' [K, B, ny], 'Ae' [B, nx, nx], 'Be' [B, nx, nu] (the estimator path alone); on a state-feedback tape they raise."""
         self._need_rollout()
-        if g_x is None and g_u is None:
-            raise ValueError('rollout_adjoint: give g_x, g_u or both')
+        ny = self._rollout_ny
+        est_names = ('eta', 'C', 'L', 'v', 'Ae', 'Be')
+        if self._rollout_shape is not None and not ny and (g_xhat is not None or g_y is not None or any(k in est_names for k in want)):
+            raise RuntimeError('rollout_adjoint: g_xhat, g_y and the gradients %s need the tape of a rollout_est (this one has no estimator)' % ', '.join(est_names))
+        if g_x is None and g_u is None and g_xhat is None and g_y is None:
+            raise ValueError('rollout_adjoint: give g_x, g_u or both' + (', or g_xhat, g_y' if ny else ''))
         if self._rollout_shape is None:
             raise RuntimeError('rollout_adjoint: no rollout has been made (mpcqp_rollout)')
         K, rows = self._rollout_shape
         B, nx, nu = self.batch, self.nx, self.nu
-        like = g_x if g_x is not None else g_u
+        like = next(g for g in (g_x, g_u, g_xhat, g_y) if g is not None)
         gx = _prep(g_x, (K + 1, B, nx), 'g_x') if g_x is not None else None
         gu = _prep(g_u, (K, B, nu), 'g_u') if g_u is not None else None
+        gxh = _prep(g_xhat, (K + 1, B, nx), 'g_xhat') if g_xhat is not None else None
+        gy = _prep(g_y, (K, B, ny), 'g_y') if g_y is not None else None
         shapes = dict(lam=(K + 1, B, nx), uminus1=(B, nu), uref=(B, nu), xref=(K, B, rows * nx), Ap=(B, nx, nx), Bp=(B, nx, nu))
+        eshapes = dict(eta=(K + 1, B, nx), C=(B, ny, nx), L=(B, nx, ny), v=(K, B, ny), Ae=(B, nx, nx), Be=(B, nx, nu)) if ny else {}
+        eo = _lib.RolloutEstIO()
+        eo.struct_size = C.sizeof(_lib.RolloutEstIO)
+        eo.G_xhat, eo.G_y = _ptr(gxh), _ptr(gy)
         Bm = 1 if batch_sum else B
         mshapes = dict(Ad=(Bm, nx, nx), Bd=(Bm, nx, nu), Qx=(Bm, nx, nx), QxN=(Bm, nx, nx), Qu=(Bm, nu, nu), QDu=(Bm, nu, nu), eps_feas=(Bm,))
         io = _lib.RolloutAdjointIO()
@@ -400,17 +437,23 @@ class BatchProblem:
         mo.struct_size, mo.batch_sum = C.sizeof(_lib.AdjointModelIO), int(bool(batch_sum))
         res = {}
         for k in want:
-            if k not in shapes and k not in mshapes:
+            if k not in shapes and k not in mshapes and k not in eshapes:
                 raise TypeError('unknown gradient %r' % k)
-            shape = shapes[k] if k in shapes else mshapes[k]
+            shape = shapes[k] if k in shapes else (mshapes[k] if k in mshapes else eshapes[k])
             a = _prep_out(out[k], shape, 'out[%r]' % k) if out is not None and k in out else self._out(like, shape)
             res[k] = a
             if k in mshapes:
                 setattr(mo, 'd_' + k, _ptr(a))
+            elif k in eshapes:
+                setattr(eo, k if k == 'eta' else 'd_' + k, _ptr(a))
             else:
                 setattr(io, k if k == 'lam' else 'd_' + k, _ptr(a))
-        self._keep = [gx, gu, res]
-        _lib.check(self._L.mpcqp_rollout_adjoint(self._h, C.byref(io), C.byref(mo)), 'mpcqp_rollout_adjoint')
+        self._keep = [gx, gu, gxh, gy, res]
+        if ny:
+            self._need_rollout_est()
+            _lib.check(self._L.mpcqp_rollout_adjoint_est(self._h, C.byref(io), C.byref(eo), C.byref(mo)), 'mpcqp_rollout_adjoint_est')
+        else:
+            _lib.check(self._L.mpcqp_rollout_adjoint(self._h, C.byref(io), C.byref(mo)), 'mpcqp_rollout_adjoint')
         return res
 
     def rollout_info(self):
@@ -434,6 +477,9 @@ class BatchProblem:
         r = dict(x=np.empty((B, self.n)), z=np.empty((B, self.m)), y=np.empty((B, self.m)),
                  step=np.empty((B, self.nx + self.nu + rows * self.nx)), status=np.zeros(B, dtype=np.int32))
         _lib.check(self._L.mpcqp_rollout_get_tape(self._h, int(k), *[_ptr(r[n]) for n in ('x', 'z', 'y', 'step', 'status')]), 'mpcqp_rollout_get_tape')
+        if self._rollout_ny:                      # (a rollout_est: the step data begin with the estimate, the plant state and the measurement are beside it)
+            r.update(x_plant=np.empty((B, self.nx)), y_meas=np.empty((B, self._rollout_ny)))
+            _lib.check(self._L.mpcqp_rollout_get_tape_est(self._h, int(k), _ptr(r['x_plant']), _ptr(r['y_meas'])), 'mpcqp_rollout_get_tape_est')
         return r
 
     def _finish_init(self, stream):
@@ -714,6 +760,9 @@ class BatchProblem:
             mt.Ad = inp(Adt, (nm, B, nx, nx), 'model_traj Ad'); mt.Bd = inp(Bdt, (nm, B, nx, nu), 'model_traj Bd')
             rc = self._L.mpcqp_mpc_loop_tv(self._h, K, C.byref(io), C.byref(mt))
             what = 'mpcqp_mpc_loop_tv'
+        elif _taped == 'est':                     # (rollout_est(): the output-feedback loop, and a tape of it)
+            rc = self._L.mpcqp_rollout_est(self._h, K, C.byref(io))
+            what = 'mpcqp_rollout_est'
         elif _taped:                              # (rollout(): the same loop, and a tape of it)
             rc = self._L.mpcqp_rollout(self._h, K, C.byref(io))
             what = 'mpcqp_rollout'

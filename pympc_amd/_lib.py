@@ -239,40 +239,40 @@ def load():
     return L
 
 
-def has_polish(L=None):
-    """True if the library exports include/mpcqp_polish.h (libmpcqp_hip.so does; the CPU twin does not)."""
+def _has(L, symbols):
+    """True if the library (None: the loaded one) exports every one of ``symbols``: libmpcqp_hip.so does, the CPU twin does not."""
     L = L if L is not None else load()
-    return all(hasattr(L, name) for name in POLISH_SYMBOLS)
+    return all(hasattr(L, name) for name in symbols)
+
+
+def has_polish(L=None):
+    """True if the library exports include/mpcqp_polish.h."""
+    return _has(L, POLISH_SYMBOLS)
 
 
 def has_model_update(L=None):
-    """True if the library exports include/mpcqp_model.h (libmpcqp_hip.so does; the CPU twin does not)."""
-    L = L if L is not None else load()
-    return all(hasattr(L, name) for name in MODEL_SYMBOLS)
+    """True if the library exports include/mpcqp_model.h."""
+    return _has(L, MODEL_SYMBOLS)
 
 
 def has_adjoint(L=None):
-    """True if the library exports include/mpcqp_adjoint.h (libmpcqp_hip.so does; the CPU twin does not)."""
-    L = L if L is not None else load()
-    return all(hasattr(L, name) for name in ADJOINT_SYMBOLS)
+    """True if the library exports include/mpcqp_adjoint.h."""
+    return _has(L, ADJOINT_SYMBOLS)
 
 
 def has_adjoint_model(L=None):
-    """True if the library exports include/mpcqp_adjoint_model.h (libmpcqp_hip.so does; the CPU twin does not)."""
-    L = L if L is not None else load()
-    return all(hasattr(L, name) for name in ADJOINT_MODEL_SYMBOLS)
+    """True if the library exports include/mpcqp_adjoint_model.h."""
+    return _has(L, ADJOINT_MODEL_SYMBOLS)
 
 
 def has_rollout(L=None):
-    """True if the library exports include/mpcqp_rollout.h (libmpcqp_hip.so does; the CPU twin does not)."""
-    L = L if L is not None else load()
-    return all(hasattr(L, name) for name in ROLLOUT_SYMBOLS)
+    """True if the library exports include/mpcqp_rollout.h."""
+    return _has(L, ROLLOUT_SYMBOLS)
 
 
 def has_rollout_est(L=None):
-    """True if the library exports include/mpcqp_rollout_est.h (libmpcqp_hip.so does; the CPU twin does not)."""
-    L = L if L is not None else load()
-    return all(hasattr(L, name) for name in ROLLOUT_EST_SYMBOLS)
+    """True if the library exports include/mpcqp_rollout_est.h."""
+    return _has(L, ROLLOUT_EST_SYMBOLS)
 
 
 def check(rc, what):

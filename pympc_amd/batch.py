@@ -11,6 +11,13 @@ import numpy as np
 from .solver import BatchProblem
 
 
+def _est_dict(estimator):
+    """What ``BatchProblem`` takes of a ``BatchLinearStateEstimator`` (None: state feedback)."""
+    if estimator is None:
+        return None
+    return dict(C=estimator.C, L=estimator.L, x_true=estimator.x_true, v=getattr(estimator, 'v', None))
+
+
 class BatchMPCController:
     def __init__(self, Ad, Bd, Np=20, Nc=None, x0=None, xref=None, uref=None, uminus1=None,
                  Qx=None, QxN=None, Qu=None, QDu=None,
@@ -189,11 +196,8 @@ class BatchMPCController:
         left with the last entry used.  Not with an estimator.
         Returns ``dict(x=[nsteps+1,B,nx], u=[nsteps,B,nu], status=[nsteps,B] (OSQP status values), iter=[nsteps,B])``
         plus ``xhat`` and ``y`` with an estimator."""
-        est = None
-        if estimator is not None:
-            est = dict(C=estimator.C, L=estimator.L, x_true=estimator.x_true, v=getattr(estimator, 'v', None))
         self.solve_count += int(nsteps)
-        out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=est, model_traj=model_traj)
+        out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=_est_dict(estimator), model_traj=model_traj)
         if model_traj is not None:
             last = (int(nsteps) - 1) // int(model_traj[2])
             host = lambda a: np.array(a[last].cpu() if hasattr(a, 'data_ptr') else a[last], dtype=float).reshape((self.B,) + tuple(a.shape[-2:]))
@@ -201,6 +205,13 @@ class BatchMPCController:
                 self.Ad = host(model_traj[0])
             if model_traj[1] is not None:
                 self.Bd = host(model_traj[1])
+        return self._after_loop(out, xref_traj, estimator)
+
+    def _after_loop(self, out, xref_traj, estimator=None, count=0):
+        """The controller's books after a device loop of any kind, and its result dict: the controller stands at the last state (with an
+        estimator: at the last estimate, which the estimator object gets too), the last reference and the last input, which is on the
+        device as u_{-1}.  ``count``: steps to add to ``solve_count`` now (a rollout counts them once it has succeeded, ``run`` before the call)."""
+        self.solve_count += count
         xt, ut, st, it = out[:4]
         res = dict(x=xt, u=ut, status=st, iter=it)
         if estimator is not None:
@@ -220,32 +231,15 @@ class BatchMPCController:
         """``run`` that keeps a tape (mpcqp_rollout, include/mpcqp_rollout.h): the same loop, the same dict, one closed-loop launch per
         step -- and afterwards ``rollout_adjoint`` differentiates a loss on the whole trajectory in one reverse sweep on the device.  No
         estimator and no model schedule in a taped rollout."""
-        xt, ut, st, it = self.prob.rollout(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)[:4]
-        self.solve_count += int(nsteps)
-        self.x0_rh = xt[-1].copy()
-        if xref_traj is not None:
-            self.xref = np.asarray(xref_traj)[-1].reshape(self.B, -1)
-        self.uminus1_rh = ut[-1].copy()
-        self._um1_on_device = True
-        self._u_last = None
-        return dict(x=xt, u=ut, status=st, iter=it)
+        out = self.prob.rollout(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
+        return self._after_loop(out, xref_traj, count=int(nsteps))
 
     def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None):
         """``run(estimator=...)`` that keeps a tape (mpcqp_rollout_est, include/mpcqp_rollout_est.h): the output-feedback loop with a
         ``BatchLinearStateEstimator`` -- the same dict (``x, u, status, iter, xhat, y``), ``estimator.x_true`` advanced in place -- and afterwards
         ``rollout_adjoint`` differentiates a loss on states, estimates, inputs and measurements through controller, plant and estimator."""
-        est = dict(C=estimator.C, L=estimator.L, x_true=estimator.x_true, v=getattr(estimator, 'v', None))
-        out = self.prob.rollout_est(nsteps, est, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
-        self.solve_count += int(nsteps)
-        xt, ut, st, it, xh, ym = out[:6]
-        self.x0_rh = xh[-1].copy()
-        estimator.x = xh[-1].copy()
-        if xref_traj is not None:
-            self.xref = np.asarray(xref_traj)[-1].reshape(self.B, -1)
-        self.uminus1_rh = ut[-1].copy()
-        self._um1_on_device = True
-        self._u_last = None
-        return dict(x=xt, u=ut, status=st, iter=it, xhat=xh, y=ym)
+        out = self.prob.rollout_est(nsteps, _est_dict(estimator), w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
+        return self._after_loop(out, xref_traj, estimator, count=int(nsteps))
 
     def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), batch_sum=False, no_reuse=False, g_xhat=None, g_y=None):
         """Push a loss on the trajectory of the last ``rollout`` back through the closed loop (mpcqp_rollout_adjoint): ``g_x`` [K+1,B,nx] =

@@ -111,50 +111,50 @@ constexpr int BALANCE_FIRST = 4;   // ... before the first one (an instance show
 struct PackItem { const double *src; double *dst; int w, stride; };
 struct PackArgs { PackItem it[24]; int n, batch; };
 struct mpcqp_handle {
-    int device, batch;
+    int device = 0, batch = 0;
     Lay L;
-    Ptrs P;
+    Ptrs P = {};
     mpcqp_settings S;
-    hipStream_t stream;
-    bool own_stream, is_setup, lds_state;
-    size_t smem_setup, smem_solve;
+    hipStream_t stream = nullptr;
+    bool own_stream = false, is_setup = false, lds_state = false;
+    size_t smem_setup = 0, smem_solve = 0;
     std::vector<void *> allocs;
-    double *u0_dev;
-    int *pending_dev, *npending_dev;   // two-launch solve: instances that need more than the first round
-    int *perm_dev;                // [batch] workgroup -> instance map (P.perm points here once a map has been built)
-    int *qperm_dev; bool qperm_set;     // [batch] the queue order of persistent launches (longest expected work first), once a map has been built
-    int *vcur_dev, *vdone_dev; unsigned *vqueue_dev;   // persistent launches: [slots] map entry each workgroup is working on; [batch] closed-loop steps done; the queue position
+    double *u0_dev = nullptr;
+    int *pending_dev = nullptr, *npending_dev = nullptr;   // two-launch solve: instances that need more than the first round
+    int *perm_dev = nullptr;      // [batch] workgroup -> instance map (P.perm points here once a map has been built)
+    int *qperm_dev = nullptr; bool qperm_set = false;     // [batch] the queue order of persistent launches (longest expected work first), once a map has been built
+    int *vcur_dev = nullptr, *vdone_dev = nullptr; unsigned *vqueue_dev = nullptr;   // persistent launches: [slots] map entry each workgroup is working on; [batch] closed-loop steps done; the queue position
     std::vector<double> work_ema; // per instance: smoothed ADMM iterations per balancing interval (host)
-    int ncu, solves_since_balance, auto_balance;
-    int loop_parts;               // queue-item parts per instance of the last persistent closed-loop launch (0: not persistent; mpcqp_dev_carry_stats)
-    void *run_buf; size_t run_bytes;     // staging of mpcqp_mpc_run (disturbances, plant, trajectories)
-    bool profiling;
+    int ncu = 0, solves_since_balance = 0, auto_balance = 1;
+    int loop_parts = 0;           // queue-item parts per instance of the last persistent closed-loop launch (0: not persistent; mpcqp_dev_carry_stats)
+    void *run_buf = nullptr; size_t run_bytes = 0;     // staging of mpcqp_mpc_run (disturbances, plant, trajectories)
+    bool profiling = false;
     hipEvent_t ev0[MAXEV], ev1[MAXEV];   // ring of event pairs around the solve-kernel launches
-    long long ev_count;
-    double run_ms;
-    long long run_launches;
-    int nevents;                         // event pairs created so far (a partially built handle is destroyed cleanly)
-    bool warm_x_pending;                 // mpcqp_warm_start replaced x: the next solve starts from z = A x (osqp_warm_start)
+    long long ev_count = 0;
+    double run_ms = 0.0;
+    long long run_launches = 0;
+    int nevents = 0;                     // event pairs created so far (a partially built handle is destroyed cleanly)
+    bool warm_x_pending = false;         // mpcqp_warm_start replaced x: the next solve starts from z = A x (osqp_warm_start)
     // mpcqp_step_host: mapped, coherent host memory the kernel reads its step data from and writes its results to
-    double *pin_in, *pin_out; void *pin_in_dev, *pin_out_dev;
-    unsigned *done_dev; unsigned long long host_seq; int pin_stride; bool pin_tried;
-    PackArgs pack;                       // device-resident sources of put() waiting for flush_puts
-    CscSeam *csc;                        // patterns of P and A of a handle made by mpcqp_create_csc
-    double *vec_buf;                     // staging of mpcqp_update_vectors' host arrays [q | l | u], allocated on first use, kept
-    bool step_blank;                     // set up through mpcqp_setup_qp: the step blob holds no x0 / u_{-1} / xref yet
-    int *fown_dev; unsigned *nshared_dev;   // mpcqp_share_factor: [batch] factor slot per instance (P.fown points here while sharing is on); how many share
+    double *pin_in = nullptr, *pin_out = nullptr; void *pin_in_dev = nullptr, *pin_out_dev = nullptr;
+    unsigned *done_dev = nullptr; unsigned long long host_seq = 0; int pin_stride = 0; bool pin_tried = false;
+    PackArgs pack = {};                  // device-resident sources of put() waiting for flush_puts
+    CscSeam *csc = nullptr;              // patterns of P and A of a handle made by mpcqp_create_csc
+    double *vec_buf = nullptr;           // staging of mpcqp_update_vectors' host arrays [q | l | u], allocated on first use, kept
+    bool step_blank = false;             // set up through mpcqp_setup_qp: the step blob holds no x0 / u_{-1} / xref yet
+    int *fown_dev = nullptr; unsigned *nshared_dev = nullptr;   // mpcqp_share_factor: [batch] factor slot per instance (P.fown points here while sharing is on); how many share
     mpcqp_polish_settings pol;           // mpcqp_set_polish (include/mpcqp_polish.h)
-    PolishArgs pq;                       // the polish's buffers (pq.status null until first use)
+    PolishArgs pq = {};                  // the polish's buffers (pq.status null until first use)
     mpcqp_adjoint_settings adj;          // mpcqp_set_adjoint (include/mpcqp_adjoint.h)
-    AdjointArgs aq;                      // the adjoint's buffers (aq.status null until first use)
-    double *adj_gw, *adj_gu0;            // staging of the caller's seeds [batch][n], [batch][nu]
-    double *um1_used; bool um1_moved;    // mpcqp_mpc_step: the u_{-1} its solve was made with, [batch][nu]; true while the step data hold the applied input instead
-    double *adj_step;                    // the adjoint's copy of the step data with that u_{-1} put back [batch][step_sz] (null until first needed)
-    double *adjm_out, *adjm_sum;         // mpcqp_adjoint_model: the per-instance model gradients (field-major, AdjointModelArgs::out) and their batch sum; null until first use
-    RolloutTape tape; void *tape_buf; size_t tape_bytes;      // mpcqp_rollout (include/mpcqp_rollout.h): the tape, one device block (null until the first rollout)
-    int tape_ny;                                               // > 0: the tape is one of the output-feedback loop (mpcqp_rollout_est, include/mpcqp_rollout_est.h)
-    int tape_xref_rows; bool tape_valid;                       // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
-    bool has_solve;                      // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
+    AdjointArgs aq = {};                 // the adjoint's buffers (aq.status null until first use)
+    double *adj_gw = nullptr, *adj_gu0 = nullptr;      // staging of the caller's seeds [batch][n], [batch][nu]
+    double *um1_used = nullptr; bool um1_moved = false;    // mpcqp_mpc_step: the u_{-1} its solve was made with, [batch][nu]; true while the step data hold the applied input instead
+    double *adj_step = nullptr;          // the adjoint's copy of the step data with that u_{-1} put back [batch][step_sz] (null until first needed)
+    double *adjm_out = nullptr, *adjm_sum = nullptr;   // mpcqp_adjoint_model: the per-instance model gradients (field-major, AdjointModelArgs::out) and their batch sum; null until first use
+    RolloutTape tape = {}; void *tape_buf = nullptr; size_t tape_bytes = 0;      // mpcqp_rollout (include/mpcqp_rollout.h): the tape, one device block (null until the first rollout)
+    int tape_ny = 0;                                           // > 0: the tape is one of the output-feedback loop (mpcqp_rollout_est, include/mpcqp_rollout_est.h)
+    int tape_xref_rows = 1; bool tape_valid = false;           // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
+    bool has_solve = false;              // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
 
 extern "C" void mpcqp_default_settings(mpcqp_settings *s) {
@@ -243,13 +243,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     mpcqp_handle *h = new mpcqp_handle();
     mpcqp_polish_default_settings(&h->pol);
     mpcqp_adjoint_default_settings(&h->adj);
-    h->device = device; h->batch = batch; h->is_setup = false; h->u0_dev = nullptr; h->run_buf = nullptr; h->run_bytes = 0; h->perm_dev = nullptr; h->vcur_dev = nullptr; h->vdone_dev = nullptr; h->vqueue_dev = nullptr; h->qperm_dev = nullptr; h->qperm_set = false; h->solves_since_balance = 0; h->auto_balance = 1; h->ncu = 0; h->loop_parts = 0;
-    h->profiling = false; h->run_ms = 0.0; h->run_launches = 0; h->ev_count = 0; h->nevents = 0; h->stream = nullptr; h->own_stream = false;
-    h->warm_x_pending = false;
-    h->csc = nullptr; h->vec_buf = nullptr; h->step_blank = false;
-    memset(&h->tape, 0, sizeof(h->tape)); h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_xref_rows = 1; h->tape_valid = false; h->tape_ny = 0;
-    h->adjm_out = nullptr; h->adjm_sum = nullptr; h->um1_used = nullptr; h->um1_moved = false; h->adj_step = nullptr;
-    h->pin_in = h->pin_out = nullptr; h->pin_in_dev = h->pin_out_dev = nullptr; h->done_dev = nullptr; h->host_seq = 0; h->pin_stride = 0; h->pin_tried = false;
+    h->device = device; h->batch = batch;
     if (s) h->S = *s; else mpcqp_default_settings(&h->S);
     h->L = make_layout(nx, nu, Np, Nc, h->S.soft_constraints);
     // (every failure from here on releases what has been created so far: mpcqp_destroy copes with a partial handle)
@@ -262,7 +256,7 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
         h->nevents = i + 1;
     }
     const Lay &L = h->L;
-    Ptrs &P = h->P; memset(&P, 0, sizeof(P));
+    Ptrs &P = h->P;
     size_t B = (size_t)batch;
     // Small problems keep the iterate x, z, y in LDS behind the common block (four workgroups per CU: 40 KB each); larger
     // ones keep it in L2/HBM.
@@ -1147,6 +1141,12 @@ __global__ __launch_bounds__(256) void k_adjoint_step(Lay L, const double *step,
         dst[idx] = (i >= L.nx && i < L.nx + L.nu) ? um1_used[(size_t)b * L.nu + (i - L.nx)] : step[idx];
     }
 }
+// The adjoint's buffers with the handle's settings (mpcqp_set_adjoint) filled in: what every kernel that runs the K_pol core on a solve starts from.
+static AdjointArgs adjoint_args(const mpcqp_handle *h) {
+    AdjointArgs Q = h->aq;
+    Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
+    return Q;
+}
 static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const double *gu0, bool raw_out) {
     if (flush_puts(h)) return MPCQP_ERR_HIP;
     // mpcqp_mpc_step has left the applied input in the step data as the NEXT u_{-1}, while the iterate belongs to the one before (um1_used):
@@ -1156,8 +1156,7 @@ static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const d
         if (!h->adj_step && dalloc(h, &h->adj_step, total)) return MPCQP_ERR_HIP;
         hipLaunchKernelGGL(k_adjoint_step, dim3((unsigned)std::min<size_t>(1024, (total + 255) / 256)), dim3(256), 0, h->stream, h->L, h->P.step, h->um1_used, h->adj_step, h->batch);
     }
-    AdjointArgs Q = h->aq;
-    Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
+    AdjointArgs Q = adjoint_args(h);
     Q.nseeds = nseeds; Q.gw = gw; Q.gu0 = gu0; Q.chain = h->L.raw ? 0 : 1;
     if (!raw_out) { Q.oq = nullptr; Q.ol = nullptr; Q.ou = nullptr; }
     KpolLaunch v = kpol_launch(h);
@@ -1180,10 +1179,25 @@ static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const d
     HIPCHK(hipGetLastError());
     return MPCQP_OK;
 }
-// The end of a call that copies to or from the caller's arrays (null: not given): wait, unless every one is a device pointer -- then the
+// The model-gradient outputs of a call, taken once from its mpcqp_adjoint_model_io (null: none): the seven pointers in field order (Ad, Bd, Qx,
+// QxN, Qu, QDu, eps_feas), whether any is given, and batch_sum as the caller wrote it (each call refuses a bad one where it did before).
+struct ModelOut { double *out[ADJM_FIELDS]; bool any; int batch_sum; };
+static int model_out(const mpcqp_adjoint_model_io *mo, const std::string &what, ModelOut *m) {
+    *m = ModelOut{};
+    if (!mo) return MPCQP_OK;
+    if (mo->struct_size != (int32_t)sizeof(mpcqp_adjoint_model_io)) return fail(MPCQP_ERR_ARG, what + ": struct_size is not sizeof(mpcqp_adjoint_model_io)");
+    double *const out[ADJM_FIELDS] = {mo->d_Ad, mo->d_Bd, mo->d_Qx, mo->d_QxN, mo->d_Qu, mo->d_QDu, mo->d_eps_feas};
+    for (int f = 0; f < ADJM_FIELDS; ++f) { m->out[f] = out[f]; if (out[f]) m->any = true; }
+    m->batch_sum = mo->batch_sum;
+    return MPCQP_OK;
+}
+// The end of a call that copies to or from the caller's arrays (null: not given; m: its model-gradient outputs too): wait, unless every one is a device pointer -- then the
 // call is stream-ordered throughout and there is nothing to wait for.
-static int sync_unless_all_device(mpcqp_handle *h, std::initializer_list<const void *> ptrs) {
-    for (const void *q : ptrs) if (q && !is_device_ptr(q)) { HIPCHK(hipStreamSynchronize(h->stream)); break; }
+static int sync_unless_all_device(mpcqp_handle *h, std::initializer_list<const void *> ptrs, const ModelOut *m = nullptr) {
+    bool host = false;
+    for (const void *q : ptrs) host = host || (q && !is_device_ptr(q));
+    if (m) for (const double *q : m->out) host = host || (q && !is_device_ptr(q));
+    if (host) HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
 static int adjoint_ready(mpcqp_handle *h, const char *what, bool chain) {
@@ -1198,15 +1212,34 @@ static void adjoint_model_offsets(const Lay &L, int *off) {
     off[0] = 0;
     for (int f = 0; f < ADJM_FIELDS; ++f) off[f + 1] = off[f] + sz[f];
 }
+// The per-instance model gradients [batch][E] and their batch sum [E], on first use, like the adjoint's other buffers.
+static int adjoint_model_alloc(mpcqp_handle *h, size_t E) {
+    if (h->adjm_out) return MPCQP_OK;
+    return dalloc(h, &h->adjm_out, (size_t)h->batch * E) || dalloc(h, &h->adjm_sum, E) ? MPCQP_ERR_HIP : MPCQP_OK;
+}
+// adjm_sum = adjm_out added over the batch (off: adjoint_model_offsets)
+static void launch_adjoint_model_sum(mpcqp_handle *h, const int *off) {
+    AdjointModelArgs M; memset(&M, 0, sizeof(M));
+    std::copy(off, off + ADJM_FIELDS + 1, M.off);
+    M.out = h->adjm_out; M.batch = h->batch;
+    hipLaunchKernelGGL(k_adjoint_model_sum, dim3((unsigned)((M.off[ADJM_FIELDS] + 15) / 16)), dim3(256), 0, h->stream, M, h->adjm_sum);
+}
+// Every field the caller asked for, from adjm_sum (one set) or adjm_out (one per instance).
+static int get_model_out(mpcqp_handle *h, const ModelOut &m, const int *off) {
+    const size_t B = (size_t)h->batch;
+    for (int f = 0; f < ADJM_FIELDS; ++f) {
+        const size_t sz = (size_t)(off[f + 1] - off[f]);
+        const double *src = m.batch_sum ? h->adjm_sum + off[f] : h->adjm_out + B * (size_t)off[f];
+        if (get(h, m.out[f], src, (m.batch_sum ? 1 : B) * sz * sizeof(double))) return MPCQP_ERR_HIP;
+    }
+    return MPCQP_OK;
+}
 // k_adjoint_model behind the k_adjoint launch of the same call, k_adjoint_model_sum behind it where the batch sum is wanted.
 static int launch_adjoint_model(mpcqp_handle *h, bool batch_sum) {
     const Lay G = polish_layout(h->L);
     AdjointModelArgs M; memset(&M, 0, sizeof(M));
     adjoint_model_offsets(G, M.off);
-    const size_t E = (size_t)M.off[ADJM_FIELDS];
-    if (!h->adjm_out) {                                      // on first use, like the adjoint's other buffers
-        if (dalloc(h, &h->adjm_out, (size_t)h->batch * E) || dalloc(h, &h->adjm_sum, E)) return MPCQP_ERR_HIP;
-    }
+    if (adjoint_model_alloc(h, (size_t)M.off[ADJM_FIELDS])) return MPCQP_ERR_HIP;
     M.rw = h->aq.x; M.ry = h->aq.y; M.w = h->P.x; M.y = h->P.y; M.model = h->P.model; M.step = h->um1_moved ? h->adj_step : h->P.step; M.status = h->aq.status;      // (the step data k_adjoint just read)
     M.out = h->adjm_out; M.batch = h->batch;
     const size_t staged = sizeof(double) * ((size_t)NT + 2 * (size_t)G.n + 2 * (size_t)G.n_x);
@@ -1214,7 +1247,7 @@ static int launch_adjoint_model(mpcqp_handle *h, bool batch_sum) {
     const size_t smem = M.staged ? staged : sizeof(double) * (size_t)NT;
     if (set_smem(k_adjoint_model, smem)) return MPCQP_ERR_HIP;
     hipLaunchKernelGGL(k_adjoint_model, dim3(h->batch), dim3(NT), smem, h->stream, G, M);
-    if (batch_sum) hipLaunchKernelGGL(k_adjoint_model_sum, dim3((unsigned)((E + 15) / 16)), dim3(256), 0, h->stream, M, h->adjm_sum);
+    if (batch_sum) launch_adjoint_model_sum(h, M.off);
     HIPCHK(hipGetLastError());
     return MPCQP_OK;
 }
@@ -1222,16 +1255,14 @@ static int launch_adjoint_model(mpcqp_handle *h, bool batch_sum) {
 static int adjoint_call(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp_adjoint_model_io *mo, const char *what) {
     const std::string w(what);
     if (io->struct_size != (int32_t)sizeof(mpcqp_adjoint_io)) return fail(MPCQP_ERR_ARG, w + ": struct_size is not sizeof(mpcqp_adjoint_io)");
-    if (mo && mo->struct_size != (int32_t)sizeof(mpcqp_adjoint_model_io)) return fail(MPCQP_ERR_ARG, w + ": struct_size is not sizeof(mpcqp_adjoint_model_io)");
+    ModelOut m;
+    if (model_out(mo, w, &m)) return MPCQP_ERR_ARG;
     if (!io->g_w && !io->g_u0) return fail(MPCQP_ERR_ARG, w + ": give g_w, g_u0 or both");
     if ((io->d_l == nullptr) != (io->d_u == nullptr)) return fail(MPCQP_ERR_ARG, w + ": d_l and d_u go together");
-    double *const mout[ADJM_FIELDS] = {mo ? mo->d_Ad : nullptr, mo ? mo->d_Bd : nullptr, mo ? mo->d_Qx : nullptr, mo ? mo->d_QxN : nullptr,
-                                       mo ? mo->d_Qu : nullptr, mo ? mo->d_QDu : nullptr, mo ? mo->d_eps_feas : nullptr};
-    bool model = false;
-    for (double *q : mout) if (q) model = true;
+    const bool model = m.any;
     const bool chain = io->d_x0 || io->d_uminus1 || io->d_xref || io->d_uref;
     if (mo) {
-        if (mo->batch_sum != 0 && mo->batch_sum != 1) return fail(MPCQP_ERR_ARG, w + ": batch_sum is 0 or 1");
+        if (m.batch_sum != 0 && m.batch_sum != 1) return fail(MPCQP_ERR_ARG, w + ": batch_sum is 0 or 1");
         if (!model && !chain && !io->d_q && !io->d_l) return fail(MPCQP_ERR_ARG, w + ": no output asked for");
     }
     int rc = adjoint_ready(h, what, chain || model);
@@ -1242,21 +1273,16 @@ static int adjoint_call(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp
     if (io->g_w) HIPCHK(hipMemcpyAsync(h->adj_gw, io->g_w, B * L.n * db, hipMemcpyDefault, h->stream));
     if (io->g_u0) HIPCHK(hipMemcpyAsync(h->adj_gu0, io->g_u0, B * L.nu * db, hipMemcpyDefault, h->stream));
     if ((rc = launch_adjoint(h, 1, io->g_w ? h->adj_gw : nullptr, io->g_u0 ? h->adj_gu0 : nullptr, io->d_q || io->d_l))) return rc;
-    if (model && (rc = launch_adjoint_model(h, mo->batch_sum != 0))) return rc;
+    if (model && (rc = launch_adjoint_model(h, m.batch_sum != 0))) return rc;
     const AdjointArgs &Q = h->aq;
     if (get(h, io->d_x0, Q.ox0, B * L.nx * db) || get(h, io->d_uminus1, Q.oum1, B * L.nu * db) || get(h, io->d_uref, Q.ouref, B * L.nu * db) ||
         get(h, io->d_xref, Q.oxref, B * (size_t)L.xref_rows * L.nx * db) || get(h, io->d_q, Q.oq, B * L.n * db) ||
         get(h, io->d_l, Q.ol, B * L.m * db) || get(h, io->d_u, Q.ou, B * L.m * db)) return MPCQP_ERR_HIP;
     if (model) {
         int off[ADJM_FIELDS + 1]; adjoint_model_offsets(L, off);
-        for (int f = 0; f < ADJM_FIELDS; ++f) {
-            const size_t sz = (size_t)(off[f + 1] - off[f]);
-            const double *src = mo->batch_sum ? h->adjm_sum + off[f] : h->adjm_out + B * (size_t)off[f];
-            if (get(h, mout[f], src, (mo->batch_sum ? 1 : B) * sz * db)) return MPCQP_ERR_HIP;
-        }
+        if (get_model_out(h, m, off)) return MPCQP_ERR_HIP;
     }
-    return sync_unless_all_device(h, {io->g_w, io->g_u0, io->d_x0, io->d_uminus1, io->d_xref, io->d_uref, io->d_q, io->d_l, io->d_u,
-                                      mout[0], mout[1], mout[2], mout[3], mout[4], mout[5], mout[6]});
+    return sync_unless_all_device(h, {io->g_w, io->g_u0, io->d_x0, io->d_uminus1, io->d_xref, io->d_uref, io->d_q, io->d_l, io->d_u}, &m);
 }
 extern "C" int mpcqp_adjoint(mpcqp_handle *h, const mpcqp_adjoint_io *io) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
@@ -1376,6 +1402,26 @@ extern "C" int mpcqp_mpc_loop(mpcqp_handle *h, int nsteps, const mpcqp_loop *io)
     return rc ? rc : loop_run(h, nsteps, io, true);
 }
 
+// io with every trajectory buffer advanced to step k0 (row k0 of x_traj and xhat_traj is written again: the state the steps before ended in).
+// The estimator's buffers move only where there is one (io->ny > 0).
+static mpcqp_loop loop_at(const mpcqp_handle *h, const mpcqp_loop *io, size_t k0) {
+    const Lay &L = h->L;
+    const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu, ny = (size_t)io->ny;
+    const size_t xblk = (size_t)(io->xref_traj && io->xref_rows ? io->xref_rows : L.xref_rows) * nx;
+    mpcqp_loop seg = *io;
+    if (seg.w) seg.w += k0 * B * nx;
+    if (seg.xref_traj) seg.xref_traj += k0 * B * xblk;
+    if (seg.x_traj) seg.x_traj += k0 * B * nx;
+    if (seg.u_traj) seg.u_traj += k0 * B * nu;
+    if (seg.status_traj) seg.status_traj += k0 * B;
+    if (seg.iter_traj) seg.iter_traj += k0 * B;
+    if (ny) {
+        if (seg.v) seg.v += k0 * B * ny;
+        if (seg.xhat_traj) seg.xhat_traj += k0 * B * nx;
+        if (seg.y_traj) seg.y_traj += k0 * B * ny;
+    }
+    return seg;
+}
 // The device loop under a schedule of models (include/mpcqp_model.h): per entry, mpcqp_update_model and one closed-loop launch of the steps it holds for.
 extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt) {
     if (!mt) return mpcqp_mpc_loop(h, nsteps, io);
@@ -1390,20 +1436,13 @@ extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *
     if (rc) return rc;
     const Lay &L = h->L;
     const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu;
-    const size_t xblk = (size_t)(io->xref_traj && io->xref_rows ? io->xref_rows : L.xref_rows) * nx;
     for (int s = 0; s < nseg; ++s) {
         const size_t k0 = (size_t)s * mt->hold;
         mpcqp_model M; memset(&M, 0, sizeof(M));
         if (mt->Ad) M.Ad = mt->Ad + (size_t)s * B * nx * nx;
         if (mt->Bd) M.Bd = mt->Bd + (size_t)s * B * nx * nu;
         if ((rc = mpcqp_update_model(h, &M))) return rc;
-        mpcqp_loop seg = *io;                       // the trajectory buffers, advanced to step k0
-        if (seg.w) seg.w += k0 * B * nx;
-        if (seg.xref_traj) seg.xref_traj += k0 * B * xblk;
-        if (seg.x_traj) seg.x_traj += k0 * B * nx;  // (its row k0 is written again: the state the last segment ended in)
-        if (seg.u_traj) seg.u_traj += k0 * B * nu;
-        if (seg.status_traj) seg.status_traj += k0 * B;
-        if (seg.iter_traj) seg.iter_traj += k0 * B;
+        const mpcqp_loop seg = loop_at(h, io, k0);
         if ((rc = loop_run(h, std::min(mt->hold, nsteps - (int)k0), &seg, s == nseg - 1))) return rc;
     }
     return MPCQP_OK;
@@ -1453,6 +1492,13 @@ extern "C" int mpcqp_rollout_release(mpcqp_handle *h) {
     memset(&h->tape, 0, sizeof(h->tape));
     return MPCQP_OK;
 }
+// What the calls that read the tape back refuse: no tape, for the estimator's part a tape without one, an entry k (null: the call takes none) out of range.
+static int tape_guard(const mpcqp_handle *h, const std::string &fn, bool est, const int *k) {
+    if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, fn + ": the handle holds no tape (call " + (est ? "mpcqp_rollout_est" : "mpcqp_rollout") + " first)");
+    if (est && h->tape_ny == 0) return fail(MPCQP_ERR_STATE, fn + ": the tape is one of mpcqp_rollout (no estimator)");
+    if (k && (*k < 0 || *k >= h->tape.nsteps)) return fail(MPCQP_ERR_ARG, fn + ": k must be in 0 .. nsteps - 1");
+    return MPCQP_OK;
+}
 // The taped loop behind mpcqp_rollout (io->ny == 0) and mpcqp_rollout_est (io->ny > 0): the refusals, the tape's one allocation and its
 // invalidation, k_rollout_tape and one closed-loop launch per step with the trajectory buffers advanced to that step.  With an estimator C, L,
 // the plant and x_true are read from the tape's copies, and x_k, x_{k+1}, y_k are written straight onto the tape (x_traj, y_traj of the step).
@@ -1485,25 +1531,17 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, co
     }
     HIPCHK(hipMemsetAsync(T.nact, 0, (3 * (size_t)nsteps * B + B) * sizeof(int), h->stream));      // (mpcqp_get_rollout_info before a sweep: all zero)
     h->tape = T; h->tape_xref_rows = L.xref_rows; h->tape_ny = io->ny;
-    const size_t xblk = (size_t)L.xref_rows * nx;
     const size_t per = (size_t)L.n + 2 * (size_t)L.m + L.step_sz + nu + 1;
     const unsigned grid = (unsigned)std::min<size_t>(1024, (B * per + 255) / 256);
     for (int k = 0; k < nsteps; ++k) {
         hipLaunchKernelGGL(k_rollout_tape, dim3(grid), dim3(256), 0, h->stream, h->L, h->P, T, k, (const double *)(h->um1_moved ? h->um1_used : nullptr));
         HIPCHK(hipGetLastError());
-        mpcqp_loop seg = *io;                       // the trajectory buffers, advanced to step k (as mpcqp_mpc_loop_tv advances them per entry)
         const size_t k0 = (size_t)k;
-        if (seg.w) seg.w += k0 * B * nx;
-        if (seg.xref_traj) seg.xref_traj += k0 * B * xblk;
-        if (seg.u_traj) seg.u_traj += k0 * B * nu;
-        if (seg.status_traj) seg.status_traj += k0 * B;
-        if (seg.iter_traj) seg.iter_traj += k0 * B;
-        if (ny) {
+        mpcqp_loop seg = loop_at(h, io, k0);
+        if (ny) {                                   // (the estimator's loop reads and writes the tape's own copies)
             seg.Ap = T.Ap; seg.Bp = T.Bp; seg.C = T.C; seg.Lgain = T.Lg; seg.x_true = T.xt;
             seg.x_traj = T.xp + k0 * B * nx; seg.y_traj = T.ym + k0 * B * ny;
-            if (seg.v) seg.v += k0 * B * ny;
-            if (seg.xhat_traj) seg.xhat_traj += k0 * B * nx;
-        } else if (seg.x_traj) seg.x_traj += k0 * B * nx;
+        }
         if ((rc = loop_run(h, 1, &seg, k == nsteps - 1))) return rc;
     }
     if (ny && (get(h, io->x_traj, T.xp, ((size_t)nsteps + 1) * B * nx * db) || get(h, io->y_traj, T.ym, (size_t)nsteps * B * ny * db) ||
@@ -1529,34 +1567,36 @@ extern "C" int mpcqp_rollout_est(mpcqp_handle *h, int nsteps, const mpcqp_loop *
 }
 extern "C" int mpcqp_rollout_get_tape_est(mpcqp_handle *h, int k, double *x_plant, double *y_meas) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
-    if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_get_tape_est: the handle holds no tape (call mpcqp_rollout_est first)");
-    if (h->tape_ny == 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_get_tape_est: the tape is one of mpcqp_rollout (no estimator)");
+    const int rc = tape_guard(h, "mpcqp_rollout_get_tape_est", true, &k);
+    if (rc) return rc;
     const RolloutTape &T = h->tape;
-    if (k < 0 || k >= T.nsteps) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_get_tape_est: k must be in 0 .. nsteps - 1");
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch, kB = (size_t)k * B, db = sizeof(double);
     if (get(h, x_plant, T.xp + kB * h->L.nx, B * h->L.nx * db) || get(h, y_meas, T.ym + kB * (size_t)h->tape_ny, B * (size_t)h->tape_ny * db)) return MPCQP_ERR_HIP;
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
+// A seed of the sweep into its place on the tape; one that is not given is zero.
+static int put_seed(mpcqp_handle *h, double *dst, const double *src, size_t bytes) {
+    if (src) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, h->stream));
+    else HIPCHK(hipMemsetAsync(dst, 0, bytes, h->stream));
+    return MPCQP_OK;
+}
 // eo: the estimator's seeds and gradients (mpcqp_rollout_adjoint_est), or null.  est: the call is mpcqp_rollout_adjoint_est.
 static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo, bool est) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
     if (io->struct_size != (int32_t)sizeof(mpcqp_rollout_adjoint_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: struct_size is not sizeof(mpcqp_rollout_adjoint_io)");
-    if (mo && mo->struct_size != (int32_t)sizeof(mpcqp_adjoint_model_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: struct_size is not sizeof(mpcqp_adjoint_model_io)");
+    ModelOut m;                                     // (its refusals say mpcqp_rollout_adjoint on the _est path too)
+    if (model_out(mo, "mpcqp_rollout_adjoint", &m)) return MPCQP_ERR_ARG;
     if (eo && eo->struct_size != (int32_t)sizeof(mpcqp_rollout_est_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_est: struct_size is not sizeof(mpcqp_rollout_est_io)");
     if (!est && !io->G_x && !io->G_u) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: give G_x, G_u or both");
     if (est && !io->G_x && !io->G_u && !(eo && (eo->G_xhat || eo->G_y))) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_est: give at least one of G_x, G_u, G_xhat, G_y");
     if (io->no_reuse != 0 && io->no_reuse != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: no_reuse is 0 or 1");
-    if (mo && mo->batch_sum != 0 && mo->batch_sum != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: batch_sum is 0 or 1");
+    if (m.batch_sum != 0 && m.batch_sum != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: batch_sum is 0 or 1");
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint before mpcqp_setup");
     if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the handle holds no tape (call mpcqp_rollout first)");
     if (!h->tape_valid) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the model or the scaling the tape was made under has been replaced (mpcqp_setup*, mpcqp_update_model, mpcqp_update_vectors with l, u) or its rollout failed: roll out again");
     if (est && h->tape_ny == 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_est: the tape is one of mpcqp_rollout (no estimator); use mpcqp_rollout_adjoint");
-    double *const mout[ADJM_FIELDS] = {mo ? mo->d_Ad : nullptr, mo ? mo->d_Bd : nullptr, mo ? mo->d_Qx : nullptr, mo ? mo->d_QxN : nullptr,
-                                       mo ? mo->d_Qu : nullptr, mo ? mo->d_QDu : nullptr, mo ? mo->d_eps_feas : nullptr};
-    bool model = false;
-    for (double *q : mout) if (q) model = true;
     HIPCHK(hipSetDevice(h->device));
     int rc = adjoint_alloc(h);
     if (rc) return rc;
@@ -1566,63 +1606,35 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     G.raw = 0; G.xref_rows = h->tape_xref_rows;     // (the tape's entries, whatever the handle has been given since)
     RolloutSweep W; memset(&W, 0, sizeof(W));
     adjoint_model_offsets(G, W.off);
-    const size_t E = (size_t)W.off[ADJM_FIELDS], B = (size_t)h->batch, K = (size_t)T.nsteps, nx = G.nx, nu = G.nu, db = sizeof(double);
-    if (!h->adjm_out) {                                      // on first use, like the adjoint's other buffers
-        if (dalloc(h, &h->adjm_out, B * E) || dalloc(h, &h->adjm_sum, E)) return MPCQP_ERR_HIP;
-    }
-    if (io->G_x) HIPCHK(hipMemcpyAsync(T.gx, io->G_x, (K + 1) * B * nx * db, hipMemcpyDefault, h->stream));
-    else HIPCHK(hipMemsetAsync(T.gx, 0, (K + 1) * B * nx * db, h->stream));
-    if (io->G_u) HIPCHK(hipMemcpyAsync(T.gu, io->G_u, K * B * nu * db, hipMemcpyDefault, h->stream));
-    else HIPCHK(hipMemsetAsync(T.gu, 0, K * B * nu * db, h->stream));
+    const size_t B = (size_t)h->batch, K = (size_t)T.nsteps, nx = G.nx, nu = G.nu, db = sizeof(double);
+    if (adjoint_model_alloc(h, (size_t)W.off[ADJM_FIELDS])) return MPCQP_ERR_HIP;      // (the sweep writes its model terms there whether or not they are asked for)
     const size_t ny = (size_t)h->tape_ny;
-    if (ny) {
-        if (eo && eo->G_xhat) HIPCHK(hipMemcpyAsync(T.gxh, eo->G_xhat, (K + 1) * B * nx * db, hipMemcpyDefault, h->stream));
-        else HIPCHK(hipMemsetAsync(T.gxh, 0, (K + 1) * B * nx * db, h->stream));
-        if (eo && eo->G_y) HIPCHK(hipMemcpyAsync(T.gy, eo->G_y, K * B * ny * db, hipMemcpyDefault, h->stream));
-        else HIPCHK(hipMemsetAsync(T.gy, 0, K * B * ny * db, h->stream));
-    }
-    AdjointArgs Q = h->aq;
-    Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
+    if (put_seed(h, T.gx, io->G_x, (K + 1) * B * nx * db) || put_seed(h, T.gu, io->G_u, K * B * nu * db)) return MPCQP_ERR_HIP;
+    if (ny && (put_seed(h, T.gxh, eo ? eo->G_xhat : nullptr, (K + 1) * B * nx * db) || put_seed(h, T.gy, eo ? eo->G_y : nullptr, K * B * ny * db))) return MPCQP_ERR_HIP;
+    AdjointArgs Q = adjoint_args(h);
     Q.nseeds = 1; Q.gw = nullptr; Q.gu0 = nullptr; Q.chain = 1; Q.ncol = 1; Q.cs = 0;
-    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = model ? 1 : 0;
+    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = m.any ? 1 : 0;
     const size_t with_carry = v.smem + db * (size_t)rollout_carry_doubles(G, (int)ny);
     W.carry_lds = with_carry <= 160 * 1024 ? 1 : 0;         // (lam, mu, g behind the common block, or in the tape's few doubles of global memory)
     const size_t smem = W.carry_lds ? with_carry : v.smem;
-    if (ny) {
-        DISPATCH_NB(G.NB, {
-            if (set_smem(k_rollout_adjoint_est<NB>, smem)) return MPCQP_ERR_HIP;
-            hipLaunchKernelGGL(k_rollout_adjoint_est<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
-        });
-    } else {
-        DISPATCH_NB(G.NB, {
-            if (set_smem(k_rollout_adjoint<NB>, smem)) return MPCQP_ERR_HIP;
-            hipLaunchKernelGGL(k_rollout_adjoint<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
-        });
-    }
+    DISPATCH_NB(G.NB, {
+        const auto kernel = ny ? k_rollout_adjoint_est<NB> : k_rollout_adjoint<NB>;      // (one sweep, with and without the estimator: mpcqp_rollout.h)
+        if (set_smem(kernel, smem)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(kernel, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
+    });
     HIPCHK(hipGetLastError());
     const size_t xw = (size_t)G.xref_rows * nx;
     if (get(h, io->lam, T.lam, (K + 1) * B * nx * db) || get(h, io->d_uminus1, T.dum1, B * nu * db) || get(h, io->d_uref, T.duref, B * nu * db) ||
         get(h, io->d_xref, T.dxref, K * B * xw * db) || get(h, io->d_Ap, T.dAp, B * nx * nx * db) || get(h, io->d_Bp, T.dBp, B * nx * nu * db)) return MPCQP_ERR_HIP;
     if (ny && eo && (get(h, eo->eta, T.eta, (K + 1) * B * nx * db) || get(h, eo->d_v, T.dv, K * B * ny * db) || get(h, eo->d_C, T.dC, B * ny * nx * db) ||
                      get(h, eo->d_L, T.dL, B * nx * ny * db) || get(h, eo->d_Ae, T.dAe, B * nx * nx * db) || get(h, eo->d_Be, T.dBe, B * nx * nu * db))) return MPCQP_ERR_HIP;
-    if (model) {
-        if (mo->batch_sum) {
-            AdjointModelArgs M; memset(&M, 0, sizeof(M));
-            adjoint_model_offsets(G, M.off);
-            M.out = h->adjm_out; M.batch = h->batch;
-            hipLaunchKernelGGL(k_adjoint_model_sum, dim3((unsigned)((E + 15) / 16)), dim3(256), 0, h->stream, M, h->adjm_sum);
-            HIPCHK(hipGetLastError());
-        }
-        for (int f = 0; f < ADJM_FIELDS; ++f) {
-            const size_t sz = (size_t)(W.off[f + 1] - W.off[f]);
-            const double *src = mo->batch_sum ? h->adjm_sum + W.off[f] : h->adjm_out + B * (size_t)W.off[f];
-            if (get(h, mout[f], src, (mo->batch_sum ? 1 : B) * sz * db)) return MPCQP_ERR_HIP;
-        }
+    if (m.any) {
+        if (m.batch_sum) { launch_adjoint_model_sum(h, W.off); HIPCHK(hipGetLastError()); }
+        if (get_model_out(h, m, W.off)) return MPCQP_ERR_HIP;
     }
     return sync_unless_all_device(h, {io->G_x, io->G_u, io->lam, io->d_uminus1, io->d_uref, io->d_xref, io->d_Ap, io->d_Bp,
-                                      mout[0], mout[1], mout[2], mout[3], mout[4], mout[5], mout[6],
                                       eo ? eo->G_xhat : nullptr, eo ? eo->G_y : nullptr, eo ? eo->eta : nullptr, eo ? eo->d_C : nullptr, eo ? eo->d_L : nullptr,
-                                      eo ? eo->d_v : nullptr, eo ? eo->d_Ae : nullptr, eo ? eo->d_Be : nullptr});
+                                      eo ? eo->d_v : nullptr, eo ? eo->d_Ae : nullptr, eo ? eo->d_Be : nullptr}, &m);
 }
 extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
     return rollout_sweep(h, io, nullptr, mo, false);
@@ -1632,7 +1644,8 @@ extern "C" int mpcqp_rollout_adjoint_est(mpcqp_handle *h, const mpcqp_rollout_ad
 }
 extern "C" int mpcqp_get_rollout_info(mpcqp_handle *h, int32_t *n_active, int32_t *n_weak, int32_t *status, int32_t *n_factor) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
-    if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_get_rollout_info: the handle holds no tape (call mpcqp_rollout first)");
+    const int rc = tape_guard(h, "mpcqp_get_rollout_info", false, nullptr);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
     const RolloutTape &T = h->tape;
     const size_t kb = sizeof(int32_t) * (size_t)T.nsteps * (size_t)h->batch;
@@ -1643,9 +1656,9 @@ extern "C" int mpcqp_get_rollout_info(mpcqp_handle *h, int32_t *n_active, int32_
 }
 extern "C" int mpcqp_rollout_get_tape(mpcqp_handle *h, int k, double *x, double *z, double *y, double *step, int32_t *status) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
-    if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_get_tape: the handle holds no tape (call mpcqp_rollout first)");
+    const int rc = tape_guard(h, "mpcqp_rollout_get_tape", false, &k);
+    if (rc) return rc;
     const RolloutTape &T = h->tape;
-    if (k < 0 || k >= T.nsteps) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_get_tape: k must be in 0 .. nsteps - 1");
     HIPCHK(hipSetDevice(h->device));
     const Lay &L = h->L;
     const size_t B = (size_t)h->batch, kB = (size_t)k * B, db = sizeof(double);

@@ -28,6 +28,16 @@ _FIXED_AT_CREATE = ('rho', 'sigma', 'scaling', 'soft_constraints', 'backend', 't
 
 _STATUS_STRINGS = {}       # status code -> OSQP's string (filled from mpcqp_status_string on first use)
 
+# the extensions beside include/mpcqp.h: feature -> (is it in the loaded library, what BatchProblem._need says where it is not)
+_FEATURES = dict(
+    polish=(_lib.has_polish, 'no solution polishing (include/mpcqp_polish.h)'),
+    adjoint=(_lib.has_adjoint, 'no adjoint derivatives (include/mpcqp_adjoint.h)'),
+    adjoint_model=(_lib.has_adjoint_model, 'no model gradients (include/mpcqp_adjoint_model.h)'),
+    rollout=(_lib.has_rollout, 'no taped rollout (include/mpcqp_rollout.h)'),
+    rollout_est=(_lib.has_rollout_est, 'no taped output-feedback rollout (include/mpcqp_rollout_est.h)'),
+    model_update=(_lib.has_model_update, 'no in-place model update (include/mpcqp_model.h)'),
+    model_traj=(_lib.has_model_update, 'no model schedule for the device loop (include/mpcqp_model.h)'))
+
 
 def _ptr(a):
     if a is None:
@@ -49,6 +59,14 @@ def _prep_out(a, shape, name):
     if not ok:
         raise ValueError('%s must be a writable C-contiguous float64 array or tensor of %d values (shape %s)' % (name, size, (shape,)))
     return a
+
+
+def _model_struct(arrs):
+    """mpcqp_model with the fields of ``arrs`` (name -> prepared array or tensor); the others stay null = not given."""
+    model = _lib.Model()
+    for k, v in arrs.items():
+        setattr(model, k, C.cast(_ptr(v), C.POINTER(C.c_double)))
+    return model
 
 
 def _prep(a, shape, name):
@@ -205,6 +223,12 @@ class BatchProblem:
             raise NotAnMPCQP(self._L.mpcqp_last_error().decode())
         _lib.check(rc, 'mpcqp_setup_csc')
 
+    def _need(self, feature):
+        """Raise NotImplementedError if the loaded library does not export ``feature`` (a key of _FEATURES); never a silent fallback."""
+        has, what = _FEATURES[feature]
+        if not has(self._L):
+            raise NotImplementedError('this build of the solver library has ' + what)
+
     _hin = None                # (step_host of a single controller: input buffer, made on first use)
     _polish = None             # mpcqp_polish_settings of the handle (None: the library has no polishing, include/mpcqp_polish.h)
 
@@ -231,8 +255,7 @@ class BatchProblem:
 
     def polish(self):
         """Polish the last solve of every instance now (mpcqp_polish: stream-ordered), with this problem's delta / polish_refine_iter."""
-        if not _lib.has_polish(self._L):
-            raise NotImplementedError('this build of the solver library has no solution polishing (include/mpcqp_polish.h)')
+        self._need('polish')
         _lib.check(self._L.mpcqp_polish(self._h), 'mpcqp_polish')
 
     def polish_status(self):
@@ -245,13 +268,9 @@ class BatchProblem:
     # -- adjoint derivatives (include/mpcqp_adjoint.h) --------------------------------------------
     _adjoint = None            # mpcqp_adjoint_settings of the handle, once changed
 
-    def _need_adjoint(self):
-        if not _lib.has_adjoint(self._L):
-            raise NotImplementedError('this build of the solver library has no adjoint derivatives (include/mpcqp_adjoint.h)')
-
     def set_adjoint(self, **kw):
         """The adjoint's own delta / refine_iter / extra_iter / weak_tol (mpcqp_set_adjoint); the polish settings are separate."""
-        self._need_adjoint()
+        self._need('adjoint')
         if self._adjoint is None:
             self._adjoint = _lib.AdjointSettings()
             self._L.mpcqp_adjoint_default_settings(C.byref(self._adjoint))
@@ -272,6 +291,26 @@ class BatchProblem:
             return torch.empty(shape, dtype=torch.float64, device=like.device)
         return np.empty(shape)
 
+    def _model_grads(self, batch_sum):
+        """(mpcqp_adjoint_model_io, its part of a gradient table): the model gradients per instance, or summed over the batch [1, ...]."""
+        B, nx, nu = 1 if batch_sum else self.batch, self.nx, self.nu
+        mo = _lib.AdjointModelIO()
+        mo.struct_size, mo.batch_sum = C.sizeof(_lib.AdjointModelIO), int(bool(batch_sum))
+        shapes = dict(Ad=(B, nx, nx), Bd=(B, nx, nu), Qx=(B, nx, nx), QxN=(B, nx, nx), Qu=(B, nu, nu), QDu=(B, nu, nu), eps_feas=(B,))
+        return mo, {k: (mo, 'd_' + k, shape) for k, shape in shapes.items()}
+
+    def _grads_out(self, want, table, out, like):
+        """The gradients named in ``want`` as a dict of arrays -- taken from ``out`` where it has them, else made like ``like`` -- each with its
+        address put where ``table`` says: name -> (ctypes struct, field, shape)."""
+        res = {}
+        for k in want:
+            if k not in table:
+                raise TypeError('unknown gradient %r' % k)
+            struct, field, shape = table[k]
+            res[k] = _prep_out(out[k], shape, 'out[%r]' % k) if out is not None and k in out else self._out(like, shape)
+            setattr(struct, field, _ptr(res[k]))
+        return res
+
     def adjoint(self, g_w=None, g_u0=None, want=('x0', 'uminus1', 'xref', 'uref'), out=None, batch_sum=False):
         """Adjoint derivatives of the current solution (mpcqp_adjoint): for the seed ``g_w`` [B, n] = dL/dw and / or ``g_u0`` [B, nu] = dL/du_0
         returns a dict with the gradients named in ``want`` -- any of 'x0' [B, nx], 'uminus1' [B, nu], 'xref' [B, rows*nx] (shape of the
@@ -282,39 +321,28 @@ class BatchProblem:
         Seeds may be numpy arrays or torch device tensors; the results are of the same kind (device tensors: stream-ordered, no wait), or
         are written into the arrays / tensors given in ``out`` (a dict by the same names).  The gradients are those of the active set the
         iterate implies; ``adjoint_info()`` reports weakly active rows."""
-        self._need_adjoint()
+        self._need('adjoint')
         if g_w is None and g_u0 is None:
             raise ValueError('adjoint: give g_w, g_u0 or both')
-        B, nx, nu = self.batch, self.nx, self.nu
+        B = self.batch
         like = g_w if g_w is not None else g_u0
         gw = _prep(g_w, (B, self.n), 'g_w') if g_w is not None else None
         gu = _prep(g_u0, (B, self.nu), 'g_u0') if g_u0 is not None else None
-        shapes = dict(x0=(B, self.nx), uminus1=(B, self.nu), xref=(B, self._xref_rows_last * self.nx), uref=(B, self.nu),
-                      q=(B, self.n), l=(B, self.m), u=(B, self.m))
-        Bm = 1 if batch_sum else B
-        mshapes = dict(Ad=(Bm, nx, nx), Bd=(Bm, nx, nu), Qx=(Bm, nx, nx), QxN=(Bm, nx, nx), Qu=(Bm, nu, nu), QDu=(Bm, nu, nu), eps_feas=(Bm,))
-        want = list(want)
-        if ('l' in want) != ('u' in want):
-            want += ['l' if 'u' in want else 'u']
-        model = any(k in mshapes for k in want)
-        if model and not _lib.has_adjoint_model(self._L):
-            raise NotImplementedError('this build of the solver library has no model gradients (include/mpcqp_adjoint_model.h)')
-        res = {}
         io = _lib.AdjointIO()
         io.struct_size = C.sizeof(_lib.AdjointIO)
         io.g_w, io.g_u0 = _ptr(gw), _ptr(gu)
-        mo = _lib.AdjointModelIO()
-        mo.struct_size, mo.batch_sum = C.sizeof(_lib.AdjointModelIO), int(bool(batch_sum))
-        for k in want:
-            if k not in shapes and k not in mshapes:
-                raise TypeError('unknown gradient %r' % k)
-            shape = shapes[k] if k in shapes else mshapes[k]
-            if out is not None and k in out:
-                a = _prep_out(out[k], shape, 'out[%r]' % k)
-            else:
-                a = self._out(like, shape)
-            res[k] = a
-            setattr(mo if k in mshapes else io, 'd_' + k, _ptr(a))
+        shapes = dict(x0=(B, self.nx), uminus1=(B, self.nu), xref=(B, self._xref_rows_last * self.nx), uref=(B, self.nu),
+                      q=(B, self.n), l=(B, self.m), u=(B, self.m))
+        table = {k: (io, 'd_' + k, shape) for k, shape in shapes.items()}
+        mo, mtable = self._model_grads(batch_sum)
+        table.update(mtable)
+        want = list(want)
+        if ('l' in want) != ('u' in want):
+            want += ['l' if 'u' in want else 'u']
+        model = any(k in mtable for k in want)
+        if model:
+            self._need('adjoint_model')
+        res = self._grads_out(want, table, out, like)
         self._keep = [gw, gu, res]
         if model:
             _lib.check(self._L.mpcqp_adjoint_model(self._h, C.byref(io), C.byref(mo)), 'mpcqp_adjoint_model')
@@ -326,7 +354,7 @@ class BatchProblem:
         """Jacobians of the first input u_0 of the current solution (mpcqp_gains: one factorization, nu seeds): dict with 'x0' [B, nu, nx],
         'uminus1' [B, nu, nu], 'xref' [B, nu, rows*nx], 'uref' [B, nu, nu] as named in ``want``; numpy, or torch tensors on the device
         of ``like``."""
-        self._need_adjoint()
+        self._need('adjoint')
         B, nu = self.batch, self.nu
         shapes = dict(x0=(B, nu, self.nx), uminus1=(B, nu, nu), xref=(B, nu, self._xref_rows_last * self.nx), uref=(B, nu, nu))
         res = {k: self._out(like, shapes[k]) for k in want}
@@ -338,7 +366,7 @@ class BatchProblem:
         """(n_active, n_weak, status) [batch] int32 of the last adjoint() / gains() (mpcqp_get_adjoint_info; synchronises): status 1 computed,
         0 the instance's solve did not end 'solved', -1 the factorization broke (outputs zero in both cases); n_weak > 0: rows on a bound
         with a zero multiplier -- the control law has a kink there and the result is a one-sided derivative."""
-        self._need_adjoint()
+        self._need('adjoint')
         out = [np.zeros(self.batch, dtype=np.int32) for _ in range(3)]
         _lib.check(self._L.mpcqp_get_adjoint_info(self._h, *[_ptr(o) for o in out]), 'mpcqp_get_adjoint_info')
         return tuple(out)
@@ -348,32 +376,24 @@ class BatchProblem:
     _rollout_ny = 0            # > 0: the tape is one of the output-feedback loop (rollout_est)
     rollout_count = 0          # rollouts made so far (pympc_amd.torch_layer: is the tape still the one of a forward?)
 
-    def _need_rollout(self):
-        if not _lib.has_rollout(self._L):
-            raise NotImplementedError('this build of the solver library has no taped rollout (include/mpcqp_rollout.h)')
-
     def rollout(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
         """``mpc_run`` that keeps a tape (mpcqp_rollout): the same arguments and results, one closed-loop launch per step, and afterwards
         ``rollout_adjoint`` can push a loss on the trajectory back through the loop.  No estimator, no model schedule."""
-        self._need_rollout()
-        res = self.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, _taped=True)
+        self._need('rollout')
+        res = self._loop('mpcqp_rollout', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj)
         self._rollout_shape = (int(nsteps), self._xref_rows_last)
         self._rollout_ny = 0
         self.rollout_count += 1
         return res
 
-    def _need_rollout_est(self):
-        if not _lib.has_rollout_est(self._L):
-            raise NotImplementedError('this build of the solver library has no taped output-feedback rollout (include/mpcqp_rollout_est.h)')
-
     def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None, out=None):
         """``mpc_run(estimator=dict(C=, L=, x_true=, v=))`` that keeps a tape (mpcqp_rollout_est): the same arguments and results
         (``x, u, status, iter, xhat, y``), and afterwards ``rollout_adjoint`` -- with ``g_xhat``, ``g_y`` and the gradients 'eta', 'C', 'L', 'v',
         'Ae', 'Be' on top -- pushes a loss on the trajectory back through controller, plant and estimator."""
-        self._need_rollout_est()
+        self._need('rollout_est')
         if estimator is None:
             raise ValueError('rollout_est: an estimator dict(C=, L=, x_true=, v=) is needed (rollout is the taped loop without one)')
-        res = self.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, _taped='est')
+        res = self._loop('mpcqp_rollout_est', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator)
         self._rollout_shape = (int(nsteps), self._xref_rows_last)
         self._rollout_ny = int(tuple(estimator['C'].shape)[-2])
         self.rollout_count += 1
@@ -381,10 +401,10 @@ class BatchProblem:
 
     def rollout_tape_bytes(self, nsteps, ny=0):
         """Device memory a tape of ``nsteps`` steps takes (mpcqp_rollout_tape_bytes; with ``ny`` outputs: mpcqp_rollout_est_tape_bytes)."""
-        self._need_rollout()
+        self._need('rollout')
         v = C.c_int64()
         if ny:
-            self._need_rollout_est()
+            self._need('rollout_est')
             _lib.check(self._L.mpcqp_rollout_est_tape_bytes(self._h, int(nsteps), int(ny), C.byref(v)), 'mpcqp_rollout_est_tape_bytes')
             return v.value
         _lib.check(self._L.mpcqp_rollout_tape_bytes(self._h, int(nsteps), C.byref(v)), 'mpcqp_rollout_tape_bytes')
@@ -392,7 +412,7 @@ class BatchProblem:
 
     def rollout_release(self):
         """Free the tape (mpcqp_rollout_release)."""
-        self._need_rollout()
+        self._need('rollout')
         _lib.check(self._L.mpcqp_rollout_release(self._h), 'mpcqp_rollout_release')
         self._rollout_shape = None
         self._rollout_ny = 0
@@ -407,7 +427,7 @@ class BatchProblem:
         On the tape of a ``rollout_est`` (mpcqp_rollout_adjoint_est): ``g_xhat`` [K+1, B, nx] = dL/dxhat_k and ``g_y`` [K, B, ny] = dL/dy_k are
         seeds too (any one of the four is enough), and ``want`` may name 'eta' [K+1, B, nx] (eta[0] = dL/dxhat_0), 'C' [B, ny, nx],
         'L' [B, nx, ny], 'v' [K, B, ny], 'Ae' [B, nx, nx], 'Be' [B, nx, nu] (the estimator path alone); on a state-feedback tape they raise."""
-        self._need_rollout()
+        self._need('rollout')
         ny = self._rollout_ny
         est_names = ('eta', 'C', 'L', 'v', 'Ae', 'Be')
         if self._rollout_shape is not None and not ny and (g_xhat is not None or g_y is not None or any(k in est_names for k in want)):
@@ -423,34 +443,23 @@ class BatchProblem:
         gu = _prep(g_u, (K, B, nu), 'g_u') if g_u is not None else None
         gxh = _prep(g_xhat, (K + 1, B, nx), 'g_xhat') if g_xhat is not None else None
         gy = _prep(g_y, (K, B, ny), 'g_y') if g_y is not None else None
-        shapes = dict(lam=(K + 1, B, nx), uminus1=(B, nu), uref=(B, nu), xref=(K, B, rows * nx), Ap=(B, nx, nx), Bp=(B, nx, nu))
-        eshapes = dict(eta=(K + 1, B, nx), C=(B, ny, nx), L=(B, nx, ny), v=(K, B, ny), Ae=(B, nx, nx), Be=(B, nx, nu)) if ny else {}
-        eo = _lib.RolloutEstIO()
-        eo.struct_size = C.sizeof(_lib.RolloutEstIO)
-        eo.G_xhat, eo.G_y = _ptr(gxh), _ptr(gy)
-        Bm = 1 if batch_sum else B
-        mshapes = dict(Ad=(Bm, nx, nx), Bd=(Bm, nx, nu), Qx=(Bm, nx, nx), QxN=(Bm, nx, nx), Qu=(Bm, nu, nu), QDu=(Bm, nu, nu), eps_feas=(Bm,))
         io = _lib.RolloutAdjointIO()
         io.struct_size, io.no_reuse = C.sizeof(_lib.RolloutAdjointIO), int(bool(no_reuse))
         io.G_x, io.G_u = _ptr(gx), _ptr(gu)
-        mo = _lib.AdjointModelIO()
-        mo.struct_size, mo.batch_sum = C.sizeof(_lib.AdjointModelIO), int(bool(batch_sum))
-        res = {}
-        for k in want:
-            if k not in shapes and k not in mshapes and k not in eshapes:
-                raise TypeError('unknown gradient %r' % k)
-            shape = shapes[k] if k in shapes else (mshapes[k] if k in mshapes else eshapes[k])
-            a = _prep_out(out[k], shape, 'out[%r]' % k) if out is not None and k in out else self._out(like, shape)
-            res[k] = a
-            if k in mshapes:
-                setattr(mo, 'd_' + k, _ptr(a))
-            elif k in eshapes:
-                setattr(eo, k if k == 'eta' else 'd_' + k, _ptr(a))
-            else:
-                setattr(io, k if k == 'lam' else 'd_' + k, _ptr(a))
+        eo = _lib.RolloutEstIO()
+        eo.struct_size = C.sizeof(_lib.RolloutEstIO)
+        eo.G_xhat, eo.G_y = _ptr(gxh), _ptr(gy)
+        table = dict(lam=(io, 'lam', (K + 1, B, nx)), uminus1=(io, 'd_uminus1', (B, nu)), uref=(io, 'd_uref', (B, nu)),
+                     xref=(io, 'd_xref', (K, B, rows * nx)), Ap=(io, 'd_Ap', (B, nx, nx)), Bp=(io, 'd_Bp', (B, nx, nu)))
+        if ny:
+            table.update(eta=(eo, 'eta', (K + 1, B, nx)), C=(eo, 'd_C', (B, ny, nx)), L=(eo, 'd_L', (B, nx, ny)), v=(eo, 'd_v', (K, B, ny)),
+                         Ae=(eo, 'd_Ae', (B, nx, nx)), Be=(eo, 'd_Be', (B, nx, nu)))
+        mo, mtable = self._model_grads(batch_sum)
+        table.update(mtable)
+        res = self._grads_out(want, table, out, like)
         self._keep = [gx, gu, gxh, gy, res]
         if ny:
-            self._need_rollout_est()
+            self._need('rollout_est')
             _lib.check(self._L.mpcqp_rollout_adjoint_est(self._h, C.byref(io), C.byref(eo), C.byref(mo)), 'mpcqp_rollout_adjoint_est')
         else:
             _lib.check(self._L.mpcqp_rollout_adjoint(self._h, C.byref(io), C.byref(mo)), 'mpcqp_rollout_adjoint')
@@ -459,7 +468,7 @@ class BatchProblem:
     def rollout_info(self):
         """(n_active [K, B], n_weak [K, B], status [K, B], n_factor [B]) int32 of the last ``rollout_adjoint`` (mpcqp_get_rollout_info;
         synchronises): per tape entry as ``adjoint_info``; n_factor: the factorizations the sweep made."""
-        self._need_rollout()
+        self._need('rollout')
         if self._rollout_shape is None:
             raise RuntimeError('rollout_info: no rollout has been made (mpcqp_rollout)')
         K = self._rollout_shape[0]
@@ -470,7 +479,7 @@ class BatchProblem:
     def rollout_tape(self, k):
         """Tape entry k (mpcqp_rollout_get_tape; verification): dict(x [B, n], z, y [B, m], step [B, nx + nu + rows*nx] = (x_k | the u_{-1}
         the solve was made with | xref), status [B])."""
-        self._need_rollout()
+        self._need('rollout')
         if self._rollout_shape is None:
             raise RuntimeError('rollout_tape: no rollout has been made (mpcqp_rollout)')
         B, rows = self.batch, self._rollout_shape[1]
@@ -506,17 +515,10 @@ class BatchProblem:
               x0, uminus1, xref):
         B, nx, nu = self.batch, self.nx, self.nu
         xref_rows = self._xref_rows(xref)
-        arrs = dict(
-            Ad=_prep(Ad, (B, nx, nx), 'Ad'), Bd=_prep(Bd, (B, nx, nu), 'Bd'),
-            Qx=_prep(Qx, (B, nx, nx), 'Qx'), QxN=_prep(QxN, (B, nx, nx), 'QxN'),
-            Qu=_prep(Qu, (B, nu, nu), 'Qu'), QDu=_prep(QDu, (B, nu, nu), 'QDu'),
-            xmin=_prep(xmin, (B, nx), 'xmin'), xmax=_prep(xmax, (B, nx), 'xmax'),
-            umin=_prep(umin, (B, nu), 'umin'), umax=_prep(umax, (B, nu), 'umax'),
-            Dumin=_prep(Dumin, (B, nu), 'Dumin'), Dumax=_prep(Dumax, (B, nu), 'Dumax'),
-            uref=_prep(uref, (B, nu), 'uref'), eps_feas=_prep(eps_feas, (B, 1), 'eps_feas'))
-        model = _lib.Model()
-        for k, v in arrs.items():
-            setattr(model, k, C.cast(_ptr(v), C.POINTER(C.c_double)))
+        given = dict(Ad=Ad, Bd=Bd, Qx=Qx, QxN=QxN, Qu=Qu, QDu=QDu, xmin=xmin, xmax=xmax, umin=umin, umax=umax, Dumin=Dumin, Dumax=Dumax,
+                     uref=uref, eps_feas=eps_feas)
+        arrs = {k: _prep(given[k], shape, k) for k, shape in self._model_shapes().items()}
+        model = _model_struct(arrs)
         x0a = _prep(x0, (B, nx), 'x0')
         uma = _prep(uminus1, (B, nu), 'uminus1')
         xra = _prep(xref, (B, xref_rows * nx), 'xref')
@@ -530,16 +532,13 @@ class BatchProblem:
         """The solver seam of mpc.py:266 with caller-built vectors (mpcqp_setup_qp): the matrices enter through the
         blocks they are made of (pympc_amd.qp_recover reads them out of a reference-layout P, A), q [B,n], l, u [B,m]
         verbatim."""
-        B, nx, nu = self.batch, self.nx, self.nu
-        arrs = dict(Ad=_prep(Ad, (B, nx, nx), 'Ad'), Bd=_prep(Bd, (B, nx, nu), 'Bd'), Qx=_prep(Qx, (B, nx, nx), 'Qx'),
-                    QxN=_prep(QxN, (B, nx, nx), 'QxN'), Qu=_prep(Qu, (B, nu, nu), 'Qu'), QDu=_prep(QDu, (B, nu, nu), 'QDu'),
-                    eps_feas=_prep(eps_feas, (B, 1), 'eps_feas'))
+        shapes = self._model_shapes()
+        given = dict(Ad=Ad, Bd=Bd, Qx=Qx, QxN=QxN, Qu=Qu, QDu=QDu, eps_feas=eps_feas)
         if uref is not None:
-            arrs['uref'] = _prep(uref, (B, nu), 'uref')
-        model = _lib.Model()
-        for k, v in arrs.items():
-            setattr(model, k, C.cast(_ptr(v), C.POINTER(C.c_double)))
-        qa, la, ua = _prep(q, (B, self.n), 'q'), self._bound(l, 'l'), self._bound(u, 'u')
+            given['uref'] = uref
+        arrs = {k: _prep(v, shapes[k], k) for k, v in given.items()}
+        model = _model_struct(arrs)
+        qa, la, ua = _prep(q, (self.batch, self.n), 'q'), self._bound(l, 'l'), self._bound(u, 'u')
         _lib.check(self._L.mpcqp_setup_qp(self._h, C.byref(model), _ptr(qa), _ptr(la), _ptr(ua)), 'mpcqp_setup_qp')
         _lib.check(self._L.mpcqp_synchronize(self._h), 'mpcqp_synchronize')
 
@@ -556,8 +555,7 @@ class BatchProblem:
         ``setup``, numpy arrays or torch device tensors, None = unchanged -- replace the problem's, the device re-equilibrates, rebuilds the rho
         vector, refactors and keeps the iterate: the next solve warm-starts from it exactly as setup + warm_start(x, y) would.  Stream-ordered
         (no wait) when every field is device memory."""
-        if not _lib.has_model_update(self._L):
-            raise NotImplementedError('this build of the solver library has no in-place model update (include/mpcqp_model.h)')
+        self._need('model_update')
         shapes = self._model_shapes()
         for k in fields:
             if k not in shapes:
@@ -565,9 +563,7 @@ class BatchProblem:
         arrs = {k: _prep(v, shapes[k], k) for k, v in fields.items() if v is not None}
         if not arrs:
             raise ValueError('update_model: give at least one model field')
-        model = _lib.Model()
-        for k, v in arrs.items():
-            setattr(model, k, C.cast(_ptr(v), C.POINTER(C.c_double)))
+        model = _model_struct(arrs)
         self._keep = [arrs]                    # (device tensors: alive until the stream has read them -- at least until the next call)
         _lib.check(self._L.mpcqp_update_model(self._h, C.byref(model)), 'mpcqp_update_model')
 
@@ -602,9 +598,6 @@ class BatchProblem:
         _lib.check(self._L.mpcqp_update(self._h, _ptr(a), _ptr(b), _ptr(c), rows), 'mpcqp_update')
         if xref is not None:
             self._xref_rows_last = rows
-        if any(hasattr(v, 'ctypes') for v in self._keep if v is not None):
-            # pageable host memory: the async copy has completed or been staged when the call returns
-            pass
 
     def update_settings(self, **kw):
         kw, polish = _split_polish(kw)
@@ -692,7 +685,7 @@ class BatchProblem:
         buf = np.frombuffer(cb, dtype=np.float64)
         return buf[:n].reshape(1, n), buf[n:].reshape(1, m), info
 
-    def mpc_run(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None, _taped=False):
+    def mpc_run(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None):
         """Device-side receding-horizon loop (mpcqp_mpc_loop): ``nsteps`` closed-loop steps
         ``u = output(); x = Ap x + Bp u + w[k]; update(x)`` of every instance without host round trips.
 
@@ -704,6 +697,11 @@ class BatchProblem:
         ``k // hold`` replaces Ad / Bd at the start of step k (``update_model``), for the controller and, without ``Ap``/``Bp``, the plant.
         Returns ``(x_traj [nsteps+1,B,nx], u_traj [nsteps,B,nu], status [nsteps,B] int32, iters [nsteps,B] int32)`` as
         numpy arrays (plus ``xhat_traj, y_traj`` with an estimator), or fills the arrays/tensors given in ``out``."""
+        return self._loop('mpcqp_mpc_loop', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj)
+
+    def _loop(self, entry, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None):
+        """``mpc_run`` through the C entry point ``entry`` -- mpcqp_mpc_loop, or mpcqp_rollout / mpcqp_rollout_est: the same loop, and a tape
+        of it; with a ``model_traj``, mpcqp_mpc_loop_tv."""
         K, B, nx, nu = int(nsteps), self.batch, self.nx, self.nu
         io = _lib.Loop()
         keep = []
@@ -745,8 +743,7 @@ class BatchProblem:
         if ny and len(out) >= 6:
             io.xhat_traj, io.y_traj = _ptr(out[4]), _ptr(out[5])
         if model_traj is not None:
-            if not _lib.has_model_update(self._L):
-                raise NotImplementedError('this build of the solver library has no model schedule for the device loop (include/mpcqp_model.h)')
+            self._need('model_traj')
             Adt, Bdt, hold = model_traj
             hold = int(hold)
             if hold < 1:
@@ -758,20 +755,13 @@ class BatchProblem:
             mt = _lib.ModelTraj()
             mt.struct_size, mt.hold, mt.nmodels = C.sizeof(_lib.ModelTraj), hold, nm
             mt.Ad = inp(Adt, (nm, B, nx, nx), 'model_traj Ad'); mt.Bd = inp(Bdt, (nm, B, nx, nu), 'model_traj Bd')
+            entry = 'mpcqp_mpc_loop_tv'
             rc = self._L.mpcqp_mpc_loop_tv(self._h, K, C.byref(io), C.byref(mt))
-            what = 'mpcqp_mpc_loop_tv'
-        elif _taped == 'est':                     # (rollout_est(): the output-feedback loop, and a tape of it)
-            rc = self._L.mpcqp_rollout_est(self._h, K, C.byref(io))
-            what = 'mpcqp_rollout_est'
-        elif _taped:                              # (rollout(): the same loop, and a tape of it)
-            rc = self._L.mpcqp_rollout(self._h, K, C.byref(io))
-            what = 'mpcqp_rollout'
         else:
-            rc = self._L.mpcqp_mpc_loop(self._h, K, C.byref(io))
-            what = 'mpcqp_mpc_loop'
+            rc = getattr(self._L, entry)(self._h, K, C.byref(io))
         if rc == -4:
             raise NotImplementedError(self._L.mpcqp_last_error().decode())
-        _lib.check(rc, what)
+        _lib.check(rc, entry)
         if xref_traj is not None:
             self._xref_rows_last = int(io.xref_rows)
         self._keep = [keep]                    # (device inputs of a stream-ordered run: alive at least until the next call)

@@ -21,15 +21,80 @@ is the container of the device buffers and the owner of the graph; no torch oper
   over the batch formed on the device (``batch_sum``).  The weight gradients are those of a symmetric perturbation: a weight that is
   parametrized symmetric (Q = L L', a diagonal) gets its true gradient.
 """
+import contextlib
+
 import torch
 
 
-def _sync_needed(K):
-    """The library works on the controller's stream: unless that IS torch's current stream, the two are ordered by waiting."""
-    return K.stream is None or int(K.stream) != int(torch.cuda.current_stream().cuda_stream)
-
-
 MODEL_PARAMS = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu')
+
+
+# ---- what the three Functions share ----------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def _ordered(K):
+    """The library works on the controller's stream: unless that IS torch's current stream, the two are ordered by waiting, torch's work
+    before the library's and the library's before what torch does next."""
+    sync = K.stream is None or int(K.stream) != int(torch.cuda.current_stream().cuda_stream)
+    if sync:
+        torch.cuda.current_stream().synchronize()
+    yield
+    if sync:
+        K.prob.synchronize()
+
+
+def _det(t):
+    return None if t is None else t.detach().to(torch.float64).contiguous()
+
+
+def _bc(t, shape):
+    """A matrix given once for the batch or per instance, as the library takes it: per instance."""
+    return None if t is None else _det(t).expand(shape).contiguous()
+
+
+def _check_args(fn, controller, params, Ap=None, Bp=None):
+    """What the public functions refuse; returns the names of ``params`` in their order."""
+    if controller.prob is None:
+        raise RuntimeError('%s needs a controller that has been set up' % fn)
+    names = tuple(params) if params else ()
+    for n in names:
+        if n not in MODEL_PARAMS:
+            raise TypeError('%s: unknown model parameter %r (one of %s)' % (fn, n, ', '.join(MODEL_PARAMS)))
+        if not hasattr(params[n], 'data_ptr') or not params[n].is_cuda or params[n].dim() not in (2, 3):
+            raise ValueError('%s: params[%r] must be a device tensor [B, ., .] or [., .]' % (fn, n))
+    if (Ap is None) != (Bp is None):
+        raise ValueError('%s: give both Ap and Bp or neither' % fn)
+    return names
+
+
+def _put_params(ctx, K, names, params):
+    """Forward: the parameters go under the controller (no solve yet); their names and shapes are what backward assembles gradients by."""
+    if names:
+        K.update_model(solve=False, **{n: _det(p) for n, p in zip(names, params)})
+    ctx.names, ctx.pshapes = names, tuple(tuple(p.shape) for p in params)
+
+
+def _param_want(ctx, needs):
+    """(the parameters that need a gradient, which parameters are unbatched, batch_sum).  One model for the whole batch: the device adds the
+    instances' gradients up (a mixture of shared and per-instance parameters takes them per instance and adds the shared ones' here)."""
+    pneed = [n for n, need in zip(ctx.names, needs) if need]
+    shared = {n: len(shp) == 2 for n, shp in zip(ctx.names, ctx.pshapes)}
+    return pneed, shared, bool(pneed) and all(shared[n] for n in pneed)
+
+
+def _param_grads(ctx, res, pneed, shared, batch_sum, paths=()):
+    """The gradient of every parameter, None where none is needed.  ``paths``: pairs of further gradients of ``res`` -- per instance, an Ad-like
+    and a Bd-like one -- that are paths into Ad / Bd too (the plant where the controller's model is the plant, the estimator): added on."""
+    pgrads = []
+    for n, shp in zip(ctx.names, ctx.pshapes):
+        v = res.get(n) if n in pneed else None
+        if v is not None:
+            v = (v[0] if batch_sum else v.sum(dim=0)) if shared[n] else v
+            for a, b in paths if n in ('Ad', 'Bd') else ():
+                p = res[a if n == 'Ad' else b]
+                v = v + (p.sum(dim=0) if shared[n] else p)
+            v = v.reshape(shp)
+        pgrads.append(v)
+    return pgrads
 
 
 class _MPCStep(torch.autograd.Function):
@@ -37,20 +102,13 @@ class _MPCStep(torch.autograd.Function):
     def forward(ctx, K, x, u_prev, xref, names, *params):
         if not x.is_cuda:
             raise ValueError('mpc_step works on device tensors (x is on %s)' % x.device)
-        sync = _sync_needed(K)
-        if sync:
-            torch.cuda.current_stream().synchronize()
-        det = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
-        if names:
-            K.update_model(solve=False, **{n: det(p) for n, p in zip(names, params)})
-        u = torch.empty((K.B, K.nu), dtype=torch.float64, device=x.device)
-        xr = det(xref)
-        K.step(det(x), det(u_prev), None if xr is None else xr.reshape(K.B, -1), out=u)
-        if sync:
-            K.prob.synchronize()
+        with _ordered(K):
+            _put_params(ctx, K, names, params)
+            u = torch.empty((K.B, K.nu), dtype=torch.float64, device=x.device)
+            xr = _det(xref)
+            K.step(_det(x), _det(u_prev), None if xr is None else xr.reshape(K.B, -1), out=u)
         ctx.K, ctx.count = K, K.solve_count
         ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (x, u_prev, xref))
-        ctx.names, ctx.pshapes = names, tuple(tuple(p.shape) for p in params)
         return u
 
     @staticmethod
@@ -62,29 +120,13 @@ class _MPCStep(torch.autograd.Function):
                                % (ctx.count, K.solve_count))
         names = ('x0', 'uminus1', 'xref')
         want = [n for n, need, shp in zip(names, ctx.needs_input_grad[1:4], ctx.shapes) if need and shp is not None]
-        pneed = [n for n, need in zip(ctx.names, ctx.needs_input_grad[5:]) if need]
-        none = (None,) * (5 + len(ctx.names))
+        pneed, shared, batch_sum = _param_want(ctx, ctx.needs_input_grad[5:])
         if not want and not pneed:
-            return none
-        # one model for the whole batch: the device adds the instances' gradients up (a mixture of shared and per-instance parameters
-        # takes them per instance and adds the shared ones' here)
-        shared = {n: len(shp) == 2 for n, shp in zip(ctx.names, ctx.pshapes)}
-        batch_sum = bool(pneed) and all(shared[n] for n in pneed)
-        sync = _sync_needed(K)
-        if sync:
-            torch.cuda.current_stream().synchronize()
-        res = K.prob.adjoint(g_u0=grad_u.to(torch.float64).contiguous(), want=want + pneed, batch_sum=batch_sum)
-        if sync:
-            K.prob.synchronize()
+            return (None,) * (5 + len(ctx.names))
+        with _ordered(K):
+            res = K.prob.adjoint(g_u0=grad_u.to(torch.float64).contiguous(), want=want + pneed, batch_sum=batch_sum)
         grads = [res[n].reshape(shp) if n in res else None for n, shp in zip(names, ctx.shapes)]
-        pgrads = []
-        for n, shp in zip(ctx.names, ctx.pshapes):
-            g = res.get(n)
-            if g is not None:
-                g = (g[0] if batch_sum else g.sum(dim=0)) if shared[n] else g
-                g = g.reshape(shp)
-            pgrads.append(g)
-        return (None,) + tuple(grads) + (None,) + tuple(pgrads)
+        return (None,) + tuple(grads) + (None,) + tuple(_param_grads(ctx, res, pneed, shared, batch_sum))
 
 
 def mpc_step(controller, x, u_prev=None, xref=None, params=None):
@@ -92,87 +134,77 @@ def mpc_step(controller, x, u_prev=None, xref=None, params=None):
     respect to the three tensors (float64 device tensors; ``u_prev`` / ``xref`` None: the controller's own, no gradient) and, with
     ``params`` -- a dict of device tensors under any of the names Ad, Bd, Qx, QxN, Qu, QDu, each [B, ...] or unbatched [...] -- with respect
     to the model the step is made with: the controller's model is replaced by them first (``update_model``)."""
-    if controller.prob is None:
-        raise RuntimeError('mpc_step needs a controller that has been set up')
-    names = tuple(params) if params else ()
-    for n in names:
-        if n not in MODEL_PARAMS:
-            raise TypeError('mpc_step: unknown model parameter %r (one of %s)' % (n, ', '.join(MODEL_PARAMS)))
-        if not hasattr(params[n], 'data_ptr') or not params[n].is_cuda or params[n].dim() not in (2, 3):
-            raise ValueError('mpc_step: params[%r] must be a device tensor [B, ., .] or [., .]' % n)
+    names = _check_args('mpc_step', controller, params)
     return _MPCStep.apply(controller, x, u_prev, xref, names, *[params[n] for n in names])
 
 
-# ---- a closed-loop rollout as one differentiable operation (include/mpcqp_rollout.h) ---------------------------------------------------
+# ---- a closed-loop rollout as one differentiable operation (include/mpcqp_rollout.h, include/mpcqp_rollout_est.h) ----------------------
+_per = lambda v, shp: v.sum(dim=0) if len(shp) == 2 else v      # (an unbatched matrix input: summed over the batch)
+# input of a rollout -> (the gradient of rollout_adjoint it is made from, how; its own shape is put on last)
+_ROLLOUT_INPUTS = dict(
+    x0=('lam', lambda v, shp: v[0]), w=('lam', lambda v, shp: v[1:]), xhat0=('eta', lambda v, shp: v[0]), v=('v', lambda v, shp: v),
+    u_prev=('uminus1', lambda v, shp: v), xref=('xref', lambda v, shp: v.sum(dim=0)), C=('C', _per), L=('L', _per), Ap=('Ap', _per), Bp=('Bp', _per))
+
+
+def _rollout_forward(ctx, K, nsteps, x_first, u_prev, xref, names, params, roll, inputs):
+    """``update_model`` of the parameters, ``update(x_first, u_prev, xref)`` with its solve (tape entry 0), then ``roll(new, st, it)`` -- the
+    taped loop, which makes its trajectories with ``new(rows, cols)``, fills the status and iteration tensors and returns (the last state
+    the controller saw, U, what forward returns) -- and the controller's and the context's books.  ``inputs``: forward's tensor inputs."""
+    with _ordered(K):
+        _put_params(ctx, K, names, params)
+        xr = _det(xref)
+        K.update(_det(x_first), _det(u_prev), None if xr is None else xr.reshape(K.B, -1))
+        new = lambda rows, cols: torch.empty((rows, K.B, cols), dtype=torch.float64, device=x_first.device)
+        st, it = (torch.empty((nsteps, K.B), dtype=torch.int32, device=x_first.device) for _ in range(2))
+        last, U, ret = roll(new, st, it)
+        K.solve_count += nsteps
+        K.x0_rh, K.uminus1_rh, K._um1_on_device, K._u_last = last, U[-1], True, None
+    ctx.K, ctx.count = K, K.prob.rollout_count
+    ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in inputs)
+    ctx.status, ctx.iters = st, it
+    return ret
+
+
+def _rollout_backward(ctx, fn, inputs, seeds, est):
+    """One ``rollout_adjoint`` call for exactly the gradients torch needs.  ``inputs``: the names of the tensor inputs (keys of
+    _ROLLOUT_INPUTS) in forward's order behind (K, nsteps) and before ``names``; ``seeds``: rollout_adjoint's, by name; ``est``: the tape
+    is one of the output-feedback loop."""
+    K = ctx.K
+    if K.prob.rollout_count != ctx.count:
+        raise RuntimeError('%s: the controller has been rolled out again since this forward (rollout %d then, %d now); '
+                           'its tape is no longer the one to differentiate.' % (fn, ctx.count, K.prob.rollout_count))
+    ni = 2 + len(inputs)
+    need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[2:ni], ctx.shapes)}
+    shape = dict(zip(inputs, ctx.shapes))
+    pneed, shared, batch_sum = _param_want(ctx, ctx.needs_input_grad[ni + 1:])
+    if not any(need.values()) and not pneed:
+        return (None,) * (ni + 1 + len(ctx.names))
+    # Ad, Bd are the estimator's model too, and without Ap, Bp the plant's: one parameter with up to three paths, of which the estimator's and
+    # the plant's come back on their own
+    paths = ((('Ae', 'Be'),) if est else ()) + ((('Ap', 'Bp'),) if shape['Ap'] is None else ())
+    want = list(dict.fromkeys(_ROLLOUT_INPUTS[n][0] for n in inputs if need[n]))
+    want += [g for pair in paths for g, m in zip(pair, ('Ad', 'Bd')) if m in pneed] + pneed
+    with _ordered(K):
+        res = K.prob.rollout_adjoint(want=want, batch_sum=batch_sum, **{k: g.to(torch.float64).contiguous() for k, g in seeds.items()})
+    grads = [_ROLLOUT_INPUTS[n][1](res[_ROLLOUT_INPUTS[n][0]], shape[n]).reshape(shape[n]) if need[n] else None for n in inputs]
+    return (None, None) + tuple(grads) + (None,) + tuple(_param_grads(ctx, res, pneed, shared, batch_sum, paths))
+
+
 class _MPCRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, K, nsteps, x0, u_prev, xref, w, Ap, Bp, names, *params):
         if not x0.is_cuda:
             raise ValueError('mpc_rollout works on device tensors (x0 is on %s)' % x0.device)
-        sync = _sync_needed(K)
-        if sync:
-            torch.cuda.current_stream().synchronize()
-        det = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
-        if names:
-            K.update_model(solve=False, **{n: det(p) for n, p in zip(names, params)})
-        xr = det(xref)
-        K.update(det(x0), det(u_prev), None if xr is None else xr.reshape(K.B, -1))      # (and the solve for x_0: tape entry 0)
-        kw = dict(dtype=torch.float64, device=x0.device)
-        X, U = torch.empty((nsteps + 1, K.B, K.nx), **kw), torch.empty((nsteps, K.B, K.nu), **kw)
-        st, it = (torch.empty((nsteps, K.B), dtype=torch.int32, device=x0.device) for _ in range(2))
-        bc = lambda t, shape: None if t is None else det(t).expand(shape).contiguous()
-        K.prob.rollout(nsteps, w=det(w), Ap=bc(Ap, (K.B, K.nx, K.nx)), Bp=bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it])
-        K.solve_count += nsteps
-        K.x0_rh, K.uminus1_rh, K._um1_on_device, K._u_last = X[-1], U[-1], True, None
-        if sync:
-            K.prob.synchronize()
-        ctx.K, ctx.count = K, K.prob.rollout_count
-        ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (x0, u_prev, xref, w, Ap, Bp))
-        ctx.names, ctx.pshapes = names, tuple(tuple(p.shape) for p in params)
-        ctx.status, ctx.iters = st, it
-        return X, U
+
+        def roll(new, st, it):
+            X, U = new(nsteps + 1, K.nx), new(nsteps, K.nu)
+            K.prob.rollout(nsteps, w=_det(w), Ap=_bc(Ap, (K.B, K.nx, K.nx)), Bp=_bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it])
+            return X[-1], U, (X, U)
+        return _rollout_forward(ctx, K, nsteps, x0, u_prev, xref, names, params, roll, (x0, u_prev, xref, w, Ap, Bp))
 
     @staticmethod
     def backward(ctx, grad_X, grad_U):
-        K = ctx.K
-        if K.prob.rollout_count != ctx.count:
-            raise RuntimeError('mpc_rollout: the controller has been rolled out again since this forward (rollout %d then, %d now); '
-                               'its tape is no longer the one to differentiate.' % (ctx.count, K.prob.rollout_count))
-        need = dict(zip(('x0', 'u_prev', 'xref', 'w', 'Ap', 'Bp'), ctx.needs_input_grad[2:8]))
-        need = {n: v and shp is not None for (n, v), shp in zip(need.items(), ctx.shapes)}
-        pneed = [n for n, v in zip(ctx.names, ctx.needs_input_grad[9:]) if v]
-        if not any(need.values()) and not pneed:
-            return (None,) * (9 + len(ctx.names))
-        own_plant = ctx.shapes[4] is not None
-        # the controller's own model as the plant: Ad, Bd are then one parameter with two paths, and the plant's comes back on its own
-        plant = [n for n, m in (('Ap', 'Ad'), ('Bp', 'Bd')) if (need[n] if own_plant else m in pneed)]
-        want = ([n for n, k in (('lam', 'x0'), ('uminus1', 'u_prev'), ('xref', 'xref')) if need[k]] + (['lam'] if need['w'] and not need['x0'] else [])
-                + plant + pneed)
-        shared = {n: len(shp) == 2 for n, shp in zip(ctx.names, ctx.pshapes)}
-        batch_sum = bool(pneed) and all(shared[n] for n in pneed)
-        sync = _sync_needed(K)
-        if sync:
-            torch.cuda.current_stream().synchronize()
-        res = K.prob.rollout_adjoint(g_x=grad_X.to(torch.float64).contiguous(), g_u=grad_U.to(torch.float64).contiguous(), want=want, batch_sum=batch_sum)
-        if sync:
-            K.prob.synchronize()
-        g = lambda v, shp: None if v is None else v.reshape(shp)
-        grads = [g(res['lam'][0] if need['x0'] else None, ctx.shapes[0]), g(res.get('uminus1'), ctx.shapes[1]),
-                 g(res['xref'].sum(dim=0) if need['xref'] else None, ctx.shapes[2]), g(res['lam'][1:] if need['w'] else None, ctx.shapes[3])]
-        for n, shp in (('Ap', ctx.shapes[4]), ('Bp', ctx.shapes[5])):
-            v = res.get(n) if own_plant and need[n] else None
-            grads.append(None if v is None else (v.sum(dim=0) if len(shp) == 2 else v).reshape(shp))
-        pgrads = []
-        for n, shp in zip(ctx.names, ctx.pshapes):
-            v = res.get(n) if n in pneed else None
-            if v is not None:
-                v = (v[0] if batch_sum else v.sum(dim=0)) if shared[n] else v
-                if not own_plant and n in ('Ad', 'Bd'):
-                    p = res['Ap' if n == 'Ad' else 'Bp']
-                    v = v + (p.sum(dim=0) if shared[n] else p)
-                v = v.reshape(shp)
-            pgrads.append(v)
-        return (None, None) + tuple(grads) + (None,) + tuple(pgrads)
+        return _rollout_backward(ctx, 'mpc_rollout', ('x0', 'u_prev', 'xref', 'w', 'Ap', 'Bp'), dict(g_x=grad_X, g_u=grad_U), False)
 
 
 def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None):
@@ -186,104 +218,28 @@ def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None,
     of ``params['Ad']`` / ``['Bd']`` include the plant path).  A step whose solve does not end 'solved' applies ``u_failure`` = uref and
     passes the gradient through the plant alone.  The tape is a copy: stepping or solving the controller between forward and backward is
     fine, another rollout is not -- the backward then raises."""
-    if controller.prob is None:
-        raise RuntimeError('mpc_rollout needs a controller that has been set up')
-    names = tuple(params) if params else ()
-    for n in names:
-        if n not in MODEL_PARAMS:
-            raise TypeError('mpc_rollout: unknown model parameter %r (one of %s)' % (n, ', '.join(MODEL_PARAMS)))
-        if not hasattr(params[n], 'data_ptr') or not params[n].is_cuda or params[n].dim() not in (2, 3):
-            raise ValueError('mpc_rollout: params[%r] must be a device tensor [B, ., .] or [., .]' % n)
-    if (Ap is None) != (Bp is None):
-        raise ValueError('mpc_rollout: give both Ap and Bp or neither')
+    names = _check_args('mpc_rollout', controller, params, Ap, Bp)
     return _MPCRollout.apply(controller, int(nsteps), x0, u_prev, xref, w, Ap, Bp, names, *[params[n] for n in names])
 
 
-# ---- the output-feedback rollout, differentiated through the estimator (include/mpcqp_rollout_est.h) -----------------------------------
 class _MPCRolloutEst(torch.autograd.Function):
     @staticmethod
     def forward(ctx, K, nsteps, x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, names, *params):
         if not x0.is_cuda:
             raise ValueError('mpc_rollout_est works on device tensors (x0 is on %s)' % x0.device)
-        sync = _sync_needed(K)
-        if sync:
-            torch.cuda.current_stream().synchronize()
-        det = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
-        if names:
-            K.update_model(solve=False, **{n: det(p) for n, p in zip(names, params)})
-        xr = det(xref)
-        K.update(det(xhat0), det(u_prev), None if xr is None else xr.reshape(K.B, -1))      # (and the solve for xhat_0: tape entry 0)
-        ny = int(C.shape[-2])
-        kw = dict(dtype=torch.float64, device=x0.device)
-        X, XH, U = torch.empty((nsteps + 1, K.B, K.nx), **kw), torch.empty((nsteps + 1, K.B, K.nx), **kw), torch.empty((nsteps, K.B, K.nu), **kw)
-        Y = torch.empty((nsteps, K.B, ny), **kw)
-        st, it = (torch.empty((nsteps, K.B), dtype=torch.int32, device=x0.device) for _ in range(2))
-        bc = lambda t, shape: None if t is None else det(t).expand(shape).contiguous()
-        est = dict(C=bc(C, (K.B, ny, K.nx)), L=bc(L, (K.B, K.nx, ny)), x_true=det(x0).clone(), v=det(v))
-        K.prob.rollout_est(nsteps, est, w=det(w), Ap=bc(Ap, (K.B, K.nx, K.nx)), Bp=bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it, XH, Y])
-        K.solve_count += nsteps
-        K.x0_rh, K.uminus1_rh, K._um1_on_device, K._u_last = XH[-1], U[-1], True, None
-        if sync:
-            K.prob.synchronize()
-        ctx.K, ctx.count = K, K.prob.rollout_count
-        ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp))
-        ctx.names, ctx.pshapes = names, tuple(tuple(p.shape) for p in params)
-        ctx.status, ctx.iters = st, it
-        return X, XH, Y, U
+
+        def roll(new, st, it):
+            ny = int(C.shape[-2])
+            X, XH, U, Y = new(nsteps + 1, K.nx), new(nsteps + 1, K.nx), new(nsteps, K.nu), new(nsteps, ny)
+            est = dict(C=_bc(C, (K.B, ny, K.nx)), L=_bc(L, (K.B, K.nx, ny)), x_true=_det(x0).clone(), v=_det(v))
+            K.prob.rollout_est(nsteps, est, w=_det(w), Ap=_bc(Ap, (K.B, K.nx, K.nx)), Bp=_bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it, XH, Y])
+            return XH[-1], U, (X, XH, Y, U)
+        return _rollout_forward(ctx, K, nsteps, xhat0, u_prev, xref, names, params, roll, (x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp))
 
     @staticmethod
     def backward(ctx, grad_X, grad_XH, grad_Y, grad_U):
-        K = ctx.K
-        if K.prob.rollout_count != ctx.count:
-            raise RuntimeError('mpc_rollout_est: the controller has been rolled out again since this forward (rollout %d then, %d now); '
-                               'its tape is no longer the one to differentiate.' % (ctx.count, K.prob.rollout_count))
-        inputs = ('x0', 'xhat0', 'C', 'L', 'v', 'u_prev', 'xref', 'w', 'Ap', 'Bp')
-        need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[2:12], ctx.shapes)}
-        shape = dict(zip(inputs, ctx.shapes))
-        pneed = [n for n, v in zip(ctx.names, ctx.needs_input_grad[13:]) if v]
-        none = (None,) * (13 + len(ctx.names))
-        if not any(need.values()) and not pneed:
-            return none
-        own_plant = shape['Ap'] is not None
-        # Ad, Bd are the estimator's model too, and without Ap, Bp the plant's: one parameter with three paths, two of which come back on their own
-        plant = [n for n, m in (('Ap', 'Ad'), ('Bp', 'Bd')) if (need[n] if own_plant else m in pneed)]
-        estp = [n for n, m in (('Ae', 'Ad'), ('Be', 'Bd')) if m in pneed]
-        want = []
-        if need['x0'] or need['w']:
-            want.append('lam')
-        want += [r for r, n in (('eta', 'xhat0'), ('C', 'C'), ('L', 'L'), ('v', 'v'), ('uminus1', 'u_prev'), ('xref', 'xref')) if need[n]]
-        want += plant + estp + pneed
-        shared = {n: len(shp) == 2 for n, shp in zip(ctx.names, ctx.pshapes)}
-        batch_sum = bool(pneed) and all(shared[n] for n in pneed)
-        sync = _sync_needed(K)
-        if sync:
-            torch.cuda.current_stream().synchronize()
-        c64 = lambda t: t.to(torch.float64).contiguous()
-        res = K.prob.rollout_adjoint(g_x=c64(grad_X), g_u=c64(grad_U), g_xhat=c64(grad_XH), g_y=c64(grad_Y), want=want, batch_sum=batch_sum)
-        if sync:
-            K.prob.synchronize()
-        per = lambda v, shp, nd: None if v is None else (v.sum(dim=0) if len(shp) == nd - 1 else v).reshape(shp)      # (an unbatched input: summed over the batch)
-        grads = [res['lam'][0].reshape(shape['x0']) if need['x0'] else None,
-                 res['eta'][0].reshape(shape['xhat0']) if need['xhat0'] else None,
-                 per(res.get('C') if need['C'] else None, shape['C'], 3), per(res.get('L') if need['L'] else None, shape['L'], 3),
-                 res['v'].reshape(shape['v']) if need['v'] else None,
-                 res['uminus1'].reshape(shape['u_prev']) if need['u_prev'] else None,
-                 res['xref'].sum(dim=0).reshape(shape['xref']) if need['xref'] else None,
-                 res['lam'][1:].reshape(shape['w']) if need['w'] else None,
-                 per(res.get('Ap') if own_plant and need['Ap'] else None, shape['Ap'], 3),
-                 per(res.get('Bp') if own_plant and need['Bp'] else None, shape['Bp'], 3)]
-        pgrads = []
-        for n, shp in zip(ctx.names, ctx.pshapes):
-            v = res.get(n) if n in pneed else None
-            if v is not None:
-                v = (v[0] if batch_sum else v.sum(dim=0)) if shared[n] else v
-                if n in ('Ad', 'Bd'):
-                    for path in (('Ae', 'Be'),) + ((('Ap', 'Bp'),) if not own_plant else ()):
-                        p = res[path[0] if n == 'Ad' else path[1]]
-                        v = v + (p.sum(dim=0) if shared[n] else p)
-                v = v.reshape(shp)
-            pgrads.append(v)
-        return (None, None) + tuple(grads) + (None,) + tuple(pgrads)
+        return _rollout_backward(ctx, 'mpc_rollout_est', ('x0', 'xhat0', 'C', 'L', 'v', 'u_prev', 'xref', 'w', 'Ap', 'Bp'),
+                                 dict(g_x=grad_X, g_u=grad_U, g_xhat=grad_XH, g_y=grad_Y), True)
 
 
 def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None):
@@ -296,16 +252,7 @@ def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xr
     ``xhat0``, ``C``, ``L``, ``v``, ``u_prev``, ``xref``, ``w``, ``Ap``, ``Bp`` and ``params`` (as in ``mpc_rollout``); the gradients of
     ``params['Ad']`` / ``['Bd']`` include the estimator's path and, with ``Ap`` / ``Bp`` None, the plant's.  ``mpc_rollout`` is the loop
     without an estimator."""
-    if controller.prob is None:
-        raise RuntimeError('mpc_rollout_est needs a controller that has been set up')
-    names = tuple(params) if params else ()
-    for n in names:
-        if n not in MODEL_PARAMS:
-            raise TypeError('mpc_rollout_est: unknown model parameter %r (one of %s)' % (n, ', '.join(MODEL_PARAMS)))
-        if not hasattr(params[n], 'data_ptr') or not params[n].is_cuda or params[n].dim() not in (2, 3):
-            raise ValueError('mpc_rollout_est: params[%r] must be a device tensor [B, ., .] or [., .]' % n)
-    if (Ap is None) != (Bp is None):
-        raise ValueError('mpc_rollout_est: give both Ap and Bp or neither')
+    names = _check_args('mpc_rollout_est', controller, params, Ap, Bp)
     for n, t in (('C', C), ('L', L)):
         if not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (2, 3):
             raise ValueError('mpc_rollout_est: %s must be a device tensor [B, ., .] or [., .]' % n)

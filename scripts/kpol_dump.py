@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Everything k_polish and k_adjoint compute, on the smallest cases that reach each of their code paths, written into one npz -- to compare
-two builds of the library bit for bit (a refactoring of mpcqp_kpol.h / mpcqp_polish.h / mpcqp_adjoint.h must not move a single bit):
+"""Everything k_polish, k_adjoint and the taped rollouts with their reverse sweeps compute, on the smallest cases that reach each of their
+code paths, written into one npz -- to compare two builds of the library bit for bit (a refactoring of mpcqp_kpol.h / mpcqp_polish.h /
+mpcqp_adjoint.h, or of the host side of mpcqp.hip, must not move a single bit):
 
     python scripts/with_lib.py <parent.so> scripts/kpol_dump.py a.npz
     python scripts/kpol_dump.py b.npz
@@ -9,7 +10,12 @@ two builds of the library bit for bit (a refactoring of mpcqp_kpol.h / mpcqp_pol
 Per case: after polish() the polished x, y, the iterate x, z, y, status_polish, obj_val / pri_res / dua_res; every output of
 adjoint(g_u0=..., want = all fourteen names) with and without batch_sum; every matrix of gains(); adjoint_info().  Cases: six golden
 fixtures, the first seed of six shapes of tests/adjoint_cases.py, a batch with an unsolved instance, a raw-vector handle (want q, l, u),
-an MPCController with polish=True stepped through update() (mpcqp_step_host), adjoint() right after BatchMPCController.step()."""
+an MPCController with polish=True stepped through update() (mpcqp_step_host), adjoint() right after BatchMPCController.step().
+Rollouts (tests/rollout_cases.py, tests/rollout_est_cases.py, the cases' own instances and step counts, seeds from default_rng(3)): per
+case of ROLLOUT, with the controller's model as the plant and with a plant of its own, the trajectory, the first and the last tape entry,
+every output of rollout_adjoint plain, with batch_sum and with no_reuse, and rollout_info() behind each; per case of ROLLOUT_EST the same
+of rollout_est with its four seeds (plain and batch_sum), then the sweep of g_x, g_u alone on that tape; and one handle taken through
+step() -> adjoint() -> rollout -> rollout_adjoint -> rollout_est -> rollout_adjoint (the moved u_{-1}, a tape replaced by one of the other kind)."""
 import os
 import sys
 import warnings
@@ -25,6 +31,10 @@ SHAPES = ('nb16_nu6', 'nb16_nu7_hard', 'nb32_nu9_held', 'nb64_nu10_held', 'nb128
 CHAINED = ('x0', 'uminus1', 'xref', 'uref')
 RAW = ('q', 'l', 'u')
 MODEL = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu', 'eps_feas')
+ROLLOUT = ('first', 'first_tvref', 'held', 'nb32_soft', 'nb64', 'nb128')
+ROLLOUT_EST = ('first', 'held', 'nb32_soft')
+SWEEP = ('lam', 'uminus1', 'uref', 'xref', 'Ap', 'Bp') + MODEL
+SWEEP_EST = SWEEP + ('eta', 'C', 'L', 'v', 'Ae', 'Be')
 
 
 def compare(a, b):
@@ -64,6 +74,85 @@ def dump_adjoint(out, tag, bp, want=CHAINED + RAW + MODEL, gains=True):
         out[tag + '/K_info'] = np.stack(bp.adjoint_info())
 
 
+def put(out, tag, d):
+    out.update({'%s/%s' % (tag, k): np.array(v) for k, v in d.items()})
+
+
+def dump_sweep(out, tag, bp, **kw):
+    """One rollout_adjoint call: every gradient it was asked for, and rollout_info() behind it."""
+    put(out, tag, bp.rollout_adjoint(**kw))
+    put(out, tag + '_info', dict(zip(('n_active', 'n_weak', 'status', 'n_factor'), bp.rollout_info())))
+
+
+def dump_tape(out, tag, bp, K):
+    for k in sorted({0, K - 1}):
+        put(out, '%s/tape%d' % (tag, k), bp.rollout_tape(k))
+
+
+def dump_rollout(out, name, ctrl):
+    import rollout_cases as rc
+    c = rc.CASES[name]
+    K, B, nx, nu = c['K'], len(c['seeds']), c['nx'], c['nu']
+    rng = np.random.default_rng(3)
+    g = dict(g_x=rng.standard_normal((K + 1, B, nx)), g_u=rng.standard_normal((K, B, nu)))
+    dA, dB = 0.02 * rng.standard_normal((B, nx, nx)), 0.02 * rng.standard_normal((B, nx, nu))
+    xr = np.stack([rc.xref_traj(name, s) for s in c['seeds']], axis=1).reshape(K, B, -1) if c['tv'] else None
+    for own in (0, 1):
+        Kc = ctrl(rc.batch_kwargs(name))
+        tag = 'rollout/%s/plant%d' % (name, own)
+        put(out, tag, Kc.rollout(K, Ap=Kc.Ad + dA if own else None, Bp=Kc.Bd + dB if own else None, xref_traj=xr))
+        dump_tape(out, tag, Kc.prob, K)
+        for v, kw in (('adj', {}), ('adj_sum', dict(batch_sum=True)), ('adj_no_reuse', dict(no_reuse=True))):
+            dump_sweep(out, '%s/%s' % (tag, v), Kc.prob, want=SWEEP, **dict(g, **kw))
+
+
+def est_inputs(name, Kc):
+    """(the estimator object of a case on controller Kc, its disturbances w, the four seeds of its sweep)"""
+    import rollout_cases as rc
+    import rollout_est_cases as ec
+    from pympc_amd.kalman import BatchLinearStateEstimator
+    c = rc.CASES[name]
+    K, B, nx, ny = c['K'], Kc.B, c['nx'], ec.ny_of(name)
+    e = ec.batch_estimator(name)
+    rng = np.random.default_rng(3)
+    g = dict(g_x=rng.standard_normal((K + 1, B, nx)), g_u=rng.standard_normal((K, B, c['nu'])), g_xhat=rng.standard_normal((K + 1, B, nx)),
+             g_y=rng.standard_normal((K, B, ny)))
+    return BatchLinearStateEstimator(Kc.x0, Kc.Ad, Kc.Bd, e['C'], e['L'], x_true=np.array(e['x_true0']), v=e['v']), e['w'], g
+
+
+def dump_rollout_est(out, name, ctrl):
+    import rollout_cases as rc
+    import rollout_est_cases as ec
+    K = rc.CASES[name]['K']
+    Kc = ctrl(ec.batch_kwargs(name))
+    est, w, g = est_inputs(name, Kc)
+    tag = 'rollout_est/' + name
+    put(out, tag, Kc.rollout_est(K, est, w=w))
+    dump_tape(out, tag, Kc.prob, K)
+    for bs in (False, True):
+        dump_sweep(out, '%s/adj%d' % (tag, bs), Kc.prob, want=SWEEP_EST, batch_sum=bs, **g)
+    dump_sweep(out, tag + '/adj_xu', Kc.prob, want=SWEEP_EST, g_x=g['g_x'], g_u=g['g_u'])
+
+
+def dump_sequence(out, ctrl, name='first'):
+    """One handle: step() -> adjoint() -> rollout -> rollout_adjoint -> rollout_est -> rollout_adjoint."""
+    import rollout_cases as rc
+    import rollout_est_cases as ec
+    K = rc.CASES[name]['K']
+    Kc = ctrl(ec.batch_kwargs(name))
+    est, w, g = est_inputs(name, Kc)
+    rng = np.random.default_rng(11)
+    tag = 'sequence'
+    out[tag + '/u'] = np.array(Kc.step(Kc.x0 + 0.01 * rng.standard_normal(Kc.x0.shape), Kc.uminus1 + 0.01 * rng.standard_normal(Kc.uminus1.shape)))
+    dump_adjoint(out, tag, Kc.prob, want=CHAINED + MODEL, gains=False)
+    put(out, tag + '/rollout', Kc.rollout(K, w=w))
+    dump_tape(out, tag + '/rollout', Kc.prob, K)
+    dump_sweep(out, tag + '/rollout/adj', Kc.prob, want=SWEEP, g_x=g['g_x'], g_u=g['g_u'])
+    put(out, tag + '/rollout_est', Kc.rollout_est(K, est, w=w))
+    dump_tape(out, tag + '/rollout_est', Kc.prob, K)
+    dump_sweep(out, tag + '/rollout_est/adj', Kc.prob, want=SWEEP_EST, **g)
+
+
 def main():
     if len(sys.argv) == 4 and sys.argv[1] == '--compare':
         sys.exit(compare(sys.argv[2], sys.argv[3]))
@@ -84,10 +173,13 @@ def main():
         K.setup()
         return K
 
-    def batch(name, seeds):
-        K = BatchMPCController(**ac.batch_kwargs(name, seeds, eps_abs=EPS, eps_rel=EPS, max_iter=400000))
+    def ctrl(args):
+        K = BatchMPCController(**dict(args, eps_abs=EPS, eps_rel=EPS, max_iter=400000))
         K.setup()
         return K
+
+    def batch(name, seeds):
+        return ctrl(ac.batch_kwargs(name, seeds))
 
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
@@ -143,6 +235,11 @@ def main():
         out['after_step/u'] = np.array(K.step(st('x0') + 0.01 * rng.standard_normal((B, st('x0').shape[1])),
                                               st('uminus1') + 0.01 * rng.standard_normal((B, st('uminus1').shape[1]))))
         dump_adjoint(out, 'after_step', K.prob)
+        for name in ROLLOUT:
+            dump_rollout(out, name, ctrl)
+        for name in ROLLOUT_EST:
+            dump_rollout_est(out, name, ctrl)
+        dump_sequence(out, ctrl)
     np.savez(sys.argv[1], **out)
     print('KPOL_DUMP %d arrays -> %s' % (len(out), sys.argv[1]))
 

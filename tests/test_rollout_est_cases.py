@@ -171,4 +171,4 @@ def test_the_functions_are_the_headers_and_a_library_without_them_is_refused():
     p = BatchProblem.__new__(BatchProblem)
     p._L = Without()
     with pytest.raises(NotImplementedError, match=r'include/mpcqp_rollout_est\.h'):
-        p._need_rollout_est()
+        p._need('rollout_est')

@@ -27,6 +27,10 @@
  * the closed-loop golden trajectories of tests/golden/make_traj.py (traj_*.npz), which the product is tested against.
  * `adaptive_rho_interval=0` (OSQP: derived from wall-clock setup time, hence not reproducible)
  * is resolved deterministically to 4*check_termination, OSQP's own rule for builds without timers.
+ * END OF A RUN (osqp_solve, "Update information and check also the termination condition if it hasn't been done during
+ * last iterations"): when the loop ends on an iteration that was not a checked one -- max_iter no multiple of
+ * check_termination, or check_termination = 0 -- update_info and the EXACT termination test run first; only a run that is
+ * still unsolved after it gets the test with 10x looser tolerances ('... inaccurate'), else 'maximum iterations reached'.
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
  */
@@ -544,8 +548,10 @@ int oracle_solve(oracle_work *w, double *x_out, double *y_out, oracle_info *info
     }
     if (!done) {
         iter = w->s.max_iter;
-        if (!can_check) update_info(w);
-        if (!check_termination(w, 1)) w->info.status = ST_MAX_ITER_REACHED;
+        /* the last iteration was not a checked one (max_iter no multiple of check_termination, or check_termination = 0):
+         * OSQP runs the exact test first and only then retries with 10x looser tolerances */
+        if (!can_check) { update_info(w); done = check_termination(w, 0); }
+        if (!done && !check_termination(w, 1)) w->info.status = ST_MAX_ITER_REACHED;
     }
     w->info.iter = iter;
     w->info.rho_estimate = compute_rho_estimate(w);

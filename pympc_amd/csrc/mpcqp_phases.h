@@ -602,23 +602,18 @@ __device__ __forceinline__ int check_body(const Lay &L, const Ptrs &P, const mpc
     };
 
     int term = 0, rho_upd = 0;
+    bool rho_stop = false;
     if (mode & COLD_PLAIN) { status = MPCQP_UNSOLVED; term = 1; }
     else {
-        if (mode & COLD_CHECK) term = check_termination(false) ? 1 : 0;
-        if (!term && (mode & COLD_FINAL)) {             // iteration limit: OSQP retries with 10x looser tolerances
+        // osqp_solve's order at a stop.  A checked iteration that terminates leaves the loop before its rho estimate.  The iteration limit on an
+        // iteration that is not a checked one (max_iter no multiple of check_termination, or check_termination = 0) makes its rho estimate inside the
+        // loop, and behind the loop come update_info and the EXACT test -- on the same iterate, so the verdict is the one formed here -- and only then,
+        // for a run that is still unsolved, the test with 10x looser tolerances.  A rho estimate that falls on the limit is made either way.
+        if (mode & (COLD_CHECK | COLD_FINAL)) term = check_termination(false) ? 1 : 0;
+        rho_stop = (mode & COLD_RHO) && !(term && (mode & COLD_CHECK));
+        if (!term && (mode & COLD_FINAL)) {
             if (!check_termination(true)) status = MPCQP_MAX_ITER_REACHED;
             term = 1;
-        }
-        if (!term && (mode & COLD_RHO)) {
-            double pri = nrm[7] / (nrm[8] + 1e-10), dua = nrm[9] / (nrm[10] + 1e-10);
-            double rn = fmin(fmax(rho * sqrt(pri / (dua + 1e-10)), RHO_MIN), RHO_MAX);
-            if (rn > rho * S_.adaptive_rho_tolerance || rn < rho / S_.adaptive_rho_tolerance) {
-                rho = rn;
-                for (int r = tid; r < L.m; r += NT) om[r] = row_rho(ctp[r], rho) * E[r] * E[r];
-                __syncthreads();
-                { int pin = 0; asm volatile("" : "+v"(pin)); run_factor_phase<NB, OCC>(&pin); asm volatile("" :: "v"(pin)); }
-                rho_upd = 1;
-            }
         }
     }
     __syncthreads();
@@ -631,6 +626,19 @@ __device__ __forceinline__ int check_body(const Lay &L, const Ptrs &P, const mpc
         for (int r = tid; r < L.m; r += NT) { double v = gy[r]; yo[r] = has_sol ? v : NAN; if (!has_sol) { gy[r] = 0.0; gz[r] = 0.0; } }
     }
     if (term && tid < L.nu) S.uo[tid] = X[L.ou + tid];                     // (the closed loop on the device: output() of the next step, with iflag[4])
+    if (rho_stop) {      // (behind the tail's reads of the iterate's LDS copy: the factorization has the work area to itself)
+        double pri = nrm[7] / (nrm[8] + 1e-10), dua = nrm[9] / (nrm[10] + 1e-10);
+        double rn = fmin(fmax(rho * sqrt(pri / (dua + 1e-10)), RHO_MIN), RHO_MAX);
+        if (rn > rho * S_.adaptive_rho_tolerance || rn < rho / S_.adaptive_rho_tolerance) {
+            rho = rn;
+            __syncthreads();
+            for (int r = tid; r < L.m; r += NT) om[r] = row_rho(ctp[r], rho) * E[r] * E[r];
+            __syncthreads();
+            { int pin = 0; asm volatile("" : "+v"(pin)); run_factor_phase<NB, OCC>(&pin); asm volatile("" :: "v"(pin)); }
+            rho_upd = 1;
+            __syncthreads();
+        }
+    }
     if (tid == 0) {
         mpcqp_info inf;                                                   // (written whole: the two running counts live in LDS, nothing is read back)
         inf.status = status; inf.iter = iter; inf.rho_updates = (S.iflag[1] += rho_upd); inf.reserved = (S.iflag[3] += 1);

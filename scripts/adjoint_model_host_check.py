@@ -75,8 +75,8 @@ def entry_source():
 def against_numpy(lib, name):
     import adjoint_ref as ar
     import adjoint_model_ref as am
-    from test_adjoint_reference import _solve
-    kw0, (P, q, A, l, u), r, (x, z, y), (D, E, c) = _solve(name, 1e-9)
+    from adjoint_cases import solve_golden
+    kw0, (P, q, A, l, u), r, (x, z, y), (D, E, c) = solve_golden(name, 1e-9)
     kw, attrs = am.full_kwargs(kw0), dict(kw0.attrs)
     g = np.random.default_rng(7).standard_normal(P.shape[0])
     res = ar.adjoint(P, A, l, u, x, z, y, D, E, c, g)

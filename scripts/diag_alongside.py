@@ -4,13 +4,13 @@ import os, sys, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
-from test_gpu_gaps import _bench_batch
+from util import bench_batch
 from pympc_amd import MPCController
 from oracle.osqp_oracle import OSQP
 cfg = sys.argv[1] if len(sys.argv) > 1 else 'cfg5'
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 B, nx, nu, Np, xbox = (1024, 12, 4, 30, 10.0) if cfg == 'cfg3' else (512, 20, 8, 100, 1.0)
-K, kws = _bench_batch(B, nx, nu, Np, xbox, 1e-3)
+K, kws = bench_batch(B, nx, nu, Np, xbox, 1e-3)
 rng = np.random.default_rng(11)
 with warnings.catch_warnings():
     warnings.simplefilter('ignore')

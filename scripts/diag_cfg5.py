@@ -4,10 +4,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
 import numpy as np
 from pympc_amd import fixtures
-from test_gpu_loop_parity import _stacked_batch, _complete
+from util import stacked_batch, complete
 B = int(os.environ.get('B', 512)); eps = float(os.environ.get('EPS', 1e-8))
-kws = [_complete(fixtures.random_lti(i, nx=20, nu=8, Np=100, xbox=1.0)) for i in range(B)]
-K = _stacked_batch(kws, eps_abs=eps, eps_rel=eps, max_iter=int(os.environ.get('MAXIT', 400000)))
+kws = [complete(fixtures.random_lti(i, nx=20, nu=8, Np=100, xbox=1.0)) for i in range(B)]
+K = stacked_batch(kws, eps_abs=eps, eps_rel=eps, max_iter=int(os.environ.get('MAXIT', 400000)))
 K.setup()
 infos = K.prob.infos()
 st = collections.Counter(K.prob.status_string(i.status) for i in infos)

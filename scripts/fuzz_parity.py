@@ -1,18 +1,18 @@
-"""One-off sweep: seeded random controllers (tests/test_gpu_parity.py::_random_case with larger dimension ranges: 32-, 64- and 128-wide
+"""One-off sweep: seeded random controllers (tests/util.py: random_case with larger dimension ranges: 32-, 64- and 128-wide
 stages, small stages on long horizons, every cyclic-reduction schedule, Nc < Np, hard and soft state constraints) -- cold solve and one warm step against the CPU oracle at tight tolerance.
 python scripts/fuzz_parity.py [first_seed] [count]"""
 import os, sys, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
-import test_gpu_parity as T
+from util import random_case, gpu_controller, oracle_controller
 from pympc_amd import fixtures
 
 first, count = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (1000, 120)
 bad = 0
 for seed in range(first, first + count):
     rng = np.random.default_rng(31000 + seed)
-    kw = T._random_case(seed)
+    kw = random_case(seed)
     kind = rng.random()
     if kind < 0.75:                                         # widen: the generator of the test-suite stops at nx = 13, nu = 5
         if kind < 0.45: nx, nu, Np = int(rng.integers(10, 50)), int(rng.integers(2, 14)), int(rng.integers(3, 16))
@@ -28,7 +28,7 @@ for seed in range(first, first + count):
             kw['Nc'] = int(rng.integers(1, Np + 1))
     soft = rng.random() < 0.8
     kw.update(eps_abs=1e-10, eps_rel=1e-10)
-    K = T._gpu_controller(kw, max_iter=400000); Ko = T._oracle_controller(kw, max_iter=400000)
+    K = gpu_controller(kw, max_iter=400000); Ko = oracle_controller(kw, max_iter=400000)
     K.SOFT_ON = Ko.SOFT_ON = soft
     tag = 'seed %d nx=%d nu=%d Np=%d Nc=%s soft=%d' % (seed, kw['Ad'].shape[0], kw['Bd'].shape[1], kw['Np'], kw.get('Nc'), soft)
     try:

@@ -160,7 +160,7 @@ def main():
         sys.exit('usage: kpol_dump.py <out.npz> | kpol_dump.py --compare <a.npz> <b.npz>')
     import adjoint_cases as ac
     import adjoint_model_ref as am
-    from util import golden_kwargs, load_golden, apply_attrs, KW
+    from util import golden_kwargs, load_golden, apply_attrs, KW, repeated
     from pympc_amd import MPCController, BatchMPCController
     out = {}
 
@@ -226,10 +226,7 @@ def main():
         kw = am.full_kwargs(golden_kwargs(load_golden('small_mimo')))
         B = 3
         st = lambda k: np.stack([np.asarray(kw[k], dtype=float)] * B)
-        K = BatchMPCController(st('Ad'), st('Bd'), Np=kw['Np'], Nc=kw.get('Nc'), x0=st('x0'), xref=st('xref'), uref=st('uref'), uminus1=st('uminus1'),
-                               Qx=st('Qx'), QxN=st('QxN'), Qu=st('Qu'), QDu=st('QDu'), xmin=st('xmin'), xmax=st('xmax'), umin=st('umin'),
-                               umax=st('umax'), Dumin=st('Dumin'), Dumax=st('Dumax'), eps_feas=kw.get('eps_feas', 1e6), eps_abs=EPS, eps_rel=EPS,
-                               max_iter=400000)
+        K = BatchMPCController(**repeated(kw, B, eps_feas=kw.get('eps_feas', 1e6), eps_abs=EPS, eps_rel=EPS, max_iter=400000))
         K.setup(solve=False)
         rng = np.random.default_rng(11)
         out['after_step/u'] = np.array(K.step(st('x0') + 0.01 * rng.standard_normal((B, st('x0').shape[1])),

@@ -17,9 +17,21 @@ m = 2 N nx + Nc nu + (Nc + 1) nu rows (dynamics | state box | input box | Delta-
 Both fallback cases are above the limit on the columns alone, whatever the rest of the block needs.  That the others do fit cannot be
 read off these numbers alone: the dynamic LDS size of each k_adjoint launch was read from the runtime's launch log (LAB_NOTES.md).
 """
+import warnings
+
 import numpy as np
 
+import util
+from util import KW, apply_attrs, golden_kwargs, load_golden, stacked, repeated
+
 SEED_BASE = 7100
+
+# The golden fixtures by complementarity at the optimum (tests/test_adjoint_reference.py says what is asserted on which list)
+STRICT = ['cart_pole', 'cart_pole_kalman', 'cart_pole_nc1', 'point_mass', 'point_mass_hard', 'point_mass_nc', 'quadcopter_nodu',
+          'random_12_4_30', 'random_12_4_30_b', 'random_12_4_30_hard', 'random_20_8_12_hard', 'random_5_3_8', 'random_5_3_8_nc',
+          'random_5_3_8_nc_hard', 'small_mimo']
+DEGENERATE = ['quadcopter', 'quadcopter_nc', 'accel_brake', 'accel_brake_hard', 'random_20_8_12', 'random_20_8_100']
+NO_INEQUALITY_ACTIVE = ['random_12_4_30', 'random_5_3_8_nc', 'cart_pole_kalman']
 
 # name -> nx, nu, Np, Nc, SOFT_ON, x0 scale, seeds, the path it is there for
 CASES = {
@@ -78,29 +90,13 @@ def batch_kwargs(name, seeds=None, **settings):
     """BatchMPCController kwargs with the case's seeds (or the given ones) as its instances."""
     c = CASES[name]
     kws = [draw(name, s)[0] for s in (c['seeds'] if seeds is None else seeds)]
-    st = lambda k: np.stack([np.asarray(kw[k], dtype=float) for kw in kws])
-    keys = ('Ad', 'Bd', 'x0', 'xref', 'uref', 'uminus1', 'Qx', 'QxN', 'Qu', 'QDu', 'xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')
-    args = {k: st(k) for k in keys}
-    args.update(Np=c['Np'], Nc=c['Nc'], eps_feas=kws[0]['eps_feas'], SOFT_ON=c['soft'])
-    args.update(settings)
-    return args
+    return stacked(kws, Nc=c['Nc'], eps_feas=kws[0]['eps_feas'], SOFT_ON=c['soft'], **settings)
 
 
 def oracle_controller(name, seed, eps):
     """The instance as an MPCController on the CPU oracle (oracle/osqp_oracle.py), set up and cold-solved at eps_abs = eps_rel = eps."""
-    import warnings
-    from pympc_amd import MPCController
-    from oracle.osqp_oracle import OSQP
     kw, attrs = draw(name, seed)
-    K = MPCController(eps_abs=eps, eps_rel=eps, **kw)
-    for a, v in attrs.items():
-        setattr(K, a, v)
-    K.prob = OSQP()
-    K.solver_settings = dict(max_iter=4000000)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        K.setup()
-    return K
+    return util.oracle_controller(kw, attrs, eps=eps, setup=True, quiet=True, max_iter=4000000)
 
 
 def oracle_state(K):
@@ -108,3 +104,98 @@ def oracle_state(K):
     x, z, y, _ = K.prob.iterate_state()
     D, E, c = K.prob.scaling()
     return (K.P, K.A, np.asarray(K.l, dtype=float), np.asarray(K.u, dtype=float), x, z, y, D, E, c)
+
+
+def oracle_qp(P, q, A, l, u, eps):
+    """The CPU oracle set up on a QP at eps_abs = eps_rel = eps (not solved)."""
+    from oracle.osqp_oracle import OSQP
+    o = OSQP()
+    o.setup(P, q, A, np.clip(l, -1e30, 1e30), np.clip(u, -1e30, 1e30), eps_abs=eps, eps_rel=eps, max_iter=4000000)
+    return o
+
+
+def solve_golden(name, eps):
+    """A golden fixture solved by the oracle: (kwargs, QP, result, (x, z, y), (D, E, c))."""
+    from polish_ref import golden_qp
+    g = load_golden(name)
+    P, q, A, l, u = qp = golden_qp(g)
+    o = oracle_qp(P, q, A, l, u, eps)
+    r = o.solve()
+    assert r.info.status == 'solved', (name, r.info.status)
+    x, z, y, _ = o.iterate_state()
+    return golden_kwargs(g), qp, r, (x, z, y), o.scaling()
+
+
+# ---- the device under the adjoint tests' settings (tests/test_gpu_adjoint.py, _shapes, _model) ------------------------------------------
+EPS = 1e-9
+# Every output of mpcqp_adjoint / mpcqp_gains against the restatement, relative to max(1, |.|_inf): the tolerance polishing holds against its
+# restatement (tests/test_gpu_polish.py) -- the same factor, the same refinement.  Measured maxima per fixture: LAB_NOTES.md.
+TOL = 1e-9
+RAW = ('q', 'l', 'u')
+CHAINED = ('x0', 'uminus1', 'xref', 'uref')
+
+
+def controller(kw, eps=EPS, **settings):
+    from pympc_amd import MPCController
+    attrs = getattr(kw, 'attrs', {})
+    kw = KW(kw); kw.attrs = attrs
+    kw.update(eps_abs=eps, eps_rel=eps)
+    K = apply_attrs(MPCController(**kw), kw)
+    K.solver_settings = dict(max_iter=400000, **settings)
+    return K
+
+
+def golden(name):
+    return golden_kwargs(load_golden(name))
+
+
+def solved(kw, **settings):
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        K = controller(kw, **settings); K.setup()
+    assert K.res.info.status == 'solved', K.res.info.status
+    return K
+
+
+def device_state(bp, b=0):
+    P, q, A, l, u = (v[b] for v in bp.export_qp())
+    x, z, y = (v[b] for v in bp.iterate_state())
+    D, E, c, _ = bp.scaling()
+    return (P, A, l, u, x, z, y, D[b], E[b], c[b])
+
+
+def random_batch(kws, eps=EPS, **settings):
+    """A BatchMPCController (not set up) of instances without a held input at eps, with instance 0's scalar eps_feas."""
+    from pympc_amd import BatchMPCController
+    return BatchMPCController(**stacked(kws, Nc=None, eps_feas=kws[0]['eps_feas'], eps_abs=eps, eps_rel=eps, max_iter=400000, **settings))
+
+
+def copies(kw, B, **settings):
+    """A BatchMPCController (not set up) of B copies of one instance at EPS, with its scalar eps_feas."""
+    from pympc_amd import BatchMPCController
+    return BatchMPCController(**repeated(kw, B, eps_feas=kw.get('eps_feas', 1e6), eps_abs=EPS, eps_rel=EPS, max_iter=400000, **settings))
+
+
+def snapshot(bp):
+    x, y, info = bp.solution()
+    return [x, y, bytes(info)] + list(bp.iterate_state()) + [np.array(bp.stats()), bp.polish_status()]
+
+
+def same(a, b):
+    return all((p == q) if isinstance(p, bytes) else np.array_equal(p, q, equal_nan=True) for p, q in zip(a, b))
+
+
+def point_mass_batch(um1_bad=2, B=5, **settings):
+    """util.point_mass_batch under the adjoint tests' settings."""
+    return util.point_mass_batch(um1_bad, B, eps_abs=EPS, eps_rel=EPS, max_iter=400000, **settings)
+
+
+def case_batch(name, seeds=None, backend=None):
+    """The case's seeds (or the given ones) as a BatchMPCController at EPS, set up and solved, on a forced backend if one is named."""
+    from pympc_amd import BatchMPCController
+    from pympc_amd.solver import forced_settings
+    K = BatchMPCController(**batch_kwargs(name, seeds, eps_abs=EPS, eps_rel=EPS, max_iter=400000))
+    with warnings.catch_warnings(), forced_settings(**({'backend': backend} if backend else {})):
+        warnings.simplefilter('ignore')
+        K.setup()
+    return K

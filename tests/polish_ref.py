@@ -16,6 +16,16 @@ import scipy.sparse.linalg as spla
 
 QP_INFTY = 1e30
 
+# fixtures on which polishing the oracle's eps-1e-3 iterate reaches x* to 1e-8 (measured by tests/test_polish_reference.py)
+EXACT = ['cart_pole_nc1', 'point_mass', 'point_mass_hard', 'point_mass_nc', 'quadcopter_nc', 'quadcopter_nodu', 'random_12_4_30',
+         'random_12_4_30_b', 'random_12_4_30_hard', 'random_20_8_12_hard', 'random_5_3_8_nc', 'random_5_3_8_nc_hard', 'small_mimo']
+# ... and on which it is accepted (EXACT and these)
+ACCEPTED = EXACT + ['accel_brake', 'accel_brake_hard', 'cart_pole', 'cart_pole_kalman']
+# the same with the oracle's default Ruiz scaling and its own (D, E, c) -- what the device does: the same fixtures are accepted; the iterate the
+# scaled iteration stops at gets the active set right (x* to 1e-8) on these
+EXACT_SCALED = ['accel_brake', 'accel_brake_hard', 'point_mass_nc', 'quadcopter_nc', 'quadcopter_nodu', 'random_12_4_30', 'random_12_4_30_b',
+                'random_12_4_30_hard', 'random_20_8_12_hard', 'random_5_3_8_nc', 'random_5_3_8_nc_hard', 'small_mimo']
+
 
 def active_set(A, l, u, x, z, y, D, E, c):
     """OSQP's rule in the scaling (D, E, c): (lower-active mask, upper-active mask)."""
@@ -69,3 +79,33 @@ def golden_qp(g):
     U = sp.triu(golden_csc(g, 'P'), format='csc')
     return (U + sp.triu(U, 1).T).tocsc(), np.asarray(g['q'], dtype=float), golden_csc(g, 'A').tocsc(), \
         np.asarray(g['l'], dtype=float), np.asarray(g['u'], dtype=float)
+
+
+# ---- the device against this restatement (tests/test_gpu_polish.py, tests/test_gpu_row_types.py) -----------------------------------
+def device_spec(bp, b=0):
+    """polish_ref on instance b of BatchProblem bp, from the iterate and scaling the device holds now."""
+    P, q, A, l, u = (v[b] for v in bp.export_qp())
+    x, z, y = (v[b] for v in bp.iterate_state())
+    D, E, c, _ = bp.scaling()
+    info = bp.infos()[b]
+    return polish(P, q, A, l, u, x, z, y, D[b], E[b], c[b], info.pri_res, info.dua_res)
+
+
+def check_against_spec(bp, idx=None):
+    """Polish the last solve of bp (polish off until now) and compare every instance in idx with polish_ref."""
+    import pytest
+    from util import rel1
+    idx = range(bp.batch) if idx is None else idx
+    refs = {b: device_spec(bp, b) for b in idx}
+    bp.polish()
+    st = bp.polish_status()
+    x, y, info = bp.solution()
+    for b, ref in refs.items():
+        assert st[b] == ref['status_polish'], (b, st[b], ref['status_polish'])
+        if st[b] == 1:
+            assert rel1(x[b], ref['x']) <= 1e-9, (b, rel1(x[b], ref['x']))
+            # (the multipliers come out of (omega / c) (A x - b) with omega / c ~ E^2 / (c delta): the rounding of A x - b, 1e6 times)
+            assert rel1(y[b], ref['y']) <= 1e-8, (b, rel1(y[b], ref['y']))
+            assert np.all(y[b][~(ref['low'] | ref['upp'])] == 0.0), (b, 'multipliers off the active set')
+            assert info[b].pri_res == pytest.approx(ref['pri_res'], abs=1e-9 * max(1.0, np.abs(ref['x']).max())), (b, info[b].pri_res, ref['pri_res'])
+    return st

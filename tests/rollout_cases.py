@@ -9,6 +9,8 @@ tests/test_rollout_cases.py asserts all of it: a seed that fails is replaced her
 """
 import numpy as np
 
+import util
+
 SEED_BASE = 7200
 
 # name -> shape, SOFT_ON, state box, factor on x0, steps, seeds, reference rows (1: constant, 0: Np + 1 rows), the path it is there for
@@ -60,28 +62,12 @@ def batch_kwargs(name, seeds=None, **settings):
     """BatchMPCController kwargs with the case's seeds (or the given ones) as its instances."""
     c = CASES[name]
     kws = [draw(name, s)[0] for s in (c['seeds'] if seeds is None else seeds)]
-    st = lambda k: np.stack([np.asarray(kw[k], dtype=float) for kw in kws])
-    keys = ('Ad', 'Bd', 'x0', 'xref', 'uref', 'uminus1', 'Qx', 'QxN', 'Qu', 'QDu', 'xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')
-    args = {k: st(k) for k in keys}
-    args.update(Np=c['Np'], Nc=c['Nc'], eps_feas=kws[0]['eps_feas'], SOFT_ON=c['soft'])
-    args.update(settings)
-    return args
+    return util.stacked(kws, Nc=c['Nc'], eps_feas=kws[0]['eps_feas'], SOFT_ON=c['soft'], **settings)
 
 
 def oracle_controller(kw, attrs, eps=1e-9):
     """An MPCController on the CPU oracle (oracle/osqp_oracle.py), set up and cold-solved at eps_abs = eps_rel = eps."""
-    import warnings
-    from pympc_amd import MPCController
-    from oracle.osqp_oracle import OSQP
-    K = MPCController(eps_abs=eps, eps_rel=eps, **kw)
-    for a, v in attrs.items():
-        setattr(K, a, v)
-    K.prob = OSQP()
-    K.solver_settings = dict(max_iter=4000000)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        K.setup()
-    return K
+    return util.oracle_controller(kw, attrs, eps=eps, setup=True, quiet=True, max_iter=4000000)
 
 
 def oracle_rollout(kw, attrs, K, Ap=None, Bp=None, w=None, xrefs=None, eps=1e-9, with_last=False):

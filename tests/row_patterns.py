@@ -85,14 +85,16 @@ def batch(nx, nu, Np, Nc=None, soft=True, B=8):
 
 
 def stack(kws, **kw):
-    """BatchMPCController kwargs for a list of draws (tests/test_gpu_parity.py: _stacked_batch)."""
-    st = lambda k: np.stack([np.asarray(d[k], dtype=float) for d in kws])
-    k0 = kws[0]
-    args = dict(Ad=st('Ad'), Bd=st('Bd'), Np=k0['Np'], Nc=k0.get('Nc'), x0=st('x0'), xref=st('xref'), uref=st('uref'), uminus1=st('uminus1'),
-                Qx=st('Qx'), QxN=st('QxN'), Qu=st('Qu'), QDu=st('QDu'), xmin=st('xmin'), xmax=st('xmax'), umin=st('umin'), umax=st('umax'),
-                Dumin=st('Dumin'), Dumax=st('Dumax'), eps_feas=np.array([[d['eps_feas']] for d in kws]), SOFT_ON=k0.get('_SOFT_ON', True))
-    args.update(kw)
-    return args
+    """BatchMPCController kwargs for a list of draws (util.stacked, with the draws' SOFT_ON)."""
+    from util import stacked
+    return stacked(kws, SOFT_ON=kws[0].get('_SOFT_ON', True), **kw)
+
+
+def oracle(kw, eps, solve=True, quiet=False):
+    """A draw as an MPCController on the CPU oracle, set up (and cold-solved) at eps_abs = eps_rel = eps."""
+    from util import oracle_controller
+    c, attrs = ctor(kw)
+    return oracle_controller(c, attrs, eps=eps, setup=True, solve=solve, quiet=quiet, max_iter=400000)
 
 
 def row_rho(E, l, u, rho):

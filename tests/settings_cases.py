@@ -42,8 +42,8 @@ ITERATION_SETTINGS = ('alpha1', 'alpha1.8', 'sigma1e-2', 'rho1', 'scaling0', 'sc
 # kernel families with an ADMM body or a check of their own
 FAMILIES = ('dense', 'bcr11', 'bcr31', 'nb32', 'border', 'grouped', 'wide64', 'wide128')
 
-# name -> family, how the instance is made (golden: tests/golden/qp_<name>.npz; group / wide: the builders of tests/test_gpu_group.py and
-# tests/test_gpu_wide.py; lti: fixtures.random_lti), the backends it is forced on (None: what mpcqp_create picks)
+# name -> family, how the instance is made (golden: tests/golden/qp_<name>.npz; group / wide: util.group_kw and util.wide_kw, the builders of
+# tests/test_gpu_group.py and tests/test_gpu_wide.py; lti: fixtures.random_lti), the backends it is forced on (None: what mpcqp_create picks)
 CASES = {
     'point_mass':          dict(family='dense',   make=('golden', 'point_mass'), backends=('dense',)),
     'cart_pole':           dict(family='dense',   make=('golden', 'cart_pole'), backends=('dense',)),
@@ -143,11 +143,11 @@ def draw(case):
         kw = golden_kwargs(load_golden(arg))
         return dict(kw), dict(kw.attrs)
     if kind == 'group':
-        from test_gpu_group import _kw
-        return _kw(arg), {'SOFT_ON': arg[4]}
+        from util import group_kw
+        return group_kw(arg), {'SOFT_ON': arg[4]}
     if kind == 'wide':
-        from test_gpu_wide import _kw
-        return _kw(arg), {}
+        from util import wide_kw
+        return wide_kw(arg), {}
     from pympc_amd import fixtures
     arg = dict(arg)
     Nc, scale = arg.pop('Nc', None), arg.pop('x0_scale', 1.0)
@@ -172,6 +172,22 @@ def controller(case, setting, oracle, eps=EPS, x0=None, **more):
         from oracle.osqp_oracle import OSQP
         K.prob = OSQP()
     K.solver_settings = dict(settings(setting), **more)
+    return K
+
+
+def infeasible_point_mass(oracle, **st):
+    """The infeasible point mass of tests/test_gpu_parity.py (u_{-1} = 5 outside what Delta-u allows), set up and solved under the settings st."""
+    from pympc_amd import MPCController, fixtures
+    kw = fixtures.point_mass()
+    kw['uminus1'] = np.array([5.0])
+    K = MPCController(**kw)
+    if oracle:
+        from oracle.osqp_oracle import OSQP
+        K.prob = OSQP()
+    K.solver_settings = dict(st)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        K.setup()
     return K
 
 

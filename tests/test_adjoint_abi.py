@@ -4,51 +4,19 @@ outside SYMBOLS, its structs mirrored field by field, its defaults as documented
 import ctypes as C
 import hashlib
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_abi_layout import header_struct, _strip_comments
+from util import repeated
+from abi import ROOT, header, header_struct, header_functions, lib_loaded, OLDER_HEADERS, twin      # noqa: F401  (twin: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADJOINT_HEADER = open(os.path.join(ROOT, 'include', 'mpcqp_adjoint.h')).read()
-
-# the headers this extension sits beside, as they were before it (sha256 of the files)
-OLDER_HEADERS = {
-    'mpcqp.h': '9b65550ae4f89a6a8ef2d36876ae97a0bc26d31d994514d8c3a1c1ab8e0832a8',
-    'mpcqp_polish.h': '8fdf6b5c286dbd74132ab41a8a18616ed4bb5d73233d1fd209293d46fbc682ad',
-    'mpcqp_model.h': '2803bb5b65ee660e7da727e459a53997cd7f6d3d0f702b18a04a1bc6b7bb2692',
-}
-
-
-def _adjoint_functions():
-    text = re.sub(r'typedef struct \{.*?\}\s*\w+\s*;', '', _strip_comments(ADJOINT_HEADER), flags=re.S)
-    return sorted(set(re.findall(r'\b(mpcqp_\w+)\s*\(', text)))
-
-
-def _lib_loaded():
-    import __graft_entry__ as g
-    from pympc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib, _lib.load()
-
-
-def _struct(name):
-    import test_abi_layout
-    old = test_abi_layout.HEADER
-    test_abi_layout.HEADER = ADJOINT_HEADER
-    try:
-        return header_struct(name)
-    finally:
-        test_abi_layout.HEADER = old
+ADJOINT_HEADER = header('mpcqp_adjoint.h')
 
 
 def test_adjoint_functions_exported_and_bound():
-    _lib, L = _lib_loaded()
-    names = _adjoint_functions()
+    _lib, L = lib_loaded()
+    names = header_functions(ADJOINT_HEADER)
     assert names == sorted(_lib.ADJOINT_SYMBOLS)
     assert not set(names) & set(_lib.SYMBOLS + _lib.POLISH_SYMBOLS + _lib.MODEL_SYMBOLS)      # the older lists are unchanged
     for n in names:
@@ -60,14 +28,14 @@ def test_adjoint_functions_exported_and_bound():
 def test_adjoint_structs_mirror_the_header():
     from pympc_amd import _lib
     kind = lambda t: 'double' if t is C.c_double else ('int32' if t in (C.c_int32, C.c_int) else 'ptr')
-    assert [(n, kind(t)) for n, t in _lib.AdjointSettings._fields_] == _struct('mpcqp_adjoint_settings')
+    assert [(n, kind(t)) for n, t in _lib.AdjointSettings._fields_] == header_struct(ADJOINT_HEADER, 'mpcqp_adjoint_settings')
     assert C.sizeof(_lib.AdjointSettings) == 4 + 4 + 8 + 8 + 4 + 4
-    assert [(n, kind(t)) for n, t in _lib.AdjointIO._fields_] == _struct('mpcqp_adjoint_io')
+    assert [(n, kind(t)) for n, t in _lib.AdjointIO._fields_] == header_struct(ADJOINT_HEADER, 'mpcqp_adjoint_io')
     assert C.sizeof(_lib.AdjointIO) == 4 + 4 + 9 * 8
 
 
 def test_adjoint_defaults():
-    _lib, L = _lib_loaded()
+    _lib, L = lib_loaded()
     s = _lib.AdjointSettings()
     L.mpcqp_adjoint_default_settings(C.byref(s))
     assert s.struct_size == C.sizeof(_lib.AdjointSettings)
@@ -81,7 +49,7 @@ def test_the_older_headers_are_unchanged():
 
 
 def test_adjoint_calls_check_their_arguments_without_a_handle():
-    _lib, L = _lib_loaded()
+    _lib, L = lib_loaded()
     s = _lib.AdjointSettings()
     L.mpcqp_adjoint_default_settings(C.byref(s))
     io = _lib.AdjointIO()
@@ -99,18 +67,6 @@ def test_adjoint_settings_are_not_solver_or_polish_settings():
             solver.make_settings(**{k: 1})
 
 
-@pytest.fixture
-def twin():
-    from pympc_amd import _lib
-    subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'oracle'), 'libmpcqp_cpu.so'])
-    old = (_lib.LIB_PATH, _lib._lib)
-    _lib.LIB_PATH, _lib._lib = os.path.join(ROOT, 'oracle', 'libmpcqp_cpu.so'), None
-    try:
-        yield _lib.load()
-    finally:
-        _lib.LIB_PATH, _lib._lib = old
-
-
 def test_adjoint_against_the_cpu_twin_is_refused(twin):
     from pympc_amd import _lib, fixtures, MPCController, BatchMPCController
     assert not _lib.has_adjoint(twin)
@@ -124,10 +80,7 @@ def test_adjoint_against_the_cpu_twin_is_refused(twin):
     for call in (lambda: bp.adjoint(g_u0=np.ones((1, bp.nu))), lambda: bp.gains(), lambda: bp.adjoint_info(), lambda: bp.set_adjoint(delta=1e-5)):
         with pytest.raises(NotImplementedError):
             call()
-    st = lambda a: np.stack([np.asarray(a, dtype=float)] * 2)
-    Kb = BatchMPCController(st(kw['Ad']), st(kw['Bd']), Np=kw['Np'], x0=st(kw['x0']), xref=st(kw['xref']), uref=st(kw['uref']),
-                            Qx=st(kw['Qx']), QxN=st(kw['QxN']), Qu=st(kw['Qu']), QDu=st(kw['QDu']), xmin=st(kw['xmin']), xmax=st(kw['xmax']),
-                            umin=st(kw['umin']), umax=st(kw['umax']), Dumin=st(kw['Dumin']), Dumax=st(kw['Dumax']), eps_feas=kw.get('eps_feas', 1e6))
+    Kb = BatchMPCController(**repeated(kw, 2, uminus1=None, eps_feas=kw.get('eps_feas', 1e6)))      # (u_{-1}: the constructor's default)
     Kb.setup()
     with pytest.raises(NotImplementedError):
         Kb.gains()

@@ -13,7 +13,7 @@ import pytest
 
 import adjoint_ref as ar
 import adjoint_model_ref as am
-from test_adjoint_reference import STRICT, _solve, _oracle
+from adjoint_cases import STRICT, solve_golden, oracle_qp
 
 FD_FIXTURES = ['random_5_3_8_nc', 'random_5_3_8_nc_hard', 'small_mimo', 'point_mass_nc', 'cart_pole_nc1', 'random_12_4_30_hard']
 
@@ -32,14 +32,14 @@ def _seed(kw, n, seed=3):
 def _case(name, xref2d=False):
     """The fixture solved by the oracle at eps 1e-11, the adjoint of a random seed on its iterate, and both restatements of the model
     gradients (computed once, read-only afterwards)."""
-    kw0, (P, q, A, l, u), r, (x, z, y), (D, E, c) = _solve(name, 1e-11)
+    kw0, (P, q, A, l, u), r, (x, z, y), (D, E, c) = solve_golden(name, 1e-11)
     kw, attrs = am.full_kwargs(kw0), dict(kw0.attrs)
     if xref2d:                                               # the same problem with its reference spelled out row by row, rows that differ
         nx = kw['Bd'].shape[0]
         kw['xref'] = np.broadcast_to(kw['xref'], (kw['Np'] + 1, nx)) + 0.05 * np.random.default_rng(5).standard_normal((kw['Np'] + 1, nx))
         (Pd, q, Ad_, l, u), K = am.build(kw, attrs)
         P, A = K.P, K.A
-        o = _oracle(P, q, A, l, u, 1e-11)
+        o = oracle_qp(P, q, A, l, u, 1e-11)
         r = o.solve()
         assert r.info.status == 'solved'
         x, z, y, _ = o.iterate_state()
@@ -77,7 +77,7 @@ def test_restatement_against_finite_differences(name):
 
     def loss(over):
         (_, q1, _, l1, u1), K = am.build(over, attrs)
-        rr = _oracle(K.P, q1, K.A, l1, u1, 1e-11).solve()
+        rr = oracle_qp(K.P, q1, K.A, l1, u1, 1e-11).solve()
         assert rr.info.status == 'solved'
         return float(g @ rr.x)
 

@@ -9,33 +9,10 @@ are fixed by name; a fixture does not move between them to make a test pass."""
 import numpy as np
 import pytest
 
-from util import golden_kwargs, load_golden
-from polish_ref import active_set as polish_active_set, golden_qp
+from polish_ref import active_set as polish_active_set
 import adjoint_ref as ar
+from adjoint_cases import STRICT, DEGENERATE, NO_INEQUALITY_ACTIVE, oracle_qp, solve_golden
 import closed_form
-
-STRICT = ['cart_pole', 'cart_pole_kalman', 'cart_pole_nc1', 'point_mass', 'point_mass_hard', 'point_mass_nc', 'quadcopter_nodu',
-          'random_12_4_30', 'random_12_4_30_b', 'random_12_4_30_hard', 'random_20_8_12_hard', 'random_5_3_8', 'random_5_3_8_nc',
-          'random_5_3_8_nc_hard', 'small_mimo']
-DEGENERATE = ['quadcopter', 'quadcopter_nc', 'accel_brake', 'accel_brake_hard', 'random_20_8_12', 'random_20_8_100']
-NO_INEQUALITY_ACTIVE = ['random_12_4_30', 'random_5_3_8_nc', 'cart_pole_kalman']
-
-
-def _oracle(P, q, A, l, u, eps):
-    from oracle.osqp_oracle import OSQP
-    o = OSQP()
-    o.setup(P, q, A, np.clip(l, -1e30, 1e30), np.clip(u, -1e30, 1e30), eps_abs=eps, eps_rel=eps, max_iter=4000000)
-    return o
-
-
-def _solve(name, eps):
-    g = load_golden(name)
-    P, q, A, l, u = qp = golden_qp(g)
-    o = _oracle(P, q, A, l, u, eps)
-    r = o.solve()
-    assert r.info.status == 'solved', (name, r.info.status)
-    x, z, y, _ = o.iterate_state()
-    return golden_kwargs(g), qp, r, (x, z, y), o.scaling()
 
 
 def _dims(kw):
@@ -44,7 +21,7 @@ def _dims(kw):
 
 
 def _gains(name, eps=1e-11):
-    kw, (P, q, A, l, u), r, (x, z, y), (D, E, c) = _solve(name, eps)
+    kw, (P, q, A, l, u), r, (x, z, y), (D, E, c) = solve_golden(name, eps)
     nx, nu, ou = _dims(kw)
     return kw, ar.gains(P, A, l, u, x, z, y, D, E, c, ar.parameter_maps(kw, kw.attrs), ou, nu)
 
@@ -59,7 +36,7 @@ def test_the_fixture_lists_are_the_golden_set():
 def test_restatement_against_finite_differences(name):
     """du0/dx0 against central differences, h = 1e-5 on l[:nx] = u[:nx] = -x0, of the oracle at eps 1e-11.  Tolerance 1e-4 max(1, |J|_inf):
     finite-difference noise is about 2 (solver error ~1e-10) / h ~ 1e-5, this is ten times that."""
-    kw, (P, q, A, l, u), r, (x, z, y), (D, E, c) = _solve(name, 1e-11)
+    kw, (P, q, A, l, u), r, (x, z, y), (D, E, c) = solve_golden(name, 1e-11)
     nx, nu, ou = _dims(kw)
     K = ar.gains(P, A, l, u, x, z, y, D, E, c, ar.parameter_maps(kw, kw.attrs), ou, nu)
     assert K['n_weak'] == 0
@@ -70,7 +47,7 @@ def test_restatement_against_finite_differences(name):
         for s in (+1.0, -1.0):
             l2, u2 = np.clip(l, -1e30, 1e30), np.clip(u, -1e30, 1e30)
             l2[j] -= s * h; u2[j] -= s * h                    # x0[j] += s h
-            rr = _oracle(P, q, A, l2, u2, 1e-11).solve()       # (a cold solve each, like the base point: both ends of a difference follow the
+            rr = oracle_qp(P, q, A, l2, u2, 1e-11).solve()     # (a cold solve each, like the base point: both ends of a difference follow the
                                                                #  same iteration path, so their solver errors largely cancel; warm-started
                                                                #  from one another they do not -- 2.8e-3 on cart_pole_kalman)
             assert rr.info.status == 'solved'
@@ -104,8 +81,8 @@ def test_restatement_equals_the_unconstrained_law(name):
 # ---- (c) the active-set rule on the iterate -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('name', STRICT)
 def test_active_set_rule_finds_the_true_set_at_parity_tolerance(name):
-    kw, (P, q, A, l, u), r9, (x, z, y), (D, E, c) = _solve(name, 1e-9)
-    _, _, r11, (x2, z2, y2), _ = _solve(name, 1e-11)
+    kw, (P, q, A, l, u), r9, (x, z, y), (D, E, c) = solve_golden(name, 1e-9)
+    _, _, r11, (x2, z2, y2), _ = solve_golden(name, 1e-11)
     eq = np.clip(l, -1e30, 1e30) == np.clip(u, -1e30, 1e30)
     pl, pu = polish_active_set(A, l, u, x, z, y, D, E, c)
     el, eu = ar.exact_active_rows(A, l, u, r11.x, r11.y)
@@ -119,14 +96,14 @@ def test_active_set_rule_finds_the_true_set_at_parity_tolerance(name):
 # ---- (d) the degenerate fixtures report their weak rows -----------------------------------------------------------------------------------
 @pytest.mark.parametrize('name', DEGENERATE)
 def test_degenerate_fixtures_report_weak_rows(name):
-    kw, (P, q, A, l, u), r9, (x, z, y), _ = _solve(name, 1e-9)
+    kw, (P, q, A, l, u), r9, (x, z, y), _ = solve_golden(name, 1e-9)
     assert ar.count_weak(l, u, z, y) > 0, name
 
 
 def test_restatement_conventions():
     """d_l / d_u: lower-active and equality rows in d_l, upper-active rows in d_u, inactive rows 0; dL/dq = -r_w; the chain for x0 is
     -r_y[:nx] (l[:nx] = u[:nx] = -x0, read off the builder)."""
-    kw, (P, q, A, l, u), r, (x, z, y), (D, E, c) = _solve('point_mass', 1e-11)
+    kw, (P, q, A, l, u), r, (x, z, y), (D, E, c) = solve_golden('point_mass', 1e-11)
     nx, nu, ou = _dims(kw)
     g = np.random.default_rng(0).standard_normal(P.shape[0])
     res = ar.adjoint(P, A, l, u, x, z, y, D, E, c, g, ar.parameter_maps(kw, kw.attrs))

@@ -2,26 +2,18 @@
 two distinct devices joined the process group, and go through scatter -> per-shard work -> all-gather.  Here on CPU: the
 same entry with the collective backend overridden to gloo and the solver left out (--dry-run); on the GPU box the driver
 runs the real thing."""
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from util import run_bench
 
 
 def _run(extra_env, *flags):
     env = dict(os.environ, MPCQP_BENCH_BACKEND='gloo', **extra_env)
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run'] + list(flags), env=env, capture_output=True, text=True, timeout=280)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
-    assert len(lines) == 1, r.stdout          # rank 0 prints ONE JSON line
-    assert r.stdout.rstrip().splitlines()[-1] == lines[0], r.stdout[-1500:]      # ... and it is the LAST line
-    return json.loads(lines[0])
+    return run_bench(env, '--dry-run', *flags)
 
 
 @pytest.mark.timeout(300)

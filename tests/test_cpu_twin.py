@@ -5,30 +5,17 @@ builder; test infrastructure).  Here, without a GPU, this exercises every ctypes
 status path the GPU run takes, against the reference-made goldens; on the GPU the same Python runs against libmpcqp_hip.so
 (tests/test_closed_loop_golden.py, tests/test_gpu_seam.py, tests/test_gpu_loop_parity.py)."""
 import os
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
-from util import golden_names, load_golden, golden_kwargs, golden_csc, update_steps, apply_attrs, traj_names, load_traj, cart_pole_plant
-from test_closed_loop_golden import _closed_loop, _no_slack_controller, _no_slack_loop
+from util import (golden_names, load_golden, golden_kwargs, golden_csc, update_steps, apply_attrs, traj_names, load_traj, cart_pole_plant, closed_loop,
+                  no_slack_controller, no_slack_loop)
+from abi import twin      # noqa: F401  (a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOFT = [n for n in golden_names() if not n.endswith('_hard')]
-
-
-@pytest.fixture
-def twin():
-    """pympc_amd bound to the CPU twin for one test (the product loader itself reads no switch: the test swaps the path)."""
-    from pympc_amd import _lib
-    subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'oracle'), 'libmpcqp_cpu.so'])
-    old = (_lib.LIB_PATH, _lib._lib)
-    _lib.LIB_PATH, _lib._lib = os.path.join(ROOT, 'oracle', 'libmpcqp_cpu.so'), None
-    try:
-        yield _lib.load()
-    finally:
-        _lib.LIB_PATH, _lib._lib = old
 
 
 def test_twin_exports_the_whole_abi(twin):
@@ -46,13 +33,13 @@ def test_drop_in_class_through_the_abi_reproduces_reference_closed_loop(twin, na
     K.solver_settings = dict(max_iter=400000)
     Ad, Bd = kw['Ad'], kw['Bd']
     plant = cart_pole_plant if name == 'cart_pole' else (lambda x, u: Ad @ x + Bd @ u)
-    _closed_loop(K, kw, g, plant, feed_golden_states=False, tol=1e-7)
+    closed_loop(K, kw, g, plant, feed_golden_states=False, tol=1e-7)
     assert type(K.prob).__name__ == 'DeviceProblem'
 
 
 def test_no_slack_shim_through_the_abi(twin):
     g = load_traj('no_slack_point_mass')
-    _no_slack_loop(_no_slack_controller(g), g, 1e-7)
+    no_slack_loop(no_slack_controller(g), g, 1e-7)
 
 
 @pytest.mark.parametrize('name', golden_names())

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from util import golden_names, load_golden, golden_csc, golden_kwargs
+from util import golden_names, load_golden, golden_csc, golden_kwargs, held_input_qp
 
 ALL = golden_names()          # (SOFT_ON = True and the *_hard fixtures of SOFT_ON = False: the pattern tells them apart)
 
@@ -91,8 +91,7 @@ def test_held_input_with_inexact_weights_through_the_c_seam(Np, Nc, Qu, QDu, nu)
     accepts the genuine pyMPC matrices (the last input block carries Np - Nc + 1 times the rounding error of Qu) and solves them."""
     from pympc_amd.solver import DeviceProblem
     from oracle.osqp_oracle import OSQP
-    from test_qp_recover import _held_input_qp
-    K = _held_input_qp(Np, Nc, Qu, QDu, nu)
+    K = held_input_qp(Np, Nc, Qu, QDu, nu)
     D = DeviceProblem(); D.setup(K.P, K.q, K.A, K.l, K.u, eps_abs=1e-9, eps_rel=1e-9, max_iter=200000)
     r = D.solve()
     O = OSQP(); O.setup(K.P, K.q, K.A, K.l, K.u, eps_abs=1e-9, eps_rel=1e-9, max_iter=200000)

@@ -4,79 +4,37 @@ differences of the device solver, without side effects on the handle, with the s
 through torch.autograd and in the example.
 
 Active sets are found at the project's parity setting eps_abs = eps_rel = 1e-9 unless a test says otherwise.  Values are compared on the
-15 fixtures with strict complementarity (STRICT of tests/test_adjoint_reference.py, fixed by name); the six degenerate ones are only asked
+15 fixtures with strict complementarity (STRICT of tests/adjoint_cases.py, fixed by name); the six degenerate ones are only asked
 to report n_weak > 0."""
 import os
 import re
 import subprocess
 import sys
-import warnings
 
 import numpy as np
 import pytest
 
-from util import golden_kwargs, load_golden, apply_attrs, KW
+from util import load_golden, rel1_any, golden_backends
 import adjoint_ref as ar
-from test_adjoint_reference import STRICT
-from test_gpu_backends import _dense_eligible, _bcr_schedule
+from adjoint_cases import (STRICT, EPS, TOL, RAW, CHAINED, golden, solved, device_state, random_batch, copies, snapshot, same,
+                           point_mass_batch)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-EPS = 1e-9
-# Every output of mpcqp_adjoint / mpcqp_gains against the restatement, relative to max(1, |.|_inf): the tolerance polishing holds against its
-# restatement (tests/test_gpu_polish.py) -- the same factor, the same refinement.  Measured maxima per fixture: LAB_NOTES.md.
-TOL = 1e-9
-RAW = ('q', 'l', 'u')
-CHAINED = ('x0', 'uminus1', 'xref', 'uref')
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max())) if b.size else 0.0
-
-
-def _ctrl(kw, eps=EPS, **settings):
-    from pympc_amd import MPCController
-    attrs = getattr(kw, 'attrs', {})
-    kw = KW(kw); kw.attrs = attrs
-    kw.update(eps_abs=eps, eps_rel=eps)
-    K = apply_attrs(MPCController(**kw), kw)
-    K.solver_settings = dict(max_iter=400000, **settings)
-    return K
-
-
-def _golden(name):
-    return golden_kwargs(load_golden(name))
-
-
-def _solved(kw, **settings):
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        K = _ctrl(kw, **settings); K.setup()
-    assert K.res.info.status == 'solved'
-    return K
-
-
-def _device_state(bp, b=0):
-    P, q, A, l, u = (v[b] for v in bp.export_qp())
-    x, z, y = (v[b] for v in bp.iterate_state())
-    D, E, c, _ = bp.scaling()
-    return (P, A, l, u, x, z, y, D[b], E[b], c[b])
 
 
 def _compare(bp, kw, label, b=0, maps=None):
     """mpcqp_adjoint with a random g_w (every output) and mpcqp_gains of instance b against the restatement on the device's own iterate.
     Returns (largest relative error, restatement of the seed)."""
     maps = ar.parameter_maps(kw, getattr(kw, 'attrs', {})) if maps is None else maps
-    st = _device_state(bp, b)
+    st = device_state(bp, b)
     g = np.random.default_rng(7).standard_normal((bp.batch, bp.n))
     ref = ar.adjoint(*st, g[b], maps)
     got = bp.adjoint(g_w=g, want=CHAINED + RAW)
     nact, nweak, status = bp.adjoint_info()
     assert status[b] == 1 and nweak[b] == 0 and ref['n_weak'] == 0, (label, status[b], nweak[b], ref['n_weak'])
     assert nact[b] == ref['n_active'], (label, nact[b], ref['n_active'])
-    errs = {k: _rel(got[k][b], ref['d_' + k if k in RAW else k]) for k in CHAINED + RAW}
+    errs = {k: rel1_any(got[k][b], ref['d_' + k if k in RAW else k]) for k in CHAINED + RAW}
     assert np.all(got['l'][b][~ref['low']] == 0.0) and np.all(got['u'][b][~ref['upp']] == 0.0), label
     nu, nx = bp.nu, bp.nx
     Kref = ar.gains(*st, maps, (bp.Np + 1) * nx, nu)
@@ -84,7 +42,7 @@ def _compare(bp, kw, label, b=0, maps=None):
     nact2, nweak2, status2 = bp.adjoint_info()
     assert status2[b] == 1 and nweak2[b] == 0 and nact2[b] == Kref['n_active'], label
     for k, kk in (('x0', 'K_x0'), ('uminus1', 'K_um1'), ('xref', 'K_xref'), ('uref', 'K_uref')):
-        errs[kk] = _rel(Kgot[k][b], Kref[kk])
+        errs[kk] = rel1_any(Kgot[k][b], Kref[kk])
     worst = max(errs.values())
     print('ADJOINT_ERR %s: max %.3e  %s' % (label, worst, ' '.join('%s=%.1e' % kv for kv in errs.items())))
     assert worst <= TOL, (label, errs)
@@ -94,32 +52,23 @@ def _compare(bp, kw, label, b=0, maps=None):
 # ---- 1. every output against the restatement, on the strict fixtures ----------------------------------------------------------------------
 @pytest.mark.parametrize('name', STRICT)
 def test_adjoint_is_the_restatement(name):
-    kw = _golden(name)
-    K = _solved(kw)
+    kw = golden(name)
+    K = solved(kw)
     _compare(K.prob.batch_problem, kw, name)
 
 
 # ---- 2. every backend --------------------------------------------------------------------------------------------------------------------
-def _backends(name):
-    out = ['sweeps']
-    if _dense_eligible(name):
-        out.append('dense')
-    if _bcr_schedule(name):
-        out += ['bcr', 'bcr8', 'bcrt']
-    return out
-
-
 @pytest.mark.parametrize('name', STRICT)
 def test_adjoint_on_every_backend(name):
     """SOFT_ON = False (the *_hard fixtures), Nc < Np (*_nc, cart_pole_nc1) and a 2-D xref (point_mass_nc) are among the strict fixtures.
     The adjoint's own factor is generic: backends differ only through the iterate that fixes the active set."""
     from pympc_amd.solver import forced_settings
-    kw = _golden(name)
+    kw = golden(name)
     maps = ar.parameter_maps(kw, kw.attrs)
     res = {}
-    for be in _backends(name):
+    for be in golden_backends(name):
         with forced_settings(backend=be):
-            K = _solved(kw)
+            K = solved(kw)
         bp = K.prob.batch_problem
         rhs = np.random.default_rng(0).standard_normal((1, bp.n))
         before = bp.kkt_solve(rhs)
@@ -130,30 +79,21 @@ def test_adjoint_on_every_backend(name):
     for be, (ref, got, Kgot) in res.items():
         assert np.array_equal(ref['low'], base[0]['low']) and np.array_equal(ref['upp'], base[0]['upp']), be
         for k in CHAINED + RAW:
-            assert _rel(got[k], base[1][k]) <= TOL, (be, k, _rel(got[k], base[1][k]))
+            assert rel1_any(got[k], base[1][k]) <= TOL, (be, k, rel1_any(got[k], base[1][k]))
         for k in CHAINED:
-            assert _rel(Kgot[k], base[2][k]) <= TOL, (be, k)
+            assert rel1_any(Kgot[k], base[2][k]) <= TOL, (be, k)
 
 
 # ---- 3. the headline shape ---------------------------------------------------------------------------------------------------------------
-def _random_batch(kws, eps=EPS, **settings):
-    from pympc_amd import BatchMPCController
-    s = lambda k: np.stack([np.asarray(kw[k], dtype=float) for kw in kws])
-    K = BatchMPCController(s('Ad'), s('Bd'), Np=kws[0]['Np'], x0=s('x0'), xref=s('xref'), uref=s('uref'), uminus1=s('uminus1'), Qx=s('Qx'), QxN=s('QxN'),
-                           Qu=s('Qu'), QDu=s('QDu'), xmin=s('xmin'), xmax=s('xmax'), umin=s('umin'), umax=s('umax'), Dumin=s('Dumin'),
-                           Dumax=s('Dumax'), eps_feas=kws[0]['eps_feas'], eps_abs=eps, eps_rel=eps, max_iter=400000, **settings)
-    return K
-
-
 def test_headline_batch_of_48():
     from pympc_amd import fixtures
     B = 48
     kws = [fixtures.random_lti(i) for i in range(B)]
-    K = _random_batch(kws); K.setup()
+    K = random_batch(kws); K.setup()
     assert all(s == 'solved' for s in K.status())
     bp = K.prob
     nx, nu, Np = 12, 4, 30
-    refs = [ar.gains(*_device_state(bp, b), ar.parameter_maps(kws[b]), (Np + 1) * nx, nu) for b in range(B)]
+    refs = [ar.gains(*device_state(bp, b), ar.parameter_maps(kws[b]), (Np + 1) * nx, nu) for b in range(B)]
     G = K.gains()
     nact, nweak, status = bp.adjoint_info()
     assert np.all(status == 1) and np.all(nweak == 0) and np.all(G['n_weak'] == 0) and np.all(G['status'] == 1)
@@ -161,7 +101,7 @@ def test_headline_batch_of_48():
     for b, ref in enumerate(refs):
         assert ref['n_weak'] == 0 and nact[b] == ref['n_active'], b
         for k in ('K_x0', 'K_um1', 'K_xref', 'K_uref'):
-            worst = max(worst, _rel(G[k][b], ref[k]))
+            worst = max(worst, rel1_any(G[k][b], ref[k]))
     nineq = [int(nact[b]) - (Np + 1) * nx for b in range(6)]
     print('ADJOINT_ERR headline48: max %.3e; active inequalities of the first six %s' % (worst, nineq))
     assert all(0 <= v <= 4 for v in nineq), nineq
@@ -175,7 +115,7 @@ def test_headline_batch_of_48():
             for s in (+1.0, -1.0):
                 kw = dict(kws[b]); x0 = np.array(kw['x0'], dtype=float); x0[j] += s * h; kw['x0'] = x0
                 pert.append(kw)
-        Kp = _random_batch(pert); Kp.setup()
+        Kp = random_batch(pert); Kp.setup()
         assert all(s == 'solved' for s in Kp.status())
         u = Kp.prob.u0()
         J = np.stack([(u[2 * j] - u[2 * j + 1]) / (2 * h) for j in range(nx)], axis=1)
@@ -185,33 +125,24 @@ def test_headline_batch_of_48():
 
 
 # ---- 4. no side effects ------------------------------------------------------------------------------------------------------------------
-def _snapshot(bp):
-    x, y, info = bp.solution()
-    return [x, y, bytes(info)] + list(bp.iterate_state()) + [np.array(bp.stats()), bp.polish_status()]
-
-
-def _same(a, b):
-    return all((p == q) if isinstance(p, bytes) else np.array_equal(p, q, equal_nan=True) for p, q in zip(a, b))
-
-
 @pytest.mark.parametrize('polish', [False, True])
 def test_adjoint_and_gains_leave_the_handle_as_it_was(polish):
     from pympc_amd import fixtures
     kws = [fixtures.random_lti(i) for i in range(4)]
-    Ka, Kb = (_random_batch(kws, eps=1e-4, polish=polish) for _ in range(2))
+    Ka, Kb = (random_batch(kws, eps=1e-4, polish=polish) for _ in range(2))
     Ka.setup(); Kb.setup()
-    before = _snapshot(Ka.prob)
-    assert _same(before, _snapshot(Kb.prob))
+    before = snapshot(Ka.prob)
+    assert same(before, snapshot(Kb.prob))
     g = np.random.default_rng(3).standard_normal((4, Ka.prob.n))
     Ka.prob.adjoint(g_w=g, g_u0=np.ones((4, 4)), want=CHAINED + RAW)
     Ka.gains()
     assert np.all(Ka.prob.adjoint_info()[2] == 1)
-    assert _same(before, _snapshot(Ka.prob))
+    assert same(before, snapshot(Ka.prob))
     # the next solve, and a 5-step device loop, against the twin that never took an adjoint
     x1 = np.stack([kw['x0'] for kw in kws]) * 0.9
     for K in (Ka, Kb):
         K.update(x1)
-    assert _same(_snapshot(Ka.prob), _snapshot(Kb.prob))
+    assert same(snapshot(Ka.prob), snapshot(Kb.prob))
     Ka.gains()
     if polish:
         for K in (Ka, Kb):
@@ -219,26 +150,12 @@ def test_adjoint_and_gains_leave_the_handle_as_it_was(polish):
     ta, tb = Ka.run(5), Kb.run(5)
     for k in ('x', 'u', 'status', 'iter'):
         assert np.array_equal(ta[k], tb[k]), k
-    assert _same(_snapshot(Ka.prob), _snapshot(Kb.prob))
+    assert same(snapshot(Ka.prob), snapshot(Kb.prob))
 
 
 # ---- 5. statuses -------------------------------------------------------------------------------------------------------------------------
-def _point_mass_batch(um1_bad=2, B=5, **settings):
-    from pympc_amd import BatchMPCController, fixtures
-    kw = fixtures.point_mass()
-    st = lambda a: np.stack([np.asarray(a, dtype=float)] * B)
-    um1 = st(kw['uminus1'] if 'uminus1' in kw else np.zeros(1))
-    um1[um1_bad] = 5.0                               # tests/test_gpu_parity.py's infeasible recipe for one instance
-    x0 = st(kw['x0']) * np.linspace(0.6, 1.0, B)[:, None]
-    K = BatchMPCController(st(kw['Ad']), st(kw['Bd']), Np=kw['Np'], x0=x0, xref=st(kw['xref']), uref=st(kw['uref']), uminus1=um1,
-                           Qx=st(kw['Qx']), QxN=st(kw['QxN']), Qu=st(kw['Qu']), QDu=st(kw['QDu']), xmin=st(kw['xmin']), xmax=st(kw['xmax']),
-                           umin=st(kw['umin']), umax=st(kw['umax']), Dumin=st(kw['Dumin']), Dumax=st(kw['Dumax']), eps_feas=kw.get('eps_feas', 1e6),
-                           eps_abs=EPS, eps_rel=EPS, max_iter=400000, **settings)
-    return K, kw
-
-
 def test_infeasible_instance_reports_status_0_and_zero_outputs():
-    K, _ = _point_mass_batch()
+    K, _ = point_mass_batch()
     K.setup()
     assert K.status()[2] == 'primal infeasible'
     g = np.random.default_rng(1).standard_normal((5, K.prob.n))
@@ -254,13 +171,13 @@ def test_infeasible_instance_reports_status_0_and_zero_outputs():
 
 
 def test_quadcopter_reports_weak_rows():
-    K = _solved(_golden('quadcopter'))
+    K = solved(golden('quadcopter'))
     G = K.gains()
     assert G['status'] == 1 and G['n_weak'] > 0, G['n_weak']
 
 
 def test_state_errors():
-    K, _ = _point_mass_batch()
+    K, _ = point_mass_batch()
     K.setup(solve=False)
     with pytest.raises(RuntimeError, match=r'\(-5\)'):          # MPCQP_ERR_STATE: nothing solved yet
         K.prob.adjoint(g_u0=np.ones((5, 1)))
@@ -287,17 +204,17 @@ def test_raw_vector_mode_gives_the_seam_gradients_only():
     with pytest.raises(RuntimeError, match=r'\(-5\)'):
         bp.gains()
     g = np.random.default_rng(5).standard_normal((1, bp.n))
-    ref = ar.adjoint(*_device_state(bp), g[0])
+    ref = ar.adjoint(*device_state(bp), g[0])
     got = bp.adjoint(g_w=g, want=RAW)
     nact, nweak, status = bp.adjoint_info()
     assert status[0] == 1 and nweak[0] == 0 and nact[0] == ref['n_active']
-    errs = {k: _rel(got[k][0], ref['d_' + k]) for k in RAW}
+    errs = {k: rel1_any(got[k][0], ref['d_' + k]) for k in RAW}
     print('ADJOINT_ERR csc_seam: %s' % errs)
     assert max(errs.values()) <= TOL, errs
 
 
 def test_adjoint_settings_are_its_own():
-    K = _solved(_golden('random_5_3_8'))
+    K = solved(golden('random_5_3_8'))
     bp = K.prob.batch_problem
     g = np.ones((1, bp.nu))
     a = bp.adjoint(g_u0=g)['x0'].copy()
@@ -314,8 +231,8 @@ def test_adjoint_settings_are_its_own():
 # ---- 6. the unconstrained gains ----------------------------------------------------------------------------------------------------------
 def test_gains_without_active_inequalities_are_the_unconstrained_gains():
     from pympc_amd.unconstrained import unconstrained_gains
-    kw = _golden('random_12_4_30')
-    K = _solved(kw)
+    kw = golden('random_12_4_30')
+    K = solved(kw)
     G = K.gains()
     nx, nu = K.nx, K.nu
     assert G['status'] == 1 and G['n_weak'] == 0
@@ -325,18 +242,10 @@ def test_gains_without_active_inequalities_are_the_unconstrained_gains():
 
 
 # ---- 7. torch ----------------------------------------------------------------------------------------------------------------------------
-def _copies(kw, B, **settings):
-    st = lambda k: np.stack([np.asarray(kw[k], dtype=float)] * B)
-    from pympc_amd import BatchMPCController
-    return BatchMPCController(st('Ad'), st('Bd'), Np=kw['Np'], Nc=kw.get('Nc'), x0=st('x0'), xref=st('xref'), uref=st('uref'), uminus1=st('uminus1'),
-                              Qx=st('Qx'), QxN=st('QxN'), Qu=st('Qu'), QDu=st('QDu'), xmin=st('xmin'), xmax=st('xmax'), umin=st('umin'), umax=st('umax'),
-                              Dumin=st('Dumin'), Dumax=st('Dumax'), eps_feas=kw.get('eps_feas', 1e6), eps_abs=EPS, eps_rel=EPS, max_iter=400000, **settings)
-
-
 def test_mpc_step_gradients_against_central_differences():
     import torch
     from pympc_amd.torch_layer import mpc_step
-    kw = dict(_golden('random_5_3_8'))
+    kw = dict(golden('random_5_3_8'))
     kw.setdefault('uminus1', np.array(kw['uref'], dtype=float))
     B, nx, nu = 8, 5, 3
     rng = np.random.default_rng(11)
@@ -346,13 +255,13 @@ def test_mpc_step_gradients_against_central_differences():
     w = rng.standard_normal((B, nu))
 
     def u_of(x_, um1_, xref_):                                   # a fresh controller, one cold step: both ends of a difference alike
-        K = _copies(kw, B); K.setup(solve=False)
+        K = copies(kw, B); K.setup(solve=False)
         return np.array(K.step(x_, um1_, xref_))
 
     dev = torch.device('cuda:0')
     t = lambda a: torch.tensor(a, dtype=torch.float64, device=dev, requires_grad=True)
     tx, tu, tr = t(x), t(um1), t(xref)
-    K = _copies(kw, B); K.setup(solve=False)
+    K = copies(kw, B); K.setup(solve=False)
     u = mpc_step(K, tx, tu, tr)
     assert u.shape == (B, nu) and u.requires_grad
     assert np.array_equal(u.detach().cpu().numpy(), u_of(x, um1, xref))
@@ -380,7 +289,7 @@ def test_mpc_step_gradients_against_central_differences():
 def test_mpc_step_failed_instances_get_zero_gradients_and_a_second_step_is_refused():
     import torch
     from pympc_amd.torch_layer import mpc_step
-    K, kw = _point_mass_batch()
+    K, kw = point_mass_batch()
     K.setup(solve=False)
     dev = torch.device('cuda:0')
     t = lambda a: torch.tensor(np.asarray(a, dtype=float), dtype=torch.float64, device=dev, requires_grad=True)
@@ -405,7 +314,7 @@ def test_adjoint_waits_for_a_solve_after_anything_that_replaces_its_inputs():
     calls refuse (MPCQP_ERR_STATE) until the next solve -- also through mpc_step's backward."""
     import torch
     from pympc_amd.torch_layer import mpc_step
-    K, kw = _point_mass_batch(um1_bad=[])
+    K, kw = point_mass_batch(um1_bad=[])
     K.setup()
     ref = K.gains()
     assert np.all(ref['status'] == 1)
@@ -428,7 +337,7 @@ def test_adjoint_waits_for_a_solve_after_anything_that_replaces_its_inputs():
 
 
 def test_adjoint_out_buffers_are_checked():
-    K, kw = _point_mass_batch(um1_bad=[])
+    K, kw = point_mass_batch(um1_bad=[])
     K.setup()
     g = np.ones((K.B, K.nu))
     with pytest.raises(ValueError, match='out'):
@@ -454,14 +363,14 @@ def test_mpc_step_gradient_reaches_a_reference_the_law_depends_on():
     dev = torch.device('cuda:0')
 
     def u_of(xref_):
-        K = _copies(kw, B); K.setup(solve=False)
+        K = copies(kw, B); K.setup(solve=False)
         return np.array(K.step(x, um1, xref_.reshape(B, -1)))
 
     for rows in (1, N):
         shape = (B, nx) if rows == 1 else (B, N, nx)
         xref = np.broadcast_to(np.asarray(kw['xref'], dtype=float), shape) + 0.01 * rng.standard_normal(shape)
         tr = torch.tensor(xref, dtype=torch.float64, device=dev, requires_grad=True)
-        K = _copies(kw, B); K.setup(solve=False)
+        K = copies(kw, B); K.setup(solve=False)
         u = mpc_step(K, torch.tensor(x, device=dev), torch.tensor(um1, device=dev), tr)
         (u * torch.tensor(w, device=dev)).sum().backward()
         _, nweak, status = K.prob.adjoint_info()

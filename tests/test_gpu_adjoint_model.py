@@ -2,7 +2,8 @@
 alone against the header's sums on the device's own r_w, r_y and iterate; end to end against the numpy restatement
 (tests/adjoint_model_ref.py, pinned on the CPU by tests/test_adjoint_model_reference.py) on the device's iterate; bit-identity with
 mpcqp_adjoint, of a later solve and of repeated calls; the batch sum; statuses and errors; torch.autograd through mpc_step(params=...)
-against central differences of the device solver; the example.  Settings and helpers are those of tests/test_gpu_adjoint.py."""
+against central differences of the device solver; the example.  Settings and helpers are those of tests/test_gpu_adjoint.py (they live in
+tests/adjoint_cases.py)."""
 import ctypes as C
 import functools
 import os
@@ -17,9 +18,9 @@ import pytest
 import adjoint_cases as ac
 import adjoint_ref as ar
 import adjoint_model_ref as am
-from test_adjoint_reference import STRICT
-from test_gpu_adjoint import TOL, EPS, RAW, CHAINED, _golden, _solved, _device_state, _random_batch, _copies, _snapshot, _same
-from test_gpu_adjoint_shapes import _batch
+from adjoint_cases import (STRICT, TOL, EPS, RAW, CHAINED, golden, solved, device_state, random_batch, copies, snapshot, same, point_mass_batch,
+                           case_batch)
+from util import rel1_any
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,11 +37,11 @@ def _golden_case(name):
     """A strict fixture solved on the device and ONE call for q, l, u and the seven model gradients (computed once, read-only afterwards).
     'random_5_3_8_nc:xref2d': the fixture with its reference given row by row, rows that differ."""
     base, _, tag = name.partition(':')
-    kw0 = _golden(base)
+    kw0 = golden(base)
     if tag:
         nx = np.asarray(kw0['Bd']).shape[0]
         kw0['xref'] = np.broadcast_to(kw0['xref'], (kw0['Np'] + 1, nx)) + 0.05 * np.random.default_rng(5).standard_normal((kw0['Np'] + 1, nx))
-    K = _solved(kw0)
+    K = solved(kw0)
     bp = K.prob.batch_problem
     g = _seed(bp)
     got = bp.adjoint(g_w=g, want=RAW + MODEL)
@@ -52,7 +53,7 @@ def _golden_case(name):
 
 @functools.lru_cache(maxsize=None)
 def _shape_case(name):
-    K = _batch(name)
+    K = case_batch(name)
     assert all(s == 'solved' for s in K.status()), (name, K.status())
     bp = K.prob
     g = _seed(bp)
@@ -118,7 +119,7 @@ def _propagated_bound(data, b, w, y, r_w, r_y):
 @pytest.mark.parametrize('name', STRICT + ['random_5_3_8_nc:xref2d'])
 def test_model_gradients_are_the_restatement_on_the_devices_iterate(name):
     bp, g, got, (nact, nweak, status), data, (kw, attrs) = _golden_case(name)
-    st = _device_state(bp)
+    st = device_state(bp)
     ref = ar.adjoint(*st, g[0])
     assert status[0] == 1 and nweak[0] == 0 and ref['n_weak'] == 0 and nact[0] == ref['n_active'], name
     w, y = st[4], st[6]
@@ -137,10 +138,10 @@ def test_model_gradients_are_the_restatement_on_the_devices_iterate(name):
 def test_bit_identity_with_mpcqp_adjoint_of_a_later_solve_and_of_repeated_calls():
     from pympc_amd import fixtures
     kws = [fixtures.random_lti(i) for i in range(4)]
-    Ka, Kb = (_random_batch(kws, eps=1e-6) for _ in range(2))
+    Ka, Kb = (random_batch(kws, eps=1e-6) for _ in range(2))
     Ka.setup(); Kb.setup()
-    before = _snapshot(Ka.prob)
-    assert _same(before, _snapshot(Kb.prob))
+    before = snapshot(Ka.prob)
+    assert same(before, snapshot(Kb.prob))
     g, gu = np.random.default_rng(3).standard_normal((4, Ka.prob.n)), np.ones((4, 4))
     plain = Kb.prob.adjoint(g_w=g, g_u0=gu, want=CHAINED + RAW)
     one = Ka.prob.adjoint(g_w=g, g_u0=gu, want=CHAINED + RAW + MODEL)
@@ -154,11 +155,11 @@ def test_bit_identity_with_mpcqp_adjoint_of_a_later_solve_and_of_repeated_calls(
     for k in MODEL:
         assert np.array_equal(one[k], only[k]) and np.array_equal(one[k], two[k]) and np.array_equal(s1[k], s2[k]), k
         assert s1[k].shape == (1,) + one[k].shape[1:]
-    assert _same(before, _snapshot(Ka.prob))
+    assert same(before, snapshot(Ka.prob))
     x1 = np.stack([kw['x0'] for kw in kws]) * 0.9
     for K in (Ka, Kb):
         K.update(x1)
-    assert _same(_snapshot(Ka.prob), _snapshot(Kb.prob))
+    assert same(snapshot(Ka.prob), snapshot(Kb.prob))
     ta, tb = Ka.run(3), Kb.run(3)
     for k in ('x', 'u', 'status', 'iter'):
         assert np.array_equal(ta[k], tb[k]), k
@@ -169,7 +170,7 @@ def test_batch_sum_is_the_sum_over_the_batch():
     """37 instances (no multiple of the sum kernel's sixteen lanes): within B . 1.2e-16 . sum_b |term_b| . 4 of numpy's sum."""
     from pympc_amd import fixtures
     B = 37
-    K = _random_batch([fixtures.random_lti(i) for i in range(B)]); K.setup()
+    K = random_batch([fixtures.random_lti(i) for i in range(B)]); K.setup()
     assert all(s == 'solved' for s in K.status())
     g = np.random.default_rng(2).standard_normal((B, K.prob.n))
     per = K.prob.adjoint(g_w=g, want=MODEL)
@@ -185,7 +186,7 @@ def test_batch_sum_is_the_sum_over_the_batch():
 def test_unsolved_instance_gets_zeros_and_adds_nothing_to_the_sum():
     name, bad = ac.INFEASIBLE
     s = ac.CASES[name]['seeds']
-    Ka, Kb = _batch(name, (s[0], s[1], bad, s[2])), _batch(name, (s[0], s[1], s[2]))
+    Ka, Kb = case_batch(name, (s[0], s[1], bad, s[2])), case_batch(name, (s[0], s[1], s[2]))
     assert Ka.status() == ['solved', 'solved', 'primal infeasible', 'solved'], Ka.status()
     ga = np.random.default_rng(7).standard_normal((4, Ka.prob.n))
     ra, rb = Ka.prob.adjoint(g_w=ga, want=MODEL), Kb.prob.adjoint(g_w=ga[[0, 1, 3]], want=MODEL)
@@ -200,8 +201,7 @@ def test_unsolved_instance_gets_zeros_and_adds_nothing_to_the_sum():
 
 
 def test_state_errors_carry_over():
-    from test_gpu_adjoint import _point_mass_batch
-    K, kw = _point_mass_batch(um1_bad=[])
+    K, kw = point_mass_batch(um1_bad=[])
     K.setup(solve=False)
     gu = np.ones((K.B, K.nu))
     with pytest.raises(RuntimeError, match=r'\(-5\)'):          # MPCQP_ERR_STATE: nothing solved yet
@@ -238,7 +238,7 @@ def test_raw_vector_mode_refuses_model_gradients():
 
 def test_struct_size_and_empty_requests_are_refused():
     from pympc_amd import _lib
-    K = _solved(_golden('point_mass'))
+    K = solved(golden('point_mass'))
     bp = K.prob.batch_problem
     gu, dst = np.ones((1, bp.nu)), np.zeros((1, bp.nx, bp.nx))
     io, mo = _lib.AdjointIO(), _lib.AdjointModelIO()
@@ -266,7 +266,7 @@ PARAMS = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu')
 
 
 def _step_inputs(name, B):
-    kw = am.full_kwargs(_golden(name))
+    kw = am.full_kwargs(golden(name))
     nx, nu = kw['Bd'].shape
     rng = np.random.default_rng(11)
     x = np.stack([kw['x0']] * B) + 0.01 * rng.standard_normal((B, nx))
@@ -277,7 +277,7 @@ def _step_inputs(name, B):
 
 def _u_of(kw, B, x, um1, **model):
     """A fresh controller, the model put under it, one cold step: both ends of a difference alike (and what mpc_step's forward does)."""
-    K = _copies(kw, B); K.setup(solve=False)
+    K = copies(kw, B); K.setup(solve=False)
     K.update_model(solve=False, **model)
     return np.array(K.step(x, um1))
 
@@ -293,7 +293,7 @@ def test_mpc_step_parameter_gradients_against_central_differences(name):
     dev = torch.device('cuda:0')
     base = {k: np.stack([kw[k]] * B) for k in PARAMS}
     params = {k: torch.tensor(v, dtype=torch.float64, device=dev, requires_grad=True) for k, v in base.items()}
-    K = _copies(kw, B); K.setup(solve=False)
+    K = copies(kw, B); K.setup(solve=False)
     u = mpc_step(K, torch.tensor(x, device=dev), torch.tensor(um1, device=dev), params=params)
     assert np.array_equal(u.detach().cpu().numpy(), _u_of(kw, B, x, um1, **base))
     (u * torch.tensor(w, device=dev)).sum().backward()
@@ -334,7 +334,7 @@ def test_mpc_step_unbatched_parameters_get_the_batch_sum_and_none_changes_nothin
     grads = []
     for batched in (True, False):
         params = {k: torch.tensor(np.stack([kw[k]] * B) if batched else kw[k], dtype=torch.float64, device=dev, requires_grad=True) for k in ('Ad', 'Bd', 'Qx')}
-        K = _copies(kw, B); K.setup(solve=False)
+        K = copies(kw, B); K.setup(solve=False)
         u = mpc_step(K, tx, tu, params=params)
         (u * tw).sum().backward()
         grads.append({k: p.grad.cpu().numpy() for k, p in params.items()})
@@ -346,7 +346,7 @@ def test_mpc_step_unbatched_parameters_get_the_batch_sum_and_none_changes_nothin
     # params=None: the layer as it was
     res = []
     for extra in ({}, dict(params=None)):
-        K = _copies(kw, B); K.setup(solve=False)
+        K = copies(kw, B); K.setup(solve=False)
         t = tx.clone().requires_grad_(True)
         u = mpc_step(K, t, tu, **extra)
         (u * tw).sum().backward()
@@ -360,10 +360,9 @@ def test_derivatives_after_a_step_are_those_of_the_u_prev_the_step_was_solved_wi
     """mpcqp_mpc_step leaves the applied input in the step data as the next u_{-1}; the active set of the first Delta-u rows and the QDu
     gradient belong to the one its solve was made with.  small_mimo sits on such a row: step() and update() + solve make the same solve, so
     gains, counts and model gradients after either agree (to the TOL of the other comparisons; the active sets exactly)."""
-    from test_gpu_adjoint import _rel
     B = 3
     kw, x, um1, w = _step_inputs('small_mimo', B)
-    Ka, Kb = _copies(kw, B), _copies(kw, B)
+    Ka, Kb = copies(kw, B), copies(kw, B)
     Ka.setup(solve=False); Kb.setup(solve=False)
     ua = np.array(Ka.step(x, um1))
     Kb.update(x, um1)
@@ -376,9 +375,9 @@ def test_derivatives_after_a_step_are_those_of_the_u_prev_the_step_was_solved_wi
     rdu = 2 * N * nx + Ka.Nc * nu
     assert np.all(np.any(rb['u'][:, rdu:rdu + nu] != 0.0, axis=1))             # ... among the first Delta-u rows, whose bounds carry u_{-1}
     for k in ('K_x0', 'K_um1', 'K_xref', 'K_uref'):
-        assert _rel(Ga[k], Gb[k]) <= TOL, (k, _rel(Ga[k], Gb[k]))
+        assert rel1_any(Ga[k], Gb[k]) <= TOL, (k, rel1_any(Ga[k], Gb[k]))
     for k in ('l', 'u') + MODEL:      # (r_w, r_y depend on the active set alone; the model gradients also on the iterates, two solves at eps 1e-9)
-        assert _rel(ra[k], rb[k]) <= (1e-6 if k in MODEL else TOL), (k, _rel(ra[k], rb[k]))
+        assert rel1_any(ra[k], rb[k]) <= (1e-6 if k in MODEL else TOL), (k, rel1_any(ra[k], rb[k]))
     assert np.array_equal(ra['l'] != 0.0, rb['l'] != 0.0) and np.array_equal(ra['u'] != 0.0, rb['u'] != 0.0)
     # the step data themselves still hold the applied input for the next step
     assert np.abs(np.array(Ka.step(x * 0.9)) - np.array(Kb.step(x * 0.9, ua))).max() <= 1e-7
@@ -387,10 +386,9 @@ def test_derivatives_after_a_step_are_those_of_the_u_prev_the_step_was_solved_wi
 def test_derivatives_after_a_device_loop_are_those_of_its_last_solve():
     """run() ends as the host loop does, with update(x, u) and a solve: the step data it leaves are the ones the iterate was solved with, so
     the calls after it agree with a twin stepped from the host."""
-    from test_gpu_adjoint import _rel
     B = 3
     kw, _, _, w = _step_inputs('small_mimo', B)
-    Ka, Kb = _copies(kw, B), _copies(kw, B)
+    Ka, Kb = copies(kw, B), copies(kw, B)
     Ka.setup(); Kb.setup()
     tr = Ka.run(2)
     x = np.stack([kw['x0']] * B)
@@ -402,11 +400,11 @@ def test_derivatives_after_a_device_loop_are_those_of_its_last_solve():
     Ga, Gb = Ka.gains(), Kb.gains()
     assert np.array_equal(Ka.prob.adjoint_info()[0], Kb.prob.adjoint_info()[0])
     for k in ('K_x0', 'K_um1', 'K_xref', 'K_uref'):
-        assert _rel(Ga[k], Gb[k]) <= TOL, (k, _rel(Ga[k], Gb[k]))
+        assert rel1_any(Ga[k], Gb[k]) <= TOL, (k, rel1_any(Ga[k], Gb[k]))
     ra, rb = (K.prob.adjoint(g_u0=w, want=('l', 'u') + MODEL) for K in (Ka, Kb))
     assert np.array_equal(ra['l'] != 0.0, rb['l'] != 0.0) and np.array_equal(ra['u'] != 0.0, rb['u'] != 0.0)
     for k in MODEL:                       # (they carry the iterates of two solves at eps 1e-9 and u_{-1}: QDu would show a moved one)
-        assert _rel(ra[k], rb[k]) <= 1e-6, (k, _rel(ra[k], rb[k]))
+        assert rel1_any(ra[k], rb[k]) <= 1e-6, (k, rel1_any(ra[k], rb[k]))
     assert np.abs(rb['QDu']).max() > 0.0
 
 

@@ -4,35 +4,25 @@ with a held input at 32-wide stages, the fallback to one seed at a time where fo
 grouped-eligible long shape with two inputs, an unsolved instance inside a column batch -- against the numpy restatement
 (tests/adjoint_ref.py) on the device's own iterate and scaling, the column code against the single-vector code on the same factor, and
 without side effects on the wide layouts.  One BatchMPCController per case, its seeds the instances: different models and active sets
-in one launch.  Tolerance, settings and helpers are those of tests/test_gpu_adjoint.py."""
+in one launch.  Tolerance, settings and helpers are those of tests/test_gpu_adjoint.py (they live in tests/adjoint_cases.py)."""
 import functools
-import warnings
 
 import numpy as np
 import pytest
 
 import adjoint_cases as ac
 import adjoint_ref as ar
-from test_gpu_adjoint import TOL, EPS, RAW, CHAINED, _rel, _device_state, _snapshot, _same
+from adjoint_cases import TOL, EPS, RAW, CHAINED, device_state, snapshot, same, case_batch
+from util import rel1_any
 
 pytestmark = pytest.mark.gpu
 GAINS = (('x0', 'K_x0'), ('uminus1', 'K_um1'), ('xref', 'K_xref'), ('uref', 'K_uref'))
 
 
-def _batch(name, seeds=None, backend=None):
-    from pympc_amd import BatchMPCController
-    from pympc_amd.solver import forced_settings
-    K = BatchMPCController(**ac.batch_kwargs(name, seeds, eps_abs=EPS, eps_rel=EPS, max_iter=400000))
-    with warnings.catch_warnings(), forced_settings(**({'backend': backend} if backend else {})):
-        warnings.simplefilter('ignore')
-        K.setup()
-    return K
-
-
 @functools.lru_cache(maxsize=None)
 def _solved(name, backend=None):
     """The case's batch, solved, and what both calls return on it (computed once, read-only afterwards)."""
-    K = _batch(name, backend=backend)
+    K = case_batch(name, backend=backend)
     assert all(s == 'solved' for s in K.status()), (name, K.status())
     bp = K.prob
     g = np.random.default_rng(7).standard_normal((bp.batch, bp.n))
@@ -63,7 +53,7 @@ def test_adjoint_and_gains_are_the_restatement(name):
     bp, case = K.prob, ac.CASES[name]
     errs = {}
     for b, seed in enumerate(case['seeds']):
-        st = _device_state(bp, b)
+        st = device_state(bp, b)
         maps = _maps(name, seed)
         ref = ar.adjoint(*st, g[b], maps)
         assert status[b] == 1 and nweak[b] == 0 and ref['n_weak'] == 0, (name, seed, status[b], nweak[b], ref['n_weak'])
@@ -74,11 +64,11 @@ def test_adjoint_and_gains_are_the_restatement(name):
         assert np.array_equal(got['l'][b] != 0.0, olow) and np.array_equal(got['u'][b] != 0.0, oupp), (name, seed)
         assert np.all(got['l'][b][~ref['low']] == 0.0) and np.all(got['u'][b][~ref['upp']] == 0.0), (name, seed)
         for k in CHAINED + RAW:
-            errs[k] = max(errs.get(k, 0.0), _rel(got[k][b], ref['d_' + k if k in RAW else k]))
+            errs[k] = max(errs.get(k, 0.0), rel1_any(got[k][b], ref['d_' + k if k in RAW else k]))
         Kref = ar.gains(*st, maps, (bp.Np + 1) * bp.nx, bp.nu)
         assert status2[b] == 1 and nweak2[b] == 0 and nact2[b] == Kref['n_active'], (name, seed)
         for k, kk in GAINS:
-            errs[kk] = max(errs.get(kk, 0.0), _rel(Kgot[k][b], Kref[kk]))
+            errs[kk] = max(errs.get(kk, 0.0), rel1_any(Kgot[k][b], Kref[kk]))
     worst = max(errs.values())
     print('ADJOINT_ERR %s: max %.3e  %s' % (name, worst, ' '.join('%s=%.1e' % kv for kv in errs.items())))
     assert worst <= TOL, (name, errs)
@@ -96,7 +86,7 @@ def test_gain_rows_are_the_adjoint_of_unit_seeds(name):
         assert np.all(bp.adjoint_info()[2] == 1), (name, j)
         for k in CHAINED:
             for b in range(bp.batch):
-                worst = max(worst, _rel(Kgot[k][b, j], one[k][b]))
+                worst = max(worst, rel1_any(Kgot[k][b, j], one[k][b]))
     print('ADJOINT_ROWS %s: largest difference between a gain row and adjoint(g_u0 = e_j) %.3e' % (name, worst))
     assert worst <= TOL, (name, worst)
 
@@ -105,7 +95,7 @@ def test_gain_rows_are_the_adjoint_of_unit_seeds(name):
 def test_unsolved_neighbour_in_a_column_batch():
     name, bad = ac.INFEASIBLE
     s = ac.CASES[name]['seeds']
-    Ka, Kb = _batch(name, (s[0], s[1], bad, s[2])), _batch(name, (s[0], s[1], s[2]))
+    Ka, Kb = case_batch(name, (s[0], s[1], bad, s[2])), case_batch(name, (s[0], s[1], s[2]))
     assert Ka.status() == ['solved', 'solved', 'primal infeasible', 'solved'], Ka.status()
     assert Kb.status() == ['solved'] * 3
     ga = np.random.default_rng(7).standard_normal((4, Ka.prob.n))
@@ -128,21 +118,21 @@ def test_unsolved_neighbour_in_a_column_batch():
 # ---- 4. no side effects on the wide layouts -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('name', ['nb64_nu6', 'nb128_nu5'])
 def test_wide_layouts_are_left_as_they_were(name):
-    Ka, Kb = _batch(name), _batch(name)
+    Ka, Kb = case_batch(name), case_batch(name)
     bp = Ka.prob
     rhs = np.random.default_rng(0).standard_normal((bp.batch, bp.n))
-    before, snap = bp.kkt_solve(rhs), _snapshot(bp)
-    assert _same(snap, _snapshot(Kb.prob))
+    before, snap = bp.kkt_solve(rhs), snapshot(bp)
+    assert same(snap, snapshot(Kb.prob))
     g = np.random.default_rng(3).standard_normal((bp.batch, bp.n))
     bp.adjoint(g_w=g, g_u0=np.ones((bp.batch, bp.nu)), want=CHAINED + RAW)
     assert np.all(Ka.gains()['status'] == 1)
     assert np.array_equal(before, bp.kkt_solve(rhs))                  # the handle's own factor is untouched
-    assert _same(snap, _snapshot(bp))
+    assert same(snap, snapshot(bp))
     # the next update and solve, against the twin that never took an adjoint
     x1 = np.asarray(Ka.x0) * 0.9
     for K in (Ka, Kb):
         K.update(x1)
-    assert _same(_snapshot(Ka.prob), _snapshot(Kb.prob))
+    assert same(snapshot(Ka.prob), snapshot(Kb.prob))
     assert np.array_equal(Ka.prob.kkt_solve(rhs), Kb.prob.kkt_solve(rhs))
 
 
@@ -156,6 +146,6 @@ def test_forced_sweeps_backend_gives_the_same(name):
     assert np.all(infos[2] == 1) and np.all(infos[1] == 0)
     for k in ('l', 'u'):
         assert np.array_equal(got[k] != 0.0, gots[k] != 0.0), k      # the same active masks
-    worst = max([_rel(gots[k], got[k]) for k in CHAINED + RAW] + [_rel(Kgots[k], Kgot[k]) for k in CHAINED])
+    worst = max([rel1_any(gots[k], got[k]) for k in CHAINED + RAW] + [rel1_any(Kgots[k], Kgot[k]) for k in CHAINED])
     print('ADJOINT_SWEEPS %s: largest difference to the automatic backend %.3e' % (name, worst))
     assert worst <= TOL, (name, worst)

@@ -8,43 +8,19 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from util import golden_names, load_golden, golden_kwargs, golden_csc, apply_attrs
+from util import golden_names, load_golden, golden_kwargs, golden_csc, controller, rel, stacked_batch, golden_dense_eligible, golden_bcr_schedule
+from util import forced as backend      # (one test here has a local called forced)
 
 pytestmark = pytest.mark.gpu
 
 
-def backend(**forced):
-    """Every controller built inside the block gets these mpcqp_settings fields (the KKT backend, include/mpcqp.h: enum mpcqp_backend)."""
-    from pympc_amd.solver import forced_settings
-    return forced_settings(**forced)
-
-
-def _dense_eligible(name):
-    g = load_golden(name)
-    kw = golden_kwargs(g)
-    nx, nu = np.atleast_2d(kw['Bd']).shape if np.ndim(kw['Bd']) == 2 else (np.asarray(kw['Ad']).shape[0], 1)
-    Np = kw['Np']
-    return (Np + 1) * (nx + nu) <= 128 and kw.get('Nc', Np) in (None, Np)
-
-
-def _bcr_schedule(name):
-    """Stage count of the cyclic-reduction schedule mpcqp_create gives the fixture (11, 21 or 31 >= Np + 1), or 0: 16 x 16 stages,
-    no held input, at most 31 stages."""
-    kw = golden_kwargs(load_golden(name))
-    nx, nu = np.atleast_2d(kw['Bd']).shape if np.ndim(kw['Bd']) == 2 else (np.asarray(kw['Ad']).shape[0], 1)
-    Np = kw['Np']
-    if nx + nu > 16 or kw.get('Nc', Np) not in (None, Np) or Np + 1 > 31:
-        return 0
-    return 11 if Np + 1 <= 11 else 21 if Np + 1 <= 21 else 31
-
-
-SMALL = [n for n in golden_names() if _dense_eligible(n)]
+SMALL = [n for n in golden_names() if golden_dense_eligible(n)]
 SWEEPS, DENSE, BCR, BCR8 = dict(backend='sweeps'), dict(backend='dense'), dict(backend='bcr'), dict(backend='bcr8')
 BACKENDS = [SWEEPS, DENSE]
 IDS = ['sweeps', 'dense']
 # block cyclic reduction (register-resident factor): any fixture with 16 x 16 stages, Nc = Np and at most 31 stages -- the BASELINE shape (12, 4, 30) with
 # compile-time dimensions, everything else (the reference's examples, the quadcopter, soft and hard state boxes) through the generic instantiations
-BCR_NAMES = [n for n in golden_names() if _bcr_schedule(n)]
+BCR_NAMES = [n for n in golden_names() if golden_bcr_schedule(n)]
 # ... and, for the same fixtures, the dense-top factor (mpcqp_latw.h) on 512-thread workgroups ('bcr8': what mpcqp_create picks for at most one
 # instance per compute unit) and on 256-thread ones ('bcrt')
 CASES = ([(n, e, i) for n in SMALL for e, i in zip(BACKENDS, IDS)] + [(n, SWEEPS, 'sweeps') for n in BCR_NAMES if n not in SMALL] + [(n, BCR, 'bcr') for n in BCR_NAMES]
@@ -52,32 +28,18 @@ CASES = ([(n, e, i) for n in SMALL for e, i in zip(BACKENDS, IDS)] + [(n, SWEEPS
 CASE_IDS = ['%s-%s' % (n, i) for n, e, i in CASES]
 
 
-def _ctrl(kw, oracle=False, **settings):
-    from pympc_amd import MPCController
-    K = apply_attrs(MPCController(**kw), kw)
-    if oracle:
-        from oracle.osqp_oracle import OSQP
-        K.prob = OSQP()
-    K.solver_settings = dict(settings)
-    return K
-
-
-def _rel(a, b):
-    return np.abs(a - b).max() / max(1e-300, np.abs(b).max())
-
-
 def test_some_fixture_is_small_enough():
     assert len(SMALL) >= 2, SMALL
-    assert {_bcr_schedule(n) for n in BCR_NAMES} == {11, 21, 31}, BCR_NAMES          # every schedule is exercised
+    assert {golden_bcr_schedule(n) for n in BCR_NAMES} == {11, 21, 31}, BCR_NAMES          # every schedule is exercised
 
 
 @pytest.mark.parametrize('name,env,tag', CASES, ids=CASE_IDS)
 def test_backend_is_the_one_asked_for(name, env, tag):
     with backend(**env):
-        K = _ctrl(golden_kwargs(load_golden(name))); K.setup(solve=False)
+        K = controller(golden_kwargs(load_golden(name))); K.setup(solve=False)
         kn = K.prob.batch_problem.kernel_name(loop=False)
-    assert kn.split(',')[4] == {'sweeps': '0', 'dense': '2', 'bcr': str(100 + _bcr_schedule(name)), 'bcr8': str(200 + _bcr_schedule(name)),
-                                'bcrt': str(200 + _bcr_schedule(name))}[tag], kn
+    assert kn.split(',')[4] == {'sweeps': '0', 'dense': '2', 'bcr': str(100 + golden_bcr_schedule(name)), 'bcr8': str(200 + golden_bcr_schedule(name)),
+                                'bcrt': str(200 + golden_bcr_schedule(name))}[tag], kn
     assert kn.startswith('w8::') == (tag == 'bcr8'), kn                     # the 512-thread kernels live in the second translation unit
 
 
@@ -85,7 +47,7 @@ def test_backend_is_the_one_asked_for(name, env, tag):
 def test_kkt_solve_matches_dense_numpy(name, env, tag):
     g = load_golden(name)
     with backend(**env):
-        K = _ctrl(golden_kwargs(g)); K.setup(solve=False)
+        K = controller(golden_kwargs(g)); K.setup(solve=False)
         bp = K.prob.batch_problem
         D, E, c, rho = bp.scaling()
         U = sp.triu(golden_csc(g, 'P')).toarray(); P = U + np.triu(U, 1).T
@@ -98,7 +60,7 @@ def test_kkt_solve_matches_dense_numpy(name, env, tag):
         for _ in range(3):
             rhs = rng.standard_normal(P.shape[0])
             sol = bp.kkt_solve(rhs[None])[0]
-            assert _rel(sol, np.linalg.solve(Kmat, rhs)) < 1e-8
+            assert rel(sol, np.linalg.solve(Kmat, rhs)) < 1e-8
 
 
 @pytest.mark.parametrize('iters', [1, 7, 40])
@@ -106,13 +68,13 @@ def test_kkt_solve_matches_dense_numpy(name, env, tag):
 def test_admm_iterates_match_oracle(name, env, tag, iters):
     kw = golden_kwargs(load_golden(name))
     with backend(**env):
-        K = _ctrl(kw); K.setup(solve=False)
+        K = controller(kw); K.setup(solve=False)
         K.prob.batch_problem.iterate(iters)
         x, z, y = K.prob.batch_problem.iterate_state()
-    Ko = _ctrl(kw, oracle=True); Ko.setup(solve=False)
+    Ko = controller(kw, oracle=True); Ko.setup(solve=False)
     Ko.prob.iterate(iters)
     xo, zo, yo, _ = Ko.prob.iterate_state()
-    assert _rel(x[0], xo) < 1e-8 and _rel(z[0], zo) < 1e-8
+    assert rel(x[0], xo) < 1e-8 and rel(z[0], zo) < 1e-8
     assert np.abs(y[0] - yo).max() < 1e-8 * max(1.0, np.abs(yo).max())
 
 
@@ -123,13 +85,13 @@ def test_default_tolerance_solve_and_optimum(name, env, tag):
     kw = golden_kwargs(g)
     with backend(**env), warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        K = _ctrl(kw); K.setup()
-        Ko = _ctrl(kw, oracle=True); Ko.setup()
+        K = controller(kw); K.setup()
+        Ko = controller(kw, oracle=True); Ko.setup()
         assert K.res.info.status == Ko.res.info.status and K.res.info.iter == Ko.res.info.iter
         assert K.res.info.rho_updates == Ko.res.info.rho_updates
         kw2 = type(kw)(kw); kw2.attrs = kw.attrs
         kw2.update(eps_abs=1e-9, eps_rel=1e-9)
-        K = _ctrl(kw2, max_iter=200000); K.setup()
+        K = controller(kw2, max_iter=200000); K.setup()
         assert K.res.info.status == 'solved'
         assert np.abs(K.output() - opt['u0']).max() <= 1e-6 * max(1e-3, np.abs(opt['u0']).max())      # north-star tolerance
 
@@ -164,14 +126,12 @@ def test_held_multi_input_on_the_dense_backend_is_reproducible():
     columns used to store two differently-ordered sums to the same entry of K from two threads, so the factor -- and every iterate
     after it -- depended on which store landed last (1e-13 from handle to handle; found by scripts/fuzz_loop.py in round 4).  Two
     handles must now agree bit for bit, and the device loop with the stepwise API as everywhere else."""
-    from pympc_amd import BatchMPCController, fixtures
+    from pympc_amd import fixtures
     nx, nu, Np, Nc, B = 4, 2, 10, 3, 4
     kws = [fixtures.random_lti(53007 + i, nx=nx, nu=nu, Np=Np, xbox=4.0) for i in range(B)]
-    stack = lambda k: np.stack([np.asarray(kw[k], dtype=float) for kw in kws])
-    keys = ('x0', 'xref', 'uref', 'uminus1', 'Qx', 'QxN', 'Qu', 'QDu', 'xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')
 
     def make():
-        K = BatchMPCController(stack('Ad'), stack('Bd'), Np=Np, Nc=Nc, **{k: stack(k) for k in keys})
+        K = stacked_batch(kws, Nc=Nc, eps_feas=1e6)
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')
             K.setup()
@@ -229,7 +189,6 @@ def test_cyclic_reduction_device_loop_is_the_stepwise_api(tag):
     output() / update() bit for bit (inputs, statuses, iteration counts), and the inputs agree with the auto-selected backend's to 1e-9 at a
     tight tolerance (different elimination orders of the same KKT solve)."""
     from pympc_amd import fixtures
-    from test_gpu_parity import _stacked_batch
     B = 24
     kws = [fixtures.random_lti(1000 + i) for i in range(B)]
     w = 0.01 * np.stack([fixtures.random_lti_noise_rng(1000 + i).standard_normal((12, 12)) for i in range(B)], axis=1)      # [step][instance][nx]
@@ -238,9 +197,9 @@ def test_cyclic_reduction_device_loop_is_the_stepwise_api(tag):
     for t in (tag, 'sweeps'):
         with backend(backend=t), warnings.catch_warnings():
             warnings.simplefilter('ignore')
-            K = _stacked_batch(kws, **tight); K.setup()
+            K = stacked_batch(kws, **tight); K.setup()
             tr = K.run(12, w=w)
-            K2 = _stacked_batch(kws, **tight); K2.setup()
+            K2 = stacked_batch(kws, **tight); K2.setup()
             for k in range(12):
                 assert np.array_equal(K2.output(), tr['u'][k]), (t, k)
                 K2.update(tr['x'][k + 1])
@@ -259,7 +218,7 @@ def test_refactorization_inside_the_cyclic_reduction_kernels_reproduces_the_setu
     g = load_golden(name)
     with backend(backend=tag), warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        K = _ctrl(golden_kwargs(g)); K.setup(solve=False)
+        K = controller(golden_kwargs(g)); K.setup(solve=False)
         bp = K.prob.batch_problem
         rhs = np.random.default_rng(2).standard_normal((1, bp.n))
         s0 = bp.kkt_solve(rhs)
@@ -267,7 +226,7 @@ def test_refactorization_inside_the_cyclic_reduction_kernels_reproduces_the_setu
         s1 = bp.kkt_solve(rhs)
         assert np.isfinite(s1).all()
         assert np.abs(s0 - s1).max() <= 1e-12 * np.abs(s0).max()
-        K2 = _ctrl(golden_kwargs(g)); K2.setup()              # ... and a cold solve with its rho updates ends 'solved' with finite numbers
+        K2 = controller(golden_kwargs(g)); K2.setup()              # ... and a cold solve with its rho updates ends 'solved' with finite numbers
         assert K2.res.info.status == 'solved' and np.isfinite(K2.res.x).all()
 
 
@@ -275,9 +234,8 @@ def test_launch_times_bracket_every_step_of_the_device_loop():
     """mpcqp_get_launch_times: per instance, entry <= end of step 0 <= ... <= end of step K-1 <= exit on one clock (100 MHz), exits within the
     HIP-event duration of the launch -- what bench.py's tail split (roofline.frac_excluding_tail) is computed from."""
     from pympc_amd import fixtures
-    from test_gpu_parity import _stacked_batch
     B, K_STEPS = 40, 8
-    K = _stacked_batch([fixtures.random_lti(2000 + i) for i in range(B)]); K.setup()
+    K = stacked_batch([fixtures.random_lti(2000 + i) for i in range(B)]); K.setup()
     bp = K.prob
     bp.profile(enable=True, reset=True)
     tr = K.run(K_STEPS)

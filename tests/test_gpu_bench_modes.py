@@ -3,14 +3,13 @@ steps on the same inputs: the outputs of the last timed step (--dump-outputs) ar
 comparison against the CPU reference.  The single-controller latency workload keeps the same split (CPU oracle beside it with --full only)."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from util import run_bench
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ['--gpus', '1', '--steps', '4', '--warmup', '2', '--batch', '64']
 
 
@@ -18,11 +17,7 @@ def _bench(tmp_path, tag, *flags):
     env = dict(os.environ, MPCQP_BENCH_LEGS=str(tmp_path / (tag + '_legs.json')))
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'MPCQP_BENCH_BACKEND', 'MPCQP_BENCH_FORCE_PG'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + list(flags), env=env, capture_output=True, text=True, timeout=280)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
-    assert len(lines) == 1 and r.stdout.rstrip().splitlines()[-1] == lines[0], r.stdout[-1500:]
-    return json.loads(lines[0])
+    return run_bench(env, *flags)
 
 
 @pytest.mark.timeout(600)

@@ -9,19 +9,9 @@ import warnings
 import numpy as np
 import pytest
 
-from util import load_traj
+from util import load_traj, bench_batch
 
 pytestmark = pytest.mark.gpu
-
-
-def _bench_batch(B, nx, nu, Np, xbox, eps):
-    from pympc_amd import BatchMPCController, fixtures
-    kws = [fixtures.random_lti(i, nx=nx, nu=nu, Np=Np, xbox=xbox) for i in range(B)]
-    stack = lambda k: np.stack([np.asarray(kw[k], dtype=float) for kw in kws])
-    K = BatchMPCController(stack('Ad'), stack('Bd'), Np=Np, x0=stack('x0'), Qx=np.eye(nx), QxN=np.eye(nx), Qu=0.1 * np.eye(nu), QDu=0.1 * np.eye(nu),
-                           xmin=-xbox * np.ones(nx), xmax=xbox * np.ones(nx), umin=-np.ones(nu), umax=np.ones(nu),
-                           Dumin=-0.5 * np.ones(nu), Dumax=0.5 * np.ones(nu), eps_feas=1e6, eps_abs=eps, eps_rel=eps)
-    return K, kws
 
 
 def _oracle_u(kw, x0, um1):
@@ -44,7 +34,7 @@ def test_benchmarked_batches_meet_the_north_star_tolerance(cfg):
     1024 cfg-3 instances (what the headline throughput depends on), applied inputs to 1e-6; ALL 512 cfg-5 instances with the differences their
     ill-conditioned KKT systems produce counted and bounded (see the comment at the assertions)."""
     B, nx, nu, Np, xbox, sample, alongside = (1024, 12, 4, 30, 10.0, 128, 1024) if cfg == 'cfg3' else (512, 20, 8, 100, 1.0, 32, 512)
-    K, kws = _bench_batch(B, nx, nu, Np, xbox, 1e-3)
+    K, kws = bench_batch(B, nx, nu, Np, xbox, 1e-3)
     rng = np.random.default_rng(11)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
@@ -178,7 +168,7 @@ def test_auto_selected_latency_backend_at_per_gpu_batches_matches_oracle(B):
     from pympc_amd import MPCController
     from oracle.osqp_oracle import OSQP
     nx, nu, Np = 12, 4, 30
-    K, kws = _bench_batch(B, nx, nu, Np, 10.0, 1e-9)
+    K, kws = bench_batch(B, nx, nu, Np, 10.0, 1e-9)
     K.solver_settings = dict(max_iter=200000)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
@@ -194,7 +184,7 @@ def test_auto_selected_latency_backend_at_per_gpu_batches_matches_oracle(B):
         assert so == 'solved' and st['status'][int(i)] == 'solved', (i, so, st['status'][int(i)])
         worst = max(worst, np.abs(U[i] - uo).max() / max(1e-3, np.abs(uo).max()))
     assert worst <= 1e-6, worst
-    K2, _ = _bench_batch(B, nx, nu, Np, 10.0, 1e-3)
+    K2, _ = bench_batch(B, nx, nu, Np, 10.0, 1e-3)
     rng = np.random.default_rng(5)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from util import group_kw, forced, stacked_batch
+
 pytestmark = pytest.mark.gpu
 
 # (nx, nu, Np, Nc, soft): g = 16 // (nx + nu) stages per block -- 3, 3, 8, 3, 2, 2, 4, 5; horizons that are and are not multiples of g; held
@@ -23,26 +25,12 @@ IDS = ['%d_%d_%d_%d%s' % (s[0], s[1], s[2], s[3], '' if s[4] else '_hard') for s
 def grouping(on):
     """Controllers built inside the block run with (1) or without (0) several small stages per 16 x 16 block (mpcqp_settings.tuning)."""
     from pympc_amd import _lib
-    from pympc_amd.solver import forced_settings
-    return forced_settings(tuning=0 if on else _lib.TUNE_NO_GROUPING)
-
-
-def _kw(shape, seed=0, **more):
-    from pympc_amd import fixtures
-    nx, nu, Np, Nc, soft = shape
-    if (nx, nu) == (4, 1):
-        kw = dict(fixtures.cart_pole()); kw.update(Np=Np)                  # the notebook's plant (unstable: what makes long horizons hard)
-    else:
-        kw = dict(fixtures.random_lti(71000 + 13 * nx + nu + seed, nx=nx, nu=nu, Np=Np, xbox=4.0))
-        kw['x0'] = 0.4 * kw['x0']
-    kw.update(Nc=Nc)
-    kw.update(more)
-    return kw
+    return forced(tuning=0 if on else _lib.TUNE_NO_GROUPING)
 
 
 def _ctrl(shape, oracle=False, settings=None, **more):
     from pympc_amd import MPCController
-    K = MPCController(**_kw(shape, **more))
+    K = MPCController(**group_kw(shape, **more))
     K.SOFT_ON = shape[4]
     if oracle:
         from oracle.osqp_oracle import OSQP
@@ -122,7 +110,7 @@ def test_solves_like_the_oracle_and_like_one_stage_per_block(shape):
             assert np.abs(info['u_seq'] - Kp.output(return_u_seq=True)[1]['u_seq']).max() <= 1e-6 * scale
         else:
             assert shape[3] < shape[2], (shape, Kp.res.info.status)          # only seen with a held input
-        kw = _kw(shape)
+        kw = group_kw(shape)
         x = np.asarray(kw['Ad']) @ np.asarray(kw['x0']) + np.asarray(kw['Bd']).reshape(len(kw['x0']), -1) @ uo
         K.update(x, uo); Ko.update(x, uo)
         assert K.res.info.status == Ko.res.info.status
@@ -131,19 +119,15 @@ def test_solves_like_the_oracle_and_like_one_stage_per_block(shape):
 
 @pytest.mark.parametrize('shape', SHAPES[:5], ids=IDS[:5])
 def test_device_loop_equals_stepwise(shape):
-    from pympc_amd import BatchMPCController
     nx, nu, Np, Nc, soft = shape
     B = 3
-    kws = [_kw(shape, seed=i) for i in range(B)]
+    kws = [group_kw(shape, seed=i) for i in range(B)]
     for i, kw in enumerate(kws):
         kw['x0'] = (1.0 + 0.1 * i) * np.asarray(kw['x0'], dtype=float)
-    keys = ('x0', 'xref', 'uref', 'uminus1', 'Qx', 'QxN', 'Qu', 'QDu', 'xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')
-    stack = lambda k: np.stack([np.asarray(kw[k], dtype=float).reshape(np.asarray(kws[0][k], dtype=float).shape) for kw in kws])
-    Bd = np.stack([np.asarray(kw['Bd'], dtype=float).reshape(nx, nu) for kw in kws])
+    Bd = np.stack([np.asarray(kw['Bd'], dtype=float).reshape(nx, nu) for kw in kws])      # (the cart pole's Bd is 1-D)
 
     def make():
-        K = BatchMPCController(stack('Ad'), Bd, Np=Np, Nc=Nc, eps_feas=np.array([[kw.get('eps_feas', 1e6)] for kw in kws]), SOFT_ON=soft,
-                               **{k: stack(k) for k in keys})
+        K = stacked_batch(kws, Bd=Bd, Nc=Nc, SOFT_ON=soft)
         K.setup()
         return K
     with warnings.catch_warnings():

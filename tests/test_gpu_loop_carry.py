@@ -4,67 +4,12 @@ owner registers -- without leaving the function.  MPCQP_TUNE_NO_CARRY leaves the
 path every step took before.  The two must agree bit for bit: trajectories, statuses, iteration counts, the handle's final iterate and record.
 Run on the GPU box with:  python -m pytest tests -m gpu
 """
-import warnings
-
 import numpy as np
 import pytest
 
+from util import carry_on_and_off
+
 pytestmark = pytest.mark.gpu
-
-
-def _stacked_batch(kws, **kw):
-    from pympc_amd import BatchMPCController
-    stack = lambda k: np.stack([np.asarray(d[k], dtype=float) for d in kws])
-    k0 = kws[0]
-    nu = k0['Bd'].shape[1]
-    uref = stack('uref') if 'uref' in k0 else np.zeros((len(kws), nu))
-    args = dict(Np=k0['Np'], Nc=k0.get('Nc'), x0=stack('x0'), xref=stack('xref'), uref=uref,
-                uminus1=stack('uminus1') if 'uminus1' in k0 else uref,
-                Qx=stack('Qx'), QxN=stack('QxN') if 'QxN' in k0 else stack('Qx'), Qu=stack('Qu'), QDu=stack('QDu'),
-                xmin=stack('xmin'), xmax=stack('xmax'), umin=stack('umin'), umax=stack('umax'), Dumin=stack('Dumin'), Dumax=stack('Dumax'),
-                eps_feas=np.array([[d.get('eps_feas', 1e6)] for d in kws]))
-    args.update(kw)
-    return BatchMPCController(stack('Ad'), stack('Bd'), **args)
-
-
-def _info_tuple(infos):
-    return np.array([(i.status, i.iter, i.rho_updates, i.obj_val, i.pri_res, i.dua_res, i.rho) for i in infos], dtype=float)
-
-
-def _both(kws, steps, nruns=1, w=None, expect_latency=True, run_kw=None, **kw):
-    """The same closed loop with and without the carry: every array it produces must agree, and so must the launch structure (queue-item parts
-    of a persistent launch).  Returns the arrays and the carry counters (carried, handed back, parts) of the run with the carry."""
-    from pympc_amd import _lib
-    from pympc_amd.solver import forced_settings
-    out, cs = [], []
-    for tuning in (0, _lib.TUNE_NO_CARRY):
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore')
-            with forced_settings(tuning=tuning):          # (the handle, and with it its settings, is made by setup())
-                K = _stacked_batch(kws, **kw)
-                K.setup()
-            if expect_latency:
-                assert '231' in K.prob.kernel_name(True).replace(' ', ''), K.prob.kernel_name(True)
-            res = []
-            for i in range(nruns):
-                rk = dict(run_kw(i)) if run_kw else {}
-                if w is not None:
-                    rk['w'] = w[steps * i:steps * (i + 1)]
-                res.append(K.run(steps, **rk))
-        arrs = {k: np.concatenate([r[k] for r in res]) for k in res[0]}
-        x, y, _ = K.prob.solution()
-        arrs['sol_x'], arrs['sol_y'] = x, y
-        arrs['info'] = _info_tuple(K.prob.infos())
-        arrs['output'] = K.output()
-        out.append(arrs)
-        cs.append(K.prob.carry_stats())
-    a, b = out
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert np.array_equal(a[k], b[k], equal_nan=True), k
-    assert cs[1][:2] == (0, 0), cs                        # (MPCQP_TUNE_NO_CARRY: the round never carries)
-    assert cs[0][2] == cs[1][2], cs                       # (... and the launch is cut into the same parts)
-    return a, cs[0]
 
 
 def test_carry_headline_batch_persistent_queue():
@@ -73,7 +18,7 @@ def test_carry_headline_batch_persistent_queue():
     B, steps = 1024, 20
     kws = [fixtures.random_lti(i) for i in range(B)]
     w = 0.01 * np.random.default_rng(3).standard_normal((steps, B, 12))
-    a, (carried, back, parts) = _both(kws, steps, w=w)
+    a, (carried, back, parts) = carry_on_and_off(kws, steps, w=w)
     assert (a['status'] == 1).mean() > 0.9
     assert parts == 4                                     # (8 / 6 / 4 / 2 steps: 256 resident slots, 16 items each)
     assert carried > 0.5 * B * (steps - parts) and back == 0, (carried, back)
@@ -84,7 +29,7 @@ def test_carry_small_batch_two_launches():
     from pympc_amd import fixtures
     kws = [fixtures.random_lti(300 + i) for i in range(7)]
     w = 0.01 * np.random.default_rng(4).standard_normal((18, 7, 12))
-    _, (carried, back, parts) = _both(kws, 9, nruns=2, w=w)
+    _, (carried, back, parts) = carry_on_and_off(kws, 9, nruns=2, w=w)
     assert parts == 0 and carried > 0 and back == 0, (carried, back, parts)
 
 
@@ -94,7 +39,7 @@ def test_carry_falls_back_at_iteration_limit():
     kws = [fixtures.random_lti(500 + i) for i in range(7)]
     for kw in kws:
         kw['uref'] = np.array([0.05, -0.02, 0.01, 0.03])
-    a, (carried, back, _) = _both(kws, 6, max_iter=30)
+    a, (carried, back, _) = carry_on_and_off(kws, 6, max_iter=30)
     assert (a['status'] != 1).any()
     assert carried <= (a['status'][:-1] == 1).sum() and back == 0      # (only a step after a solved one can be carried into)
 
@@ -104,7 +49,7 @@ def test_carry_with_rho_updates_mid_solve():
     from pympc_amd import fixtures
     kws = [fixtures.random_lti(700 + i) for i in range(7)]
     w = 0.01 * np.random.default_rng(5).standard_normal((8, 7, 12))
-    a, (carried, back, _) = _both(kws, 8, w=w, eps_abs=1e-9, eps_rel=1e-9, max_iter=20000)
+    a, (carried, back, _) = carry_on_and_off(kws, 8, w=w, eps_abs=1e-9, eps_rel=1e-9, max_iter=20000)
     assert (a['status'] == 1).all()
     assert carried > 0 and back == 0
 
@@ -115,7 +60,7 @@ def test_carry_around_an_infeasible_step():
     kws = [fixtures.random_lti(600 + i) for i in range(7)]
     kws[1]['uminus1'] = np.array([5.0, 0.0, 0.0, 0.0])
     kws[4]['uminus1'] = np.array([0.0, -7.0, 0.0, 0.0])
-    a, (carried, _, _) = _both(kws, 6)
+    a, (carried, _, _) = carry_on_and_off(kws, 6)
     assert carried > 0
     assert np.array_equal(a['u'][0, 1], kws[1]['uref']) and np.array_equal(a['u'][0, 4], kws[4]['uref'])      # (u_failure after setup's solve)
 
@@ -126,7 +71,7 @@ def test_carry_off_with_a_moving_reference():
     B, steps = 7, 6
     kws = [fixtures.random_lti(800 + i) for i in range(B)]
     xref = np.zeros((steps, B, 12)); xref[:, :, 0] = 0.05 * np.arange(steps)[:, None]
-    _, (carried, _, _) = _both(kws, steps, run_kw=lambda i: dict(xref_traj=xref))
+    _, (carried, _, _) = carry_on_and_off(kws, steps, run_kw=lambda i: dict(xref_traj=xref))
     assert carried == 0
 
 
@@ -143,7 +88,7 @@ def test_carry_off_with_output_feedback():
 
     def run_kw(i):
         return dict(estimator=BatchLinearStateEstimator(st('x0'), st('Ad'), st('Bd'), C, Lg, x_true=st('x0').copy(), v=v))
-    _, (carried, _, _) = _both(kws, steps, run_kw=run_kw)
+    _, (carried, _, _) = carry_on_and_off(kws, steps, run_kw=run_kw)
     assert carried == 0
 
 
@@ -156,6 +101,6 @@ def test_carry_hands_back_when_a_row_type_changes():
     kws = [fixtures.random_lti(1100 + i) for i in range(B)]
     w = 0.01 * np.random.default_rng(7).standard_normal((steps, B, 12))
     w[3, 2, 0] = np.nan
-    a, (carried, back, _) = _both(kws, steps, w=w, max_iter=2000)
+    a, (carried, back, _) = carry_on_and_off(kws, steps, w=w, max_iter=2000)
     assert back >= 1 and carried > back, (carried, back)
     assert np.isnan(a['x'][4, 2]).any() and np.isfinite(a['x'][:, [0, 1, 3, 4, 5, 6]]).all()

@@ -12,30 +12,9 @@ import warnings
 import numpy as np
 import pytest
 
-from util import load_traj, load_golden, golden_kwargs, kkt_certificate
+from util import load_traj, load_golden, golden_kwargs, kkt_certificate, stacked_batch, complete
 
 pytestmark = pytest.mark.gpu
-
-
-def _stacked_batch(kws, **kw):
-    from pympc_amd import BatchMPCController
-    stack = lambda k: np.stack([np.asarray(d[k], dtype=float) for d in kws])
-    k0 = kws[0]
-    args = dict(Np=k0['Np'], Nc=k0.get('Nc'), x0=stack('x0'), xref=stack('xref'), uref=stack('uref'), uminus1=stack('uminus1'),
-                Qx=stack('Qx'), QxN=stack('QxN'), Qu=stack('Qu'), QDu=stack('QDu'), xmin=stack('xmin'), xmax=stack('xmax'),
-                umin=stack('umin'), umax=stack('umax'), Dumin=stack('Dumin'), Dumax=stack('Dumax'),
-                eps_feas=np.array([[d.get('eps_feas', 1e6)] for d in kws]))
-    args.update(kw)
-    return BatchMPCController(stack('Ad'), stack('Bd'), **args)
-
-
-def _complete(kw):
-    """Fixture dict with every optional controller argument spelled out (what the stacked constructor wants)."""
-    kw = dict(kw)
-    nx, nu = kw['Ad'].shape[0], kw['Bd'].shape[1]
-    kw.setdefault('uref', np.zeros(nu)); kw.setdefault('xref', np.zeros(nx)); kw.setdefault('uminus1', kw['uref'])
-    kw.setdefault('QxN', kw['Qx'])
-    return kw
 
 
 # ---- (a) the reference class's own closed loops, linear plants -------------------------------------------------------
@@ -48,9 +27,9 @@ def test_device_loop_follows_reference_class_trajectories(name):
     input / state range in every step (north-star criterion), the states being the device's own, not the golden ones."""
     from pympc_amd import fixtures
     g = load_traj(name)
-    kw = _complete(fixtures.NAMED[str(g['fixture'])]())
+    kw = complete(fixtures.NAMED[str(g['fixture'])]())
     xs, us = g['x'], g['u']
-    K = _stacked_batch([kw, kw], eps_abs=1e-10, eps_rel=1e-10, max_iter=400000)
+    K = stacked_batch([kw, kw], eps_abs=1e-10, eps_rel=1e-10, max_iter=400000)
     K.setup()
     assert all(s == 'solved' for s in K.status())
     tr = K.run(len(us))
@@ -60,7 +39,7 @@ def test_device_loop_follows_reference_class_trajectories(name):
         assert np.abs(tr['u'][:, b] - us).max() <= 1e-6 * su, (name, np.abs(tr['u'][:, b] - us).max(axis=1).argmax())
         assert np.abs(tr['x'][:, b] - xs).max() <= 1e-6 * sx
     # chained launches (what bench.py does) visit the same trajectory
-    K2 = _stacked_batch([kw], eps_abs=1e-10, eps_rel=1e-10, max_iter=400000); K2.setup()
+    K2 = stacked_batch([kw], eps_abs=1e-10, eps_rel=1e-10, max_iter=400000); K2.setup()
     parts = [K2.run(5) for _ in range(len(us) // 5)]
     uc = np.concatenate([p['u'][:, 0] for p in parts])
     assert np.abs(uc - us[:len(uc)]).max() <= 1e-6 * su
@@ -76,10 +55,10 @@ def test_device_loop_matches_oracle_closed_loop(dims):
     from oracle.osqp_oracle import OSQP
     nx, nu, Np, B, K_STEPS = dims
     xbox = 10.0 if nx == 12 else 1.0
-    kws = [_complete(fixtures.random_lti(50 + i, nx=nx, nu=nu, Np=Np, xbox=xbox)) for i in range(B)]
+    kws = [complete(fixtures.random_lti(50 + i, nx=nx, nu=nu, Np=Np, xbox=xbox)) for i in range(B)]
     rng = np.random.default_rng(21)
     w = 0.01 * rng.standard_normal((K_STEPS, B, nx))
-    Kd = _stacked_batch(kws, eps_abs=1e-9, eps_rel=1e-9, max_iter=400000); Kd.setup()
+    Kd = stacked_batch(kws, eps_abs=1e-9, eps_rel=1e-9, max_iter=400000); Kd.setup()
     tr = Kd.run(K_STEPS, w=w)
     assert (tr['status'] == 1).all()
     for b, kw in enumerate(kws):
@@ -103,10 +82,10 @@ def test_device_loop_default_tolerance_iterates_like_oracle():
     from pympc_amd import MPCController, fixtures
     from oracle.osqp_oracle import OSQP
     B, K_STEPS = 4, 10
-    kws = [_complete(fixtures.random_lti(60 + i)) for i in range(B)]
+    kws = [complete(fixtures.random_lti(60 + i)) for i in range(B)]
     rng = np.random.default_rng(22)
     w = 0.01 * rng.standard_normal((K_STEPS, B, 12))
-    Kd = _stacked_batch(kws); Kd.setup()
+    Kd = stacked_batch(kws); Kd.setup()
     tr = Kd.run(K_STEPS, w=w)
     for b, kw in enumerate(kws):
         Ko = MPCController(**kw); Ko.prob = OSQP()
@@ -128,13 +107,13 @@ def test_device_loop_output_feedback_follows_reference_classes(name):
     from pympc_amd import fixtures
     from pympc_amd.kalman import BatchLinearStateEstimator
     g = load_traj(name)
-    kw = _complete(fixtures.NAMED[str(g['fixture'])]())
+    kw = complete(fixtures.NAMED[str(g['fixture'])]())
     us, xs, xh = g['u'], g['x'], g['xhat']
     K_STEPS = len(us)
     st = lambda M: np.asarray(M, dtype=float)[None]
     est = BatchLinearStateEstimator(st(kw['x0']), st(kw['Ad']), st(kw['Bd']), st(g['C']), st(g['L']),
                                     x_true=st(g['x_true0']).copy(), v=g['v'][:, None, :])
-    K = _stacked_batch([kw], eps_abs=1e-10, eps_rel=1e-10, max_iter=400000); K.setup()
+    K = stacked_batch([kw], eps_abs=1e-10, eps_rel=1e-10, max_iter=400000); K.setup()
     tr = K.run(K_STEPS, w=g['w'][:, None, :], estimator=est)
     assert (tr['status'] == 1).all()
     assert np.abs(tr['u'][:, 0] - us).max() <= 1e-6 * max(1e-3, np.abs(us).max())
@@ -154,8 +133,8 @@ def test_cfg5_full_size_batch_properties():
     # bench.py's instances 0..511, except 276 (replaced by 512): cold-started at eps 1e-8, OSQP's adaptive-rho rule
     # oscillates on it for ever -- in the CPU oracle exactly as on the GPU (both 'maximum iterations reached' after 400000
     # iterations and ~845 rho updates; 143 s on the CPU, too slow to repeat here).  At the bench tolerance it solves.
-    kws = [_complete(fixtures.random_lti(i if i != 276 else 512, nx=nx, nu=nu, Np=Np, xbox=1.0)) for i in range(B)]
-    K = _stacked_batch(kws, eps_abs=1e-8, eps_rel=1e-8, max_iter=400000)
+    kws = [complete(fixtures.random_lti(i if i != 276 else 512, nx=nx, nu=nu, Np=Np, xbox=1.0)) for i in range(B)]
+    K = stacked_batch(kws, eps_abs=1e-8, eps_rel=1e-8, max_iter=400000)
     K.setup()
     U, info = K.output(return_status=True, return_x_seq=True, return_u_seq=True, return_eps_seq=True)
     assert all(s == 'solved' for s in info['status']), [(i, s) for i, s in enumerate(info['status']) if s != 'solved']

@@ -11,27 +11,12 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from util import golden_names, load_golden, golden_kwargs, golden_csc, update_steps, apply_attrs
+from util import (golden_names, load_golden, golden_kwargs, golden_csc, update_steps, gpu_controller, oracle_controller, rel,
+                  stacked_batch, random_case)
 
 pytestmark = pytest.mark.gpu
 
 DEVICE_FIXTURES = golden_names()
-
-
-def _gpu_controller(kw, **settings):
-    from pympc_amd import MPCController
-    K = apply_attrs(MPCController(**kw), kw)
-    K.solver_settings = dict(settings)
-    return K
-
-
-def _oracle_controller(kw, **settings):
-    from pympc_amd import MPCController
-    from oracle.osqp_oracle import OSQP
-    K = apply_attrs(MPCController(**kw), kw)
-    K.prob = OSQP()
-    K.solver_settings = dict(settings)
-    return K
 
 
 def _eff(P):
@@ -44,14 +29,10 @@ def _clip(v):
     return np.clip(v, -1e30, 1e30)
 
 
-def _rel(a, b):
-    return np.abs(a - b).max() / max(1e-300, np.abs(b).max())
-
-
 @pytest.mark.parametrize('name', DEVICE_FIXTURES)
 def test_device_built_qp_matches_reference(name):
     g = load_golden(name)
-    K = _gpu_controller(golden_kwargs(g))
+    K = gpu_controller(golden_kwargs(g))
     K.setup(solve=False)
     bp = K.prob.batch_problem
     P, q, A, l, u = bp.export_qp()
@@ -73,18 +54,18 @@ def test_device_built_qp_matches_reference(name):
 def test_equilibration_matches_oracle(name):
     g = load_golden(name)
     kw = golden_kwargs(g)
-    K = _gpu_controller(kw); K.setup(solve=False)
-    Ko = _oracle_controller(kw); Ko.setup(solve=False)
+    K = gpu_controller(kw); K.setup(solve=False)
+    Ko = oracle_controller(kw); Ko.setup(solve=False)
     D, E, c, rho = K.prob.batch_problem.scaling()
     Do, Eo, co = Ko.prob.scaling()
-    assert _rel(D[0], Do) < 1e-12 and _rel(E[0], Eo) < 1e-12 and abs(c[0] - co) / co < 1e-12
+    assert rel(D[0], Do) < 1e-12 and rel(E[0], Eo) < 1e-12 and abs(c[0] - co) / co < 1e-12
     assert rho[0] == 0.1
 
 
 @pytest.mark.parametrize('name', DEVICE_FIXTURES)
 def test_kkt_solve_matches_dense(name):
     g = load_golden(name)
-    K = _gpu_controller(golden_kwargs(g)); K.setup(solve=False)
+    K = gpu_controller(golden_kwargs(g)); K.setup(solve=False)
     bp = K.prob.batch_problem
     D, E, c, rho = bp.scaling()
     P, A = _eff(golden_csc(g, 'P')), golden_csc(g, 'A').toarray()
@@ -96,7 +77,7 @@ def test_kkt_solve_matches_dense(name):
     rhs = rng.standard_normal(P.shape[0])
     sol = bp.kkt_solve(rhs[None])[0]
     ref = np.linalg.solve(Kmat, rhs)
-    assert _rel(sol, ref) < 1e-8
+    assert rel(sol, ref) < 1e-8
     assert np.abs(Kmat @ sol - rhs).max() < 1e-8 * max(1.0, np.abs(Kmat).max() * np.abs(sol).max())
 
 
@@ -105,13 +86,13 @@ def test_kkt_solve_matches_dense(name):
 def test_admm_iterates_match_oracle(name, iters):
     g = load_golden(name)
     kw = golden_kwargs(g)
-    K = _gpu_controller(kw); K.setup(solve=False)
-    Ko = _oracle_controller(kw); Ko.setup(solve=False)
+    K = gpu_controller(kw); K.setup(solve=False)
+    Ko = oracle_controller(kw); Ko.setup(solve=False)
     K.prob.batch_problem.iterate(iters)
     Ko.prob.iterate(iters)
     x, z, y = K.prob.batch_problem.iterate_state()
     xo, zo, yo, _ = Ko.prob.iterate_state()
-    assert _rel(x[0], xo) < 1e-8 and _rel(z[0], zo) < 1e-8
+    assert rel(x[0], xo) < 1e-8 and rel(z[0], zo) < 1e-8
     assert np.abs(y[0] - yo).max() < 1e-8 * max(1.0, np.abs(yo).max())
 
 
@@ -122,12 +103,12 @@ def test_default_tolerance_solve_matches_oracle(name):
     kw = golden_kwargs(g)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        K = _gpu_controller(kw); K.setup()
-        Ko = _oracle_controller(kw); Ko.setup()
+        K = gpu_controller(kw); K.setup()
+        Ko = oracle_controller(kw); Ko.setup()
     assert K.res.info.status == Ko.res.info.status
     assert K.res.info.iter == Ko.res.info.iter
     assert K.res.info.rho_updates == Ko.res.info.rho_updates
-    assert _rel(K.res.x, Ko.res.x) < 1e-6
+    assert rel(K.res.x, Ko.res.x) < 1e-6
     assert abs(K.res.info.obj_val - Ko.res.info.obj_val) <= 1e-7 * max(1.0, abs(Ko.res.info.obj_val))
     assert np.allclose(K.output(), Ko.output(), rtol=1e-6, atol=1e-9)
 
@@ -139,13 +120,13 @@ def test_optimum_parity_1e6(name):
     opt = load_golden(name, prefix='opt_')
     kw = golden_kwargs(g)
     kw.update(eps_abs=1e-11, eps_rel=1e-11)          # the tolerance the goldens were made at (make_optimum.py)
-    K = _gpu_controller(kw, max_iter=400000)
+    K = gpu_controller(kw, max_iter=400000)
     K.setup()
     assert K.res.info.status == 'solved'
     u0 = K.output()
     scale = max(np.abs(opt['u0']).max(), 1e-3)
     assert np.abs(u0 - opt['u0']).max() <= 1e-6 * scale
-    assert _rel(K.res.x, opt['x']) < 1e-6
+    assert rel(K.res.x, opt['x']) < 1e-6
     assert abs(K.res.info.obj_val - float(opt['obj_val'])) <= 1e-8 * max(1.0, abs(float(opt['obj_val'])))
 
 
@@ -155,8 +136,8 @@ def test_closed_loop_matches_oracle(name):
     g = load_golden(name)
     kw = golden_kwargs(g)
     kw.update(eps_abs=1e-9, eps_rel=1e-9)
-    K = _gpu_controller(kw, max_iter=100000); K.setup()
-    Ko = _oracle_controller(kw, max_iter=100000); Ko.setup()
+    K = gpu_controller(kw, max_iter=100000); K.setup()
+    Ko = oracle_controller(kw, max_iter=100000); Ko.setup()
     Ad, Bd = kw['Ad'], kw['Bd']
     x = np.array(kw['x0'], dtype=float)
     for step in range(12):
@@ -177,8 +158,8 @@ def test_infeasible_problem_reports_like_oracle():
     kw['uminus1'] = np.array([5.0])
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter('always')
-        K = _gpu_controller(kw); K.setup()
-        Ko = _oracle_controller(kw); Ko.setup()
+        K = gpu_controller(kw); K.setup()
+        Ko = oracle_controller(kw); Ko.setup()
     assert Ko.res.info.status == 'primal infeasible'
     assert K.res.info.status == Ko.res.info.status
     assert K.res.info.iter == Ko.res.info.iter
@@ -193,21 +174,17 @@ def test_infeasible_problem_reports_like_oracle():
 
 
 def test_batch_matches_per_instance_oracle():
-    from pympc_amd import BatchMPCController, fixtures
+    from pympc_amd import fixtures
     B = 6
     kws = [fixtures.random_lti(100 + i) for i in range(B)]
-    stack = lambda k: np.stack([kw[k] for kw in kws])
-    K = BatchMPCController(stack('Ad'), stack('Bd'), Np=30, x0=stack('x0'), xref=stack('xref'), uref=stack('uref'),
-                           uminus1=stack('uminus1'), Qx=stack('Qx'), QxN=stack('QxN'), Qu=stack('Qu'), QDu=stack('QDu'),
-                           xmin=stack('xmin'), xmax=stack('xmax'), umin=stack('umin'), umax=stack('umax'),
-                           Dumin=stack('Dumin'), Dumax=stack('Dumax'), eps_feas=1e6, eps_abs=1e-9, eps_rel=1e-9)
+    K = stacked_batch(kws, eps_feas=1e6, eps_abs=1e-9, eps_rel=1e-9)
     K.setup()
     U, info = K.output(return_status=True, return_x_seq=True)
     assert all(s == 'solved' for s in info['status'])
     xs = []
     for i, kw in enumerate(kws):
         kw = dict(kw); kw.update(eps_abs=1e-9, eps_rel=1e-9)
-        Ko = _oracle_controller(kw); Ko.setup()
+        Ko = oracle_controller(kw); Ko.setup()
         uo = Ko.output()
         assert np.abs(U[i] - uo).max() <= 1e-6 * max(np.abs(uo).max(), 1e-3)
         xs.append(kw['Ad'] @ kw['x0'] + kw['Bd'] @ uo)
@@ -216,7 +193,7 @@ def test_batch_matches_per_instance_oracle():
     U2 = K.output()
     for i, kw in enumerate(kws):
         kw = dict(kw); kw.update(eps_abs=1e-9, eps_rel=1e-9)
-        Ko = _oracle_controller(kw); Ko.setup(); u1 = Ko.output(); Ko.update(xs[i]); uo = Ko.output()
+        Ko = oracle_controller(kw); Ko.setup(); u1 = Ko.output(); Ko.update(xs[i]); uo = Ko.output()
         assert np.abs(U2[i] - uo).max() <= 1e-6 * max(np.abs(uo).max(), 1e-3)
 
 
@@ -284,18 +261,6 @@ def test_device_resident_inputs_match_host_inputs():
     assert sol == 4 * B and it >= 25 * sol and chk >= sol
 
 
-def _stacked_batch(kws, **kw):
-    from pympc_amd import BatchMPCController
-    stack = lambda k: np.stack([np.asarray(d[k], dtype=float) for d in kws])
-    k0 = kws[0]
-    args = dict(Np=k0['Np'], Nc=k0.get('Nc'), x0=stack('x0'), xref=stack('xref'), uref=stack('uref'), uminus1=stack('uminus1'),
-                Qx=stack('Qx'), QxN=stack('QxN'), Qu=stack('Qu'), QDu=stack('QDu'), xmin=stack('xmin'), xmax=stack('xmax'),
-                umin=stack('umin'), umax=stack('umax'), Dumin=stack('Dumin'), Dumax=stack('Dumax'),
-                eps_feas=np.array([[d.get('eps_feas', 1e6)] for d in kws]))
-    args.update(kw)
-    return BatchMPCController(stack('Ad'), stack('Bd'), **args)
-
-
 @pytest.mark.parametrize('case', ['random_12_4_30', 'cart_pole', 'quadcopter_nc', 'random_20_8_12'])
 def test_device_loop_matches_stepwise_api(case):
     """mpcqp_mpc_run (update -> solve -> output -> plant on the device for K steps) against the same
@@ -315,8 +280,8 @@ def test_device_loop_matches_stepwise_api(case):
     B, nx = len(kws), kws[0]['Ad'].shape[0]
     rng = np.random.default_rng(5)
     w = 0.01 * rng.standard_normal((K_STEPS, B, nx))
-    Kd = _stacked_batch(kws); Kd.setup()
-    Ks = _stacked_batch(kws); Ks.setup()
+    Kd = stacked_batch(kws); Kd.setup()
+    Ks = stacked_batch(kws); Ks.setup()
     tr = Kd.run(K_STEPS, w=w)
     assert np.array_equal(tr['x'][0], Ks.x0_rh)
     for k in range(K_STEPS):
@@ -342,13 +307,13 @@ def test_device_loop_custom_plant_and_failure_fallback():
     for kw in kws:
         kw['uref'] = np.array([0.05, -0.02, 0.01, 0.03])
     Ap = np.stack([kw['Ad'] * 0.9 for kw in kws]); Bp = np.stack([kw['Bd'] * 1.1 for kw in kws])
-    K = _stacked_batch(kws); K.setup()
+    K = stacked_batch(kws); K.setup()
     tr = K.run(5, Ap=Ap, Bp=Bp)
     for k in range(5):
         xn = np.einsum('bij,bj->bi', Ap, tr['x'][k]) + np.einsum('bij,bj->bi', Bp, tr['u'][k])
         assert np.allclose(xn, tr['x'][k + 1], rtol=1e-13, atol=1e-14)
     assert (tr['status'] == 1).all()
-    Kf = _stacked_batch(kws, max_iter=10); Kf.setup()
+    Kf = stacked_batch(kws, max_iter=10); Kf.setup()
     trf = Kf.run(3)
     assert np.isin(trf['status'], (-2, 2)).all() and (trf['iter'] == 10).all()     # max-iter / solved inaccurate: not 'solved'
     assert np.array_equal(trf['u'], np.broadcast_to(np.stack([kw['uref'] for kw in kws]), trf['u'].shape))
@@ -367,8 +332,8 @@ def test_device_loop_time_varying_reference():
                 kw['xref'] = np.tile(kw['xref'], (Np + 1, 1))
         per = (Np + 1) * nx if rows_full else nx
         xr = 0.1 * rng.standard_normal((K_STEPS, B, per))
-        Kd = _stacked_batch(kws); Kd.setup()
-        Ks = _stacked_batch(kws); Ks.setup()
+        Kd = stacked_batch(kws); Kd.setup()
+        Ks = stacked_batch(kws); Ks.setup()
         tr = Kd.run(K_STEPS, xref_traj=xr)
         for k in range(K_STEPS):
             u = Ks.output()
@@ -399,10 +364,10 @@ def test_device_loop_output_feedback_matches_reference_style_loop():
     x_true0 = np.stack([kw['x0'] * 1.05 for kw in kws])         # the controller starts from a wrong estimate
     st = lambda M: np.stack([M] * B)
     est = BatchLinearStateEstimator(np.stack([kw['x0'] for kw in kws]), st(Ad), st(Bd), st(Cd), st(L), x_true=x_true0.copy(), v=v)
-    Kd = _stacked_batch(kws); Kd.setup()
+    Kd = stacked_batch(kws); Kd.setup()
     tr = Kd.run(K_STEPS, w=w, estimator=est)
     # host replica: numpy estimator, stepwise controller
-    Ks = _stacked_batch(kws); Ks.setup()
+    Ks = stacked_batch(kws); Ks.setup()
     KF = BatchLinearStateEstimator(np.stack([kw['x0'] for kw in kws]), st(Ad), st(Bd), st(Cd), st(L))
     x = x_true0.copy()
     for k in range(K_STEPS):
@@ -421,6 +386,8 @@ def test_device_loop_output_feedback_matches_reference_style_loop():
 
 @pytest.mark.parametrize('dims', [(1, 1, 2, 2), (2, 1, 3, 1), (3, 2, 5, 5), (13, 3, 6, 6), (12, 5, 4, 2), (24, 8, 4, 4), (20, 12, 3, 3),
                                   (4, 1, 150, 75), (2, 2, 64, 64), (3, 12, 20, 20), (3, 12, 22, 22)])
+
+
 def test_boundary_dimensions_match_oracle(dims):
     """Shapes at the edges of the device code paths: smallest problem (nx=nu=1, Np=2), nx+nu = 16/17 (block size switch),
     nx+nu = 32 (largest 32-wide stage), Nc = 1, long horizons with Nc < Np (the reference's Kalman example uses Np=150, Nc=75),
@@ -434,7 +401,7 @@ def test_boundary_dimensions_match_oracle(dims):
     if Nc != Np:
         kw['Nc'] = Nc
     kw.update(eps_abs=1e-9, eps_rel=1e-9)
-    K = _gpu_controller(kw, max_iter=200000); Ko = _oracle_controller(kw, max_iter=200000)
+    K = gpu_controller(kw, max_iter=200000); Ko = oracle_controller(kw, max_iter=200000)
     with warnings.catch_warnings():
         warnings.simplefilter('error')
         K.setup(); Ko.setup()
@@ -452,7 +419,7 @@ def test_boundary_dimensions_match_oracle(dims):
 def test_unsupported_dimensions_fail_loudly():
     from pympc_amd import fixtures
     kw = dict(fixtures.random_lti(1, nx=120, nu=12, Np=3))      # nx + nu > 128 (32 < nx + nu <= 128: tests/test_gpu_wide.py)
-    K = _gpu_controller(kw)
+    K = gpu_controller(kw)
     with pytest.raises(NotImplementedError):
         K.setup()
 
@@ -465,7 +432,7 @@ def test_device_loop_recovers_from_infeasible_step_like_stepwise():
     kws = [fixtures.random_lti(600 + i) for i in range(4)]
     kws[1]['uminus1'] = np.array([5.0, 0.0, 0.0, 0.0])        # needs u_0[0] in [4.5, 5.5] but u <= 1
     kws[3]['uminus1'] = np.array([0.0, -7.0, 0.0, 0.0])
-    Kd = _stacked_batch(kws); Ks = _stacked_batch(kws)
+    Kd = stacked_batch(kws); Ks = stacked_batch(kws)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         Kd.setup(); Ks.setup()
@@ -490,8 +457,8 @@ def test_device_loop_long_run_stays_bounded_and_solved():
     kws = [fixtures.random_lti(700 + i) for i in range(64)]
     rng = np.random.default_rng(11)
     w = 0.05 * rng.standard_normal((400, 64, 12))
-    Ka = _stacked_batch(kws); Ka.setup()
-    Kb = _stacked_batch(kws); Kb.setup()
+    Ka = stacked_batch(kws); Ka.setup()
+    Kb = stacked_batch(kws); Kb.setup()
     ta = Ka.run(400, w=w)
     parts = [Kb.run(100, w=w[100 * i:100 * (i + 1)]) for i in range(4)]
     assert np.array_equal(ta['u'], np.concatenate([p['u'] for p in parts]))
@@ -505,8 +472,8 @@ def test_mpc_step_equals_update_then_output():
     and the u_failure fallback."""
     from pympc_amd import fixtures
     kws = [fixtures.random_lti(800 + i) for i in range(5)]
-    Ka = _stacked_batch(kws); Ka.setup()
-    Kb = _stacked_batch(kws); Kb.setup()
+    Ka = stacked_batch(kws); Ka.setup()
+    Kb = stacked_batch(kws); Kb.setup()
     x = Ka.x0_rh.copy()
     rng = np.random.default_rng(2)
     ua, ub = Ka.output(), Kb.output()
@@ -516,7 +483,7 @@ def test_mpc_step_equals_update_then_output():
         Ka.update(x); ua = Ka.output()
         ub = Kb.step(x, ub if k == 0 else None)            # u_{-1} handed over by the previous step from k = 1 on
         assert np.array_equal(ua, ub), k
-    Kf = _stacked_batch(kws, max_iter=10); Kf.setup()
+    Kf = stacked_batch(kws, max_iter=10); Kf.setup()
     uf = Kf.step(x)
     assert np.array_equal(uf, Kf.uref)                     # not 'solved' after 10 iterations -> u_failure
 
@@ -535,7 +502,7 @@ def test_load_balancing_map_never_changes_results(monkeypatch):
         from pympc_amd import _lib
         from pympc_amd.solver import forced_settings
         with forced_settings(tuning=0 if flag == '1' else _lib.TUNE_NO_BALANCE):
-            K = _stacked_batch(kws); K.setup()
+            K = stacked_batch(kws); K.setup()
         parts = [K.run(10, w=w[10 * i:10 * (i + 1)]) for i in range(3)]       # the map is rebuilt after every launch
         x = parts[-1]['x'][-1]
         us = []
@@ -563,7 +530,7 @@ def test_persistent_queue_never_changes_results(B, steps):
     out = []
     for tuning in (0, _lib.TUNE_NO_PARTS, _lib.TUNE_NO_QUEUE):
         with forced_settings(tuning=tuning, **({'backend': 'sweeps'} if B > 1024 else {})):
-            K = _stacked_batch(kws); K.setup()
+            K = stacked_batch(kws); K.setup()
         parts = [K.run(steps, w=w[steps * i:steps * (i + 1)]) for i in range(2)]
         out.append(tuple(np.concatenate([p[k] for p in parts]) for k in ('u', 'x', 'iter', 'status')) + (K.prob.solution()[0],))
     for other in out[1:]:
@@ -585,7 +552,7 @@ def test_three_quarter_slots_never_change_results():
     out = []
     for tuning in (0, _lib.TUNE_NO_QUEUE, 10 << 24):
         with forced_settings(tuning=tuning):
-            K = _stacked_batch(kws); K.setup()
+            K = stacked_batch(kws); K.setup()
         assert K.prob.kernel_name(True).replace(' ', '').startswith('k_mpc_run<32,false'), K.prob.kernel_name(True)
         parts = [K.run(steps, w=w[steps * i:steps * (i + 1)]) for i in range(2)]
         out.append(tuple(np.concatenate([p[k] for p in parts]) for k in ('u', 'x', 'iter', 'status')) + (K.prob.solution()[0],))
@@ -594,50 +561,13 @@ def test_three_quarter_slots_never_change_results():
             assert np.array_equal(a, b)
 
 
-def _random_case(seed):
-    """A seeded random controller: dimensions, horizon split, bound pattern (finite / one-sided / absent), weights
-    (including semidefinite ones) and reference shape are all drawn."""
-    from pympc_amd import fixtures
-    rng = np.random.default_rng(7000 + seed)
-    nx = int(rng.integers(1, 14)); nu = int(rng.integers(1, 6))
-    Np = int(rng.integers(2, 26)); Nc = int(rng.integers(1, Np + 1)) if rng.random() < 0.5 else Np
-    kw = dict(fixtures.random_lti(9000 + seed, nx=nx, nu=nu, Np=Np, xbox=4.0))
-    kw['x0'] = 0.5 * kw['x0']
-    if Nc != Np:
-        kw['Nc'] = Nc
-    inf = np.inf
-    def pattern(lo, hi):
-        lo, hi = lo.copy(), hi.copy()
-        for i in range(lo.size):
-            t = rng.random()
-            if t < 0.2: lo[i] = -inf
-            elif t < 0.4: hi[i] = inf
-            elif t < 0.5: lo[i], hi[i] = -inf, inf
-        return lo, hi
-    kw['xmin'], kw['xmax'] = pattern(kw['xmin'], kw['xmax'])
-    kw['Dumin'], kw['Dumax'] = pattern(kw['Dumin'], kw['Dumax'])
-    if rng.random() < 0.3:
-        kw['umin'], kw['umax'] = pattern(kw['umin'], kw['umax'])
-    w = rng.random()
-    if w < 0.25: kw['QDu'] = np.zeros((nu, nu))                       # Qu > 0 keeps the optimum unique
-    elif w < 0.5: kw['Qu'] = np.zeros((nu, nu))                       # QDu > 0 does
-    G = rng.standard_normal((nx, nx)); kw['Qx'] = G @ G.T / nx        # dense PSD state weight
-    if rng.random() < 0.5: kw['QxN'] = 3.0 * kw['Qx']
-    if rng.random() < 0.3: kw['xref'] = 0.2 * rng.standard_normal((Np + 1, nx))
-    else: kw['xref'] = 0.2 * rng.standard_normal(nx)
-    kw['uref'] = 0.1 * rng.standard_normal(nu)
-    kw['uminus1'] = 0.1 * rng.standard_normal(nu)
-    kw['eps_feas'] = float(10.0 ** rng.integers(2, 7))
-    return kw
-
-
 @pytest.mark.parametrize('seed', range(24))
 def test_randomised_controllers_match_oracle(seed):
     """Seeded random controllers (shapes, Nc < Np, one-sided and absent bounds, semidefinite weights, 1-D / 2-D references):
     cold solve and one warm step against the oracle at tight tolerance; statuses must agree too."""
-    kw = _random_case(seed)
+    kw = random_case(seed)
     kw.update(eps_abs=1e-10, eps_rel=1e-10)     # the reference author's own parity setting (test_scripts/main_du.py:125)
-    K = _gpu_controller(kw, max_iter=400000); Ko = _oracle_controller(kw, max_iter=400000)
+    K = gpu_controller(kw, max_iter=400000); Ko = oracle_controller(kw, max_iter=400000)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         K.setup(); Ko.setup()
@@ -658,8 +588,8 @@ def test_step_after_output_uses_the_output_as_previous_input():
     kws = [fixtures.random_lti(820 + i) for i in range(4)]
     for kw in kws:
         kw['uminus1'] = np.array([0.4, -0.3, 0.2, 0.1])       # differs from what output() will return
-    Ka = _stacked_batch(kws); Ka.setup()
-    Kb = _stacked_batch(kws); Kb.setup()
+    Ka = stacked_batch(kws); Ka.setup()
+    Kb = stacked_batch(kws); Kb.setup()
     ua, ub = Ka.output(), Kb.output()
     x = np.einsum('bij,bj->bi', Ka.Ad, Ka.x0_rh) + np.einsum('bij,bj->bi', Ka.Bd, ua)
     Ka.update(x); ua = Ka.output()
@@ -676,8 +606,8 @@ def test_loop_reference_shape_is_checked_and_may_change():
     from pympc_amd import fixtures
     kws = [fixtures.random_lti(830 + i) for i in range(2)]
     B, nx, Np = 2, 12, 30
-    Kd = _stacked_batch(kws); Kd.setup()
-    Ks = _stacked_batch(kws); Ks.setup()
+    Kd = stacked_batch(kws); Kd.setup()
+    Ks = stacked_batch(kws); Ks.setup()
     rng = np.random.default_rng(6)
     with pytest.raises(ValueError):
         Kd.run(3, xref_traj=np.zeros((3, B, 5)))
@@ -698,15 +628,15 @@ def test_warm_start_sets_z_like_osqp():
     """osqp.warm_start(x=, y=) also sets z = A x; the next solve must then iterate exactly like the oracle's."""
     from pympc_amd import fixtures
     kw = dict(fixtures.random_lti(840))
-    K = _gpu_controller(kw); K.setup()
-    Ko = _oracle_controller(kw); Ko.setup()
+    K = gpu_controller(kw); K.setup()
+    Ko = oracle_controller(kw); Ko.setup()
     rng = np.random.default_rng(8)
     x, y = 0.1 * rng.standard_normal(K.prob.n), 0.1 * rng.standard_normal(K.prob.m)
     K.prob.warm_start(x=x, y=y); Ko.prob.warm_start(x=x, y=y)
     K.prob.batch_problem.iterate(3); Ko.prob.iterate(3)
     xg, zg, yg = K.prob.batch_problem.iterate_state()
     xo, zo, yo, _ = Ko.prob.iterate_state()
-    assert _rel(xg[0], xo) < 1e-8 and _rel(zg[0], zo) < 1e-8 and np.abs(yg[0] - yo).max() < 1e-8 * max(1.0, np.abs(yo).max())
+    assert rel(xg[0], xo) < 1e-8 and rel(zg[0], zo) < 1e-8 and np.abs(yg[0] - yo).max() < 1e-8 * max(1.0, np.abs(yo).max())
 
 
 @pytest.mark.parametrize('name', ['quadcopter', 'random_20_8_12', 'point_mass_nc'])
@@ -715,13 +645,13 @@ def test_refactor_rewrites_the_same_factor(name):
     the reduced-KKT solve and the next solve are bit-identical with and without it."""
     g = load_golden(name)
     kw = golden_kwargs(g)
-    K = _gpu_controller(kw); K.setup(solve=True)
+    K = gpu_controller(kw); K.setup(solve=True)
     bp = K.prob.batch_problem
     rhs = np.random.default_rng(11).standard_normal((1, bp.n))
     before = bp.kkt_solve(rhs)
     bp.refactor(); bp.synchronize()
     assert np.array_equal(bp.kkt_solve(rhs), before)
-    K2 = _gpu_controller(kw); K2.setup(solve=True)
+    K2 = gpu_controller(kw); K2.setup(solve=True)
     x = np.asarray(kw['x0'], float)
     for _ in range(3):
         u = K.output(); u2 = K2.output()
@@ -751,7 +681,7 @@ def test_persistent_queue_with_output_feedback_and_a_moving_reference():
     out = []
     for tuning in (0, _lib.TUNE_NO_QUEUE):
         with forced_settings(tuning=tuning):
-            K = _stacked_batch(kws); K.setup()
+            K = stacked_batch(kws); K.setup()
         est = BatchLinearStateEstimator(st('x0'), st('Ad'), st('Bd'), C, Lg, x_true=st('x0').copy(), v=v)
         tr = K.run(steps, w=w, xref_traj=xref, estimator=est)
         out.append((tr['u'], tr['x'], tr['xhat'], tr['y'], tr['iter'], tr['status'], est.x_true.copy()))

@@ -6,10 +6,8 @@ import warnings
 import numpy as np
 import pytest
 
-from util import golden_names, load_golden, golden_kwargs, apply_attrs
-from polish_ref import polish as polish_ref, golden_qp
-from test_polish_reference import ACCEPTED, EXACT_SCALED as EXACT
-from test_gpu_backends import _dense_eligible, _bcr_schedule
+from util import golden_names, load_golden, golden_kwargs, apply_attrs, rel1, golden_backends, repeated, stacked_batch, point_mass_batch
+from polish_ref import golden_qp, check_against_spec, ACCEPTED, EXACT_SCALED as EXACT
 
 pytestmark = pytest.mark.gpu
 
@@ -19,10 +17,6 @@ EPS = 1e-3
 def _opt(name):
     import os
     return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'opt_%s.npz' % name))
-
-
-def _rel(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def _ctrl(kw, eps=EPS, **settings):
@@ -38,33 +32,6 @@ def _ctrl(kw, eps=EPS, **settings):
 
 def _golden_ctrl(name, **settings):
     return _ctrl(golden_kwargs(load_golden(name)), **settings)
-
-
-def _spec(bp, b=0):
-    """polish_ref on instance b of BatchProblem bp, from the iterate and scaling the device holds now."""
-    P, q, A, l, u = (v[b] for v in bp.export_qp())
-    x, z, y = (v[b] for v in bp.iterate_state())
-    D, E, c, _ = bp.scaling()
-    info = bp.infos()[b]
-    return polish_ref(P, q, A, l, u, x, z, y, D[b], E[b], c[b], info.pri_res, info.dua_res)
-
-
-def _check_against_spec(bp, idx=None):
-    """Polish the last solve of bp (polish off until now) and compare every instance in idx with polish_ref."""
-    idx = range(bp.batch) if idx is None else idx
-    refs = {b: _spec(bp, b) for b in idx}
-    bp.polish()
-    st = bp.polish_status()
-    x, y, info = bp.solution()
-    for b, ref in refs.items():
-        assert st[b] == ref['status_polish'], (b, st[b], ref['status_polish'])
-        if st[b] == 1:
-            assert _rel(x[b], ref['x']) <= 1e-9, (b, _rel(x[b], ref['x']))
-            # (the multipliers come out of (omega / c) (A x - b) with omega / c ~ E^2 / (c delta): the rounding of A x - b, 1e6 times)
-            assert _rel(y[b], ref['y']) <= 1e-8, (b, _rel(y[b], ref['y']))
-            assert np.all(y[b][~(ref['low'] | ref['upp'])] == 0.0)
-            assert info[b].pri_res == pytest.approx(ref['pri_res'], abs=1e-9 * max(1.0, np.abs(ref['x']).max()))
-    return st
 
 
 # ---- 1. accuracy at the reference tolerance ---------------------------------------------------------------------------------------------
@@ -86,10 +53,10 @@ def test_polish_at_pympcs_tolerance(name):
     if name in ACCEPTED:
         assert sp == 1, name                        # accepted from the oracle's iterate on the CPU: the device must accept too
     if name in EXACT:
-        assert _rel(K.res.x, opt['x']) <= 1e-8, (name, _rel(K.res.x, opt['x']))
+        assert rel1(K.res.x, opt['x']) <= 1e-8, (name, rel1(K.res.x, opt['x']))
         u0 = K.output()
         assert np.abs(u0 - opt['u0']).max() <= 1e-8 * max(1.0, np.abs(opt['u0']).max()), name
-        assert _rel(K0.res.x, opt['x']) > 1e-8       # what polishing changed
+        assert rel1(K0.res.x, opt['x']) > 1e-8       # what polishing changed
 
 
 def test_named_fixtures_include_the_headline_shape_and_the_cart_pole():
@@ -105,30 +72,21 @@ def test_device_polish_is_the_spec(name):
     bp = K.prob.batch_problem
     if K.res.info.status != 'solved':
         pytest.fail('not solved')
-    _check_against_spec(bp)
+    check_against_spec(bp)
 
 
 # ---- 3. every backend, grouped stages, wide stages ---------------------------------------------------------------------------------------
-def _backends(name):
-    out = ['sweeps']
-    if _dense_eligible(name):
-        out.append('dense')
-    if _bcr_schedule(name):
-        out += ['bcr', 'bcr8', 'bcrt']
-    return out
-
-
 @pytest.mark.parametrize('name', ['random_12_4_30', 'point_mass', 'small_mimo', 'quadcopter_nodu', 'random_5_3_8_nc'])
 def test_polish_agrees_across_backends_and_leaves_the_handle_factor(name):
     from pympc_amd.solver import forced_settings
     res = {}
-    for be in _backends(name):
+    for be in golden_backends(name):
         with forced_settings(backend=be):
             K = _golden_ctrl(name); K.setup()
         bp = K.prob.batch_problem
         rhs = np.random.default_rng(0).standard_normal((1, bp.n))
         before = bp.kkt_solve(rhs)
-        st = _check_against_spec(bp)
+        st = check_against_spec(bp)
         after = bp.kkt_solve(rhs)
         assert np.array_equal(before, after), be          # the handle's own factor is untouched
         res[be] = (st[0], bp.solution()[0][0])
@@ -136,7 +94,7 @@ def test_polish_agrees_across_backends_and_leaves_the_handle_factor(name):
     for be, (st, x) in res.items():
         assert st == base[0], be
         if st == 1:
-            assert _rel(x, base[1]) <= 1e-10, (be, _rel(x, base[1]))
+            assert rel1(x, base[1]) <= 1e-10, (be, rel1(x, base[1]))
 
 
 def _kw(**over):
@@ -154,6 +112,8 @@ def _kw(**over):
     lambda: __import__('pympc_amd').fixtures.random_lti(4, nx=60, nu=20, Np=4),          # stages 65..128 wide
     lambda: _kw(Np=20, Nc=5),                                                             # held input, bordered factor
 ], ids=['grouped', 'grouped_held', 'wide64', 'wide128', 'held'])
+
+
 def test_polish_on_grouped_and_wide_layouts(make):
     from util import KW
     kw = make()
@@ -165,7 +125,7 @@ def test_polish_on_grouped_and_wide_layouts(make):
     bp = K.prob.batch_problem
     rhs = np.random.default_rng(1).standard_normal((1, bp.n))
     before = bp.kkt_solve(rhs)
-    _check_against_spec(bp)
+    check_against_spec(bp)
     assert np.array_equal(before, bp.kkt_solve(rhs))
 
 
@@ -174,10 +134,7 @@ def test_shared_factor_map_survives_polishing():
     kw = fixtures.random_lti(7)
     B = 8
     st = lambda a: np.stack([np.asarray(a, dtype=float)] * B)
-    K = BatchMPCController(st(kw['Ad']), st(kw['Bd']), Np=30, x0=st(kw['x0']), xref=st(kw['xref']), uref=st(kw['uref']), uminus1=st(kw['uminus1']),
-                           Qx=st(kw['Qx']), QxN=st(kw['QxN']), Qu=st(kw['Qu']), QDu=st(kw['QDu']), xmin=st(kw['xmin']), xmax=st(kw['xmax']),
-                           umin=st(kw['umin']), umax=st(kw['umax']), Dumin=st(kw['Dumin']), Dumax=st(kw['Dumax']), eps_feas=1e6,
-                           eps_abs=EPS, eps_rel=EPS, backend='sweeps', polish=True)
+    K = BatchMPCController(**repeated(kw, B, eps_feas=1e6, eps_abs=EPS, eps_rel=EPS, backend='sweeps', polish=True))
     K.setup(solve=False)
     n = K.share_factor()
     assert n == B
@@ -190,17 +147,7 @@ def test_shared_factor_map_survives_polishing():
 
 # ---- 4. mixed batch ---------------------------------------------------------------------------------------------------------------------
 def _point_mass_batch(polish):
-    from pympc_amd import BatchMPCController, fixtures
-    kw = fixtures.point_mass()
-    B = 5
-    st = lambda a: np.stack([np.asarray(a, dtype=float)] * B)
-    um1 = st(kw['uminus1'] if 'uminus1' in kw else np.zeros(1))
-    um1[2] = 5.0                                    # tests/test_gpu_parity.py's infeasible recipe for instance 2
-    x0 = st(kw['x0']) * np.linspace(0.6, 1.0, B)[:, None]
-    K = BatchMPCController(st(kw['Ad']), st(kw['Bd']), Np=kw['Np'], x0=x0, xref=st(kw['xref']), uref=st(kw['uref']), uminus1=um1,
-                           Qx=st(kw['Qx']), QxN=st(kw['QxN']), Qu=st(kw['Qu']), QDu=st(kw['QDu']), xmin=st(kw['xmin']), xmax=st(kw['xmax']),
-                           umin=st(kw['umin']), umax=st(kw['umax']), Dumin=st(kw['Dumin']), Dumax=st(kw['Dumax']), eps_feas=kw.get('eps_feas', 1e6),
-                           eps_abs=EPS, eps_rel=EPS, polish=polish)
+    K, _ = point_mass_batch(eps_abs=EPS, eps_rel=EPS, polish=polish)      # (instance 2 infeasible: tests/test_gpu_parity.py's recipe)
     K.setup()
     return K
 
@@ -233,7 +180,7 @@ def test_accepted_polish_becomes_the_warm_start():
     bp.solve_async()
     x2, _, info2 = bp.solution()
     assert info2[0].status == 1 and info2[0].iter == bp.settings.check_termination
-    assert _rel(x2[0], _opt('random_12_4_30')['x']) <= 1e-8
+    assert rel1(x2[0], _opt('random_12_4_30')['x']) <= 1e-8
 
 
 # ---- 6. rejection -----------------------------------------------------------------------------------------------------------------------
@@ -261,7 +208,7 @@ def test_drop_in_controller_and_seam_return_the_optimum():
     prob.setup(P, q, A, l, u, eps_abs=EPS, eps_rel=EPS, polish=True)
     res = prob.solve()
     assert res.info.status == 'solved' and res.info.status_polish == 1
-    assert _rel(res.x, opt['x']) <= 1e-8
+    assert rel1(res.x, opt['x']) <= 1e-8
     prob.update_settings(polish=False)
     assert prob.solve().info.status_polish == 0
     prob.update_settings(polish=True)
@@ -271,10 +218,7 @@ def test_drop_in_controller_and_seam_return_the_optimum():
 def test_device_loop_refuses_polishing():
     from pympc_amd import BatchMPCController, fixtures
     kw = fixtures.point_mass()
-    st = lambda a: np.stack([np.asarray(a, dtype=float)] * 2)
-    K = BatchMPCController(st(kw['Ad']), st(kw['Bd']), Np=kw['Np'], x0=st(kw['x0']), xref=st(kw['xref']), uref=st(kw['uref']),
-                           Qx=st(kw['Qx']), QxN=st(kw['QxN']), Qu=st(kw['Qu']), QDu=st(kw['QDu']), xmin=st(kw['xmin']), xmax=st(kw['xmax']),
-                           umin=st(kw['umin']), umax=st(kw['umax']), Dumin=st(kw['Dumin']), Dumax=st(kw['Dumax']), eps_feas=kw.get('eps_feas', 1e6), polish=True)
+    K = BatchMPCController(**repeated(kw, 2, uminus1=None, eps_feas=kw.get('eps_feas', 1e6), polish=True))      # (u_{-1}: the constructor's default)
     K.setup()
     with pytest.raises(NotImplementedError):
         K.run(3)
@@ -317,12 +261,8 @@ def test_polish_inside_mpc_step_and_the_stepwise_controller():
 
 # ---- 8. the headline shape ---------------------------------------------------------------------------------------------------------------
 def _random_batch(idx, eps, **settings):
-    from pympc_amd import BatchMPCController, fixtures
-    kws = [fixtures.random_lti(int(i)) for i in idx]
-    s = lambda k: np.stack([kw[k] for kw in kws])
-    K = BatchMPCController(s('Ad'), s('Bd'), Np=30, x0=s('x0'), xref=s('xref'), uref=s('uref'), uminus1=s('uminus1'), Qx=s('Qx'), QxN=s('QxN'),
-                           Qu=s('Qu'), QDu=s('QDu'), xmin=s('xmin'), xmax=s('xmax'), umin=s('umin'), umax=s('umax'), Dumin=s('Dumin'),
-                           Dumax=s('Dumax'), eps_feas=1e6, eps_abs=eps, eps_rel=eps, max_iter=400000, **settings)
+    from pympc_amd import fixtures
+    K = stacked_batch([fixtures.random_lti(int(i)) for i in idx], eps_feas=1e6, eps_abs=eps, eps_rel=eps, max_iter=400000, **settings)
     K.setup()
     return K
 
@@ -336,7 +276,7 @@ def test_headline_batch_1024_x_12_4_30():
     sample = np.arange(0, B, B // 64)
     # the same 64 instances unpolished, polished on demand against the spec
     K64 = _random_batch(sample, EPS)
-    st64 = _check_against_spec(K64.prob)
+    st64 = check_against_spec(K64.prob)
     assert np.array_equal(st64, st[sample])
     # polished u0 against the optimum (the same instances solved to eps 1e-11)
     Kopt = _random_batch(sample, 1e-11)

@@ -7,6 +7,8 @@ import warnings
 import numpy as np
 import pytest
 
+from util import stacked_batch
+
 pytestmark = pytest.mark.gpu
 
 
@@ -51,18 +53,15 @@ def test_random_shape_matches_oracle(seed):
 
 @pytest.mark.parametrize('seed', range(24))
 def test_random_shape_device_loop_equals_stepwise(seed):
-    from pympc_amd import BatchMPCController, fixtures
+    from pympc_amd import fixtures
     rng = np.random.default_rng(63000 + seed)
     nx, nu, Np, Nc = _shape(rng)
     B = int(rng.integers(1, 5))
     soft = bool(rng.random() < 0.75)
     kws = [fixtures.random_lti(64000 + 7 * seed + i, nx=nx, nu=nu, Np=Np, xbox=4.0) for i in range(B)]
-    keys = ('x0', 'xref', 'uref', 'uminus1', 'Qx', 'QxN', 'Qu', 'QDu', 'xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')
-    stack = lambda k: np.stack([np.asarray(kw[k], dtype=float) for kw in kws])
 
     def make():
-        K = BatchMPCController(stack('Ad'), stack('Bd'), Np=Np, Nc=Nc, eps_feas=np.array([[kw.get('eps_feas', 1e6)] for kw in kws]),
-                               SOFT_ON=soft, **{k: stack(k) for k in keys})
+        K = stacked_batch(kws, Nc=Nc, SOFT_ON=soft)
         K.setup()
         return K
     with warnings.catch_warnings():

@@ -2,15 +2,13 @@
 `nccl` (= RCCL) process group on its device and run what N > 1 ranks run around the timed region -- scatter of the problem data, barrier,
 all-gather of u* (per step on the stepwise path, per launch on the device loop), max-reduction of the elapsed time -- with a communicator
 of one.  Not a scaling measurement (the driver's 8-GPU run is that); it shows the branch executes on the hardware and leaves the results alone."""
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
+from util import run_bench
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ['--gpus', '1', '--steps', '4', '--warmup', '2', '--batch', '64', '--no-cpu-baseline', '--no-other-path', '--no-refactor-timing']
 
 
@@ -21,13 +19,8 @@ def _bench(force, *flags):
     if force:
         env['MPCQP_BENCH_FORCE_PG'] = '1'
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + FLAGS + list(flags), env=env, capture_output=True, text=True, timeout=280)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
-    assert len(lines) == 1, r.stdout
-    # the driver parses the LAST stdout line: RCCL's banner (C stdio, written when its buffer is flushed) must not land behind it
-    assert r.stdout.rstrip().splitlines()[-1] == lines[0], r.stdout[-1500:]
-    return json.loads(lines[0])
+    # (run_bench: the driver parses the LAST stdout line -- RCCL's banner, C stdio written when its buffer is flushed, must not land behind it)
+    return run_bench(env, *FLAGS, *flags)
 
 
 @pytest.mark.timeout(600)

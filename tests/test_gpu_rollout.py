@@ -15,93 +15,14 @@ import pytest
 
 import rollout_cases as rc
 import rollout_ref as rr
+from rollout_dev import TOL, FD_TOL, SOLVED, CHAIN, ctrl as _ctrl, inputs as _inputs, forward as _forward, ref_tape as _ref_tape
+from util import rel1_any as _rel
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-EPS = 1e-9
-TOL = 1e-9                 # against the restatement, relative to max(1, |.|_inf)  (tests/test_gpu_adjoint.py)
-FD_TOL = 1e-4              # central differences, relative to max(1, |fd|_inf)      (ibid.)
-SOLVED = 1
-CHAIN = ('lam', 'uminus1', 'uref', 'xref', 'Ap', 'Bp')
 MODEL = rr.MODEL_NAMES
 NAMES = sorted(rc.CASES)
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max())) if b.size else 0.0
-
-
-def _ctrl(name, seeds=None, over=None, **settings):
-    from pympc_amd import BatchMPCController
-    args = rc.batch_kwargs(name, seeds, eps_abs=EPS, eps_rel=EPS, **dict(dict(max_iter=400000), **settings))
-    args.update(over or {})
-    K = BatchMPCController(**args)
-    K.setup()
-    return K
-
-
-def _inputs(name, own_plant, with_w, seeds=None):
-    """Plant, disturbance and reference trajectory of one forward variant of a case: dict(Ap, Bp, w, xref_traj), None where not given."""
-    c = rc.CASES[name]
-    seeds = c['seeds'] if seeds is None else seeds
-    B, K, nx, nu = len(seeds), c['K'], c['nx'], c['nu']
-    rng = np.random.default_rng(17)
-    kws = [rc.draw(name, s)[0] for s in seeds]
-    dA, dB, w = 0.02 * rng.standard_normal((B, nx, nx)), 0.02 * rng.standard_normal((B, nx, nu)), 0.01 * rng.standard_normal((K, B, nx))
-    io = dict(Ap=None, Bp=None, w=w if with_w else None, xref_traj=None)
-    if own_plant:
-        io['Ap'] = np.stack([kw['Ad'] for kw in kws]) + dA
-        io['Bp'] = np.stack([kw['Bd'] for kw in kws]) + dB
-    if c['tv']:
-        io['xref_traj'] = np.stack([rc.xref_traj(name, s) for s in seeds], axis=1).reshape(K, B, -1)
-    return io
-
-
-_fwd = {}
-
-
-def _forward(name, own_plant=False, with_w=False):
-    """One forward variant of a case, made once: K one-step device loops on one controller with everything the handle holds read between
-    them, and rollout(K) on another.  The reference every test of the variant shares; nobody changes it."""
-    key = (name, own_plant, with_w)
-    if key in _fwd:
-        return _fwd[key]
-    c = rc.CASES[name]
-    K = c['K']
-    io = _inputs(name, own_plant, with_w)
-    Ka = _ctrl(name)
-    seq, held = [], []
-    um1, xref = np.array(Ka.uminus1), np.array(Ka.xref).reshape(Ka.B, -1)
-    for k in range(K):
-        x, z, y = Ka.prob.iterate_state()
-        held.append(dict(x=x, z=z, y=y, status=np.array([i.status for i in Ka.prob.infos()]), um1=um1.copy(), xref=xref.copy()))
-        tr = Ka.run(1, w=None if io['w'] is None else io['w'][k:k + 1], Ap=io['Ap'], Bp=io['Bp'],
-                    xref_traj=None if io['xref_traj'] is None else io['xref_traj'][k:k + 1])
-        held[-1]['x0'] = tr['x'][0].copy()
-        seq.append(tr)
-        um1 = tr['u'][0].copy()
-        if io['xref_traj'] is not None:
-            xref = io['xref_traj'][k].copy()
-    Kb = _ctrl(name)
-    tr = Kb.rollout(K, **io)
-    tape = [Kb.prob.rollout_tape(k) for k in range(K)]
-    D, E, cs, _ = Kb.prob.scaling()
-    _fwd[key] = dict(Ka=Ka, Kb=Kb, seq=seq, held=held, tr=tr, tape=tape, io=io, scaling=(D, E, cs), refs={})
-    return _fwd[key]
-
-
-def _ref_tape(f, name, b):
-    """Instance b's tape in the form of tests/rollout_ref.py, from the DEVICE's tape."""
-    c = rc.CASES[name]
-    nx, nu = c['nx'], c['nu']
-    out = []
-    for e in f['tape']:
-        xr = e['step'][b, nx + nu:]
-        out.append(dict(x=e['x'][b], z=e['z'][b], y=e['y'][b], x0=e['step'][b, :nx], um1=e['step'][b, nx:nx + nu],
-                        xref=xr.reshape(-1, nx) if xr.size > nx else xr, solved=bool(e['status'][b] == SOLVED)))
-    return out
 
 
 def _reference(f, name, b, gx, gu):

@@ -6,6 +6,7 @@ differences of run(estimator=...) itself; a failed step; refusals; the state-fee
 
 Everything is solved at the project's parity setting eps_abs = eps_rel = 1e-9.  TOL and FD_TOL are those of tests/test_gpu_rollout.py."""
 import ctypes as C
+import functools
 import os
 import re
 import subprocess
@@ -17,112 +18,19 @@ import pytest
 import rollout_cases as rc
 import rollout_est_cases as ec
 import rollout_est_ref as er
+import rollout_dev as rd
+from rollout_dev import TOL, FD_TOL, SOLVED, CHAIN, estimator as _estimator
+from util import rel1_any as _rel
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-EPS = 1e-9
-TOL = 1e-9                 # against the restatement, relative to max(1, |.|_inf)
-FD_TOL = 1e-4              # central differences, relative to max(1, |fd|_inf)
-SOLVED = 1
-CHAIN = ('lam', 'uminus1', 'uref', 'xref', 'Ap', 'Bp')
 ESTG = ('eta', 'C', 'L', 'v', 'Ae', 'Be')
 MODEL = er.MODEL_NAMES
 EVERY = CHAIN + ESTG + MODEL
 PER_STEP = ('lam', 'eta', 'xref', 'v')                     # [K(+1), B, .]: instance b is [:, b]
 NAMES = sorted(ec.SEEDS)
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max())) if b.size else 0.0
-
-
-def _ctrl(name, seeds=None, over=None, **settings):
-    from pympc_amd import BatchMPCController
-    seeds = ec.SEEDS[name] if seeds is None else seeds
-    args = rc.batch_kwargs(name, seeds, eps_abs=EPS, eps_rel=EPS, **dict(dict(max_iter=400000), **settings))
-    args.update(over or {})
-    K = BatchMPCController(**args)
-    K.setup()
-    return K
-
-
-def _estimator(K, e, v=None, x_true=None):
-    from pympc_amd.kalman import BatchLinearStateEstimator
-    return BatchLinearStateEstimator(K.x0, K.Ad, K.Bd, e['C'], e['L'], x_true=np.array(e['x_true0'] if x_true is None else x_true), v=v)
-
-
-def _inputs(name, own_plant, noisy, seeds=None):
-    """One forward variant of a case: dict(e = the stacked estimators, Ap, Bp, w, v, xref_traj), None where not given."""
-    c = rc.CASES[name]
-    seeds = ec.SEEDS[name] if seeds is None else seeds
-    B, nx, nu = len(seeds), c['nx'], c['nu']
-    e = ec.batch_estimator(name, seeds)
-    rng = np.random.default_rng(17)
-    dA, dB = 0.02 * rng.standard_normal((B, nx, nx)), 0.02 * rng.standard_normal((B, nx, nu))
-    io = dict(e=e, Ap=None, Bp=None, w=e['w'] if noisy else None, v=e['v'] if noisy else None, xref_traj=None)
-    if own_plant:
-        kws = [rc.draw(name, s)[0] for s in seeds]
-        io['Ap'] = np.stack([kw['Ad'] for kw in kws]) + dA
-        io['Bp'] = np.stack([kw['Bd'] for kw in kws]) + dB
-    if c['tv']:
-        io['xref_traj'] = np.stack([rc.xref_traj(name, s) for s in seeds], axis=1).reshape(c['K'], B, -1)
-    return io
-
-
-def _twin(name, io, seeds=None):
-    """K calls of run(1, estimator=...) on one controller, with everything the handle and the estimator hold read between them."""
-    K = rc.CASES[name]['K']
-    Ka = _ctrl(name, seeds)
-    est = _estimator(Ka, io['e'])
-    seq, held = [], []
-    um1, xref = np.array(Ka.uminus1), np.array(Ka.xref).reshape(Ka.B, -1)
-    for k in range(K):
-        x, z, y = Ka.prob.iterate_state()
-        held.append(dict(x=x, z=z, y=y, status=np.array([i.status for i in Ka.prob.infos()]), um1=um1.copy(), xref=xref.copy(), x_plant=est.x_true.copy()))
-        est.v = None if io['v'] is None else io['v'][k:k + 1]
-        tr = Ka.run(1, estimator=est, w=None if io['w'] is None else io['w'][k:k + 1], Ap=io['Ap'], Bp=io['Bp'],
-                    xref_traj=None if io['xref_traj'] is None else io['xref_traj'][k:k + 1])
-        held[-1].update(x0=tr['xhat'][0].copy(), y_meas=tr['y'][0].copy())
-        seq.append(tr)
-        um1 = tr['u'][0].copy()
-        if io['xref_traj'] is not None:
-            xref = io['xref_traj'][k].copy()
-    return Ka, est, seq, held
-
-
-_fwd = {}
-
-
-def _forward(name, own_plant=False, noisy=False):
-    """One forward variant of a case, made once: the twin, and rollout_est(K) on another controller.  Shared by the tests; nobody changes it."""
-    key = (name, own_plant, noisy)
-    if key in _fwd:
-        return _fwd[key]
-    K = rc.CASES[name]['K']
-    io = _inputs(name, own_plant, noisy)
-    Ka, esta, seq, held = _twin(name, io)
-    Kb = _ctrl(name)
-    estb = _estimator(Kb, io['e'], v=io['v'])
-    tr = Kb.rollout_est(K, estb, w=io['w'], Ap=io['Ap'], Bp=io['Bp'])
-    tape = [Kb.prob.rollout_tape(k) for k in range(K)]
-    D, E, cs, _ = Kb.prob.scaling()
-    _fwd[key] = dict(Ka=Ka, Kb=Kb, esta=esta, estb=estb, seq=seq, held=held, tr=tr, tape=tape, io=io, scaling=(D, E, cs), refs={}, seeds=ec.SEEDS[name])
-    return _fwd[key]
-
-
-def _ref_tape(f, name, b):
-    """Instance b's tape in the form of tests/rollout_est_ref.py, from the DEVICE's tape."""
-    c = rc.CASES[name]
-    nx, nu = c['nx'], c['nu']
-    out = []
-    for e in f['tape']:
-        xr = e['step'][b, nx + nu:]
-        out.append(dict(x=e['x'][b], z=e['z'][b], y=e['y'][b], x0=e['step'][b, :nx], um1=e['step'][b, nx:nx + nu],
-                        xref=xr.reshape(-1, nx) if xr.size > nx else xr, solved=bool(e['status'][b] == SOLVED),
-                        x_plant=e['x_plant'][b], y_meas=e['y_meas'][b]))
-    return out
+_ctrl, _inputs, _twin, _forward, _ref_tape = (functools.partial(f, est=True) for f in (rd.ctrl, rd.inputs, rd.twin, rd.forward, rd.ref_tape))
 
 
 def _reference(f, name, b, g):

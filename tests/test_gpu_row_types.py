@@ -4,12 +4,15 @@ through the raw seam.  Per instance against the reduced KKT matrix built from th
 -> workgroup map and the closed loop's carry must not change a result.
 Run on the GPU box with:  python -m pytest tests/test_gpu_row_types.py -m gpu
 """
+import functools
 import warnings
 
 import numpy as np
 import pytest
 
 import row_patterns as rp
+from polish_ref import check_against_spec
+from util import eligible_backends, rel, info_tuple, carry_on_and_off
 
 pytestmark = pytest.mark.gpu
 
@@ -32,21 +35,11 @@ SHAPES = {
 }
 
 
-def _backends(nx, nu, Np, Nc, soft):
-    """Every backend mpcqp_create may be forced to for the shape ('sweeps' = the streaming kernel the shape takes without a
-    register-resident factor: grouped, wide, huge, bordered included)."""
-    out = ['sweeps']
-    if Nc in (None, Np) and (Np + 1) * (nx + nu) <= 128:
-        out.append('dense')
-    if Nc in (None, Np) and nx + nu <= 16 and Np + 1 <= 31:
-        out += ['bcr', 'bcr8', 'bcrt']
-    return out
-
-
-CASES = [(s, t) for s in SHAPES for t in _backends(*SHAPES[s])]
+CASES = [(s, t) for s in SHAPES for t in eligible_backends(*SHAPES[s][:4])]
 CASE_IDS = ['%s-%s' % c for c in CASES]
 FLIPPED = (3, 6)
 _cache = {}
+_oracle = functools.partial(rp.oracle, quiet=True)
 
 
 def _kws(sid):
@@ -71,21 +64,6 @@ def _dev(kws, tag, eps, solve=True, **kw):
     return K
 
 
-def _oracle(kw, eps, solve=True):
-    from pympc_amd import MPCController
-    from oracle.osqp_oracle import OSQP
-    c, attrs = rp.ctor(kw)
-    K = MPCController(**dict(c, eps_abs=eps, eps_rel=eps))
-    for k, v in attrs.items():
-        setattr(K, k, v)
-    K.prob = OSQP()
-    K.solver_settings = dict(max_iter=400000)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        K.setup(solve=solve)
-    return K
-
-
 def _oracle_solves(sid, eps):
     key = (sid, 'solve', eps)
     if key not in _cache:
@@ -105,10 +83,6 @@ def _oracle_iterates(sid, iters):
     return _cache[key]
 
 
-def _rel(a, b):
-    return np.abs(a - b).max() / max(1e-300, np.abs(b).max())
-
-
 def _check_kkt(bp, seed=5):
     """kkt_solve with a different right-hand side per instance, each row against its own reduced KKT matrix: backward error
     <= 1e-12 (tests/test_gpu_gaps.py) and forward error <= 1e-8 (tests/test_gpu_backends.py)."""
@@ -119,7 +93,7 @@ def _check_kkt(bp, seed=5):
         Km = rp.reduced_kkt(bp, b)
         back = np.abs(Km @ sol[b] - rhs[b]).max() / (np.abs(Km) @ np.abs(sol[b]) + np.abs(rhs[b])).max()
         assert back <= 1e-12, (b, back)
-        assert _rel(sol[b], np.linalg.solve(Km, rhs[b])) < 1e-8, b
+        assert rel(sol[b], np.linalg.solve(Km, rhs[b])) < 1e-8, b
 
 
 def _check_solves(K, sid, eps, idx=None):
@@ -135,10 +109,6 @@ def _check_solves(K, sid, eps, idx=None):
         else:
             uo = xo[n_x:n_x + n_u]
             assert np.abs(x[b][n_x:n_x + n_u] - uo).max() <= 1e-6 * max(1e-3, np.abs(uo).max()), b
-
-
-def _info_tuple(infos):
-    return np.array([(i.status, i.iter, i.rho_updates, i.obj_val, i.pri_res, i.dua_res, i.rho) for i in infos], dtype=float)
 
 
 def _mode(tag, nx, nu, Np):
@@ -173,7 +143,7 @@ def test_admm_iterates_match_oracle_per_instance(sid, tag):
         K.prob.iterate(iters)
         x, z, y = K.prob.iterate_state()
         for b, (xo, zo, yo) in enumerate(_oracle_iterates(sid, iters)):
-            assert _rel(x[b], xo) < 1e-8 and _rel(z[b], zo) < 1e-8, (iters, b, _rel(x[b], xo), _rel(z[b], zo))
+            assert rel(x[b], xo) < 1e-8 and rel(z[b], zo) < 1e-8, (iters, b, rel(x[b], xo), rel(z[b], zo))
             assert np.abs(y[b] - yo).max() < 1e-8 * max(1.0, np.abs(yo).max()), (iters, b)
 
 
@@ -196,7 +166,7 @@ def test_reversed_instance_order_gives_bit_identical_results(sid, tag):
     for order in (kws, kws[::-1]):
         K = _dev(order, tag, 1e-3)
         x, y, _ = K.prob.solution()
-        out.append((x, y, _info_tuple(K.prob.infos())) + tuple(K.prob.iterate_state()))
+        out.append((x, y, info_tuple(K.prob.infos())) + tuple(K.prob.iterate_state()))
     for a, b in zip(*out):
         assert np.array_equal(a, b[::-1])
 
@@ -253,7 +223,7 @@ def test_row_type_changes_through_the_seam(sid, tag):
                     uo = xo[n_x:n_x + n_u]
                     assert np.abs(x[b][n_x:n_x + n_u] - uo).max() <= 1e-6 * max(1e-3, np.abs(uo).max()), (k, b)
             assert np.array_equal(x[others], xn[others]) and np.array_equal(y[others], yn[others])
-            assert np.array_equal(_info_tuple(info)[others], _info_tuple(infon)[others])
+            assert np.array_equal(info_tuple(info)[others], info_tuple(infon)[others])
             _check_kkt(Kf.prob, seed=k)
 
 
@@ -308,12 +278,11 @@ def test_headline_kernel_closed_loop_on_mixed_patterns():
 # ---- g. the closed loop's carry on mixed patterns ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize('B', [64, 1024])
 def test_carry_on_mixed_patterns_headline_kernel(B):
-    from test_gpu_loop_carry import _both
     kws = [rp.ctor(rp.draw(s, 12, 4, 30))[0] for s in range(B)]
     assert rp.kinds_present([rp.draw(s, 12, 4, 30) for s in range(B)]) >= rp.ALL_KINDS
     steps = 12
     w = 0.01 * np.random.default_rng(8).standard_normal((steps, B, 12))
-    a, (carried, back, parts) = _both(kws, steps, w=w)
+    a, (carried, back, parts) = carry_on_and_off(kws, steps, w=w)
     assert (parts > 0) == (B == 1024), parts                 # (1024 instances: a persistent launch)
     assert (a['status'] == 1).mean() > 0.9
     assert carried > 0, (carried, back)
@@ -326,7 +295,6 @@ def test_carry_on_mixed_patterns_generic_kernels(sid, tag):
     bit (where the round carries at all), and the device loop against the stepwise API bit for bit.  The batches hold Delta-u equality and loose Delta-u rows (the rows
     latw_carry re-types with u_{-1})."""
     from pympc_amd.solver import forced_settings
-    from test_gpu_loop_carry import _both
     nx, nu, Np, _, _ = SHAPES[sid]
     draws = _kws(sid)
     assert {('du', 'eq'), ('du', 'absent')} <= rp.kinds_present(draws)
@@ -337,7 +305,7 @@ def test_carry_on_mixed_patterns_generic_kernels(sid, tag):
     kn = K.prob.kernel_name(True).replace(' ', '')
     assert kn.split(',')[2:5] == ['0', '0', str(_mode(tag, nx, nu, Np))] and kn.startswith('w8::') == (tag == 'bcr8'), kn
     with forced_settings(backend=tag):
-        a, (carried, back, _) = _both(kws, steps, w=w, expect_latency=False)
+        a, (carried, back, _) = carry_on_and_off(kws, steps, w=w, expect_latency=False)
     # the round carries where it runs the fast termination test (admm_latw: one group of four stages per wave -- every schedule on 512
     # threads, schedule 11 on 256); several groups per wave (schedules 21 and 31 on 256 threads) take the generic check, which never carries
     if tag == 'bcr8' or Np + 1 <= 11:
@@ -359,7 +327,6 @@ def test_carry_on_mixed_patterns_generic_kernels(sid, tag):
 @pytest.mark.parametrize('sid', ['12_4_30', '4_1_20'])
 def test_polish_on_mixed_patterns(sid):
     """Equality and loose rows go through the active-set rule of the polish (tests/polish_ref.py) on every instance."""
-    from test_gpu_polish import _check_against_spec
     K = _dev(_kws(sid), 'auto', 1e-3)
-    st = _check_against_spec(K.prob)
+    st = check_against_spec(K.prob)
     assert (st == 1).any(), st

@@ -8,7 +8,6 @@ infeasibility tolerance, and settings changed between two solves of one handle. 
 at the defaults (tests/test_gpu_gaps.py, tests/test_gpu_parity.py, tests/test_gpu_backends.py).
 Run on the GPU box with:  python -m pytest tests -m gpu
 """
-import contextlib
 import warnings
 
 import numpy as np
@@ -16,26 +15,13 @@ import pytest
 import scipy.sparse as sp
 
 import settings_cases as sc
+from util import rel, forced, stacked_batch, bcr_schedule, shape_of
 
 pytestmark = pytest.mark.gpu
 
 
-def forced(backend, **more):
-    """Controllers built inside the block run on this KKT backend (None: what mpcqp_create picks)."""
-    from pympc_amd.solver import forced_settings
-    kw = dict(more)
-    if backend is not None:
-        kw['backend'] = backend
-    return forced_settings(**kw) if kw else contextlib.nullcontext()
-
-
-def _rel(a, b):
-    return np.abs(a - b).max() / max(1e-300, np.abs(b).max())
-
-
 def _bcr_schedule(case):
-    kw, _ = sc.draw(case)
-    return 11 if kw['Np'] + 1 <= 11 else 21 if kw['Np'] + 1 <= 21 else 31
+    return bcr_schedule(*shape_of(sc.draw(case)[0]))
 
 
 def assert_backend(case, backend, bp):
@@ -102,7 +88,7 @@ def test_scaling_iterates_and_kkt_solve_match_the_oracle(case, backend, setting)
     bp = K.prob.batch_problem
     D, E, c, rho = bp.scaling()
     Do, Eo, co = sc.oracle_iterate(case, setting, 1)[3]
-    assert _rel(D[0], Do) < 1e-12 and _rel(E[0], Eo) < 1e-12 and abs(c[0] - co) / co < 1e-12
+    assert rel(D[0], Do) < 1e-12 and rel(E[0], Eo) < 1e-12 and abs(c[0] - co) / co < 1e-12
     if setting == 'scaling0':
         assert (D[0] == 1.0).all() and (E[0] == 1.0).all() and c[0] == 1.0
     assert rho[0] == st.get('rho', 0.1)
@@ -118,19 +104,18 @@ def test_scaling_iterates_and_kkt_solve_match_the_oracle(case, backend, setting)
     for _ in range(2):
         rhs = rng.standard_normal(P.shape[0])
         sol = bp.kkt_solve(rhs[None])[0]
-        assert _rel(sol, np.linalg.solve(Kmat, rhs)) < 1e-8, (case, backend, setting)
+        assert rel(sol, np.linalg.solve(Kmat, rhs)) < 1e-8, (case, backend, setting)
     for n in (1, 7, 40):
         Kn = _device(case, backend, setting, solve=False)
         Kn.prob.batch_problem.iterate(n)
         x, z, y = Kn.prob.batch_problem.iterate_state()
         xo, zo, yo, _ = sc.oracle_iterate(case, setting, n)
-        assert _rel(x[0], xo) < 1e-8 and _rel(z[0], zo) < 1e-8, (case, backend, setting, n, _rel(x[0], xo), _rel(z[0], zo))
+        assert rel(x[0], xo) < 1e-8 and rel(z[0], zo) < 1e-8, (case, backend, setting, n, rel(x[0], xo), rel(z[0], zo))
         assert np.abs(y[0] - yo).max() < 1e-8 * max(1.0, np.abs(yo).max()), (case, backend, setting, n)
 
 
 # ---- 3. the closed loop on the device -----------------------------------------------------------------------------------------------------
 def _batch(case, setting, **more):
-    from test_gpu_loop_carry import _stacked_batch
     kw, attrs = sc.draw(case)
     kws = []
     for f in sc.LOOPS[(case, setting)]:
@@ -138,7 +123,7 @@ def _batch(case, setting, **more):
         for k in ('uref', 'uminus1', 'umin', 'umax', 'Dumin', 'Dumax'):
             d[k] = np.atleast_1d(np.asarray(d[k], dtype=float))
         kws.append(d)
-    return _stacked_batch(kws, SOFT_ON=attrs.get('SOFT_ON', True), **dict(sc.settings(setting), **more)), kws
+    return stacked_batch(kws, SOFT_ON=attrs.get('SOFT_ON', True), **dict(sc.settings(setting), **more)), kws
 
 
 LOOPS = sc.device_loops()
@@ -202,7 +187,7 @@ def test_warm_start_off_starts_every_solve_from_zero(case, backend):
             O = OSQP(); O.setup(P, q0, A, l0, u0, warm_start=ws, eps_abs=sc.EPS, eps_rel=sc.EPS)
             a = O.solve(); O.update(q=q1, l=l1, u=u1); b = O.solve()
             ref[ws] = (a, b)
-        assert _rel(ref[True][1].x, ref[False][1].x) > 1e-5                  # (a warm second solve would be seen)
+        assert rel(ref[True][1].x, ref[False][1].x) > 1e-5                  # (a warm second solve would be seen)
         with forced(backend):
             dev = DeviceProblem()
             dev.setup(P, q0, A, l0, u0, warm_start=False, eps_abs=sc.EPS, eps_rel=sc.EPS)
@@ -216,13 +201,14 @@ def test_warm_start_off_starts_every_solve_from_zero(case, backend):
 # ---- 5. the infeasibility tolerance -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('st', [dict(eps_prim_inf=1e-7), dict(check_termination=7), dict(eps_prim_inf=1e-7, check_termination=7)],
                          ids=['eps_prim_inf1e-7', 'chk7', 'eps_prim_inf1e-7_chk7'])
+
+
 def test_primal_infeasibility_is_reported_where_the_oracle_reports_it(st):
     """The infeasible point mass of tests/test_gpu_parity.py:172-187: 'primal infeasible' at 75 iterations with eps_prim_inf = 1e-7 (25 at the
     default), at 28 with check_termination = 7, at 119 after four rho updates with both (tests/test_settings_cases.py pins the oracle's
     numbers); x is NaN and output() is uref."""
-    from test_settings_cases import infeasible_point_mass
     from pympc_amd import fixtures
-    K, Ko = infeasible_point_mass(False, **st), infeasible_point_mass(True, **st)
+    K, Ko = sc.infeasible_point_mass(False, **st), sc.infeasible_point_mass(True, **st)
     assert Ko.res.info.status == 'primal infeasible'
     assert sc.triple(K.res.info) == sc.triple(Ko.res.info), (sc.triple(K.res.info), sc.triple(Ko.res.info))
     assert np.all(np.isnan(K.res.x))

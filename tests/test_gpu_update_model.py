@@ -12,30 +12,15 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from util import load_golden, golden_kwargs, apply_attrs
+from util import load_golden, golden_kwargs, controller, rel, stacked_batch, forced, golden_backends
 from ltv_models import new_model, with_model, model_schedule
-from test_gpu_backends import _dense_eligible, _bcr_schedule, backend
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ['cart_pole', 'quadcopter_nc', 'random_12_4_30', 'random_20_8_12_hard', 'point_mass']
-CASES = [(n, t) for n in NAMES for t in (['sweeps'] + (['dense'] if _dense_eligible(n) else []) + (['bcr', 'bcr8', 'bcrt'] if _bcr_schedule(n) else []))]
+CASES = [(n, t) for n in NAMES for t in golden_backends(n)]
 IDS = ['%s-%s' % c for c in CASES]
 ERR_ARG, ERR_UNSUPPORTED, ERR_STATE, NON_CVX = -1, -4, -5, -7
-
-
-def _ctrl(kw, oracle=False, **settings):
-    from pympc_amd import MPCController
-    K = apply_attrs(MPCController(**kw), kw)
-    if oracle:
-        from oracle.osqp_oracle import OSQP
-        K.prob = OSQP()
-    K.solver_settings = dict(settings)
-    return K
-
-
-def _rel(a, b):
-    return np.abs(a - b).max() / max(1e-300, np.abs(b).max())
 
 
 def _info(i):
@@ -68,8 +53,8 @@ def test_qp_scaling_and_iterate_after_update_model(name, tag):
     new = new_model(kw)
     kwn = with_model(kw, new)
     with _quiet():
-        with backend(backend=tag):
-            K = _ctrl(kw); K.setup()
+        with forced(backend=tag):
+            K = controller(kw); K.setup()
             bp = K.prob.batch_problem
             x0, z0, y0 = bp.iterate_state()
             xs0, ys0, i0 = bp.solution()
@@ -79,7 +64,7 @@ def test_qp_scaling_and_iterate_after_update_model(name, tag):
             assert np.array_equal(x0, x1) and np.array_equal(y0, y1)
             assert np.array_equal(xs0, xs1) and np.array_equal(ys0, ys1) and _info(i0[0]) == _info(i1[0])
             # the QP the device now holds
-            Kh = _ctrl(kwn); Kh.x0_rh, Kh.uminus1_rh = np.copy(Kh.x0), np.copy(Kh.uminus1)
+            Kh = controller(kwn); Kh.x0_rh, Kh.uminus1_rh = np.copy(Kh.x0), np.copy(Kh.uminus1)
             Ph, qh, Ah, lh, uh = qp_build.build_qp(Kh)[:5]
             P, q, A, l, u = bp.export_qp()
             U = sp.triu(Ph).toarray()
@@ -87,14 +72,14 @@ def test_qp_scaling_and_iterate_after_update_model(name, tag):
             assert np.allclose(q[0], qh, rtol=2e-15, atol=1e-300)
             assert np.array_equal(l[0], np.clip(lh, -1e30, 1e30)) and np.array_equal(u[0], np.clip(uh, -1e30, 1e30))
             # scaling
-            Kf = _ctrl(kwn); Kf.setup(solve=False)
+            Kf = controller(kwn); Kf.setup(solve=False)
             bf = Kf.prob.batch_problem
             for a, b in zip(bp.scaling(), bf.scaling()):
                 assert np.array_equal(a, b)
-            Ko = _ctrl(kwn, oracle=True); Ko.setup(solve=False)
+            Ko = controller(kwn, oracle=True); Ko.setup(solve=False)
             D, E, c, rho = bp.scaling()
             Do, Eo, co = Ko.prob.scaling()
-            assert _rel(D[0], Do) < 1e-12 and _rel(E[0], Eo) < 1e-12 and abs(c[0] - co) / co < 1e-12
+            assert rel(D[0], Do) < 1e-12 and rel(E[0], Eo) < 1e-12 and abs(c[0] - co) / co < 1e-12
             assert rho[0] == 0.1
             # one iteration from the kept iterate = one iteration of the setup + warm_start route
             Kf.prob.warm_start(x=x0[0], y=y0[0])
@@ -112,27 +97,27 @@ def test_solve_after_update_model(name, tag):
     new = new_model(kw)
     kwn = with_model(kw, new)
     with _quiet():
-        with backend(backend=tag):
-            K = _ctrl(kw); K.setup()
+        with forced(backend=tag):
+            K = controller(kw); K.setup()
             x0, _, y0 = K.prob.batch_problem.iterate_state()
             K.update_model(**new)
-            Kf = _ctrl(kwn); Kf.setup(solve=False)
+            Kf = controller(kwn); Kf.setup(solve=False)
             Kf.prob.warm_start(x=x0[0], y=y0[0])
             Kf.solve()
             assert np.array_equal(K.res.x, Kf.res.x) and np.array_equal(K.res.y, Kf.res.y)
             assert _res_info(K.res) == _res_info(Kf.res)
-            Ko = _ctrl(kwn, oracle=True); Ko.setup(solve=False)
+            Ko = controller(kwn, oracle=True); Ko.setup(solve=False)
             Ko.prob.warm_start(x=x0[0], y=y0[0])
             Ko.solve()
             assert K.res.info.status == Ko.res.info.status and K.res.info.iter == Ko.res.info.iter
             assert K.res.info.rho_updates == Ko.res.info.rho_updates
-            assert _rel(K.res.x, Ko.res.x) < 1e-6
+            assert rel(K.res.x, Ko.res.x) < 1e-6
             # tight tolerance
             tight = dict(eps_abs=1e-9, eps_rel=1e-9)
-            Kt = _ctrl(with_model(kw, tight), max_iter=200000); Kt.setup()
+            Kt = controller(with_model(kw, tight), max_iter=200000); Kt.setup()
             xt, _, yt = Kt.prob.batch_problem.iterate_state()
             Kt.update_model(**new)
-            Kot = _ctrl(with_model(kwn, tight), oracle=True, max_iter=200000); Kot.setup(solve=False)
+            Kot = controller(with_model(kwn, tight), oracle=True, max_iter=200000); Kot.setup(solve=False)
             Kot.prob.warm_start(x=xt[0], y=yt[0])
             Kot.solve()
             assert Kt.res.info.status == 'solved' and Kot.res.info.status == 'solved'
@@ -152,22 +137,21 @@ def _solution_bytes(bp):
 
 @pytest.mark.parametrize('tag', ['sweeps', 'bcr', 'bcr8'])
 def test_batch_with_a_different_model_per_instance_and_only_some_fields(tag):
-    from test_gpu_parity import _stacked_batch
     B = 6
     kws = _batch_kws(B)
     news = [new_model(kw, seed=10 + i) for i, kw in enumerate(kws)]
     fields = ('Bd', 'Qx', 'umax', 'Dumin')
     stack = lambda k: np.stack([n[k] for n in news])
     with _quiet():
-        with backend(backend=tag):
-            K = _stacked_batch(kws); K.setup()
+        with forced(backend=tag):
+            K = stacked_batch(kws); K.setup()
             K.update(np.stack([0.9 * np.asarray(kw['x0']) for kw in kws]))        # a warm solve: the iterate is not the cold start's
             x0, _, y0 = K.prob.iterate_state()
             u_before = K.prob.u0()
             K.update_model(solve=False, **{k: stack(k) for k in fields})
             assert np.array_equal(K.prob.u0(), u_before)
             K.solve()
-            Kf = _stacked_batch([dict(kw, **{k: n[k] for k in fields}, x0=0.9 * np.asarray(kw['x0'])) for kw, n in zip(kws, news)]); Kf.setup(solve=False)
+            Kf = stacked_batch([dict(kw, **{k: n[k] for k in fields}, x0=0.9 * np.asarray(kw['x0'])) for kw, n in zip(kws, news)]); Kf.setup(solve=False)
             Kf.prob.warm_start(x0, y0)
             Kf.solve()
             a, b = _solution_bytes(K.prob), _solution_bytes(Kf.prob)
@@ -181,7 +165,6 @@ def test_shared_factor_survives_a_model_update():
     """One model in every instance, then one NEW model in every instance: the whole batch shares instance 0's factor again, and the results are
     those of a batch that never shares (MPCQP_TUNE_NO_SHARE)."""
     from pympc_amd import fixtures, _lib
-    from test_gpu_parity import _stacked_batch
     B = 8
     kw = fixtures.random_lti(41, nx=20, nu=8, Np=12, xbox=3.0)                   # 32 x 32 stages: the streaming backend
     new = new_model(kw, seed=5)
@@ -190,7 +173,7 @@ def test_shared_factor_survives_a_model_update():
     out = {}
     with _quiet():
         for tuning in (0, _lib.TUNE_NO_SHARE):
-            K = _stacked_batch([kw] * B, tuning=tuning); K.setup()
+            K = stacked_batch([kw] * B, tuning=tuning); K.setup()
             if not tuning:
                 assert K.share_factor() == B
             K.update(xs)
@@ -214,11 +197,11 @@ def test_step_host_and_polish_after_update_model(name, polish):
     new = new_model(kw)
     x1 = 0.95 * np.asarray(kw['x0'], dtype=float)
     with _quiet():
-        K = _ctrl(kw, polish=polish); K.setup()
+        K = controller(kw, polish=polish); K.setup()
         x0, _, y0 = K.prob.batch_problem.iterate_state()
         K.update_model(solve=False, **new)
         K.update(x1)
-        Kf = _ctrl(with_model(kw, new), polish=polish); Kf.setup(solve=False)
+        Kf = controller(with_model(kw, new), polish=polish); Kf.setup(solve=False)
         Kf.prob.warm_start(x=x0[0], y=y0[0])
         Kf.update(x1)
         assert np.array_equal(K.res.x, Kf.res.x) and np.array_equal(K.res.y, Kf.res.y)
@@ -235,7 +218,7 @@ def test_raw_vector_mode_keeps_q_l_u():
     from pympc_amd.solver import DeviceProblem
     kw = golden_kwargs(load_golden('random_12_4_30'))
     new = {k: v for k, v in new_model(kw).items() if k in ('Ad', 'Bd')}
-    build = lambda kws: (lambda K: qp_build.build_qp(K)[:5])(_ctrl(kws))
+    build = lambda kws: (lambda K: qp_build.build_qp(K)[:5])(controller(kws))
     P, q, A, l, u = build(kw)
     Pn, qn, An, ln, un = build(with_model(kw, new))
     assert np.array_equal(q, qn) and np.array_equal(l, ln) and np.array_equal(u, un)      # (only A changes with Ad, Bd)
@@ -261,7 +244,6 @@ def test_raw_vector_mode_keeps_q_l_u():
 def test_loop_tv_is_the_segment_sequence_written_on_the_host(B, hold):
     """run(model_traj=) = per entry update_model(entry, solve=False) and run(min(hold, rest)) on the advanced trajectories, bit for bit -- at a
     batch that is resident at once and at one that goes through the persistent queue; nsteps is not a multiple of hold."""
-    from test_gpu_parity import _stacked_batch
     nsteps = 7
     nm = (nsteps + hold - 1) // hold
     kws = _batch_kws(B, seed0=3000)
@@ -269,8 +251,8 @@ def test_loop_tv_is_the_segment_sequence_written_on_the_host(B, hold):
     Adt, Bdt = np.stack([s[0] for s in sched], axis=1), np.stack([s[1] for s in sched], axis=1)      # [nm, B, ...]
     wn = 0.01 * np.random.default_rng(4).standard_normal((nsteps, B, 12))
     with _quiet():
-        Kd = _stacked_batch(kws); Kd.setup()
-        Ks = _stacked_batch(kws); Ks.setup()
+        Kd = stacked_batch(kws); Kd.setup()
+        Ks = stacked_batch(kws); Ks.setup()
         tr = Kd.run(nsteps, w=wn, model_traj=(Adt, Bdt, hold))
         xs, us, ss, its = [], [], [], []
         for s in range(nm):
@@ -299,15 +281,14 @@ def test_loop_tv_matches_the_oracle_stepped_in_python(name, hold):
     'solved'.  The schedule is tests/ltv_models.model_schedule at amplitude 0.03: a seeded smooth perturbation of Ad, Bd under which the oracle ALONE
     (its own plant, CPU only) ends all 14 steps 'solved' on these fixtures at hold 1 and 3 -- checked at 0.03 and 0.1 when the test was written.  The
     oracle is stepped with the device's states and inputs, like the stepwise controller of test_device_loop_matches_stepwise_api."""
-    from test_gpu_parity import _stacked_batch
     nsteps = 14
     nm = (nsteps + hold - 1) // hold
     kw = golden_kwargs(load_golden(name))
     kt = with_model(kw, dict(eps_abs=1e-9, eps_rel=1e-9))
     Adt, Bdt = model_schedule(kw['Ad'], kw['Bd'], nm, amp=0.03)
     with _quiet():
-        Kd = _stacked_batch([kt], eps_abs=1e-9, eps_rel=1e-9, max_iter=100000); Kd.setup()
-        Ko = _ctrl(kt, oracle=True, max_iter=100000); Ko.setup()
+        Kd = stacked_batch([kt], eps_abs=1e-9, eps_rel=1e-9, max_iter=100000); Kd.setup()
+        Ko = controller(kt, oracle=True, max_iter=100000); Ko.setup()
         assert Ko.res.info.status == 'solved'
         tr = Kd.run(nsteps, model_traj=(Adt[:, None], Bdt[:, None], hold))
         for k in range(nsteps):
@@ -325,14 +306,13 @@ def test_loop_tv_matches_the_oracle_stepped_in_python(name, hold):
 def test_loop_tv_with_device_resident_buffers_and_no_schedule():
     """Everything in device memory (torch tensors): the same numbers as with host arrays; model_traj=None is mpcqp_mpc_loop."""
     import torch
-    from test_gpu_parity import _stacked_batch
     B, nsteps, hold = 5, 6, 2
     kws = _batch_kws(B, seed0=3500)
     sched = [model_schedule(kw['Ad'], kw['Bd'], 3, seed=i) for i, kw in enumerate(kws)]
     Adt, Bdt = np.stack([s[0] for s in sched], axis=1), np.stack([s[1] for s in sched], axis=1)
     with _quiet():
-        Kh = _stacked_batch(kws); Kh.setup()
-        Kd = _stacked_batch(kws); Kd.setup()
+        Kh = stacked_batch(kws); Kh.setup()
+        Kd = stacked_batch(kws); Kd.setup()
         th = Kh.run(nsteps, model_traj=(Adt, None, hold))
         dev = lambda a, dt=torch.float64: torch.zeros(a.shape, dtype=dt, device='cuda')
         out = [dev(th['x']), dev(th['u']), dev(th['status'], torch.int32), dev(th['iter'], torch.int32)]
@@ -349,7 +329,6 @@ def test_loop_tv_with_device_resident_buffers_and_no_schedule():
 def test_error_codes():
     from pympc_amd import _lib
     from pympc_amd.solver import BatchProblem
-    from test_gpu_parity import _stacked_batch
     L = _lib.load()
     assert _lib.has_model_update(L)
     kws = _batch_kws(2)
@@ -366,7 +345,7 @@ def test_error_codes():
     with pytest.raises(ValueError):
         bp.update_model()
     with _quiet():
-        K = _stacked_batch(kws); K.setup()
+        K = stacked_batch(kws); K.setup()
     h = K.prob._h
     assert L.mpcqp_update_model(h, None) == ERR_ARG and L.mpcqp_update_model(h, C.byref(_lib.Model())) == ERR_ARG
     before = _solution_bytes(K.prob)
@@ -409,8 +388,8 @@ def test_indefinite_qx_reports_non_convex(tag):
     iterate is kept, so a good model given before the next solve clears the verdict and solves."""
     kw = golden_kwargs(load_golden('cart_pole'))
     with _quiet():
-        with backend(backend=tag):
-            K = _ctrl(kw); K.setup()
+        with forced(backend=tag):
+            K = controller(kw); K.setup()
             bp = K.prob.batch_problem
             K.update_model(Qx=-1e6 * np.eye(4), QxN=-1e6 * np.eye(4), solve=False)
             i = bp.infos()[0]

@@ -2,28 +2,9 @@
 headline batch), two for 32 x 32 stages, one for the latency kernels (register-resident factor).  A shared non-inlined phase
 once inherited the one-per-CU register budget and silently halved the headline throughput -- so the compiler's own
 resource remarks of the build (pympc_amd/libmpcqp_hip.kernel_resources.txt, written by csrc/build.sh) are checked."""
-import os
 import re
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PATH = os.path.join(ROOT, 'pympc_amd', 'libmpcqp_hip.kernel_resources.txt')
-
-
-def _kernels():
-    if not os.path.exists(PATH):
-        pytest.skip('no kernel_resources.txt next to the library (built without csrc/build.sh)')
-    out, cur = {}, None
-    for line in open(PATH):
-        m = re.match(r'\s*Function Name: (\S+)', line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.match(r'\s*([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+)', line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
-    return out
+from util import kernel_resources
 
 
 def _run_kernels(ks):
@@ -37,7 +18,7 @@ def _run_kernels(ks):
 
 
 def test_occupancy_of_the_solve_kernels():
-    rk = _run_kernels(_kernels())
+    rk = _run_kernels(kernel_resources())
     assert rk, 'no k_mpc_run instantiation in the resource remarks'
     for (nb, lds, nxt, nut, mode, loop), v in rk.items():
         vg, occ = int(v['VGPRs']), int(v['Occupancy'])
@@ -54,7 +35,7 @@ def test_the_512_thread_latency_kernels_fit_two_waves_per_simd():
     """mpcqp_w8.hip: eight waves per workgroup share a compute unit's four SIMDs two by two, so a wave has 256 registers -- the kernels must
     be allocated for exactly that (occupancy 2), and the scratch the whole call tree asks for stays small (the hot loop itself is
     spill-free: the factorization phase is what uses it)."""
-    ks = _kernels()
+    ks = kernel_resources()
     w8 = {n: v for n, v in ks.items() if n.startswith('_ZN2w89k_mpc_runILi16E')}
     # cyclic reduction: (12,4) and generic at 31 stages, generic at 21 and 11; grouped stages (the reference cart pole and generic), with and without a held
     # input; solve and closed loop of each
@@ -70,7 +51,7 @@ def test_scratch_of_the_hot_kernels_stays_where_it_was():
     seen with ROCm 7.2 (bytes per lane over the kernel's call tree; the ADMM phases themselves use 6-10 scratch instructions, SGPR spill lanes):
     628 / 500 for the four-per-CU kernels (their factorization phase), 68 for 32 x 32 stages, 244 / 116 for the 512-thread latency kernels,
     68 for the 512-thread cart-pole kernels."""
-    ks = _kernels()
+    ks = kernel_resources()
     rk = _run_kernels(ks)
     # (round 6: the kernel's own frame grew by ~ 60 bytes -- the persistent loop around the instance -- 780 / 668 for the four-per-CU kernels, 316 / 204 for the
     #  512-thread latency kernels, whose ADMM phase itself went from 148 to 80 bytes)
@@ -87,7 +68,7 @@ def test_scratch_of_the_hot_kernels_stays_where_it_was():
 def test_the_adjoint_kernels():
     """k_adjoint<16> holds the one-seed and the four-column code at the full register budget of one workgroup per CU without scratch
     (DESIGN.md section 5f); the wider instantiations exist and are resident."""
-    ks = _kernels()
+    ks = kernel_resources()
     ad = {int(m.group(1)): v for n, v in ks.items() for m in [re.match(r'_Z9k_adjointILi(\d+)EE', n)] if m}
     assert sorted(ad) == [16, 32, 64, 128], sorted(ad)
     assert int(ad[16]['ScratchSize']) == 0 and int(ad[16]['VGPRs']) == 256 and int(ad[16]['Occupancy']) >= 1, ad[16]
@@ -98,7 +79,7 @@ def test_the_adjoint_kernels():
 def test_the_polish_kernels():
     """k_polish<16> shares K_pol's factorization and refined solve with k_adjoint (mpcqp_kpol.h, every helper force-inlined) and, like it,
     runs one workgroup per CU at the full register budget; the wider instantiations exist and are resident; none has scratch."""
-    ks = _kernels()
+    ks = kernel_resources()
     po = {int(m.group(1)): v for n, v in ks.items() for m in [re.match(r'_Z8k_polishILi(\d+)EE', n)] if m}
     assert sorted(po) == [16, 32, 64, 128], sorted(po)
     assert int(po[16]['VGPRs']) == 256, po[16]

@@ -2,70 +2,28 @@
 _lib.MODEL_SYMBOLS -- never by _lib.SYMBOLS, which stays the list of mpcqp.h --, its struct is mirrored field by field by _lib.ModelTraj,
 and a library without it (the CPU twin under oracle/) still loads and runs the package, which then takes the generic route."""
 import ctypes as C
-import os
-import re
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
 from util import load_golden, golden_kwargs
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header(name):
-    return re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', name)).read(), flags=re.S)
-
-
-def _functions(text):
-    text = re.sub(r'typedef struct \{.*?\}\s*\w+\s*;', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(mpcqp_\w+)\s*\(', text)))
-
-
-def _struct(text, name):
-    """[(field, kind)] of `typedef struct { ... } name;`, kind in {'double', 'int32', 'ptr'}."""
-    body = re.search(r'typedef struct \{([^{}]*)\}\s*%s\s*;' % name, text).group(1)
-    fields = []
-    for decl in body.split(';'):
-        decl = ' '.join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r'(const )?(double|int32_t)\s*(.*)', decl)
-        assert m, decl
-        for item in m.group(3).split(','):
-            item = item.strip()
-            fields.append((item.lstrip('* ').strip(), 'ptr' if item.startswith('*') else ('double' if m.group(2) == 'double' else 'int32')))
-    return fields
+from abi import header, header_struct, header_functions, twin      # noqa: F401  (twin: a fixture)
 
 
 def test_model_symbols_are_the_header_and_stay_out_of_the_core_list():
     from pympc_amd import _lib
-    assert sorted(_lib.MODEL_SYMBOLS) == _functions(_header('mpcqp_model.h'))
+    assert sorted(_lib.MODEL_SYMBOLS) == header_functions(header('mpcqp_model.h'))
     assert not set(_lib.MODEL_SYMBOLS) & set(_lib.SYMBOLS)
-    assert not set(_lib.MODEL_SYMBOLS) & set(_functions(_header('mpcqp.h')))
+    assert not set(_lib.MODEL_SYMBOLS) & set(header_functions(header('mpcqp.h')))
 
 
 def test_model_traj_mirrors_the_header():
     from pympc_amd import _lib
     kind = lambda t: 'double' if t is C.c_double else ('int32' if t in (C.c_int32, C.c_int) else 'ptr')
-    assert [(n, kind(t)) for n, t in _lib.ModelTraj._fields_] == _struct(_header('mpcqp_model.h'), 'mpcqp_model_traj')
+    assert [(n, kind(t)) for n, t in _lib.ModelTraj._fields_] == header_struct(header('mpcqp_model.h'), 'mpcqp_model_traj')
     assert C.sizeof(_lib.ModelTraj) == 4 * 4 + 2 * 8
     assert _lib.ModelTraj.Ad.offset == 16 and _lib.ModelTraj.Bd.offset == 24
-
-
-@pytest.fixture
-def twin():
-    """pympc_amd bound to the CPU twin for one test (as in tests/test_cpu_twin.py)."""
-    from pympc_amd import _lib
-    subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'oracle'), 'libmpcqp_cpu.so'])
-    old = (_lib.LIB_PATH, _lib._lib)
-    _lib.LIB_PATH, _lib._lib = os.path.join(ROOT, 'oracle', 'libmpcqp_cpu.so'), None
-    try:
-        yield _lib.load()
-    finally:
-        _lib.LIB_PATH, _lib._lib = old
 
 
 def test_twin_lacks_the_model_symbols_and_the_package_still_loads(twin):

@@ -2,34 +2,17 @@
 pympc_amd._lib outside SYMBOLS, its settings struct mirrored field by field, its defaults OSQP's; a library without it (the CPU twin)
 refuses polish=True instead of ignoring it.  No GPU needed."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
 
-from test_abi_layout import header_struct, _strip_comments
+from abi import header, header_struct, header_functions, lib_loaded, twin      # noqa: F401  (twin: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-POLISH_HEADER = open(os.path.join(ROOT, 'include', 'mpcqp_polish.h')).read()
-
-
-def _polish_functions():
-    text = re.sub(r'typedef struct \{.*?\}\s*\w+\s*;', '', _strip_comments(POLISH_HEADER), flags=re.S)
-    return sorted(set(re.findall(r'\b(mpcqp_\w+)\s*\(', text)))
-
-
-def _lib_loaded():
-    import __graft_entry__ as g
-    from pympc_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib, _lib.load()
+POLISH_HEADER = header('mpcqp_polish.h')
 
 
 def test_polish_functions_exported_and_bound():
-    _lib, L = _lib_loaded()
-    names = _polish_functions()
+    _lib, L = lib_loaded()
+    names = header_functions(POLISH_HEADER)
     assert names == sorted(_lib.POLISH_SYMBOLS)
     assert not set(names) & set(_lib.SYMBOLS)            # mpcqp.h's list is unchanged
     for n in names:
@@ -40,20 +23,14 @@ def test_polish_functions_exported_and_bound():
 
 def test_polish_struct_mirrors_the_header():
     from pympc_amd import _lib
-    import test_abi_layout
-    old = test_abi_layout.HEADER
-    test_abi_layout.HEADER = POLISH_HEADER
-    try:
-        fields = header_struct('mpcqp_polish_settings')
-    finally:
-        test_abi_layout.HEADER = old
+    fields = header_struct(POLISH_HEADER, 'mpcqp_polish_settings')
     kind = lambda t: 'double' if t is C.c_double else ('int32' if t in (C.c_int32, C.c_int) else 'ptr')
     assert [(n, kind(t)) for n, t in _lib.PolishSettings._fields_] == fields
     assert C.sizeof(_lib.PolishSettings) == 4 + 4 + 8 + 4 + 4
 
 
 def test_polish_defaults_are_osqps():
-    _lib, L = _lib_loaded()
+    _lib, L = lib_loaded()
     s = _lib.PolishSettings()
     L.mpcqp_polish_default_settings(C.byref(s))
     assert s.struct_size == C.sizeof(_lib.PolishSettings)
@@ -69,24 +46,12 @@ def test_polish_settings_are_no_longer_ignored():
 
 
 def test_set_polish_checks_its_arguments_without_a_handle():
-    _lib, L = _lib_loaded()
+    _lib, L = lib_loaded()
     s = _lib.PolishSettings()
     L.mpcqp_polish_default_settings(C.byref(s))
     assert L.mpcqp_set_polish(None, C.byref(s)) == -1
     assert L.mpcqp_polish(None) == -1
     assert L.mpcqp_get_polish_info(None, None) == -1
-
-
-@pytest.fixture
-def twin():
-    from pympc_amd import _lib
-    subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'oracle'), 'libmpcqp_cpu.so'])
-    old = (_lib.LIB_PATH, _lib._lib)
-    _lib.LIB_PATH, _lib._lib = os.path.join(ROOT, 'oracle', 'libmpcqp_cpu.so'), None
-    try:
-        yield _lib.load()
-    finally:
-        _lib.LIB_PATH, _lib._lib = old
 
 
 def test_polish_true_against_the_cpu_twin_is_refused(twin):

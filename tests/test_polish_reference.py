@@ -10,18 +10,9 @@ import numpy as np
 import pytest
 
 from util import golden_names, load_golden
-from polish_ref import golden_qp, polish
+from polish_ref import golden_qp, polish, EXACT, ACCEPTED, EXACT_SCALED
 
 EPS = 1e-3
-# fixtures on which polishing the oracle's eps-1e-3 iterate reaches x* to 1e-8 (measured by this file)
-EXACT = ['cart_pole_nc1', 'point_mass', 'point_mass_hard', 'point_mass_nc', 'quadcopter_nc', 'quadcopter_nodu', 'random_12_4_30',
-         'random_12_4_30_b', 'random_12_4_30_hard', 'random_20_8_12_hard', 'random_5_3_8_nc', 'random_5_3_8_nc_hard', 'small_mimo']
-# ... and on which it is accepted (EXACT and these)
-ACCEPTED = EXACT + ['accel_brake', 'accel_brake_hard', 'cart_pole', 'cart_pole_kalman']
-# the same with the oracle's default Ruiz scaling and its own (D, E, c) -- what the device does: the same fixtures are accepted; the iterate the
-# scaled iteration stops at gets the active set right (x* to 1e-8) on these
-EXACT_SCALED = ['accel_brake', 'accel_brake_hard', 'point_mass_nc', 'quadcopter_nc', 'quadcopter_nodu', 'random_12_4_30', 'random_12_4_30_b',
-                'random_12_4_30_hard', 'random_20_8_12_hard', 'random_5_3_8_nc', 'random_5_3_8_nc_hard', 'small_mimo']
 
 
 def oracle_polish(name, eps=EPS):

@@ -4,29 +4,14 @@ import numpy as np
 import pytest
 
 from pympc_amd.controller import MPCController
-from util import golden_names, load_golden, golden_kwargs, golden_csc, update_steps, apply_attrs
-
-
-class _NullProb:
-    """Stands in for the solver so that only the host logic runs (like the capture stub)."""
-    def __init__(self):
-        self.n = None
-    def setup(self, P, q, A, l, u, **kw):
-        self.n = P.shape[0]
-        self.kw = kw
-    def update(self, **kw):
-        self.last = kw
-    def solve(self):
-        class R: pass
-        r = R(); r.x = np.zeros(self.n); r.info = R(); r.info.status = 'solved'; r.info.obj_val = 0.0
-        return r
+from util import golden_names, load_golden, golden_kwargs, golden_csc, update_steps, apply_attrs, NullProb
 
 
 @pytest.mark.parametrize('name', golden_names())
 def test_build_matches_reference(name):
     g = load_golden(name)
     K = apply_attrs(MPCController(**golden_kwargs(g)), golden_kwargs(g))
-    K.prob = _NullProb()
+    K.prob = NullProb()
     K.setup(solve=False)
     for which, M in (('P', K.P), ('A', K.A)):
         R = golden_csc(g, which)
@@ -47,7 +32,7 @@ def test_build_matches_reference(name):
 def test_update_matches_reference(name):
     g = load_golden(name)
     K = apply_attrs(MPCController(**golden_kwargs(g)), golden_kwargs(g))
-    K.prob = _NullProb()
+    K.prob = NullProb()
     K.setup(solve=False)
     for s, st in enumerate(update_steps(g)):
         K.update(st['x'], u=st['u'], xref=st['xref'], solve=False)

@@ -4,26 +4,22 @@ CPU twin) makes the Python methods raise NotImplementedError.  No GPU needed."""
 import ctypes as C
 import hashlib
 import os
-import re
 
 import numpy as np
 import pytest
 
-from test_abi_layout import _strip_comments
-from test_adjoint_abi import _lib_loaded, twin, OLDER_HEADERS      # noqa: F401  (twin: a fixture)
-from test_adjoint_model_abi import _struct, ADJOINT_HEADER_SHA256
+from util import repeated
+from abi import ROOT, header, header_struct, header_functions, lib_loaded, OLDER_HEADERS, ADJOINT_HEADER_SHA256, ADJOINT_MODEL_HEADER_SHA256
+from abi import twin      # noqa: F401  (a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, 'include', 'mpcqp_rollout.h')).read()
-ADJOINT_MODEL_HEADER_SHA256 = 'f76953e39fa025bfa214a6583c869c633d8a432f86e2631fac754d6156cbdc41'
+HEADER = header('mpcqp_rollout.h')
 FUNCTIONS = ['mpcqp_get_rollout_info', 'mpcqp_rollout', 'mpcqp_rollout_adjoint', 'mpcqp_rollout_get_tape', 'mpcqp_rollout_release',
              'mpcqp_rollout_tape_bytes']
 
 
 def test_the_functions_are_exported_and_bound():
-    _lib, L = _lib_loaded()
-    text = re.sub(r'typedef struct \{.*?\}\s*\w+\s*;', '', _strip_comments(HEADER), flags=re.S)
-    names = sorted(set(re.findall(r'\b(mpcqp_\w+)\s*\(', text)))
+    _lib, L = lib_loaded()
+    names = header_functions(HEADER)
     assert names == sorted(_lib.ROLLOUT_SYMBOLS) == FUNCTIONS
     assert not set(names) & set(_lib.SYMBOLS + _lib.POLISH_SYMBOLS + _lib.MODEL_SYMBOLS + _lib.ADJOINT_SYMBOLS + _lib.ADJOINT_MODEL_SYMBOLS)
     for n in names:
@@ -36,7 +32,7 @@ def test_the_struct_mirrors_the_header():
     from pympc_amd import _lib
     kind = lambda t: 'double' if t is C.c_double else ('int32' if t in (C.c_int32, C.c_int) else 'ptr')
     fields = [(n, kind(t)) for n, t in _lib.RolloutAdjointIO._fields_]
-    assert fields == _struct('mpcqp_rollout_adjoint_io', HEADER)
+    assert fields == header_struct(HEADER, 'mpcqp_rollout_adjoint_io')
     assert [n for n, _ in fields] == ['struct_size', 'no_reuse', 'G_x', 'G_u', 'lam', 'd_uminus1', 'd_uref', 'd_xref', 'd_Ap', 'd_Bp']
     assert C.sizeof(_lib.RolloutAdjointIO) == 4 + 4 + 8 * 8
     assert 'mpcqp_loop' in HEADER and 'mpcqp_adjoint_model_io' in HEADER      # (the forward call takes the loop's struct, the sweep the model gradients')
@@ -53,7 +49,7 @@ def test_every_older_header_is_unchanged():
 
 
 def test_the_calls_check_their_arguments_without_a_handle():
-    _lib, L = _lib_loaded()
+    _lib, L = lib_loaded()
     io, lo, mo = _lib.RolloutAdjointIO(), _lib.Loop(), _lib.AdjointModelIO()
     n = C.c_int64()
     assert L.mpcqp_rollout(None, 3, C.byref(lo)) == -1
@@ -68,10 +64,7 @@ def test_a_rollout_against_the_cpu_twin_is_refused(twin):
     from pympc_amd import _lib, fixtures, BatchMPCController
     assert not _lib.has_rollout(twin)
     kw = fixtures.point_mass()
-    st = lambda a: np.stack([np.asarray(a, dtype=float)] * 2)
-    Kb = BatchMPCController(st(kw['Ad']), st(kw['Bd']), Np=kw['Np'], x0=st(kw['x0']), xref=st(kw['xref']), uref=st(kw['uref']),
-                            Qx=st(kw['Qx']), QxN=st(kw['QxN']), Qu=st(kw['Qu']), QDu=st(kw['QDu']), xmin=st(kw['xmin']), xmax=st(kw['xmax']),
-                            umin=st(kw['umin']), umax=st(kw['umax']), Dumin=st(kw['Dumin']), Dumax=st(kw['Dumax']), eps_feas=kw.get('eps_feas', 1e6))
+    Kb = BatchMPCController(**repeated(kw, 2, uminus1=None, eps_feas=kw.get('eps_feas', 1e6)))      # (u_{-1}: the constructor's default)
     Kb.setup()
     tr = Kb.run(2)                                         # everything else works as before
     assert tr['x'].shape == (3, 2, 2)

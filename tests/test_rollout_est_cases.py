@@ -3,7 +3,6 @@ against central differences of the stepped output-feedback loop on the oracle, a
 compiled from the header.  No GPU needed."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -157,11 +156,9 @@ def test_the_struct_is_the_one_a_c_compiler_lays_out(tmp_path):
 
 
 def test_the_functions_are_the_headers_and_a_library_without_them_is_refused():
-    from test_abi_layout import _strip_comments
     from pympc_amd import _lib
-    header = open(os.path.join(ROOT, 'include', 'mpcqp_rollout_est.h')).read()
-    text = re.sub(r'typedef struct \{.*?\}\s*\w+\s*;', '', _strip_comments(header), flags=re.S)
-    assert sorted(set(re.findall(r'\b(mpcqp_\w+)\s*\(', text))) == sorted(_lib.ROLLOUT_EST_SYMBOLS) == FUNCTIONS
+    from abi import header, header_functions
+    assert header_functions(header('mpcqp_rollout_est.h')) == sorted(_lib.ROLLOUT_EST_SYMBOLS) == FUNCTIONS
     assert not set(FUNCTIONS) & set(_lib.SYMBOLS + _lib.ROLLOUT_SYMBOLS + _lib.ADJOINT_SYMBOLS + _lib.ADJOINT_MODEL_SYMBOLS + _lib.MODEL_SYMBOLS + _lib.POLISH_SYMBOLS)
 
     class Without:                                         # a library that exports none of them

@@ -3,11 +3,11 @@ is resident.  It carries k_adjoint's state and the recursion's on top, so it may
 number is pinned here.  k_adjoint and k_polish keep theirs (tests/test_kernel_resources.py)."""
 import re
 
-from test_kernel_resources import _kernels
+from util import kernel_resources
 
 
 def test_the_rollout_kernels():
-    ks = _kernels()
+    ks = kernel_resources()
     ro = {int(m.group(1)): v for n, v in ks.items() for m in [re.match(r'_Z17k_rollout_adjointILi(\d+)EE', n)] if m}
     assert sorted(ro) == [16, 32, 64, 128], sorted(ro)
     for nb, v in ro.items():

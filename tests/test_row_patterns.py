@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import row_patterns as rp
-from test_cpu_twin import twin  # noqa: F401  (fixture)
+from abi import twin  # noqa: F401  (fixture)
 
 # the pinned shapes of tests/test_gpu_row_types.py: (nx, nu, Np, Nc, soft)
 SHAPES = [(12, 4, 30, None, True), (10, 3, 30, None, True), (6, 2, 20, None, True), (12, 4, 10, None, True), (3, 1, 30, None, True),
@@ -70,19 +70,6 @@ def test_pinned_batches_hold_every_row_kind(shape):
         kw = new
 
 
-def _oracle(kw, eps):
-    from pympc_amd import MPCController
-    from oracle.osqp_oracle import OSQP
-    c, attrs = rp.ctor(kw)
-    K = MPCController(**dict(c, eps_abs=eps, eps_rel=eps))
-    for k, v in attrs.items():
-        setattr(K, k, v)
-    K.prob = OSQP()
-    K.solver_settings = dict(max_iter=400000)
-    K.setup()
-    return K
-
-
 @pytest.mark.parametrize('shape', [SHAPES[0], SHAPES[4], SHAPES[11], SHAPES[13]], ids=[IDS[0], IDS[4], IDS[11], IDS[13]])
 def test_mixed_batch_and_type_changes_through_the_twin(twin, shape):  # noqa: F811
     """The mixed batch on the twin, then three successive flip_types updates of every instance through update_vectors, against the oracle
@@ -95,7 +82,7 @@ def test_mixed_batch_and_type_changes_through_the_twin(twin, shape):  # noqa: F8
         warnings.simplefilter('ignore')
         K = BatchMPCController(**rp.stack(kws, eps_abs=1e-9, eps_rel=1e-9, max_iter=400000))
         K.setup()
-        Ko = [_oracle(kw, 1e-9) for kw in kws]
+        Ko = [rp.oracle(kw, 1e-9) for kw in kws]
         rngs = [np.random.default_rng(100 + b) for b in range(len(kws))]
         cur = list(kws)
         for step in range(4):

@@ -1,14 +1,10 @@
 """The table of tests/settings_cases.py pinned on the CPU oracle: every listed pair and loop keeps its counts across the tolerance band, every
 setting is listed for every kernel family and can be told from the defaults where it is listed, the paths the settings are named for are taken,
 and a run whose last iteration was not a checked one ends as osqp_solve ends it (oracle/osqp_ref.c).  No GPU needed."""
-import numpy as np
 import pytest
 
 import settings_cases as sc
-
-
-def _rel(a, b):
-    return np.abs(a - b).max() / max(1e-300, np.abs(b).max())
+from util import rel
 
 
 @pytest.mark.parametrize('case,setting', sc.pairs(), ids=['%s-%s' % p for p in sc.pairs()])
@@ -62,7 +58,7 @@ def _told_from_the_defaults(case, setting):
         return True, (t, t0)
     x, z, y, _ = sc.oracle_iterate(case, setting, 40)
     x0, z0, y0, _ = sc.oracle_iterate(case, 'default', 40)
-    d = max(_rel(x, x0), _rel(z, z0), _rel(y, y0))
+    d = max(rel(x, x0), rel(z, z0), rel(y, y0))
     return d > 1e-4, (t, d)
 
 
@@ -122,30 +118,14 @@ def test_an_infeasible_problem_at_an_unchecked_limit_is_not_called_inaccurate():
     """The infeasible point mass of tests/test_gpu_parity.py (certificate at iteration 25 with the defaults) stopped at max_iter = 30 with
     check_termination = 0: the exact test finds the certificate."""
     for st in (dict(), dict(check_termination=0, max_iter=30)):
-        K = infeasible_point_mass(True, **st)
+        K = sc.infeasible_point_mass(True, **st)
         assert K.res.info.status == 'primal infeasible' and K.res.info.iter == (30 if st else 25), (st, K.res.info.status, K.res.info.iter)
-
-
-def infeasible_point_mass(oracle, **st):
-    import warnings
-    from pympc_amd import MPCController, fixtures
-    kw = fixtures.point_mass()
-    kw['uminus1'] = np.array([5.0])
-    K = MPCController(**kw)
-    if oracle:
-        from oracle.osqp_oracle import OSQP
-        K.prob = OSQP()
-    K.solver_settings = dict(st)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        K.setup()
-    return K
 
 
 def test_the_infeasibility_tolerance_moves_the_certificate():
     """What tests/test_gpu_settings.py holds the device to: eps_prim_inf = 1e-7 delays 'primal infeasible' from 25 to 75 iterations; with
     check_termination = 7 from 28 to 119 (four rho updates on the way)."""
-    got = [(K.res.info.status, K.res.info.iter) for K in (infeasible_point_mass(True, **st) for st in INFEASIBLE_SETTINGS)]
+    got = [(K.res.info.status, K.res.info.iter) for K in (sc.infeasible_point_mass(True, **st) for st in INFEASIBLE_SETTINGS)]
     assert got == [('primal infeasible', 25), ('primal infeasible', 75), ('primal infeasible', 28), ('primal infeasible', 119)], got
 
 

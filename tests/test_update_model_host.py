@@ -5,19 +5,10 @@ import warnings
 import numpy as np
 import pytest
 
-from util import load_golden, golden_kwargs, apply_attrs
+from util import load_golden, golden_kwargs, oracle_controller
 from ltv_models import new_model, with_model, MODEL_FIELDS
 
 NAMES = ['cart_pole', 'quadcopter_nc', 'random_12_4_30', 'random_20_8_12_hard', 'point_mass']
-
-
-def _oracle_controller(kw, **settings):
-    from pympc_amd import MPCController
-    from oracle.osqp_oracle import OSQP
-    K = apply_attrs(MPCController(**kw), kw)
-    K.prob = OSQP()
-    K.solver_settings = dict(settings)
-    return K
 
 
 def _same_sparse(a, b):
@@ -31,9 +22,9 @@ def test_public_qp_is_that_of_a_controller_constructed_with_the_new_model(name):
     new = new_model(kw)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        K = _oracle_controller(kw); K.setup()
+        K = oracle_controller(kw); K.setup()
         K.update_model(**new)
-        Kn = _oracle_controller(with_model(kw, new)); Kn.setup(solve=False)
+        Kn = oracle_controller(with_model(kw, new)); Kn.setup(solve=False)
     assert _same_sparse(K.P, Kn.P) and _same_sparse(K.A, Kn.A)
     assert np.array_equal(K.q, Kn.q) and np.array_equal(K.l, Kn.l) and np.array_equal(K.u, Kn.u)
     for k in MODEL_FIELDS:
@@ -47,12 +38,12 @@ def test_result_is_fresh_setup_warm_start_solve_written_by_hand(name):
     new = new_model(kw)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        K = _oracle_controller(kw); K.setup()
+        K = oracle_controller(kw); K.setup()
         x, y = K.res.x.copy(), K.res.y.copy()
         old_prob = K.prob
         K.update_model(**new)
         assert K.prob is not old_prob and isinstance(K.prob, OSQP)
-        Kn = _oracle_controller(with_model(kw, new)); Kn.setup(solve=False)
+        Kn = oracle_controller(with_model(kw, new)); Kn.setup(solve=False)
         O = OSQP()
         O.setup(Kn.P, Kn.q, Kn.A, Kn.l, Kn.u, warm_start=True, eps_abs=Kn.eps_rel, eps_rel=Kn.eps_abs)
         O.warm_start(x=x, y=y)
@@ -68,7 +59,7 @@ def test_update_model_in_the_middle_of_a_closed_loop_uses_the_current_step_data(
     new = new_model(kw)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        K = _oracle_controller(kw); K.setup()
+        K = oracle_controller(kw); K.setup()
         x = np.array(kw['x0'], dtype=float)
         for _ in range(3):
             u = K.output()
@@ -76,7 +67,7 @@ def test_update_model_in_the_middle_of_a_closed_loop_uses_the_current_step_data(
             K.update(x, u)
         u = K.output()
         K.update_model(Ad=new['Ad'], Bd=new['Bd'], solve=False)
-        Kn = _oracle_controller(with_model(kw, dict(Ad=new['Ad'], Bd=new['Bd'], x0=x, uminus1=u))); Kn.setup(solve=False)
+        Kn = oracle_controller(with_model(kw, dict(Ad=new['Ad'], Bd=new['Bd'], x0=x, uminus1=u))); Kn.setup(solve=False)
     assert _same_sparse(K.A, Kn.A) and _same_sparse(K.P, Kn.P)
     assert np.array_equal(K.q, Kn.q) and np.array_equal(K.l, Kn.l) and np.array_equal(K.u, Kn.u)
 
@@ -88,7 +79,7 @@ def test_partial_updates_leave_the_other_attributes_alone(fields):
     attrs = MODEL_FIELDS + ('uref', 'eps_feas', 'x0', 'xref', 'uminus1', 'Np', 'Nc', 'eps_rel', 'eps_abs')
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        K = _oracle_controller(kw); K.setup()
+        K = oracle_controller(kw); K.setup()
         before = {k: getattr(K, k) for k in attrs}
         K.update_model(**{k: new[k] for k in fields})
     for k in attrs:
@@ -109,7 +100,7 @@ def test_invalid_shapes_raise_the_constructors_errors():
     kw = golden_kwargs(load_golden('random_12_4_30'))
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        K = _oracle_controller(kw); K.setup()
+        K = oracle_controller(kw); K.setup()
     nx, nu = 12, 4
     bad = dict(Ad=np.ones((nx, nx + 1)), Bd=np.ones((nx + 1, nu)), Qx=np.eye(nx + 1), QxN=np.ones((nx + 1, nx)), Qu=np.eye(nu + 1), QDu=np.ones((nu, nu + 1)),
                xmin=np.ones(nx + 1), xmax=np.ones((nx, 1)), umin=np.ones(nu - 1), umax=np.ones((2, 2)), Dumin=np.ones((nu, 1)), Dumax=np.ones(nu + 1),

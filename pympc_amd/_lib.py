@@ -39,6 +39,14 @@ ROLLOUT_SYMBOLS = ['mpcqp_rollout', 'mpcqp_rollout_tape_bytes', 'mpcqp_rollout_r
 # include/mpcqp_rollout_est.h: likewise -- the taped rollout of the output-feedback loop, differentiated through the estimator
 ROLLOUT_EST_SYMBOLS = ['mpcqp_rollout_est', 'mpcqp_rollout_est_tape_bytes', 'mpcqp_rollout_adjoint_est', 'mpcqp_rollout_get_tape_est']
 
+# include/mpcqp_riccati.h: likewise -- batched discrete algebraic Riccati equations and their adjoint, without a handle
+RICCATI_SYMBOLS = ['mpcqp_riccati_default_settings', 'mpcqp_dare', 'mpcqp_dare_adjoint']
+
+
+class RiccatiSettings(C.Structure):
+    """mpcqp_riccati_settings (include/mpcqp_riccati.h)."""
+    _fields_ = [('struct_size', C.c_int32), ('max_iter', C.c_int32), ('gain_form', C.c_int32), ('reserved', C.c_int32), ('tol', C.c_double)]
+
 
 class PolishSettings(C.Structure):
     """mpcqp_polish_settings (include/mpcqp_polish.h)."""
@@ -235,6 +243,13 @@ def load():
         L.mpcqp_rollout_get_tape_est.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p]
         for name in ROLLOUT_EST_SYMBOLS:
             getattr(L, name).restype = C.c_int
+    if has_riccati(L):
+        L.mpcqp_riccati_default_settings.argtypes = [C.POINTER(RiccatiSettings)]
+        L.mpcqp_riccati_default_settings.restype = None
+        L.mpcqp_dare.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RiccatiSettings)] + [C.c_void_p] * 9
+        L.mpcqp_dare_adjoint.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RiccatiSettings)] + [C.c_void_p] * 14
+        for name in RICCATI_SYMBOLS[1:]:
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -273,6 +288,11 @@ def has_rollout(L=None):
 def has_rollout_est(L=None):
     """True if the library exports include/mpcqp_rollout_est.h."""
     return _has(L, ROLLOUT_EST_SYMBOLS)
+
+
+def has_riccati(L=None):
+    """True if the library exports include/mpcqp_riccati.h."""
+    return _has(L, RICCATI_SYMBOLS)
 
 
 def check(rc, what):

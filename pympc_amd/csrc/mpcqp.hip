@@ -65,6 +65,7 @@ static inline void cpu_relax() {
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
+int mpcqp_set_error(int code, const char *msg) { return fail(code, msg); }      // the way of mpcqp_riccati.hip to mpcqp_last_error
 #define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
     return fail(MPCQP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 

@@ -257,3 +257,57 @@ def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xr
         if not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (2, 3):
             raise ValueError('mpc_rollout_est: %s must be a device tensor [B, ., .] or [., .]' % n)
     return _MPCRolloutEst.apply(controller, int(nsteps), x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, names, *[params[n] for n in names])
+
+
+# ---- the discrete algebraic Riccati equation as a differentiable operation (include/mpcqp_riccati.h) ------------------------------------
+class _Dare(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gain_form, A, B, Q, R):
+        from . import riccati
+        X, K, status, _, _ = riccati.dare(A, B, Q, R, gain_form=gain_form)
+        ctx.save_for_backward(A, B, Q, R, X, K)
+        ctx.gain_form, ctx.status = gain_form, status
+        return X, K, status
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_K, _):
+        from . import riccati
+        A, B, Q, R, X, K = ctx.saved_tensors
+        want = [n for n, need in zip('ABQR', ctx.needs_input_grad[1:]) if need]
+        if not want:
+            return (None,) * 5
+        g = riccati.dare_adjoint(A, B, Q, R, X, K, status=ctx.status, G_X=grad_X, G_K=grad_K, gain_form=ctx.gain_form, want=want)
+        # (an unbatched input beside batched ones: one matrix shared by the batch, its gradient the sum over it)
+        return (None,) + tuple(None if n not in g else (g[n].sum(dim=0) if p.dim() == 2 and g[n].dim() == 3 else g[n]) for n, p in zip('ABQR', (A, B, Q, R)))
+
+
+def _riccati_args(fn, **mats):
+    for n, t in mats.items():
+        if not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (2, 3):
+            raise ValueError('%s: %s must be a device tensor [B, ., .] or [., .]' % (fn, n))
+
+
+def dare(A, B, Q, R, gain_form=0):
+    """``(X, K)`` of X = A'XA - A'XB (R + B'XB)^-1 B'XA + Q for device tensors [B, ., .] or unbatched [., .] (``pympc_amd.riccati.dare``):
+    forward is ONE mpcqp_dare call, backward ONE mpcqp_dare_adjoint call, both on torch's current stream.  ``gain_form`` 0: K = (R + B'XB)^-1
+    B'XA, 1: (R + B'XB)^-1 B'X.  Differentiable with respect to all four; the gradients of Q and R are those of a symmetric perturbation, an
+    unbatched input beside batched ones gets the sum over the batch, an instance that did not converge returns zeros and contributes a zero
+    gradient.  ``X.status`` ( = ``K.status``): the int32 status per instance (1 converged, 0 not, -1 not positive definite)."""
+    _riccati_args('dare', A=A, B=B, Q=Q, R=R)
+    X, K, status = _Dare.apply(int(gain_form), A, B, Q, R)
+    X.status = K.status = status
+    return X, K
+
+
+def kalman_gain(A, C, Qn, Rn, type='filter'):
+    """``(L, P)`` of the stationary Kalman filter ('filter': L = P C' (C P C' + Rn)^-1) or predictor ('predictor': L = A P C' (C P C' + Rn)^-1)
+    of x+ = A x + w, y = C x + v -- the meaning of ``pympc_amd.kalman.kalman_design_simple`` -- as ``dare`` of the dual problem
+    (A', C', Qn, Rn): differentiable with respect to A, C and the noise covariances Qn, Rn.  L is [.., nx, ny]; ``L.status``, ``P.status``
+    as in ``dare``."""
+    if type not in ('filter', 'predictor'):
+        raise ValueError("Unknown Kalman design type. Specify either filter or predictor!")
+    _riccati_args('kalman_gain', A=A, C=C, Qn=Qn, Rn=Rn)
+    P, G = dare(A.transpose(-1, -2).contiguous(), C.transpose(-1, -2).contiguous(), Qn, Rn, gain_form=1 if type == 'filter' else 0)
+    L = G.transpose(-1, -2).contiguous()
+    L.status = P.status
+    return L, P

@@ -121,27 +121,75 @@ __device__ __forceinline__ void latw_load(const double *F, d4 *fr) {
 // LDS vectors of the round (stage-major, stride 16; mpcqp_lat.h): tb right-hand side / solution, cb c_e of the reduction -- and, at the top stages'
 // slots, the top's solution until level 1 back has copied it into tb; each seen through the lane bases of the four block rotations.
 struct LatwVecs { double *tb, *cb; const double *t1, *t2, *t3, *c1, *c2, *c3; double *xt, *x2; };      // (xt: the top's compact input, per-lane base as tb; x2: fused schedule, the top stages' contributions from the next group)
-// four LDS reads per input vector (one read and three DPP block rotations instead: measured, see LAB_NOTES.md)
-template <bool FROMC>
-__device__ __forceinline__ void latw_mv_lds(const d4 a, const LatwVecs &v, int off, double &p, double &q) {
-    const double i0 = FROMC ? v.cb[off] : v.tb[off], i1 = FROMC ? v.c1[off] : v.t1[off], i2 = FROMC ? v.c2[off] : v.t2[off], i3 = FROMC ? v.c3[off] : v.t3[off];
-    p = __builtin_amdgcn_mfma_f64_4x4x4f64(a[0], i0, p, 0, 0, 0);
-    q = __builtin_amdgcn_mfma_f64_4x4x4f64(a[2], i2, q, 0, 0, 0);
-    p = __builtin_amdgcn_mfma_f64_4x4x4f64(a[1], i1, p, 0, 0, 0);
-    q = __builtin_amdgcn_mfma_f64_4x4x4f64(a[3], i3, q, 0, 0, 0);
+// One 8-byte LDS read that STAYS one.  Left alone, the backend merges two plain reads off one base into ds_read2_b64 / ds_read2st64_b64, which the LDS
+// serves at half rate under the 32-bank rule: 8 array cycles for the pair where two ds_read_b64 take 2 each (64 banks; a view read touches 16 distinct
+// 8-byte addresses per wave, 8 per 32-lane half, the rest broadcast: conflict-free).  A volatile access through an LDS-typed pointer is not merged, keeps
+// its immediate offset, and is still one the compiler counts (its own s_waitcnt lgkmcnt(n) ladder in front of each consumer); through the generic pointer
+// it would be a flat load.  Volatile reads are not CSE'd either, so every phase below reads each distinct vector ONCE, by hand, in order of need.
+// (Measured against plain reads, no bit moved: one (12,4,30) instance alone 6 455 -> 6 069 cycles per iteration, no register more -- LAB_NOTES.md, round 8.)
+typedef const volatile __attribute__((address_space(3))) double latw_ldsd;
+__device__ __forceinline__ double latw_ld(const double *p) { return *(latw_ldsd *)p; }
+// four LDS reads per input vector (one read and three DPP block rotations instead: measured, see LAB_NOTES.md): the vector of stage STAGE as the MFMA
+// steps want it, through the lane bases of the four block rotations
+struct LatwIn { double i0, i1, i2, i3; };
+template <bool FROMC, int STAGE>
+__device__ __forceinline__ LatwIn latw_in(const LatwVecs &v) {
+    constexpr int off = STAGE * 16;
+    LatwIn x;                                             // (requested in the order the MFMA steps consume them: 0, 2, 1, 3)
+    x.i0 = latw_ld((FROMC ? v.cb : v.tb) + off); x.i2 = latw_ld((FROMC ? v.c2 : v.t2) + off);
+    x.i1 = latw_ld((FROMC ? v.c1 : v.t1) + off); x.i3 = latw_ld((FROMC ? v.c3 : v.t3) + off);
+    return x;
+}
+__device__ __forceinline__ void latw_mv_lds(const d4 a, const LatwIn &x, double &p, double &q) {
+    p = __builtin_amdgcn_mfma_f64_4x4x4f64(a[0], x.i0, p, 0, 0, 0);
+    q = __builtin_amdgcn_mfma_f64_4x4x4f64(a[2], x.i2, q, 0, 0, 0);
+    p = __builtin_amdgcn_mfma_f64_4x4x4f64(a[1], x.i1, p, 0, 0, 0);
+    q = __builtin_amdgcn_mfma_f64_4x4x4f64(a[3], x.i3, q, 0, 0, 0);
 }
 
+// ordinal of a task among the tasks of its kind and level that wave W owns; how many it owns (compile time)
+constexpr int latw_ord(int N, int W, int L, int kind, int tq) { int o = 0; for (int t = 0; t < tq; ++t) if (latw_owner(N, L, kind, t) == W) ++o; return o; }
+constexpr int latw_mine(int N, int W, int L, int kind) { return latw_ord(N, W, L, kind, lat_count(N, L, kind)); }
+// the vector of stage e among the inputs wave W has read for its kept stages of level L (2 * ordinal + side), -1 if none of them
+constexpr int latw_kept_input(int N, int W, int L, int e) {
+    const int h = 1 << L;
+    for (int t = 0; t < lat_count(N, L, 0); ++t)
+        if (latw_owner(N, L, 0, t) == W) {
+            const int i = lat_stage(L, 0, t);
+            if (i - h == e) return 2 * latw_ord(N, W, L, 0, t);
+            if (i + h == e && i + h < N) return 2 * latw_ord(N, W, L, 0, t) + 1;
+        }
+    return -1;
+}
+constexpr int latw_atleast1(int n) { return n > 0 ? n : 1; }
+
+// forward tasks of level L that wave W owns: every input of the phase requested up front, in the order the tasks consume them, each distinct vector once
 template <int N, int W, int L>
 __device__ __forceinline__ void latw_fwd(const d4 *fr, const LatwVecs &v) {
-    constexpr int h = 1 << L;
+    constexpr int h = 1 << L, NK = latw_mine(N, W, L, 0), NE = latw_mine(N, W, L, 1);
+    double p0[latw_atleast1(NK)];
+    LatwIn xk[latw_atleast1(2 * NK)], xe[latw_atleast1(NE)];
     static_for<0, lat_count(N, L, 0)>([&](auto tc) {
         constexpr int t = decltype(tc)::value, i = lat_stage(L, 0, t);
         if constexpr (latw_owner(N, L, 0, t) == W) {
-            constexpr int s = latw_slot(N, W, L, 0, t);
-            double p = v.tb[i * 16], q = 0.0;                 // (the stage's own right-hand side starts the chain)
-            if constexpr (latw_fused(N) && L == 1) p += v.x2[((i + 1) / 4 - 1) * 16];      // (its level-0 contribution from the next group's first stage)
-            latw_mv_lds<false>(fr[s], v, (i - h) * 16, p, q);
-            if constexpr (i + h < N) latw_mv_lds<false>(fr[s + 1], v, (i + h) * 16, p, q);
+            constexpr int o = latw_ord(N, W, L, 0, t);
+            p0[o] = latw_ld(v.tb + i * 16);                   // (the stage's own right-hand side starts the chain)
+            if constexpr (latw_fused(N) && L == 1) p0[o] += latw_ld(v.x2 + ((i + 1) / 4 - 1) * 16);      // (its level-0 contribution from the next group's first stage)
+            xk[2 * o] = latw_in<false, i - h>(v);
+            if constexpr (i + h < N) xk[2 * o + 1] = latw_in<false, i + h>(v);
+        }
+    });
+    static_for<0, lat_count(N, L, 1)>([&](auto tc) {
+        constexpr int t = decltype(tc)::value, e = lat_stage(L, 1, t);
+        if constexpr (latw_owner(N, L, 1, t) == W && latw_kept_input(N, W, L, e) < 0) xe[latw_ord(N, W, L, 1, t)] = latw_in<false, e>(v);
+    });
+    static_for<0, lat_count(N, L, 0)>([&](auto tc) {
+        constexpr int t = decltype(tc)::value, i = lat_stage(L, 0, t);
+        if constexpr (latw_owner(N, L, 0, t) == W) {
+            constexpr int s = latw_slot(N, W, L, 0, t), o = latw_ord(N, W, L, 0, t);
+            double p = p0[o], q = 0.0;
+            latw_mv_lds(fr[s], xk[2 * o], p, q);
+            if constexpr (i + h < N) latw_mv_lds(fr[s + 1], xk[2 * o + 1], p, q);
             // (level 1 keeps exactly the top stages 4 (r + 1) - 1: their reduced right-hand side goes to the top's compact Xt --
             //  nobody reads tb there before level 1 back has put the top's solution in its place)
             if constexpr (L == 1) v.xt[((i + 1) / 4 - 1) * 16] = p + q;
@@ -151,39 +199,60 @@ __device__ __forceinline__ void latw_fwd(const d4 *fr, const LatwVecs &v) {
     static_for<0, lat_count(N, L, 1)>([&](auto tc) {
         constexpr int t = decltype(tc)::value, e = lat_stage(L, 1, t);
         if constexpr (latw_owner(N, L, 1, t) == W) {
-            constexpr int s1 = latw_slot(N, W, L, 1, t);
+            constexpr int s1 = latw_slot(N, W, L, 1, t), ki = latw_kept_input(N, W, L, e);
             double p = 0.0, q = 0.0;
-            latw_mv_lds<false>(fr[s1], v, e * 16, p, q);
+            if constexpr (ki >= 0) latw_mv_lds(fr[s1], xk[ki], p, q);
+            else latw_mv_lds(fr[s1], xe[latw_ord(N, W, L, 1, t)], p, q);
             v.cb[e * 16] = p + q;
         }
     });
 }
-// level 0 forward of wave W's own four stages (fused schedule), called right behind the right-hand side without a barrier
+// level 0 forward of wave W's own four stages (fused schedule), called right behind the right-hand side without a barrier (a wave reads its own LDS
+// writes in order): the vectors of 4w and 4w+2 and the right-hand sides of 4w+1 and 4w+3, each read once
 template <int N, int W>
 __device__ __forceinline__ void latw_fwd0_own(const d4 *fr, const LatwVecs &v) {
     constexpr int s0 = 4 * W;
-    if constexpr (s0 < N) { double p = 0.0, q = 0.0; latw_mv_lds<false>(fr[0], v, s0 * 16, p, q); v.cb[s0 * 16] = p + q; }
-    if constexpr (s0 + 2 < N) { double p = 0.0, q = 0.0; latw_mv_lds<false>(fr[1], v, (s0 + 2) * 16, p, q); v.cb[(s0 + 2) * 16] = p + q; }
-    if constexpr (s0 + 1 < N) {
-        double p = v.tb[(s0 + 1) * 16], q = 0.0;
-        latw_mv_lds<false>(fr[2], v, s0 * 16, p, q);
-        if constexpr (s0 + 2 < N) latw_mv_lds<false>(fr[3], v, (s0 + 2) * 16, p, q);
-        v.tb[(s0 + 1) * 16] = p + q;
+    if constexpr (s0 < N) {
+        const LatwIn xa = latw_in<false, s0>(v);
+        LatwIn xb{};
+        double b1 = 0.0, b3 = 0.0;
+        if constexpr (s0 + 2 < N) xb = latw_in<false, s0 + 2>(v);
+        if constexpr (s0 + 1 < N) b1 = latw_ld(v.tb + (s0 + 1) * 16);
+        if constexpr (s0 + 3 < N) b3 = latw_ld(v.tb + (s0 + 3) * 16);
+        { double p = 0.0, q = 0.0; latw_mv_lds(fr[0], xa, p, q); v.cb[s0 * 16] = p + q; }
+        if constexpr (s0 + 2 < N) { double p = 0.0, q = 0.0; latw_mv_lds(fr[1], xb, p, q); v.cb[(s0 + 2) * 16] = p + q; }
+        if constexpr (s0 + 1 < N) {
+            double p = b1, q = 0.0;
+            latw_mv_lds(fr[2], xa, p, q);
+            if constexpr (s0 + 2 < N) latw_mv_lds(fr[3], xb, p, q);
+            v.tb[(s0 + 1) * 16] = p + q;
+        }
+        if constexpr (s0 + 3 < N) { double p = b3, q = 0.0; latw_mv_lds(fr[4], xb, p, q); v.tb[(s0 + 3) * 16] = p + q; }
+        if constexpr (W > 0) { double p = 0.0, q = 0.0; latw_mv_lds(fr[5], xa, p, q); v.x2[(W - 1) * 16] = p + q; }
     }
-    if constexpr (s0 + 3 < N) { double p = v.tb[(s0 + 3) * 16], q = 0.0; latw_mv_lds<false>(fr[4], v, (s0 + 2) * 16, p, q); v.tb[(s0 + 3) * 16] = p + q; }
-    if constexpr (W > 0 && s0 < N) { double p = 0.0, q = 0.0; latw_mv_lds<false>(fr[5], v, s0 * 16, p, q); v.x2[(W - 1) * 16] = p + q; }
 }
-// back substitution of level L; TOPIN: the neighbours are top stages whose solution still sits in cb (level 1)
+// back substitution of level L; TOPIN: the neighbours are top stages whose solution still sits in cb (level 1).  The inputs of all the wave's tasks up front.
 template <int N, int W, int L, bool TOPIN>
 __device__ __forceinline__ void latw_bwd(const d4 *fr, const LatwVecs &v) {
-    constexpr int h = 1 << L;
+    constexpr int h = 1 << L, NB2 = latw_mine(N, W, L, 2);
+    double p0[latw_atleast1(NB2)];
+    LatwIn xn[latw_atleast1(2 * NB2)];
     static_for<0, lat_count(N, L, 2)>([&](auto tc) {
         constexpr int t = decltype(tc)::value, e = lat_stage(L, 2, t);
         if constexpr (latw_owner(N, L, 2, t) == W) {
-            constexpr int s = latw_slot(N, W, L, 2, t), s2 = s + (e - h >= 0 ? 1 : 0);
-            double p = v.cb[e * 16], q = 0.0;
-            if constexpr (e - h >= 0) latw_mv_lds<TOPIN>(fr[s], v, (e - h) * 16, p, q);
-            if constexpr (e + h < N) latw_mv_lds<TOPIN>(fr[s2], v, (e + h) * 16, p, q);
+            constexpr int o = latw_ord(N, W, L, 2, t);
+            p0[o] = latw_ld(v.cb + e * 16);
+            if constexpr (e - h >= 0) xn[2 * o] = latw_in<TOPIN, e - h>(v);
+            if constexpr (e + h < N) xn[2 * o + 1] = latw_in<TOPIN, e + h>(v);
+        }
+    });
+    static_for<0, lat_count(N, L, 2)>([&](auto tc) {
+        constexpr int t = decltype(tc)::value, e = lat_stage(L, 2, t);
+        if constexpr (latw_owner(N, L, 2, t) == W) {
+            constexpr int s = latw_slot(N, W, L, 2, t), s2 = s + (e - h >= 0 ? 1 : 0), o = latw_ord(N, W, L, 2, t);
+            double p = p0[o], q = 0.0;
+            if constexpr (e - h >= 0) latw_mv_lds(fr[s], xn[2 * o], p, q);
+            if constexpr (e + h < N) latw_mv_lds(fr[s2], xn[2 * o + 1], p, q);
             v.tb[e * 16] = p + q;
         }
     });
@@ -193,32 +262,43 @@ template <int N, int W>
 __device__ __forceinline__ void latw_bwd1(const d4 *fr, const LatwVecs &v) {
     static_for<0, BcrFmt::top_count(N)>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
-        if constexpr (r % NWAVES == W) v.tb[latw_top_stage(r) * 16] = v.cb[latw_top_stage(r) * 16];
+        if constexpr (r % NWAVES == W) v.tb[latw_top_stage(r) * 16] = latw_ld(v.cb + latw_top_stage(r) * 16);
     });
     latw_bwd<N, W, 1, true>(fr, v);
 }
 
-// level 1 back and level 0 back of wave W's own stages in one phase (fused schedule); the top's solution is read from cb where the neighbour is a top stage
+// level 1 back and level 0 back of wave W's own stages in one phase (fused schedule); the top's solution is read from cb where the neighbour is a top stage:
+// the top's rows 4w-1 and 4w+3 and the three c_e up front; x(4w+1) goes to its two consumers from the registers of the lane that computed it and through
+// the three rotated views of what that wave has just stored (its own LDS write, in order)
 template <int N, int W>
 __device__ __forceinline__ void latw_bwd_own(const d4 *fr, const LatwVecs &v) {
     constexpr int bb = latw_back_base(N, W), e1 = 4 * W + 1, ea = 4 * W, eb = 4 * W + 2;
-    if constexpr (W < BcrFmt::top_count(N)) v.tb[latw_top_stage(W) * 16] = v.cb[latw_top_stage(W) * 16];      // (the top's row W into tb, for the owner passes)
+    LatwIn xl{}, xr{}, x1{};
+    double c1 = 0.0, ca = 0.0, cb2 = 0.0;
+    if constexpr (e1 < N) c1 = latw_ld(v.cb + e1 * 16);
+    if constexpr (ea - 1 >= 0 && ea < N) xl = latw_in<true, ea - 1>(v);
+    if constexpr (e1 + 2 < N) xr = latw_in<true, e1 + 2>(v);
+    if constexpr (ea < N) ca = latw_ld(v.cb + ea * 16);
+    if constexpr (eb < N) cb2 = latw_ld(v.cb + eb * 16);
+    if constexpr (W < BcrFmt::top_count(N)) v.tb[latw_top_stage(W) * 16] = xr.i0;      // (the top's row W into tb, for the owner passes)
     if constexpr (e1 < N) {
-        double p = v.cb[e1 * 16], q = 0.0;
-        if constexpr (e1 - 2 >= 0) latw_mv_lds<true>(fr[bb], v, (e1 - 2) * 16, p, q);
-        if constexpr (e1 + 2 < N) latw_mv_lds<true>(fr[bb + 1], v, (e1 + 2) * 16, p, q);
-        v.tb[e1 * 16] = p + q;
+        double p = c1, q = 0.0;
+        if constexpr (e1 - 2 >= 0) latw_mv_lds(fr[bb], xl, p, q);
+        if constexpr (e1 + 2 < N) latw_mv_lds(fr[bb + 1], xr, p, q);
+        x1.i0 = p + q;
+        v.tb[e1 * 16] = x1.i0;
+        x1.i2 = latw_ld(v.t2 + e1 * 16); x1.i1 = latw_ld(v.t1 + e1 * 16); x1.i3 = latw_ld(v.t3 + e1 * 16);
     }
     if constexpr (ea < N) {
-        double p = v.cb[ea * 16], q = 0.0;
-        if constexpr (ea - 1 >= 0) latw_mv_lds<true>(fr[bb + 2], v, (ea - 1) * 16, p, q);
-        if constexpr (ea + 1 < N) latw_mv_lds<false>(fr[bb + 3], v, (ea + 1) * 16, p, q);
+        double p = ca, q = 0.0;
+        if constexpr (ea - 1 >= 0) latw_mv_lds(fr[bb + 2], xl, p, q);
+        if constexpr (ea + 1 < N) latw_mv_lds(fr[bb + 3], x1, p, q);
         v.tb[ea * 16] = p + q;
     }
     if constexpr (eb < N) {
-        double p = v.cb[eb * 16], q = 0.0;
-        latw_mv_lds<false>(fr[bb + 4], v, (eb - 1) * 16, p, q);
-        if constexpr (eb + 1 < N) latw_mv_lds<true>(fr[bb + 5], v, (eb + 1) * 16, p, q);
+        double p = cb2, q = 0.0;
+        latw_mv_lds(fr[bb + 4], x1, p, q);
+        if constexpr (eb + 1 < N) latw_mv_lds(fr[bb + 5], xr, p, q);
         v.tb[eb * 16] = p + q;
     }
 }

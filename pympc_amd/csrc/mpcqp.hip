@@ -25,7 +25,8 @@
 // This file: host side and C ABI (include/mpcqp.h).  Device code: mpcqp_layout.h, mpcqp_qp.h, mpcqp_factor.h, mpcqp_sweeps.h,
 // mpcqp_group.h, mpcqp_bcr.h, mpcqp_wide.h, mpcqp_huge.h, mpcqp_dense.h, mpcqp_border.h, mpcqp_phases.h, mpcqp_tiny.h, mpcqp_lat.h, mpcqp_latw.h,
 // mpcqp_kernels.h (the last block also compiled at 512 threads per workgroup by mpcqp_w8.hip); host only:
-// mpcqp_csc.h (one translation unit).
+// mpcqp_plan.h (what mpcqp_create decides before it allocates -- backend, LDS layout, solve kernel -- and the getters' arithmetic on it:
+// no HIP call, runs without a GPU), mpcqp_csc.h (one translation unit).  The solve kernels' instantiations: the two tables of mpcqp_defs.h.
 //
 // FP64 throughout.  No CPU fallback exists in this library.
 
@@ -86,6 +87,7 @@ int mpcqp_set_error(int code, const char *msg) { return fail(code, msg); }      
 #include "mpcqp_latw.h"
 #include "mpcqp_kernels.h"
 #include "mpcqp_latw_check.h"
+#include "mpcqp_plan.h"
 #include "mpcqp_kpol.h"
 #include "mpcqp_polish.h"
 #include "mpcqp_adjoint.h"
@@ -96,12 +98,8 @@ int mpcqp_set_error(int code, const char *msg) { return fail(code, msg); }      
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-constexpr int BCR_STAGES = 31;      // the largest stage count the register-resident cyclic reduction is instantiated for (Np = 30: the BASELINE shape)
-// The static schedule of mpcqp_lat.h exists for 11, 21 and 31 stages; a problem runs the smallest one that holds its N = Np + 1 stages (the rest
-// are identity padding: factor_bcr).  0: too long a horizon for this backend.
-static int bcr_schedule(int N) { return N <= 11 ? 11 : N <= 21 ? 21 : N <= BCR_STAGES ? BCR_STAGES : 0; }
 // mpcqp_w8.hip: the second translation unit (NT = 512).  kargs: this unit's RunKArgs, byte for byte the other's.
-int mpcqp_w8_launch(const void *kargs, size_t kargs_bytes, int spec12_4, int sched, int loop, int grid, size_t smem, hipStream_t stream);
+int mpcqp_w8_launch(const void *kargs, size_t kargs_bytes, const RunKernelId &id, int loop, int grid, size_t smem, hipStream_t stream);
 #ifdef MPCQP_RUN_TIMING
 void mpcqp_w8_ticks(unsigned long long *out16);
 #endif
@@ -111,14 +109,12 @@ constexpr int BALANCE_FIRST = 4;   // ... before the first one (an instance show
 
 struct PackItem { const double *src; double *dst; int w, stride; };
 struct PackArgs { PackItem it[24]; int n, batch; };
-struct mpcqp_handle {
-    int device = 0, batch = 0;
-    Lay L;
+struct mpcqp_handle : Plan {       // the plan (mpcqp_plan.h: ncu, batch, L, lds_state, smem, fsz, kernel) and what runs it on a device
+    int device = 0;
     Ptrs P = {};
     mpcqp_settings S;
     hipStream_t stream = nullptr;
-    bool own_stream = false, is_setup = false, lds_state = false;
-    size_t smem_setup = 0, smem_solve = 0;
+    bool own_stream = false, is_setup = false;
     std::vector<void *> allocs;
     double *u0_dev = nullptr;
     int *pending_dev = nullptr, *npending_dev = nullptr;   // two-launch solve: instances that need more than the first round
@@ -126,7 +122,7 @@ struct mpcqp_handle {
     int *qperm_dev = nullptr; bool qperm_set = false;     // [batch] the queue order of persistent launches (longest expected work first), once a map has been built
     int *vcur_dev = nullptr, *vdone_dev = nullptr; unsigned *vqueue_dev = nullptr;   // persistent launches: [slots] map entry each workgroup is working on; [batch] closed-loop steps done; the queue position
     std::vector<double> work_ema; // per instance: smoothed ADMM iterations per balancing interval (host)
-    int ncu = 0, solves_since_balance = 0, auto_balance = 1;
+    int solves_since_balance = 0, auto_balance = 1;
     int loop_parts = 0;           // queue-item parts per instance of the last persistent closed-loop launch (0: not persistent; mpcqp_dev_carry_stats)
     void *run_buf = nullptr; size_t run_bytes = 0;     // staging of mpcqp_mpc_run (disturbances, plant, trajectories)
     bool profiling = false;
@@ -189,41 +185,6 @@ extern "C" int mpcqp_device_count(void) {
     return n;
 }
 
-static Lay make_layout(int nx, int nu, int Np, int Nc, int soft) {
-    Lay L; memset(&L, 0, sizeof(L));
-    L.nx = nx; L.nu = nu; L.Np = Np; L.Nc = Nc; L.N = Np + 1; L.nb = nx + nu;
-    L.n_x = L.N * nx; L.n_u = Nc * nu;
-    L.soft = soft ? 1 : 0;
-    L.n = (L.soft ? 2 : 1) * L.n_x + L.n_u; L.m = 2 * L.n_x + L.n_u + (Nc + 1) * nu;
-    L.ou = L.n_x; L.oe = L.n_x + L.n_u;
-    L.rs = L.n_x; L.ri = 2 * L.n_x; L.rdu = 2 * L.n_x + L.n_u;
-    L.NB = L.nb <= 16 ? 16 : L.nb <= 32 ? 32 : L.nb <= 64 ? 64 : 128;
-    L.border = Nc < Np ? 1 : 0;
-    L.NcT = L.border ? Nc - 1 : Nc;
-    L.rnx = 1.0f / (float)nx; L.rnu = 1.0f / (float)nu;
-    int o = 0;
-    L.oAd = o; o += nx * nx; L.oBd = o; o += nx * nu;
-    L.oxmin = o; o += nx; L.oxmax = o; o += nx;
-    L.oumin = o; o += nu; L.oumax = o; o += nu; L.oDumin = o; o += nu; L.oDumax = o; o += nu;
-    L.ouref = o; o += nu; L.oeps = o; o += 1;
-    L.hot_sz = o;
-    L.oQx = o; o += nx * nx; L.oQxN = o; o += nx * nx; L.oQu = o; o += nu * nu; L.oQDu = o; o += nu * nu;
-    L.model_sz = o;
-    L.hot_lds = L.hot_sz;                              // (mpcqp_create: model_sz where the weight matrices fit in LDS beside everything else)
-    L.odu0 = nx + nu + L.N * nx;
-    L.step_sz = L.odu0 + 2 * nu;
-    L.raw = 0;
-    L.xref_rows = 1;
-    L.fstage = L.NB == 16 ? FactorFmt<16>::STAGE : L.NB == 32 ? FactorFmt<32>::STAGE : L.NB == 64 ? WideFmt::STAGE : HugeFmt::STAGE;
-    L.fhead = L.NB == 16 ? FactorFmt<16>::HEAD : L.NB == 32 ? FactorFmt<32>::HEAD : 0;
-    L.ffwd = L.NB == 16 ? FactorFmt<16>::FWD : L.NB == 32 ? FactorFmt<32>::FWD : L.NB == 64 ? WideFmt::NN : HugeFmt::NN;      // (non-zero: the factor starts at the stages)
-    L.ftab = L.NB == 16 ? FactorFmt<16>::TAB : L.NB == 32 ? FactorFmt<32>::TAB : 0;
-    L.tsz = L.m + L.N * L.NB * (L.NB >= 64 ? 2 : 1);   // [W (m) | Tc (N*NB)] (+ the second stage-major vector of the wide solve); mpcqp_create widens it where the factorization needs more
-    L.NR = L.N * L.nb; L.dld = L.NR | 1;               // dense mode (decided in mpcqp_create): unknowns, odd LDS row stride
-    L.nw = NWAVES; L.bcrtop = 0;                        // (mpcqp_create: eight waves and a dense top for the kernels of mpcqp_w8.hip)
-    return L;
-}
-
 template <class T>
 static int dalloc(mpcqp_handle *h, T **p, size_t count) {
     void *q = nullptr;
@@ -234,9 +195,11 @@ static int dalloc(mpcqp_handle *h, T **p, size_t count) {
     return 0;
 }
 
+// Four steps: argument checks; device and stream; the plan (mpcqp_plan.h) for the device's compute units; allocation.
 extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, int nu, int Np, int Nc, const mpcqp_settings *s) {
-    if (!out || batch < 1 || nx < 1 || nu < 1 || Np < 2 || Nc < 1 || Nc > Np) return fail(MPCQP_ERR_ARG, "mpcqp_create: bad dimensions");
-    if (nx + nu > 128) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_create: nx+nu > 128 is not implemented");
+    std::string why;
+    if (!out) return fail(MPCQP_ERR_ARG, "mpcqp_create: bad dimensions");
+    if (int rc = plan_check_dims(batch, nx, nu, Np, Nc, &why)) return fail(rc, why);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MPCQP_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(MPCQP_ERR_ARG, "mpcqp_create: bad device index");
@@ -244,9 +207,8 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     mpcqp_handle *h = new mpcqp_handle();
     mpcqp_polish_default_settings(&h->pol);
     mpcqp_adjoint_default_settings(&h->adj);
-    h->device = device; h->batch = batch;
+    h->device = device;
     if (s) h->S = *s; else mpcqp_default_settings(&h->S);
-    h->L = make_layout(nx, nu, Np, Nc, h->S.soft_constraints);
     // (every failure from here on releases what has been created so far: mpcqp_destroy copes with a partial handle)
     auto hip_fail = [&](hipError_t e, const char *what) { std::string msg = std::string(what) + ": " + hipGetErrorString(e); mpcqp_destroy(h); return fail(MPCQP_ERR_HIP, msg); };
     { hipError_t e = hipStreamCreate(&h->stream); if (e != hipSuccess) { h->stream = nullptr; return hip_fail(e, "hipStreamCreate"); } }
@@ -256,68 +218,13 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
         e = hipEventCreate(&h->ev1[i]); if (e != hipSuccess) { hipEventDestroy(h->ev0[i]); return hip_fail(e, "hipEventCreate"); }
         h->nevents = i + 1;
     }
+    int ncu = 0;
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess) ncu = prop.multiProcessorCount; }
+    if (int rc = make_plan(ncu, batch, nx, nu, Np, Nc, h->S, h, &why)) { mpcqp_destroy(h); return fail(rc, why); }
     const Lay &L = h->L;
     Ptrs &P = h->P;
-    size_t B = (size_t)batch;
-    // Small problems keep the iterate x, z, y in LDS behind the common block (four workgroups per CU: 40 KB each); larger
-    // ones keep it in L2/HBM.
-    const size_t state_doubles = (size_t)(L.n + 2 * L.m);
-    // (an LDS-resident iterate's termination check reads the weight matrices from LDS too -- check_norms_own: behind W in the work area unless
-    //  they are staged with the hot prefix -- so the work area of such a handle holds at least W and them: short horizons of wide stages only)
-    const int tsz_plain = L.tsz;
-    if (L.NB <= 32) h->L.tsz = std::max(L.tsz, L.m + (L.model_sz - L.hot_sz));
-    h->lds_state = L.NB <= 32 && sizeof(double) * ((size_t)smem_common_doubles(L) + state_doubles) <= 40 * 1024 && L.m <= 4 * NT && L.N * L.NB <= 2 * NT && L.n_u + L.nu <= NT;      // (the owner map of the parallel phases: two state elements and one input element per thread)
-    if (!h->lds_state) h->L.tsz = tsz_plain;
-    // The smallest ones (the reference's own examples) solve the KKT system with a register-resident dense inverse (mpcqp_dense.h).
-    // (mpcqp_settings.backend forces a choice -- what tests/test_gpu_backends.py runs every eligible fixture through; a forced backend the shape
-    //  is not eligible for is refused, never silently replaced)
-    const int want = h->S.backend;
-    auto refuse = [&](const char *what) { mpcqp_destroy(h); return fail(MPCQP_ERR_UNSUPPORTED, std::string("mpcqp_create: backend ") + what + " is not available for this shape"); };
-    if (want < MPCQP_BACKEND_AUTO || want > MPCQP_BACKEND_BCRT) { mpcqp_destroy(h); return fail(MPCQP_ERR_ARG, "mpcqp_create: unknown mpcqp_settings.backend"); }
-    const bool dense_shape = h->lds_state && L.NB == 16 && L.NR <= DenseFmt::ROWS;      // (Nc < Np included: the dense inverse holds the held input's couplings itself)
-    if (want == MPCQP_BACKEND_DENSE && !dense_shape) return refuse("DENSE");
-    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess) h->ncu = prop.multiProcessorCount; }
-    // (AUTO: up to six instances per compute unit -- measured on (3,1,30), (4,1,20), (2,2,12), (6,2,10), (12,4,7), device loop: ahead of both other backends by 1.2 - 2.3 x up to
-    //  512 instances, by 0.94 - 1.4 x at 1024, behind the bandwidth kernel by 0 - 18 % at 2048)
-    const bool dense = dense_shape && (want == MPCQP_BACKEND_DENSE || (want == MPCQP_BACKEND_AUTO && (h->ncu <= 0 || batch <= 6 * h->ncu)));
-    h->L.dense = dense ? 1 : 0;
-    if (dense) h->L.tsz += DenseFmt::SCRATCH;
-    // Up to three instances per compute unit (one resident, the others queued): the latency backend (block cyclic reduction, factor resident on the compute unit) for
-    // 16 x 16 stages and horizons of up to 30 steps -- the BASELINE shape (12, 4, 30) with compile-time dimensions, anything else with nx + nu <= 16 through
-    // the generic instantiations.  Larger batches stream the chain format (the bandwidth backend).
-    const bool bcr_shape = !dense && h->lds_state && L.NB == 16 && !L.border && bcr_schedule(L.N) > 0;
-    const bool want_bcr = want == MPCQP_BACKEND_BCR || want == MPCQP_BACKEND_BCR8 || want == MPCQP_BACKEND_BCRT;
-    if (want_bcr && !bcr_shape) return refuse("BCR");
-    // AUTO, measured against the bandwidth kernel (device loop and stepwise path, 1024 .. 4096 instances; LAB_NOTES.md):
-    //   * horizons of 21 .. 30 steps (the 31-stage schedule: every wave owns one group of four stages and the kernel runs on five barriers per iteration, mpcqp_latw.h) with
-    //     stages too wide for the bandwidth kernel to pack two per block (nx + nu > 8): at EVERY batch size -- (12,4,30) 1.52 / 1.66 / 1.72 M solves/s against 1.28 / 1.37 /
-    //     1.47 M at 1024 / 2048 / 4096 instances, (12,4,25) 1.54 / 1.69 / 1.75 against 1.43 / 1.50 / 1.68, (8,8,30) 1.93 / 2.13 / 2.20 against 1.50 / 1.72 / 1.94, (6,3,28) 1.80 /
-    //     1.90 / 2.02 against 1.44 / 1.77 / 1.88, (10,6,24) 1.79 / 1.88 / 1.93 against 1.60 / 1.77 / 2.01, (12,4,21) level (1.56 / 1.69 / 1.75 against 1.59 / 1.70 / 1.84);
-    //   * anything else it is eligible for: up to three instances per compute unit -- at 768 instances (12,4,10) 2.32 against 2.21, (6,2,20) 1.71 / 1.61; beyond that the
-    //     bandwidth kernel is ahead on short or padded schedules ((12,4,10) 2.63 against 2.36 at 1024, (12,4,14) 2.17 / 1.80) and on stages it packs ((6,2,20) 2.63 / 2.04 and
-    //     (5,1,30) 1.72 / 1.63 at 2048).
-    const bool bcr_any_batch = bcr_schedule(L.N) == 31 && L.N >= 22 && L.nb > 8;
-    const bool bcr = bcr_shape && (want == MPCQP_BACKEND_AUTO ? (h->ncu > 0 && (bcr_any_batch || batch <= 3 * h->ncu)) : want_bcr);
-    h->L.bcr = bcr ? bcr_schedule(L.N) : 0;
-    // What AUTO runs it on: 512-thread workgroups (two waves per SIMD) with a dense top (mpcqp_latw.h, mpcqp_w8.hip) -- 128 / 256 / 512 instances
-    // 608 k / 1.03 M / 1.13 M solves/s against 506 k / 841 k / 935 k on four waves with the plain reduction (MPCQP_BACKEND_BCR, mpcqp_lat.h).
-    // MPCQP_BACKEND_BCRT: the dense-top format on four waves (533 k / 890 k: what the eight waves add on top of the format).  DESIGN.md section 5b.
-    const bool bcr8 = bcr && (want == MPCQP_BACKEND_BCR8 || want == MPCQP_BACKEND_AUTO);
-    const bool bcrt = bcr8 || (bcr && want == MPCQP_BACKEND_BCRT);
-    h->L.bcrtop = bcrt ? BcrFmt::top_count(h->L.bcr) : 0;
-    h->L.nw = bcr8 ? 8 : NWAVES;
-    // Small stages (nx + nu <= 8) that neither of the register-resident backends takes: several stages per 16 x 16 block (mpcqp_group.h) -- the
-    // chain and the factor shrink by the group size.  (Worth it once the chain is long: at least three super-stages.)
-    const int grp = (!dense && !bcr && L.NB == 16 && group_size(L.nb) >= 2 && group_count(L.N, group_size(L.nb)) >= 3 && !(h->S.tuning & MPCQP_TUNE_NO_GROUPING)) ? group_size(L.nb) : 0;
-    h->L.grp = grp;
-    if (grp) {
-        h->L.fstage = GroupFmt::REC; h->L.fhead = 0; h->L.ffwd = GroupFmt::NN; h->L.ftab = 0;
-        h->L.tsz += (group_count(L.N, grp) + 2) * L.NB;    // the grouped vector Tg behind Tc (+ the two slots of the middle stage's inputs)
-    }
-    const int NS = h->L.bcr;                                        // stages of the schedule (>= L.N)
-    if (bcr) h->L.tsz = std::max(h->L.tsz + NS * L.NB, LAT_LDS_DOUBLES(NS));      // the stage-major vectors of the latency round (mpcqp_lat.h); c_e of the streaming solve
-    P.fsz = dense ? (long long)DenseFmt::DOUBLES : bcr ? BcrFmt::doubles(NS, bcrt) : grp ? (long long)(group_count(L.N, grp) + 1) * GroupFmt::REC
-                  : (long long)L.fhead + (long long)L.N * L.fstage;
+    const size_t B = (size_t)batch;
+    P.fsz = h->fsz;
     int rc = 0;
     rc |= dalloc(h, &P.model, B * L.model_sz); rc |= dalloc(h, &P.step, B * L.step_sz);
     rc |= dalloc(h, &P.D, B * L.n); rc |= dalloc(h, &P.E, B * L.m); rc |= dalloc(h, &P.c, B);
@@ -328,59 +235,18 @@ extern "C" int mpcqp_create(mpcqp_handle **out, int device, int batch, int nx, i
     rc |= dalloc(h, &P.xo, B * L.n); rc |= dalloc(h, &P.yo, B * L.m);
     rc |= dalloc(h, &P.dx, B * L.n); rc |= dalloc(h, &P.dy, B * L.m);
     rc |= dalloc(h, &P.qv, B * (size_t)(L.n_x + L.n_u));
-    if (bcr) rc |= dalloc(h, &P.bws, B * (size_t)NS * BcrFmt::WSTAGE);
+    if (L.bcr) rc |= dalloc(h, &P.bws, B * (size_t)L.bcr * BcrFmt::WSTAGE);
     if (L.NB == 128) rc |= dalloc(h, &P.bws, B * (size_t)HugeFmt::GWS);      // (the factorization's work matrices of 128-wide stages)
     if (L.border) { rc |= dalloc(h, &P.Bb, B * (size_t)L.nu * L.N * L.NB); rc |= dalloc(h, &P.Zb, B * (size_t)L.nu * L.N * L.NB); rc |= dalloc(h, &P.Sig, B * (size_t)L.nu * L.nu); }
     rc |= dalloc(h, &P.Dt, B * L.n); rc |= dalloc(h, &P.Et, B * L.m);
     rc |= dalloc(h, &P.ctype, B * L.m); rc |= dalloc(h, &P.info, B); rc |= dalloc(h, &P.stats, 10);
-        rc |= dalloc(h, &h->u0_dev, B * L.nu); rc |= dalloc(h, &h->um1_used, B * L.nu);
+    rc |= dalloc(h, &h->u0_dev, B * L.nu); rc |= dalloc(h, &h->um1_used, B * L.nu);
     rc |= dalloc(h, &P.work, B); rc |= dalloc(h, &h->perm_dev, B);
     rc |= dalloc(h, &h->vcur_dev, (size_t)std::max(4 * h->ncu, 1)); rc |= dalloc(h, &h->vqueue_dev, 4); rc |= dalloc(h, &h->vdone_dev, B); rc |= dalloc(h, &h->qperm_dev, B);
     rc |= dalloc(h, &P.tstamp, (size_t)TS_STRIDE * B);
     rc |= dalloc(h, &h->pending_dev, B); rc |= dalloc(h, &h->npending_dev, 4);
     if (h->S.tuning & MPCQP_TUNE_NO_BALANCE) h->auto_balance = 0;
     if (rc) { std::string msg = g_err; mpcqp_destroy(h); return fail(MPCQP_ERR_HIP, msg); }
-    // The factorization's workspace starts at the work area T, the last part of the common block,
-    // and may run on into the iterate area (dead while a factorization runs); T is widened only where even that is short.
-    const int toplds = bcrt ? LATW_TOP_LDS(NS) + 2 : 0;      // the round's LDS copy of the top inverse, behind the iterate (+ alignment slack)
-    const int fws = dense ? L.NR * L.dld + 2 * DenseFmt::ROWS + L.m + L.n : bcr ? BcrFmt::lds_doubles(h->L.nw, L.m + L.n, bcrt ? BcrFmt::top_count(NS) : 0) : (L.NB == 16 ? FactorCfg<16>::WS : L.NB == 32 ? FactorCfg<32>::WS : L.NB == 64 ? WideFmt::WS : HugeFmt::WS);
-    // (a held input, Nc < Np: border_factor also forms Sigma and its inverse, 2 nu^2 doubles, at the start of T -- more than any factorization
-    //  workspace once nu is large: (30, 40, 3, 2) needs 3 200 doubles where the 128-wide factorization asks for 264)
-    const int need = std::max(fws, (L.border && !dense) ? 2 * L.nu * L.nu : 0);
-    const int avail = L.tsz + (h->lds_state ? (int)state_doubles : 0) + toplds;
-    if (avail < need) h->L.tsz += need - avail;
-    h->smem_setup = sizeof(double) * ((size_t)smem_common_doubles(h->L) + (h->lds_state ? state_doubles : 0) + (size_t)toplds);      // every kernel gets the full block
-    // At most one instance per compute unit and an iterate that does not qualify for the LDS-resident owner map: stage it (with the metric
-    // vectors, the linear cost and the border matrices) into LDS for the length of a round if one workgroup's LDS holds it (admm_round_global).
-    {
-        const size_t stage_doubles = 2 * (size_t)L.n + 3 * (size_t)L.m + (size_t)(L.n_x + L.n_u) + (L.border ? 2 * (size_t)L.nu * L.N * L.NB + (size_t)L.nu * L.nu : 0);
-        const bool specialised = L.NB == 32 && L.nx == 20 && L.nu == 8 && !L.border;      // (the BASELINE cfg-5 instantiation has compile-time dimensions and no staged round)
-        const bool lstage = !h->lds_state && !dense && !bcr && !specialised && h->ncu > 0 && batch <= h->ncu && h->smem_setup + sizeof(double) * stage_doubles <= 150 * 1024
-                            && !(h->S.tuning & MPCQP_TUNE_NO_LSTAGE);
-        h->L.lstage = lstage ? 1 : 0;
-        if (lstage) h->smem_setup += sizeof(double) * stage_doubles;
-        // ... and of those, the ones on grouped stages (nx + nu <= 8 on a long horizon: the reference's notebook (4,1,150,75) and Kalman (4,1,200,200)
-        // examples with compile-time dimensions, anything else generically) run the 512-thread instantiation of the same kernel (mpcqp_w8.hip):
-        // eight waves for the owner passes that are half of their iteration
-        if (lstage && h->L.grp > 1 && !(h->S.tuning & MPCQP_TUNE_NO_W8)) {
-            h->smem_setup += sizeof(double) * 16 * (8 - h->L.nw);      // (the reduction scratch grows with the waves: smem_common)
-            h->L.nw = 8;
-        }
-    }
-    {   // The weight matrices [Qx | QxN | Qu | QDu] ride with the hot prefix into LDS (Lay::hot_lds) where that costs no residency: the kernels that
-        // run one workgroup per compute unit (latency backends, 512 threads, wide stages) or two (32 x 32 stages), not the four-per-CU bandwidth
-        // kernel of 16 x 16 stages, whose 40 KB are spoken for.
-        const size_t extra = sizeof(double) * (size_t)(h->L.model_sz - h->L.hot_sz);
-        const int occ = (h->L.nw == 8 || h->L.dense || h->L.bcr || h->L.NB > 32) ? 1 : h->L.NB <= 16 ? 4 : 2;
-        if ((h->smem_setup + extra + 1024) * (size_t)occ <= 160 * 1024) { h->L.hot_lds = h->L.model_sz; h->smem_setup += extra; }
-    }
-    h->smem_solve = h->smem_setup;
-    if (h->smem_solve > 160 * 1024) { mpcqp_destroy(h); return fail(MPCQP_ERR_UNSUPPORTED, "problem too large for one workgroup's LDS"); }
-    // check_norms_own reads the weight matrices through LDS views (as_lds): with an LDS-resident iterate they must BE in LDS -- staged with the hot
-    // prefix, or behind W in the work area.  The sizing above guarantees it; a layout change that breaks it must fail here, not give wrong residuals.
-    if (h->lds_state && h->L.hot_lds == h->L.hot_sz && h->L.tsz - h->L.m < h->L.model_sz - h->L.hot_sz) {
-        mpcqp_destroy(h); return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_create: internal layout error: the weight matrices of an LDS-resident handle do not fit behind W");
-    }
     *out = h;
     return MPCQP_OK;
 }
@@ -516,8 +382,8 @@ static int launch_setup(mpcqp_handle *h, bool keep = false) {
         hipLaunchKernelGGL(k_setup_factor_bcr, dim3(h->batch), dim3(NT), fac, h->stream, h->L, h->P);
     } else {
         DISPATCH_NB(L.NB, {
-            if (set_smem(k_setup_factor<NB>, h->smem_setup)) return MPCQP_ERR_HIP;
-            hipLaunchKernelGGL(k_setup_factor<NB>, dim3(h->batch), dim3(NT), h->smem_setup, h->stream, h->L, h->P);
+            if (set_smem(k_setup_factor<NB>, h->smem)) return MPCQP_ERR_HIP;
+            hipLaunchKernelGGL(k_setup_factor<NB>, dim3(h->batch), dim3(NT), h->smem, h->stream, h->L, h->P);
         });
     }
     HIPCHK(hipGetLastError());
@@ -621,8 +487,8 @@ extern "C" int mpcqp_update_vectors(mpcqp_handle *h, const double *q, const doub
         // tables behind them are materialised once from the controller data (q from (xref, uref, u_{-1}); du0 from u_{-1})
         if (!q || !l || !u) {
             DISPATCH_NB(h->L.NB, {
-                if (set_smem(k_export<NB>, h->smem_setup)) return MPCQP_ERR_HIP;
-                hipLaunchKernelGGL(k_export<NB>, dim3(h->batch), dim3(NT), h->smem_setup, h->stream, h->L, h->P, (double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr);
+                if (set_smem(k_export<NB>, h->smem)) return MPCQP_ERR_HIP;
+                hipLaunchKernelGGL(k_export<NB>, dim3(h->batch), dim3(NT), h->smem, h->stream, h->L, h->P, (double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr);
             });
             HIPCHK(hipGetLastError());
             hipLaunchKernelGGL(k_keep_du0, dim3((h->batch * h->L.nu + 255) / 256), dim3(256), 0, h->stream, h->L, h->P, h->batch);
@@ -723,9 +589,7 @@ extern "C" int mpcqp_update_settings(mpcqp_handle *h, const mpcqp_settings *s) {
 // 512 instances 121 / 138 / 148-150 / 141-144 / 137-138; 768 instances - / - / 153 / - / 145; 1024 instances 119 / - / 153 / 166 / 177 (two full rounds: all slots).
 static int run_grid(const mpcqp_handle *h, int nsteps) {
     const Lay &L = h->L;
-    const bool one_at_a_time = L.bcr || L.dense || L.NB > 32 || L.nw == 8;
-    int occ = one_at_a_time ? 1 : (L.NB <= 16 ? 4 : 2);
-    if (h->smem_solve > 0) occ = std::max(1, std::min(occ, (int)((size_t)160 * 1024 / h->smem_solve)));
+    const int occ = plan_occupancy(*h);
     const int full = h->ncu * occ;
     const int q = (h->S.tuning >> MPCQP_TUNE_SLOTS_SHIFT) & 0x1F;      // (development: resident workgroups in eighths of a workgroup per compute unit)
     if (q) return std::max(1, std::min(full, h->ncu * q / 8));
@@ -765,22 +629,11 @@ static RunKArgs run_kernel_args(mpcqp_handle *h, const RunArgs &R0, int *grid) {
     return A;
 }
 template <int NB, bool LDSS, int NXT, int NUT, int MODE>
-static int launch_run_t(mpcqp_handle *h, const RunArgs &R) {
-    int grid;
-    const RunKArgs A = run_kernel_args(h, R, &grid);
-    if (A.R.vdone && hipMemsetAsync(h->vdone_dev, 0, sizeof(int) * (size_t)h->batch, h->stream) != hipSuccess) return MPCQP_ERR_HIP;
-    if (R.nsteps > 0) {
-        if (set_smem(k_mpc_run<NB, LDSS, NXT, NUT, MODE, true>, h->smem_solve)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL((k_mpc_run<NB, LDSS, NXT, NUT, MODE, true>), dim3(grid), dim3(NT), h->smem_solve, h->stream, A);
-    } else {
-        if (set_smem(k_mpc_run<NB, LDSS, NXT, NUT, MODE, false>, h->smem_solve)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL((k_mpc_run<NB, LDSS, NXT, NUT, MODE, false>), dim3(grid), dim3(NT), h->smem_solve, h->stream, A);
-    }
+static int launch_run_t(mpcqp_handle *h, const RunKArgs &A, int grid) {
+    auto kernel = A.R.nsteps > 0 ? k_mpc_run<NB, LDSS, NXT, NUT, MODE, true> : k_mpc_run<NB, LDSS, NXT, NUT, MODE, false>;
+    if (set_smem(kernel, h->smem)) return MPCQP_ERR_HIP;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), h->smem, h->stream, A);
     return 0;
-}
-template <int NB, bool LDSS>
-static int launch_run_generic(mpcqp_handle *h, const RunArgs &R) {
-    return h->L.border ? launch_run_t<NB, LDSS, 0, 0, MODE_BORDER>(h, R) : launch_run_t<NB, LDSS, 0, 0, MODE_CHAIN>(h, R);
 }
 
 // Load balancing across CUs.  All workgroups of a launch are resident at once (a few per CU) and an instance keeps its
@@ -812,7 +665,8 @@ static int rebalance(mpcqp_handle *h) {
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return h->work_ema[a] > h->work_ema[b]; });
     // One workgroup per compute unit at a time (the latency kernels, wide stages): workgroups start in index order as compute units come
     // free, so the map is the longest-expected-work-first list -- the classic greedy schedule, makespan within one instance of the mean.
-    const bool one_at_a_time = h->L.bcr || h->L.dense || h->L.NB > 32 || h->L.nw == 8;
+    const int occ = kernel_occupancy(h->kernel);      // (by __launch_bounds__, whatever the LDS block leaves room for)
+    const bool one_at_a_time = occ == 1;
     const int full_rows = B / ncu;
     for (int j = 0; j < B; ++j) {
         const int row = j / ncu, pos = j % ncu;
@@ -826,7 +680,6 @@ static int rebalance(mpcqp_handle *h) {
     // instances are ALL resident at once (B <= slots) the launch ends with its slowest instance.  Every instance that is NOT expected to need more than
     // 1.15 x the median's iterations idles `units` x 3.5 us in each of its iterations, leaving its share of the memory system to the stragglers.
     {
-        const int occ = one_at_a_time ? 1 : (h->L.NB <= 16 ? 4 : 2);
         const int units = std::min((h->S.tuning >> 8) & 0xFF, 64);
         if (units && !one_at_a_time && !h->lds_state && !h->L.lstage && B <= occ * ncu) {
             const double wmed = h->work_ema[order[B / 2]];
@@ -863,32 +716,18 @@ static int launch_run(mpcqp_handle *h, RunArgs R, int plain_iters) {
         }
         HIPCHK(hipEventRecord(h->ev0[e], h->stream));
     }
-    int rc;
-    if (L.dense) rc = launch_run_t<16, true, 0, 0, MODE_DENSE>(h, R);
-    else if (L.nw == 8) {                           // 512-thread workgroups: the other translation unit (cyclic reduction with a dense top, or one long-horizon controller on grouped stages)
-        int grid;
-        const RunKArgs A = run_kernel_args(h, R, &grid);
-        if (A.R.vdone) HIPCHK(hipMemsetAsync(h->vdone_dev, 0, sizeof(int) * (size_t)h->batch, h->stream));
-        rc = L.bcr ? mpcqp_w8_launch(&A, sizeof(A), L.bcr == 31 && L.nx == 12 && L.nu == 4, L.bcr, R.nsteps > 0, grid, h->smem_solve, h->stream)
-                   : mpcqp_w8_launch(&A, sizeof(A), L.border, 0, R.nsteps > 0, grid, h->smem_solve, h->stream);
-        if (rc) return fail(MPCQP_ERR_HIP, "mpcqp_w8_launch failed");
+    int grid, rc = MPCQP_ERR_STATE;
+    const RunKArgs A = run_kernel_args(h, R, &grid);
+    if (A.R.vdone) HIPCHK(hipMemsetAsync(h->vdone_dev, 0, sizeof(int) * (size_t)h->batch, h->stream));
+    const RunKernelId &id = h->kernel;
+    if (id.w8) {                                    // 512-thread workgroups: the other translation unit
+        if (mpcqp_w8_launch(&A, sizeof(A), id, R.nsteps > 0, grid, h->smem, h->stream)) return fail(MPCQP_ERR_HIP, "mpcqp_w8_launch failed");
+        rc = 0;
     }
-    else if (L.bcrtop && L.bcr == 31 && L.nx == 12 && L.nu == 4) rc = launch_run_t<16, true, 12, 4, MODE_BCRT + 31>(h, R);
-    else if (L.bcrtop && L.bcr == 31) rc = launch_run_t<16, true, 0, 0, MODE_BCRT + 31>(h, R);
-    else if (L.bcrtop && L.bcr == 21) rc = launch_run_t<16, true, 0, 0, MODE_BCRT + 21>(h, R);
-    else if (L.bcrtop && L.bcr == 11) rc = launch_run_t<16, true, 0, 0, MODE_BCRT + 11>(h, R);
-    else if (L.bcr == 31 && L.nx == 12 && L.nu == 4) rc = launch_run_t<16, true, 12, 4, MODE_BCR + 31>(h, R);
-    else if (L.bcr == 31) rc = launch_run_t<16, true, 0, 0, MODE_BCR + 31>(h, R);
-    else if (L.bcr == 21) rc = launch_run_t<16, true, 0, 0, MODE_BCR + 21>(h, R);
-    else if (L.bcr == 11) rc = launch_run_t<16, true, 0, 0, MODE_BCR + 11>(h, R);
-    else if (L.NB == 16 && h->lds_state && L.nx == 12 && L.nu == 4 && !L.border) rc = launch_run_t<16, true, 12, 4, MODE_CHAIN>(h, R);
-    else if (L.NB == 32 && !h->lds_state && L.nx == 20 && L.nu == 8 && !L.border) rc = launch_run_t<32, false, 20, 8, MODE_CHAIN>(h, R);
-    // (the reference's cart pole -- its example system, and the Kalman notebook's long horizon -- with compile-time dimensions in the global-iterate kernel)
-    else if (L.NB == 16 && !h->lds_state && L.nx == 4 && L.nu == 1) rc = L.border ? launch_run_t<16, false, 4, 1, MODE_BORDER>(h, R) : launch_run_t<16, false, 4, 1, MODE_CHAIN>(h, R);
-    else if (L.NB == 16) rc = h->lds_state ? launch_run_generic<16, true>(h, R) : launch_run_generic<16, false>(h, R);
-    else if (L.NB == 32) rc = h->lds_state ? launch_run_generic<32, true>(h, R) : launch_run_generic<32, false>(h, R);
-    else if (L.NB == 64) rc = launch_run_generic<64, false>(h, R);
-    else rc = launch_run_generic<128, false>(h, R);
+#define X(NB, LDSS, NXT, NUT, MODE) else if (same_kernel(id, RunKernelId{NB, LDSS, NXT, NUT, MODE, false})) rc = launch_run_t<NB, LDSS, NXT, NUT, MODE>(h, A, grid);
+    MPCQP_RUN_KERNELS_256(X)
+#undef X
+    if (rc == MPCQP_ERR_STATE) return fail(rc, "launch_run: the planned solve kernel is not in the table");
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     if (h->profiling) { HIPCHK(hipEventRecord(h->ev1[e], h->stream)); h->ev_count += 1; }
@@ -1690,8 +1529,8 @@ extern "C" int mpcqp_eq_solve(mpcqp_handle *h, int sweeps, int cold, double tol,
     Scratch sc;
     HIPCHK(sc.get(&dres, (size_t)h->batch * 5));
     DISPATCH_NB(h->L.NB, {
-        if (set_smem(k_eq_solve<NB>, h->smem_setup)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL(k_eq_solve<NB>, dim3(h->batch), dim3(NT), h->smem_setup, h->stream, h->L, h->P, sweeps, cold, tol, dres);
+        if (set_smem(k_eq_solve<NB>, h->smem)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_eq_solve<NB>, dim3(h->batch), dim3(NT), h->smem, h->stream, h->L, h->P, sweeps, cold, tol, dres);
     });
     HIPCHK(hipGetLastError());
     if (h->pq.status) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * (size_t)h->batch, h->stream));      // (the polish setting is ignored here)
@@ -1882,119 +1721,37 @@ extern "C" int mpcqp_get_shape(mpcqp_handle *h, int *nx, int *nu, int *Np, int *
     return MPCQP_OK;
 }
 
+// Arithmetic on the handle's plan: mpcqp_plan.h says what each figure counts.
 extern "C" int mpcqp_get_dims(mpcqp_handle *h, int *n, int *m, int64_t *factor_doubles, int64_t *nnzL) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
-    const Lay &L = h->L;
-    if (n) *n = L.n;
-    if (m) *m = L.m;
-    if (factor_doubles) *factor_doubles = h->P.fsz;
-    if (nnzL) {      // structural nonzeros of the block factor (diagonal included) + the eliminated eps pivots
-        int64_t nb = L.nb, nx = L.nx;
-        const int64_t T = L.NcT;                       // stages with an input inside the tridiagonal part
-        int64_t full = T * (nb * (nb + 1) / 2) + (int64_t)(L.N - T) * (nx * (nx + 1) / 2);
-        int64_t sub = (T > 0 ? (T - 1) * (nx * nb + (int64_t)L.nu * L.nu) + nx * nb : 0) + (int64_t)(L.N - 1 - T) * nx * nx;
-        int64_t border = L.border ? (int64_t)L.nu * (L.n_x + T * L.nu) + (int64_t)L.nu * (L.nu + 1) / 2 : 0;
-        *nnzL = full + sub + border + (L.soft ? 2 * (int64_t)L.n_x : 0);
-    }
+    plan_dims(*h, n, m, factor_doubles, nnzL);
     return MPCQP_OK;
 }
 
-// Bytes one instance moves between the memory system (HBM / Infinity Cache / L2) and its compute unit BY DESIGN of these
-// kernels -- the roofline numerator bench.py uses ("Roofline accounting"):
-//   per ADMM iteration : the factor stream (FactorFmt, mpcqp_factor.h).  16 x 16 stages: forward matrices of N-1 stages, packed
-//                        S^-1 of N stages, N-1 stage tables and [G | G'], once each; 32 x 32 stages (S^-1-only): packed S^-1
-//                        twice, one table per sweep, [G | G'] by each sweeping wave.  Problems whose iterate does not fit
-//                        LDS also read and write x, z, y and read omega, s, q every iteration; Nc < Np adds the two border matrices.
-//   per round (check)  : residual evaluation inputs (weights, D, E, omega, s, last increments), the round's load/store of
-//                        the LDS-resident iterate and of the per-thread register copies of omega, s, q.
-//   per solve          : the begin phase (step data, E, constraint types, q rebuild) and the solution write-out.
 extern "C" int mpcqp_get_stream_bytes(mpcqp_handle *h, int64_t *per_iter, int64_t *per_round, int64_t *per_solve) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
-    const Lay &L = h->L;
-    const int64_t n = L.n, m = L.m, nq = L.n_x + L.n_u, NB = L.NB;
-    const int64_t sinv = L.fstage - L.ffwd - L.ftab;
-    int64_t it = (L.dense || L.bcr) ? 0 /* the factor sits in registers for the round */ : !L.ffwd ? 2 * (int64_t)L.N * sinv + (int64_t)L.N * L.ftab + 2 * (int64_t)L.fhead   // S^-1-only build: S^-1 twice, one of the two tables per sweep, [G | G'] by each sweeping wave
-                         : (int64_t)(L.N - 1) * L.ffwd + (int64_t)L.N * sinv + (int64_t)(L.N - 1) * L.ftab + L.fhead;   // forward matrices once, S^-1 once, the tables, G / G' once each
-    if (L.NB >= 64) it = (3 * (int64_t)L.N - 2) * (int64_t)L.NB * L.NB;      // wide stages: S^-1 of every stage, M and M' of all but the last
-    if (L.grp) it = (3 * (int64_t)group_count(L.N, L.grp) - 1) * GroupFmt::NN;      // grouped small stages: S^-1 of every super-stage, forward matrix and its transpose of all but the ends, the middle's second pair
-    if (!h->lds_state && !L.lstage) it += (2 * n + 4 * m) /* x, z, y read + written */ + (m + L.n_x) /* omega */ + (n + L.n_x) /* s */ + nq /* q */;
-    if (L.border && !L.dense) it += 2 * (int64_t)L.nu * L.N * NB;      // (the dense inverse holds the held input's couplings itself)
-    int64_t rd = (L.model_sz - L.hot_lds) /* the weight matrices, unless they are staged with the hot prefix */ + 2 * n + 2 * m /* D, s, E, omega */ + n + m /* dx, dy */;
-    if (L.dense) rd += DenseFmt::DOUBLES;               // the round's load of K^-1 into registers
-    if (L.bcr && !L.bcrtop) rd += (int64_t)L.bcr * BcrFmt::REC - 4 * BcrFmt::NN;      // ... of the cyclic-reduction fragments (the two end stages have one neighbour)
-    int64_t fr = 0;
-    if (L.bcrtop) {                                     // ... of levels 0 and 1 (the top inverse and G, G' enter LDS once per kernel prologue: admm_latw)
-        for (int l = 0; l < 2; ++l) for (int kind = 0; kind < 3; ++kind) for (int t = 0; t < lat_count(L.bcr, l, kind); ++t) fr += lat_nfr(L.bcr, l, kind, t);
-        rd += fr * BcrFmt::NN;
-    }
-    rd += (h->lds_state || L.lstage) ? 2 * (n + 2 * m) /* iterate in and out of LDS */ + (m + L.n_x) + (n + L.n_x) + nq : (n + 2 * m);
-    if (L.lstage && L.border) rd += 2 * (int64_t)L.nu * L.N * NB;      // the border matrices staged with it
-    int64_t sv = L.hot_lds + L.step_sz + 3 * m /* E, types, omega */ + nq + 2 * (n + m) /* solution out, iterate read */;
-    if (L.bcrtop && L.nw == 8 && (L.bcr + 3) / 4 <= 8 && L.hot_lds > L.hot_sz) {
-        // The 512-thread latency round with its own termination test (latw_check): a round boundary moves the level fragments, the increments (written by
-        // the last iteration, read back by the test) and the three scalings per lane the test clips the certificates with; the owners' registers are
-        // loaded once per SOLVE (iterate, metric, linear cost), the iterate, the solution and the record written once per solve; the top inverse and the hot
-        // prefix enter LDS once per kernel prologue -- per queue item of a persistent closed-loop launch, about every fifth solve (QUEUE_ITEMS_PER_SLOT).
-        // (Spill traffic around the non-inlined test -- ~ 110 bytes per lane and round in the write counter -- is NOT design traffic and not in here.)
-        rd = fr * BcrFmt::NN + 2 * (n + m) /* dx, dy out and back */ + 3 * 64 * 8 /* E of the owned rows */;
-        sv = L.step_sz + 3 * m + nq                                            /* begin: E, types, omega looked at, q written */
-           + (2 * n + 3 * m + nq)                                              /* the round's prologue: x, s, q, omega, z, y */
-           + (n + 2 * m) + (n + m)                                             /* the solve's end: iterate, reported solution */
-           + ((int64_t)L.bcrtop * L.bcrtop * BcrFmt::NN + L.hot_lds) / 5;     /* kernel prologue, amortised */
-    }
-    if (per_iter) *per_iter = 8 * it;
-    if (per_round) *per_round = 8 * rd;
-    if (per_solve) *per_solve = 8 * sv;
+    plan_stream_bytes(*h, per_iter, per_round, per_solve);
     return MPCQP_OK;
 }
 
-// Matrix-core instructions (v_mfma_f64_4x4x4_4b_f64, 512 flop each, a quarter of them useful in a mat-vec) one instance issues per
-// ADMM iteration with this handle's backend -- the numerator of the MFMA roofline bench.py reports for the latency backend.
 extern "C" int mpcqp_get_work(mpcqp_handle *h, int64_t *mfma_per_iter) {
     if (!h || !mfma_per_iter) return fail(MPCQP_ERR_ARG, "null argument");
-    const Lay &L = h->L;
-    int64_t mv = 0;                                  // 16 x 16 mat-vecs (four MFMAs each)
-    if (L.dense || L.NB >= 64) mv = 0;               // vector ALU only
-    else if (L.bcr) {
-        for (int l = 0; l < (L.bcrtop ? 2 : bcr_levels(L.bcr)); ++l)
-            for (int kind = 0; kind < 3; ++kind) for (int t = 0; t < lat_count(L.bcr, l, kind); ++t) mv += lat_nfr(L.bcr, l, kind, t);
-        // (the dense top runs on the vector ALU: 512 nt^2 flop per iteration, not counted here)
-        mv += 2 * ((L.bcr + 3) / 4);                 // G v and G'W: one group per four stages each
-    } else if (L.grp) mv = 3 * (int64_t)group_count(L.N, L.grp) - 1;      // forward 1, backward 2 mat-vecs per super-stage, the middle stage
-    else {
-        const int64_t blk = (L.NB / 16) * (L.NB / 16);
-        mv = L.ffwd ? (int64_t)(L.N - 1) * blk * 3 + 3 * blk : (int64_t)(L.N - 1) * blk * 4 + 3 * blk;      // forward 1 (or 2) + backward 2 mat-vecs per stage, the middle stage
-    }
-    *mfma_per_iter = 4 * mv;
+    *mfma_per_iter = plan_mfma_per_iter(*h);
     return MPCQP_OK;
 }
 
-// How many workgroups of the handle's solve kernel one compute unit holds at a time (the kernels' __launch_bounds__ occupancy, run_occupancy in
-// mpcqp_kernels.h, capped by what the dynamic LDS block leaves room for) and the compute units of the handle's device: bench.py's "instances in
-// flight" (what the memory-side cache sees) = the product.
 extern "C" int mpcqp_get_occupancy(mpcqp_handle *h, int *workgroups_per_cu, int *compute_units, int *threads_per_workgroup) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
-    const Lay &L = h->L;
-    const bool one_at_a_time = L.bcr || L.dense || L.NB > 32 || L.nw == 8;
-    int occ = one_at_a_time ? 1 : (L.NB <= 16 ? 4 : 2);
-    const size_t lds_cu = 160 * 1024;
-    if (h->smem_solve > 0) occ = std::max(1, std::min(occ, (int)(lds_cu / h->smem_solve)));
-    if (workgroups_per_cu) *workgroups_per_cu = occ;
+    if (workgroups_per_cu) *workgroups_per_cu = plan_occupancy(*h);
     if (compute_units) *compute_units = h->ncu;
-    if (threads_per_workgroup) *threads_per_workgroup = L.nw == 8 ? 512 : 256;
+    if (threads_per_workgroup) *threads_per_workgroup = plan_threads(*h);
     return MPCQP_OK;
 }
 
-// Name of the k_mpc_run instantiation the handle's solves (loop = 0) or closed-loop runs (loop = 1) launch, spelled as
-// rocprofv3 prints it (without spaces) -- so that bench.py and the profile summaries name the same kernel.
+// Name of the k_mpc_run instantiation the handle's solves (loop = 0) or closed-loop runs (loop = 1) launch: the id launch_run dispatches on.
 extern "C" int mpcqp_kernel_name(mpcqp_handle *h, int loop, char *buf, int buflen) {
     if (!h || !buf || buflen < 1) return fail(MPCQP_ERR_ARG, "null argument");
-    const Lay &L = h->L;
-    const bool spec = L.dense ? false : (L.NB == 16 && !L.bcr && !h->lds_state && L.nx == 4 && L.nu == 1) ? true :
-                      !L.border && (L.bcr ? (L.bcr == 31 && L.nx == 12 && L.nu == 4)
-                                          : ((L.NB == 16 && h->lds_state && L.nx == 12 && L.nu == 4) || (L.NB == 32 && !h->lds_state && L.nx == 20 && L.nu == 8)));
-    snprintf(buf, (size_t)buflen, "%sk_mpc_run<%d,%s,%d,%d,%d,%s>", L.nw == 8 ? "w8::" : "", L.NB, h->lds_state ? "true" : "false", spec ? L.nx : 0, spec ? L.nu : 0,
-             L.dense ? MODE_DENSE : L.bcr ? (L.bcrtop ? MODE_BCRT : MODE_BCR) + L.bcr : L.border ? MODE_BORDER : MODE_CHAIN, loop ? "true" : "false");
+    run_kernel_name(h->kernel, loop != 0, buf, (size_t)buflen);
     return MPCQP_OK;
 }
 
@@ -2021,8 +1778,8 @@ extern "C" int mpcqp_export_qp(mpcqp_handle *h, double *Pm, double *Am, double *
     if (q) HIPCHK(sc.get(&dq, B * L.n));
     if (l && u) { HIPCHK(sc.get(&dl, B * L.m)); HIPCHK(sc.get(&du, B * L.m)); }
     DISPATCH_NB(L.NB, {
-        if (set_smem(k_export<NB>, h->smem_setup)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL(k_export<NB>, dim3(h->batch), dim3(NT), h->smem_setup, h->stream, h->L, h->P, dP, dA, dq, dl, du);
+        if (set_smem(k_export<NB>, h->smem)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_export<NB>, dim3(h->batch), dim3(NT), h->smem, h->stream, h->L, h->P, dP, dA, dq, dl, du);
     });
     HIPCHK(hipGetLastError());
     int rc = 0;
@@ -2063,8 +1820,8 @@ extern "C" int mpcqp_debug_kkt_solve(mpcqp_handle *h, const double *rhs, double 
     HIPCHK(sc.get(&dr, (size_t)h->batch * L.n)); HIPCHK(sc.get(&ds, (size_t)h->batch * L.n));
     HIPCHK(hipMemcpyAsync(dr, rhs, bytes, hipMemcpyDefault, h->stream));
     DISPATCH_NB(L.NB, {
-        if (set_smem(k_kkt_solve<NB>, h->smem_setup)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL(k_kkt_solve<NB>, dim3(h->batch), dim3(NT), h->smem_setup, h->stream, h->L, h->P, dr, ds);
+        if (set_smem(k_kkt_solve<NB>, h->smem)) return MPCQP_ERR_HIP;
+        hipLaunchKernelGGL(k_kkt_solve<NB>, dim3(h->batch), dim3(NT), h->smem, h->stream, h->L, h->P, dr, ds);
     });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(sol, ds, bytes, hipMemcpyDefault, h->stream));

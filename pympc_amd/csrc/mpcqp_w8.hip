@@ -1,5 +1,5 @@
 // mpcqp_w8.hip -- second translation unit of libmpcqp_hip.so: the solve / closed-loop kernel of the latency backend with 512-THREAD workgroups
-// (eight waves, two per SIMD) for handles with at most one instance per compute unit (mpcqp_create: Lay::nw = 8; mpcqp_latw.h says why).
+// (eight waves, two per SIMD) for handles with at most one instance per compute unit (mpcqp_plan.h: Lay::nw = 8; mpcqp_latw.h says why).
 //
 // The device code of this library is written against the compile-time workgroup size NT (mpcqp_defs.h): here the same headers are compiled once
 // more with NT = 512, inside namespace w8 so that nothing collides with the 256-thread instantiations of mpcqp.hip.  Only k_mpc_run of the
@@ -7,7 +7,8 @@
 // long horizon (grouped stages, round staged in LDS), the sweeps kernel: half of its iteration is owner passes that eight waves run faster than
 // four; their begin / check / factorization phases are the common ones at 512 threads.  Setup, export and the verification kernels of such a handle run from mpcqp.hip at 256 threads -- every phase sizes
 // its loops by NT, and the data in memory does not know how many threads wrote it.
-// Host side: one function, called by launch_run in mpcqp.hip.
+// What is instantiated here is the table MPCQP_RUN_KERNELS_512 of mpcqp_defs.h, every row for LOOP false and true, and nothing else.
+// Host side: one function, called by launch_run in mpcqp.hip with the RunKernelId the handle's plan chose (run_kernel_id in mpcqp_plan.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -40,32 +41,23 @@ namespace w8 {
 #include "mpcqp_kernels.h"
 #include "mpcqp_latw_check.h"
 
-template <int NXT, int NUT, int MODE, bool LOOP, bool LDSS = true>
-static int launch(const RunKArgs &A, int grid, size_t smem, hipStream_t stream) {
-    auto kernel = k_mpc_run<16, LDSS, NXT, NUT, MODE, LOOP>;
+template <int NB, bool LDSS, int NXT, int NUT, int MODE>
+static int launch(const RunKArgs &A, bool loop, int grid, size_t smem, hipStream_t stream) {
+    auto kernel = loop ? k_mpc_run<NB, LDSS, NXT, NUT, MODE, true> : k_mpc_run<NB, LDSS, NXT, NUT, MODE, false>;
     if (smem > 48 * 1024 && hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return 1;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), smem, stream, A);
     return 0;
 }
-template <int NXT, int NUT, int MODE, bool LDSS = true>
-static int launch_lp(const RunKArgs &A, int loop, int grid, size_t smem, hipStream_t stream) {
-    return loop ? launch<NXT, NUT, MODE, true, LDSS>(A, grid, smem, stream) : launch<NXT, NUT, MODE, false, LDSS>(A, grid, smem, stream);
-}
 }  // namespace w8
 
-// sched: 11 / 21 / 31 = the cyclic-reduction schedule (spec12_4: the BASELINE shape with compile-time dimensions); 0 = ONE long-horizon controller
-// on grouped stages with the round staged in LDS (the reference's cart pole -- its notebook and Kalman examples -- with compile-time dimensions,
-// any other nx + nu <= 8 through the generic instantiation), spec12_4 then says "held input"
-int mpcqp_w8_launch(const void *kargs, size_t kargs_bytes, int spec12_4, int sched, int loop, int grid, size_t smem, hipStream_t stream) {
+// id: a row of MPCQP_RUN_KERNELS_512 (mpcqp_defs.h), chosen by run_kernel_id in mpcqp_plan.h.  3: not one of this unit's kernels.
+int mpcqp_w8_launch(const void *kargs, size_t kargs_bytes, const RunKernelId &id, int loop, int grid, size_t smem, hipStream_t stream) {
     using namespace w8;
     if (kargs_bytes != sizeof(RunKArgs)) return 2;
     RunKArgs A; memcpy(&A, kargs, sizeof(A));
-    if (sched == 0 && A.L.nx == 4 && A.L.nu == 1) return spec12_4 ? launch_lp<4, 1, MODE_BORDER, false>(A, loop, grid, smem, stream) : launch_lp<4, 1, MODE_CHAIN, false>(A, loop, grid, smem, stream);
-    if (sched == 0) return spec12_4 ? launch_lp<0, 0, MODE_BORDER, false>(A, loop, grid, smem, stream) : launch_lp<0, 0, MODE_CHAIN, false>(A, loop, grid, smem, stream);
-    if (sched == 31 && spec12_4) return launch_lp<12, 4, MODE_BCRT + 31>(A, loop, grid, smem, stream);
-    if (sched == 31) return launch_lp<0, 0, MODE_BCRT + 31>(A, loop, grid, smem, stream);
-    if (sched == 21) return launch_lp<0, 0, MODE_BCRT + 21>(A, loop, grid, smem, stream);
-    if (sched == 11) return launch_lp<0, 0, MODE_BCRT + 11>(A, loop, grid, smem, stream);
+#define X(NB, LDSS, NXT, NUT, MODE) if (same_kernel(id, RunKernelId{NB, LDSS, NXT, NUT, MODE, true})) return launch<NB, LDSS, NXT, NUT, MODE>(A, loop != 0, grid, smem, stream);
+    MPCQP_RUN_KERNELS_512(X)
+#undef X
     return 3;
 }
 

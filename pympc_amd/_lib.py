@@ -39,6 +39,10 @@ ROLLOUT_SYMBOLS = ['mpcqp_rollout', 'mpcqp_rollout_tape_bytes', 'mpcqp_rollout_r
 # include/mpcqp_rollout_est.h: likewise -- the taped rollout of the output-feedback loop, differentiated through the estimator
 ROLLOUT_EST_SYMBOLS = ['mpcqp_rollout_est', 'mpcqp_rollout_est_tape_bytes', 'mpcqp_rollout_adjoint_est', 'mpcqp_rollout_get_tape_est']
 
+# include/mpcqp_adjoint_bounds.h: likewise -- the adjoint chained into the constraint bounds, for the single solve and for the sweeps
+ADJOINT_BOUNDS_SYMBOLS = ['mpcqp_adjoint_bounds', 'mpcqp_rollout_adjoint_bounds']
+ADJOINT_BOUNDS_NAMES = ('xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')      # the outputs of mpcqp_adjoint_bounds_io, in its order
+
 # include/mpcqp_riccati.h: likewise -- batched discrete algebraic Riccati equations and their adjoint, without a handle
 RICCATI_SYMBOLS = ['mpcqp_riccati_default_settings', 'mpcqp_dare', 'mpcqp_dare_adjoint']
 
@@ -71,6 +75,12 @@ class AdjointModelIO(C.Structure):
     """mpcqp_adjoint_model_io (include/mpcqp_adjoint_model.h): model gradients out; host or device pointers, None = not wanted."""
     _fields_ = [('struct_size', C.c_int32), ('batch_sum', C.c_int32), ('d_Ad', C.c_void_p), ('d_Bd', C.c_void_p), ('d_Qx', C.c_void_p),
                 ('d_QxN', C.c_void_p), ('d_Qu', C.c_void_p), ('d_QDu', C.c_void_p), ('d_eps_feas', C.c_void_p)]
+
+
+class AdjointBoundsIO(C.Structure):
+    """mpcqp_adjoint_bounds_io (include/mpcqp_adjoint_bounds.h): bound gradients out; host or device pointers, None = not wanted."""
+    _fields_ = [('struct_size', C.c_int32), ('batch_sum', C.c_int32), ('d_xmin', C.c_void_p), ('d_xmax', C.c_void_p), ('d_umin', C.c_void_p),
+                ('d_umax', C.c_void_p), ('d_Dumin', C.c_void_p), ('d_Dumax', C.c_void_p)]
 
 
 class RolloutAdjointIO(C.Structure):
@@ -243,6 +253,11 @@ def load():
         L.mpcqp_rollout_get_tape_est.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p]
         for name in ROLLOUT_EST_SYMBOLS:
             getattr(L, name).restype = C.c_int
+    if has_adjoint_bounds(L):
+        L.mpcqp_adjoint_bounds.argtypes = [H, C.POINTER(AdjointIO), C.POINTER(AdjointModelIO), C.POINTER(AdjointBoundsIO)]
+        L.mpcqp_rollout_adjoint_bounds.argtypes = [H, C.POINTER(RolloutAdjointIO), C.POINTER(RolloutEstIO), C.POINTER(AdjointModelIO), C.POINTER(AdjointBoundsIO)]
+        for name in ADJOINT_BOUNDS_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     if has_riccati(L):
         L.mpcqp_riccati_default_settings.argtypes = [C.POINTER(RiccatiSettings)]
         L.mpcqp_riccati_default_settings.restype = None
@@ -288,6 +303,11 @@ def has_rollout(L=None):
 def has_rollout_est(L=None):
     """True if the library exports include/mpcqp_rollout_est.h."""
     return _has(L, ROLLOUT_EST_SYMBOLS)
+
+
+def has_adjoint_bounds(L=None):
+    """True if the library exports include/mpcqp_adjoint_bounds.h."""
+    return _has(L, ADJOINT_BOUNDS_SYMBOLS)
 
 
 def has_riccati(L=None):

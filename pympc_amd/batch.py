@@ -246,7 +246,8 @@ class BatchMPCController:
         dL/dx_k, ``g_u`` [K,B,nu] = dL/du_k.  Returns the gradients named in ``want`` -- 'lam' [K+1,B,nx] (lam[0] = dL/dx0, lam[k+1] =
         dL/dw[k]), 'uminus1', 'uref' [B,nu], 'xref' [K,B,rows*nx], 'Ap' [B,nx,nx], 'Bp' [B,nx,nu] (the plant path alone: with the
         controller's own model as the plant, add them to 'Ad', 'Bd'), and 'Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu', 'eps_feas' summed over the
-        steps (``batch_sum``: and over the batch) -- plus ``n_weak`` [K,B], ``status`` [K,B] per step and ``n_factor`` [B], the
+        steps (``batch_sum``: and over the batch), and likewise the bound gradients 'xmin', 'xmax' [B,nx], 'umin', 'umax', 'Dumin', 'Dumax'
+        [B,nu] (mpcqp_rollout_adjoint_bounds: the bounds are constant over the tape) -- plus ``n_weak`` [K,B], ``status`` [K,B] per step and ``n_factor`` [B], the
         factorizations the sweep made.  numpy in, numpy out; torch device tensors in, device tensors out.  After ``rollout_est``: ``g_xhat``
         [K+1,B,nx] = dL/dxhat_k and ``g_y`` [K,B,ny] = dL/dy_k seed the sweep too, and ``want`` may name 'eta' [K+1,B,nx] (eta[0] = dL/dxhat_0),
         'C' [B,ny,nx], 'L' [B,nx,ny], 'v' [K,B,ny] and 'Ae' [B,nx,nx], 'Be' [B,nx,nu], the estimator path alone (add them to 'Ad', 'Bd')."""
@@ -269,8 +270,9 @@ class BatchMPCController:
         """Vector-Jacobian products of the last solve (mpcqp_adjoint): for ``g_u0`` [B,nu] = dL/du_0 and / or ``g_w`` [B,n] = dL/dw returns
         ``dict(x0 [B,nx], uminus1 [B,nu], xref [B,rows*nx], uref [B,nu], n_weak [B], status [B])`` = dL/d(x0, u_{-1}, xref, uref).  ``want`` may
         also name the model gradients 'Ad' [B,nx,nx], 'Bd' [B,nx,nu], 'Qx', 'QxN' [B,nx,nx], 'Qu', 'QDu' [B,nu,nu], 'eps_feas' [B]
-        (mpcqp_adjoint_model; ``batch_sum``: summed over the batch, leading dimension 1 -- see ``BatchProblem.adjoint``).  numpy in, numpy
-        out; torch device tensors in, device tensors out."""
+        (mpcqp_adjoint_model; ``batch_sum``: summed over the batch, leading dimension 1 -- see ``BatchProblem.adjoint``) and the bound
+        gradients 'xmin', 'xmax' [B,nx], 'umin', 'umax', 'Dumin', 'Dumax' [B,nu] (mpcqp_adjoint_bounds; ``batch_sum`` likewise).  numpy in,
+        numpy out; torch device tensors in, device tensors out."""
         res = self.prob.adjoint(g_w=g_w, g_u0=g_u0, want=want, batch_sum=batch_sum)
         _, n_weak, status = self.prob.adjoint_info()
         res.update(n_weak=n_weak, status=status)

@@ -330,7 +330,8 @@ class MPCController:
         """Vector-Jacobian products of the last solve for the seed ``g_u0`` [nu] = dL/du_0 and / or ``g_w`` [n] = dL/dw (mpcqp_adjoint,
         mpcqp_adjoint_model): a dict with the gradients named in ``want`` -- 'x0', 'uminus1', 'xref', 'uref', 'q', 'l', 'u' and the model
         gradients 'Ad' [nx, nx], 'Bd' [nx, nu], 'Qx', 'QxN' [nx, nx], 'Qu', 'QDu' [nu, nu], 'eps_feas' (weights: with respect to a symmetric
-        perturbation) -- plus ``n_weak`` and ``status`` as in ``gains()``.  A weight whose cost term this controller runs without (the
+        perturbation) and the bound gradients 'xmin', 'xmax' [nx], 'umin', 'umax', 'Dumin', 'Dumax' [nu] (mpcqp_adjoint_bounds) -- plus
+        ``n_weak`` and ``status`` as in ``gains()``.  A weight whose cost term this controller runs without (the
         switches JX_ON, JU_ON, JDU_ON) gets zero.  An addition to the reference's class."""
         bp = getattr(self.prob, 'batch_problem', None)
         if bp is None or not hasattr(bp, 'adjoint'):

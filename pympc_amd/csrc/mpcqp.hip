@@ -50,6 +50,7 @@
 #include "../../include/mpcqp_adjoint_model.h"
 #include "../../include/mpcqp_rollout.h"
 #include "../../include/mpcqp_rollout_est.h"
+#include "../../include/mpcqp_adjoint_bounds.h"
 
 #include "mpcqp_defs.h"
 
@@ -92,6 +93,7 @@ int mpcqp_set_error(int code, const char *msg) { return fail(code, msg); }      
 #include "mpcqp_polish.h"
 #include "mpcqp_adjoint.h"
 #include "mpcqp_adjoint_model.h"
+#include "mpcqp_adjoint_bounds.h"
 #include "mpcqp_rollout.h"
 #include "mpcqp_csc.h"
 
@@ -148,6 +150,7 @@ struct mpcqp_handle : Plan {       // the plan (mpcqp_plan.h: ncu, batch, L, lds
     double *um1_used = nullptr; bool um1_moved = false;    // mpcqp_mpc_step: the u_{-1} its solve was made with, [batch][nu]; true while the step data hold the applied input instead
     double *adj_step = nullptr;          // the adjoint's copy of the step data with that u_{-1} put back [batch][step_sz] (null until first needed)
     double *adjm_out = nullptr, *adjm_sum = nullptr;   // mpcqp_adjoint_model: the per-instance model gradients (field-major, AdjointModelArgs::out) and their batch sum; null until first use
+    double *adjb_out = nullptr, *adjb_sum = nullptr;   // mpcqp_adjoint_bounds: the per-instance bound gradients (field-major, AdjointBoundsArgs::out: the tail of adjm_out's block, where the sweep expects them) and their batch sum; null until first use
     RolloutTape tape = {}; void *tape_buf = nullptr; size_t tape_bytes = 0;      // mpcqp_rollout (include/mpcqp_rollout.h): the tape, one device block (null until the first rollout)
     int tape_ny = 0;                                           // > 0: the tape is one of the output-feedback loop (mpcqp_rollout_est, include/mpcqp_rollout_est.h)
     int tape_xref_rows = 1; bool tape_valid = false;           // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
@@ -1053,16 +1056,21 @@ static void adjoint_model_offsets(const Lay &L, int *off) {
     for (int f = 0; f < ADJM_FIELDS; ++f) off[f + 1] = off[f] + sz[f];
 }
 // The per-instance model gradients [batch][E] and their batch sum [E], on first use, like the adjoint's other buffers.
+// The bound gradients (mpcqp_adjoint_bounds.h) live behind the model's in the same block: adjb_out = adjm_out + batch E.
 static int adjoint_model_alloc(mpcqp_handle *h, size_t E) {
     if (h->adjm_out) return MPCQP_OK;
-    return dalloc(h, &h->adjm_out, (size_t)h->batch * E) || dalloc(h, &h->adjm_sum, E) ? MPCQP_ERR_HIP : MPCQP_OK;
+    const size_t EB = (size_t)adjoint_bounds_entries(h->L);
+    if (dalloc(h, &h->adjm_out, (size_t)h->batch * (E + EB)) || dalloc(h, &h->adjm_sum, E) || dalloc(h, &h->adjb_sum, EB)) return MPCQP_ERR_HIP;
+    h->adjb_out = h->adjm_out + (size_t)h->batch * E;
+    return MPCQP_OK;
 }
-// adjm_sum = adjm_out added over the batch (off: adjoint_model_offsets)
-static void launch_adjoint_model_sum(mpcqp_handle *h, const int *off) {
+// adjm_sum = adjm_out added over the batch (off: adjoint_model_offsets); or, given both, `sum` = the field-major buffer `out` (off: its own table)
+static void launch_adjoint_model_sum(mpcqp_handle *h, const int *off, double *out = nullptr, double *sum = nullptr) {
     AdjointModelArgs M; memset(&M, 0, sizeof(M));
     std::copy(off, off + ADJM_FIELDS + 1, M.off);
-    M.out = h->adjm_out; M.batch = h->batch;
-    hipLaunchKernelGGL(k_adjoint_model_sum, dim3((unsigned)((M.off[ADJM_FIELDS] + 15) / 16)), dim3(256), 0, h->stream, M, h->adjm_sum);
+    M.out = out ? out : h->adjm_out; M.batch = h->batch;
+    if (M.off[ADJM_FIELDS] < 1) return;
+    hipLaunchKernelGGL(k_adjoint_model_sum, dim3((unsigned)((M.off[ADJM_FIELDS] + 15) / 16)), dim3(256), 0, h->stream, M, sum ? sum : h->adjm_sum);
 }
 // Every field the caller asked for, from adjm_sum (one set) or adjm_out (one per instance).
 static int get_model_out(mpcqp_handle *h, const ModelOut &m, const int *off) {
@@ -1091,21 +1099,74 @@ static int launch_adjoint_model(mpcqp_handle *h, bool batch_sum) {
     HIPCHK(hipGetLastError());
     return MPCQP_OK;
 }
-// mpcqp_adjoint (mo null) and mpcqp_adjoint_model: one k_adjoint launch, the model kernels behind it where mo asks for anything.
-static int adjoint_call(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp_adjoint_model_io *mo, const char *what) {
+// ---- the bound gradients (include/mpcqp_adjoint_bounds.h, mpcqp_adjoint_bounds.h) ----------------------------------------------
+// The bound-gradient outputs of a call, taken once from its mpcqp_adjoint_bounds_io (null: none): the six pointers in field order (xmin, xmax,
+// umin, umax, Dumin, Dumax), whether any is given, and batch_sum.
+struct BoundsOut { double *out[ADJB_FIELDS]; bool any; int batch_sum; };
+static int bounds_out(const mpcqp_adjoint_bounds_io *bo, const std::string &what, BoundsOut *o) {
+    *o = BoundsOut{};
+    if (!bo) return MPCQP_OK;
+    if (bo->struct_size != (int32_t)sizeof(mpcqp_adjoint_bounds_io)) return fail(MPCQP_ERR_ARG, what + ": struct_size is not sizeof(mpcqp_adjoint_bounds_io)");
+    if (bo->batch_sum != 0 && bo->batch_sum != 1) return fail(MPCQP_ERR_ARG, what + ": batch_sum of mpcqp_adjoint_bounds_io is 0 or 1");
+    double *const out[ADJB_FIELDS] = {bo->d_xmin, bo->d_xmax, bo->d_umin, bo->d_umax, bo->d_Dumin, bo->d_Dumax};
+    for (int f = 0; f < ADJB_FIELDS; ++f) { o->out[f] = out[f]; if (out[f]) o->any = true; }
+    o->batch_sum = bo->batch_sum;
+    return MPCQP_OK;
+}
+// Entries of the bound gradients of one instance, field by field, as prefix sums -- in the table k_adjoint_model_sum reads: the fields beyond the sixth are empty.
+static void adjoint_bounds_offsets(const Lay &L, int *off) {
+    const int sz[ADJB_FIELDS] = {L.nx, L.nx, L.nu, L.nu, L.nu, L.nu};
+    off[0] = 0;
+    for (int f = 0; f < ADJM_FIELDS; ++f) off[f + 1] = off[f] + (f < ADJB_FIELDS ? sz[f] : 0);
+}
+// The per-instance bound gradients [batch][E] and their batch sum [E], on first use: one block with the model's (adjoint_model_alloc).
+static int adjoint_bounds_alloc(mpcqp_handle *h) {
+    int off[ADJM_FIELDS + 1]; adjoint_model_offsets(h->L, off);
+    return adjoint_model_alloc(h, (size_t)off[ADJM_FIELDS]);
+}
+// The batch sum where it is wanted, then every field the caller asked for, from adjb_sum (one set) or adjb_out (one per instance).
+static int get_bounds_out(mpcqp_handle *h, const BoundsOut &o) {
+    int off[ADJM_FIELDS + 1]; adjoint_bounds_offsets(h->L, off);
+    if (o.batch_sum) { launch_adjoint_model_sum(h, off, h->adjb_out, h->adjb_sum); HIPCHK(hipGetLastError()); }
+    const size_t B = (size_t)h->batch;
+    for (int f = 0; f < ADJB_FIELDS; ++f) {
+        const size_t sz = (size_t)(off[f + 1] - off[f]);
+        const double *src = o.batch_sum ? h->adjb_sum + off[f] : h->adjb_out + B * (size_t)off[f];
+        if (get(h, o.out[f], src, (o.batch_sum ? 1 : B) * sz * sizeof(double))) return MPCQP_ERR_HIP;
+    }
+    return MPCQP_OK;
+}
+// k_adjoint_bounds behind the k_adjoint launch of the same call: the rows of seed 0 reduced to the bounds.
+static int launch_adjoint_bounds(mpcqp_handle *h) {
+    if (adjoint_bounds_alloc(h)) return MPCQP_ERR_HIP;
+    AdjointBoundsArgs M; memset(&M, 0, sizeof(M));
+    M.act = h->aq.K.act; M.ry = h->aq.y; M.status = h->aq.status; M.out = h->adjb_out; M.batch = h->batch;
+    hipLaunchKernelGGL(k_adjoint_bounds, dim3(h->batch), dim3(NT), 0, h->stream, h->L, M);
+    HIPCHK(hipGetLastError());
+    return MPCQP_OK;
+}
+static bool any_host(const BoundsOut &o) {
+    for (const double *q : o.out) if (q && !is_device_ptr(q)) return true;
+    return false;
+}
+// mpcqp_adjoint (mo, bo null), mpcqp_adjoint_model (bo null) and mpcqp_adjoint_bounds: one k_adjoint launch, the model kernels behind it where
+// mo asks for anything, the bound kernel where bo does.
+static int adjoint_call(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp_adjoint_model_io *mo, const char *what, const mpcqp_adjoint_bounds_io *bo = nullptr) {
     const std::string w(what);
     if (io->struct_size != (int32_t)sizeof(mpcqp_adjoint_io)) return fail(MPCQP_ERR_ARG, w + ": struct_size is not sizeof(mpcqp_adjoint_io)");
     ModelOut m;
     if (model_out(mo, w, &m)) return MPCQP_ERR_ARG;
+    BoundsOut bd;
+    if (bounds_out(bo, w, &bd)) return MPCQP_ERR_ARG;
     if (!io->g_w && !io->g_u0) return fail(MPCQP_ERR_ARG, w + ": give g_w, g_u0 or both");
     if ((io->d_l == nullptr) != (io->d_u == nullptr)) return fail(MPCQP_ERR_ARG, w + ": d_l and d_u go together");
     const bool model = m.any;
     const bool chain = io->d_x0 || io->d_uminus1 || io->d_xref || io->d_uref;
     if (mo) {
         if (m.batch_sum != 0 && m.batch_sum != 1) return fail(MPCQP_ERR_ARG, w + ": batch_sum is 0 or 1");
-        if (!model && !chain && !io->d_q && !io->d_l) return fail(MPCQP_ERR_ARG, w + ": no output asked for");
     }
-    int rc = adjoint_ready(h, what, chain || model);
+    if ((mo || bo) && !model && !bd.any && !chain && !io->d_q && !io->d_l) return fail(MPCQP_ERR_ARG, w + ": no output asked for");
+    int rc = adjoint_ready(h, what, chain || model || bd.any);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
     if ((rc = adjoint_alloc(h))) return rc;
@@ -1114,6 +1175,7 @@ static int adjoint_call(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp
     if (io->g_u0) HIPCHK(hipMemcpyAsync(h->adj_gu0, io->g_u0, B * L.nu * db, hipMemcpyDefault, h->stream));
     if ((rc = launch_adjoint(h, 1, io->g_w ? h->adj_gw : nullptr, io->g_u0 ? h->adj_gu0 : nullptr, io->d_q || io->d_l))) return rc;
     if (model && (rc = launch_adjoint_model(h, m.batch_sum != 0))) return rc;
+    if (bd.any && (rc = launch_adjoint_bounds(h))) return rc;
     const AdjointArgs &Q = h->aq;
     if (get(h, io->d_x0, Q.ox0, B * L.nx * db) || get(h, io->d_uminus1, Q.oum1, B * L.nu * db) || get(h, io->d_uref, Q.ouref, B * L.nu * db) ||
         get(h, io->d_xref, Q.oxref, B * (size_t)L.xref_rows * L.nx * db) || get(h, io->d_q, Q.oq, B * L.n * db) ||
@@ -1122,6 +1184,8 @@ static int adjoint_call(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp
         int off[ADJM_FIELDS + 1]; adjoint_model_offsets(L, off);
         if (get_model_out(h, m, off)) return MPCQP_ERR_HIP;
     }
+    if (bd.any && get_bounds_out(h, bd)) return MPCQP_ERR_HIP;
+    if (any_host(bd)) HIPCHK(hipStreamSynchronize(h->stream));
     return sync_unless_all_device(h, {io->g_w, io->g_u0, io->d_x0, io->d_uminus1, io->d_xref, io->d_uref, io->d_q, io->d_l, io->d_u}, &m);
 }
 extern "C" int mpcqp_adjoint(mpcqp_handle *h, const mpcqp_adjoint_io *io) {
@@ -1131,6 +1195,10 @@ extern "C" int mpcqp_adjoint(mpcqp_handle *h, const mpcqp_adjoint_io *io) {
 extern "C" int mpcqp_adjoint_model(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
     return adjoint_call(h, io, mo, mo ? "mpcqp_adjoint_model" : "mpcqp_adjoint");
+}
+extern "C" int mpcqp_adjoint_bounds(mpcqp_handle *h, const mpcqp_adjoint_io *io, const mpcqp_adjoint_model_io *mo, const mpcqp_adjoint_bounds_io *bo) {
+    if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
+    return adjoint_call(h, io, mo, bo ? "mpcqp_adjoint_bounds" : mo ? "mpcqp_adjoint_model" : "mpcqp_adjoint", bo);
 }
 extern "C" int mpcqp_gains(mpcqp_handle *h, double *K_x0, double *K_uminus1, double *K_xref, double *K_uref) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
@@ -1423,11 +1491,21 @@ static int put_seed(mpcqp_handle *h, double *dst, const double *src, size_t byte
     return MPCQP_OK;
 }
 // eo: the estimator's seeds and gradients (mpcqp_rollout_adjoint_est), or null.  est: the call is mpcqp_rollout_adjoint_est.
-static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo, bool est) {
+// bo: the bound gradients (mpcqp_rollout_adjoint_bounds), or null.
+static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo, bool est,
+                         const mpcqp_adjoint_bounds_io *bo = nullptr) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
     if (io->struct_size != (int32_t)sizeof(mpcqp_rollout_adjoint_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: struct_size is not sizeof(mpcqp_rollout_adjoint_io)");
     ModelOut m;                                     // (its refusals say mpcqp_rollout_adjoint on the _est path too)
     if (model_out(mo, "mpcqp_rollout_adjoint", &m)) return MPCQP_ERR_ARG;
+    BoundsOut bd;
+    if (bounds_out(bo, "mpcqp_rollout_adjoint_bounds", &bd)) return MPCQP_ERR_ARG;
+    if (bo) {
+        const bool other = io->lam || io->d_uminus1 || io->d_uref || io->d_xref || io->d_Ap || io->d_Bp || m.any ||
+                           (eo && (eo->eta || eo->d_C || eo->d_L || eo->d_v || eo->d_Ae || eo->d_Be));
+        if (!bd.any && !other) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_bounds: no output asked for");
+        if (bd.any && m.any && bd.batch_sum != m.batch_sum) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_bounds: batch_sum of mo and of bo differ");
+    }
     if (eo && eo->struct_size != (int32_t)sizeof(mpcqp_rollout_est_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_est: struct_size is not sizeof(mpcqp_rollout_est_io)");
     if (!est && !io->G_x && !io->G_u) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: give G_x, G_u or both");
     if (est && !io->G_x && !io->G_u && !(eo && (eo->G_xhat || eo->G_y))) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_est: give at least one of G_x, G_u, G_xhat, G_y");
@@ -1453,7 +1531,7 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (ny && (put_seed(h, T.gxh, eo ? eo->G_xhat : nullptr, (K + 1) * B * nx * db) || put_seed(h, T.gy, eo ? eo->G_y : nullptr, K * B * ny * db))) return MPCQP_ERR_HIP;
     AdjointArgs Q = adjoint_args(h);
     Q.nseeds = 1; Q.gw = nullptr; Q.gu0 = nullptr; Q.chain = 1; Q.ncol = 1; Q.cs = 0;
-    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = m.any ? 1 : 0;
+    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = (m.any ? ROLLOUT_WANT_MODEL : 0) | (bd.any ? ROLLOUT_WANT_BOUNDS : 0);
     const size_t with_carry = v.smem + db * (size_t)rollout_carry_doubles(G, (int)ny);
     W.carry_lds = with_carry <= 160 * 1024 ? 1 : 0;         // (lam, mu, g behind the common block, or in the tape's few doubles of global memory)
     const size_t smem = W.carry_lds ? with_carry : v.smem;
@@ -1472,6 +1550,8 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
         if (m.batch_sum) { launch_adjoint_model_sum(h, W.off); HIPCHK(hipGetLastError()); }
         if (get_model_out(h, m, W.off)) return MPCQP_ERR_HIP;
     }
+    if (bd.any && get_bounds_out(h, bd)) return MPCQP_ERR_HIP;
+    if (any_host(bd)) HIPCHK(hipStreamSynchronize(h->stream));
     return sync_unless_all_device(h, {io->G_x, io->G_u, io->lam, io->d_uminus1, io->d_uref, io->d_xref, io->d_Ap, io->d_Bp,
                                       eo ? eo->G_xhat : nullptr, eo ? eo->G_y : nullptr, eo ? eo->eta : nullptr, eo ? eo->d_C : nullptr, eo ? eo->d_L : nullptr,
                                       eo ? eo->d_v : nullptr, eo ? eo->d_Ae : nullptr, eo ? eo->d_Be : nullptr}, &m);
@@ -1481,6 +1561,10 @@ extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoin
 }
 extern "C" int mpcqp_rollout_adjoint_est(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo) {
     return rollout_sweep(h, io, eo, mo, true);
+}
+extern "C" int mpcqp_rollout_adjoint_bounds(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo,
+                                            const mpcqp_adjoint_model_io *mo, const mpcqp_adjoint_bounds_io *bo) {
+    return rollout_sweep(h, io, eo, mo, eo != nullptr, bo);
 }
 extern "C" int mpcqp_get_rollout_info(mpcqp_handle *h, int32_t *n_active, int32_t *n_weak, int32_t *status, int32_t *n_factor) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");

@@ -8,7 +8,9 @@
 //             kpol_solve / adjoint_update, adjoint_outputs -- followed by the sums of adjoint_model_entry (mpcqp_adjoint_model.h), with the
 //             recursion of include/mpcqp_rollout.h around it.  lam, mu and g are carried in LDS behind the common block, or in a few doubles
 //             of global memory where that block already fills the workgroup's LDS.  The model gradients accumulate in the per-instance
-//             buffer k_adjoint_model writes (field-major: k_adjoint_model_sum adds it over the batch), the plant gradients in one of the tape's.
+//             buffer k_adjoint_model writes (field-major: k_adjoint_model_sum adds it over the batch), the plant gradients in one of the tape's,
+//             the bound gradients (ROLLOUT_WANT_BOUNDS: adjoint_bounds_entry, mpcqp_adjoint_bounds.h) behind the model's in the same buffer,
+//             which is where k_adjoint_bounds writes too.
 //   reuse     the metric of K_pol is s = delta / D^2 (fixed) and omega = E^2 / delta on the active rows: it follows from the active set alone.
 //             The rows whose state differs from the one in place are counted while the set is written; where there is none and a factor
 //             is in place, kpol_factor is skipped.  The factorization is deterministic: the same bits either way.
@@ -47,8 +49,12 @@ struct RolloutTape {
 struct RolloutSweep {
     double *mout;                 // the model gradients, field f of instance b: mout + batch off[f] + b (off[f + 1] - off[f])  (AdjointModelArgs::out)
     int off[ADJM_FIELDS + 1];
-    int no_reuse, carry_lds, want_model;
+    int no_reuse, carry_lds;
+    int want_model;               // bit 0: the model gradients; bit 1 (ROLLOUT_WANT_BOUNDS): the bound gradients too, field-major (AdjointBoundsArgs::out,
+                                  // mpcqp_adjoint_bounds.h) behind the model's: mout + batch off[ADJM_FIELDS].  (A flag bit and a fixed place, not two more
+                                  // kernel arguments: the sweep has no scalar register to spare, and one that is not asked for bounds must cost what it did.)
 };
+constexpr int ROLLOUT_WANT_MODEL = 1, ROLLOUT_WANT_BOUNDS = 2;
 
 // lam | lam as the plant alone gives it | d_x0 of the step | g | mu | d_uref of the step | d_uref so far
 // with an estimator (ny > 0), behind them: eta | eta before d_x0 | s | xhat[k|k] | t | r | innovation
@@ -112,6 +118,11 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
     for (int i = tid; i < nx; i += NT) { const double v = T.gx[((size_t)K * B + b) * nx + i]; lam[i] = v; T.lam[((size_t)K * B + b) * nx + i] = v; }
     for (int j = tid; j < nu; j += NT) { mu[j] = 0.0; dur[j] = 0.0; }
     for (int e = tid; e < EN; e += NT) mdst(e) = 0.0;
+    auto bdst = [&](int e) -> double & {                 // (called under ROLLOUT_WANT_BOUNDS only)
+        const int f = e < 2 * nx ? e / nx : 2 + (e - 2 * nx) / nu, sz = f < 2 ? nx : nu, off = f < 2 ? f * nx : 2 * nx + (f - 2) * nu;
+        return W.mout[(size_t)B * (EN + off) + (size_t)b * sz + (e - off)];
+    };
+    if (W.want_model & ROLLOUT_WANT_BOUNDS) for (int e = tid; e < adjoint_bounds_entries(L); e += NT) bdst(e) = 0.0;
     for (int e = tid; e < nx * nx; e += NT) dAp[e] = 0.0;
     for (int e = tid; e < nx * nu; e += NT) dBp[e] = 0.0;
     if (EST) {                                           // eta_K = G_xh[K]
@@ -221,7 +232,9 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
                 // 4. the chain rule into x_k, u_{-1}, xref, uref; 5. the model gradients of this entry onto the sums
                 const AdjointOut o{dx0, mu, T.dxref + kb * xw, durk, nullptr, nullptr, nullptr};
                 adjoint_outputs(c, act, xs, ys, 0, 1, o);
-                if (W.want_model) for (int e = tid; e < EN; e += NT) mdst(e) += adjoint_model_entry(L, M, wa, xs, ya, ys, model, step, e, 0, 1);
+                if (W.want_model & ROLLOUT_WANT_MODEL) for (int e = tid; e < EN; e += NT) mdst(e) += adjoint_model_entry(L, M, wa, xs, ya, ys, model, step, e, 0, 1);
+                if (W.want_model & ROLLOUT_WANT_BOUNDS)      // (dL/db = r_y of this entry onto the bounds; a sweep that is not asked runs none of it)
+                    for (int e = tid; e < adjoint_bounds_entries(L); e += NT) bdst(e) += adjoint_bounds_entry(L, act, ys, e);
                 __syncthreads();
                 if (EST) for (int i = tid; i < nx; i += NT) { lam[i] = lamn[i]; eta[i] = etan[i] + dx0[i]; }
                 else for (int i = tid; i < nx; i += NT) lam[i] = lamn[i] + dx0[i];

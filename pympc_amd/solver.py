@@ -33,6 +33,7 @@ _FEATURES = dict(
     polish=(_lib.has_polish, 'no solution polishing (include/mpcqp_polish.h)'),
     adjoint=(_lib.has_adjoint, 'no adjoint derivatives (include/mpcqp_adjoint.h)'),
     adjoint_model=(_lib.has_adjoint_model, 'no model gradients (include/mpcqp_adjoint_model.h)'),
+    adjoint_bounds=(_lib.has_adjoint_bounds, 'no bound gradients (include/mpcqp_adjoint_bounds.h)'),
     rollout=(_lib.has_rollout, 'no taped rollout (include/mpcqp_rollout.h)'),
     rollout_est=(_lib.has_rollout_est, 'no taped output-feedback rollout (include/mpcqp_rollout_est.h)'),
     model_update=(_lib.has_model_update, 'no in-place model update (include/mpcqp_model.h)'),
@@ -299,6 +300,13 @@ class BatchProblem:
         shapes = dict(Ad=(B, nx, nx), Bd=(B, nx, nu), Qx=(B, nx, nx), QxN=(B, nx, nx), Qu=(B, nu, nu), QDu=(B, nu, nu), eps_feas=(B,))
         return mo, {k: (mo, 'd_' + k, shape) for k, shape in shapes.items()}
 
+    def _bound_grads(self, batch_sum):
+        """(mpcqp_adjoint_bounds_io, its part of a gradient table): the bound gradients per instance, or summed over the batch [1, ...]."""
+        B = 1 if batch_sum else self.batch
+        bo = _lib.AdjointBoundsIO()
+        bo.struct_size, bo.batch_sum = C.sizeof(_lib.AdjointBoundsIO), int(bool(batch_sum))
+        return bo, {k: (bo, 'd_' + k, (B, self.nx if k in ('xmin', 'xmax') else self.nu)) for k in _lib.ADJOINT_BOUNDS_NAMES}
+
     def _grads_out(self, want, table, out, like):
         """The gradients named in ``want`` as a dict of arrays -- taken from ``out`` where it has them, else made like ``like`` -- each with its
         address put where ``table`` says: name -> (ctypes struct, field, shape)."""
@@ -316,7 +324,9 @@ class BatchProblem:
         returns a dict with the gradients named in ``want`` -- any of 'x0' [B, nx], 'uminus1' [B, nu], 'xref' [B, rows*nx] (shape of the
         last upload), 'uref' [B, nu], 'q' [B, n], 'l', 'u' [B, m], and of the model gradients 'Ad' [B, nx, nx], 'Bd' [B, nx, nu], 'Qx', 'QxN'
         [B, nx, nx], 'Qu', 'QDu' [B, nu, nu], 'eps_feas' [B] (mpcqp_adjoint_model, include/mpcqp_adjoint_model.h: the same call, the same
-        single factorization; the weight gradients are those of a symmetric perturbation).  ``batch_sum``: the model gradients come summed
+        single factorization; the weight gradients are those of a symmetric perturbation), and of the bound gradients 'xmin', 'xmax'
+        [B, nx], 'umin', 'umax', 'Dumin', 'Dumax' [B, nu] (mpcqp_adjoint_bounds, include/mpcqp_adjoint_bounds.h: the multipliers of the active
+        rows summed onto the bound each sits on).  ``batch_sum``: the model and bound gradients come summed
         over the batch, with a leading dimension of 1 -- one model shared by many states; the sum is formed on the device in a fixed order.
         Seeds may be numpy arrays or torch device tensors; the results are of the same kind (device tensors: stream-ordered, no wait), or
         are written into the arrays / tensors given in ``out`` (a dict by the same names).  The gradients are those of the active set the
@@ -336,15 +346,22 @@ class BatchProblem:
         table = {k: (io, 'd_' + k, shape) for k, shape in shapes.items()}
         mo, mtable = self._model_grads(batch_sum)
         table.update(mtable)
+        bo, btable = self._bound_grads(batch_sum)
+        table.update(btable)
         want = list(want)
         if ('l' in want) != ('u' in want):
             want += ['l' if 'u' in want else 'u']
         model = any(k in mtable for k in want)
+        bounds = any(k in btable for k in want)
         if model:
             self._need('adjoint_model')
+        if bounds:
+            self._need('adjoint_bounds')
         res = self._grads_out(want, table, out, like)
         self._keep = [gw, gu, res]
-        if model:
+        if bounds:
+            _lib.check(self._L.mpcqp_adjoint_bounds(self._h, C.byref(io), C.byref(mo) if model else None, C.byref(bo)), 'mpcqp_adjoint_bounds')
+        elif model:
             _lib.check(self._L.mpcqp_adjoint_model(self._h, C.byref(io), C.byref(mo)), 'mpcqp_adjoint_model')
         else:                                     # (without a model gradient: the call as it always was)
             _lib.check(self._L.mpcqp_adjoint(self._h, C.byref(io)), 'mpcqp_adjoint')
@@ -422,7 +439,8 @@ class BatchProblem:
         ``g_u`` [K, B, nu] = dL/du_k returns a dict with the gradients named in ``want`` -- 'lam' [K+1, B, nx] (lam[0] = dL/dx0,
         lam[k+1] = dL/dw[k]), 'uminus1' [B, nu], 'uref' [B, nu], 'xref' [K, B, rows*nx] (entry k: the reference step k was solved with),
         'Ap' [B, nx, nx], 'Bp' [B, nx, nu] (the plant path alone) and the model gradients of ``adjoint`` ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu',
-        'eps_feas'; ``batch_sum`` as there), summed over the steps.  ``no_reuse``: factor at every step (the same bits, for measurements).
+        'eps_feas'; ``batch_sum`` as there) and bound gradients ('xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax': mpcqp_rollout_adjoint_bounds),
+        summed over the steps.  ``no_reuse``: factor at every step (the same bits, for measurements).
         numpy in, numpy out; torch device tensors in, device tensors out (stream-ordered, no wait).
         On the tape of a ``rollout_est`` (mpcqp_rollout_adjoint_est): ``g_xhat`` [K+1, B, nx] = dL/dxhat_k and ``g_y`` [K, B, ny] = dL/dy_k are
         seeds too (any one of the four is enough), and ``want`` may name 'eta' [K+1, B, nx] (eta[0] = dL/dxhat_0), 'C' [B, ny, nx],
@@ -456,9 +474,18 @@ class BatchProblem:
                          Ae=(eo, 'd_Ae', (B, nx, nx)), Be=(eo, 'd_Be', (B, nx, nu)))
         mo, mtable = self._model_grads(batch_sum)
         table.update(mtable)
+        bo, btable = self._bound_grads(batch_sum)
+        table.update(btable)
+        bounds = any(k in btable for k in want)
+        if bounds:
+            self._need('adjoint_bounds')
         res = self._grads_out(want, table, out, like)
         self._keep = [gx, gu, gxh, gy, res]
-        if ny:
+        if bounds:
+            if ny:
+                self._need('rollout_est')
+            _lib.check(self._L.mpcqp_rollout_adjoint_bounds(self._h, C.byref(io), C.byref(eo) if ny else None, C.byref(mo), C.byref(bo)), 'mpcqp_rollout_adjoint_bounds')
+        elif ny:
             self._need('rollout_est')
             _lib.check(self._L.mpcqp_rollout_adjoint_est(self._h, C.byref(io), C.byref(eo), C.byref(mo)), 'mpcqp_rollout_adjoint_est')
         else:

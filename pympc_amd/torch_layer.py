@@ -20,6 +20,10 @@ is the container of the device buffers and the owner of the graph; no torch oper
   ``mpcqp_adjoint_model`` call (include/mpcqp_adjoint_model.h) for exactly the gradients torch needs, an unbatched parameter's as the sum
   over the batch formed on the device (``batch_sum``).  The weight gradients are those of a symmetric perturbation: a weight that is
   parametrized symmetric (Q = L L', a diagonal) gets its true gradient.
+* ``bounds``: the constraint bounds as an input of the layer -- a dict of device tensors under the names xmin, xmax, umin, umax, Dumin,
+  Dumax, each [B, nx | nu] or unbatched [nx | nu].  They go under the controller in the same ``update_model`` call as ``params``; backward
+  asks the same one adjoint call (mpcqp_adjoint_bounds / mpcqp_rollout_adjoint_bounds, include/mpcqp_adjoint_bounds.h) for their
+  gradients too: the multipliers of the active rows summed onto the bound each sits on, zero for a bound that is nowhere active.
 """
 import contextlib
 
@@ -27,6 +31,7 @@ import torch
 
 
 MODEL_PARAMS = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu')
+BOUND_PARAMS = ('xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')      # (the outputs of mpcqp_adjoint_bounds_io: pympc_amd._lib.ADJOINT_BOUNDS_NAMES)
 
 
 # ---- what the three Functions share ----------------------------------------------------------------------------------------------------
@@ -51,8 +56,8 @@ def _bc(t, shape):
     return None if t is None else _det(t).expand(shape).contiguous()
 
 
-def _check_args(fn, controller, params, Ap=None, Bp=None):
-    """What the public functions refuse; returns the names of ``params`` in their order."""
+def _check_args(fn, controller, params, Ap=None, Bp=None, bounds=None):
+    """What the public functions refuse; returns (the names of ``params`` in their order followed by those of ``bounds``, their tensors)."""
     if controller.prob is None:
         raise RuntimeError('%s needs a controller that has been set up' % fn)
     names = tuple(params) if params else ()
@@ -61,23 +66,30 @@ def _check_args(fn, controller, params, Ap=None, Bp=None):
             raise TypeError('%s: unknown model parameter %r (one of %s)' % (fn, n, ', '.join(MODEL_PARAMS)))
         if not hasattr(params[n], 'data_ptr') or not params[n].is_cuda or params[n].dim() not in (2, 3):
             raise ValueError('%s: params[%r] must be a device tensor [B, ., .] or [., .]' % (fn, n))
+    bnames = tuple(bounds) if bounds else ()
+    for n in bnames:
+        if n not in BOUND_PARAMS:
+            raise TypeError('%s: unknown bound %r (one of %s)' % (fn, n, ', '.join(BOUND_PARAMS)))
+        if not hasattr(bounds[n], 'data_ptr') or not bounds[n].is_cuda or bounds[n].dim() not in (1, 2):
+            raise ValueError('%s: bounds[%r] must be a device tensor [B, .] or [.]' % (fn, n))
     if (Ap is None) != (Bp is None):
         raise ValueError('%s: give both Ap and Bp or neither' % fn)
-    return names
+    return names + bnames, [params[n] for n in names] + [bounds[n] for n in bnames]
 
 
 def _put_params(ctx, K, names, params):
-    """Forward: the parameters go under the controller (no solve yet); their names and shapes are what backward assembles gradients by."""
+    """Forward: the parameters -- model and bounds, one ``update_model`` call -- go under the controller (no solve yet); their names and shapes
+    are what backward assembles gradients by."""
     if names:
         K.update_model(solve=False, **{n: _det(p) for n, p in zip(names, params)})
     ctx.names, ctx.pshapes = names, tuple(tuple(p.shape) for p in params)
 
 
 def _param_want(ctx, needs):
-    """(the parameters that need a gradient, which parameters are unbatched, batch_sum).  One model for the whole batch: the device adds the
+    """(the parameters, bounds among them, that need a gradient, which parameters are unbatched, batch_sum).  One model for the whole batch: the device adds the
     instances' gradients up (a mixture of shared and per-instance parameters takes them per instance and adds the shared ones' here)."""
     pneed = [n for n, need in zip(ctx.names, needs) if need]
-    shared = {n: len(shp) == 2 for n, shp in zip(ctx.names, ctx.pshapes)}
+    shared = {n: len(shp) == (1 if n in BOUND_PARAMS else 2) for n, shp in zip(ctx.names, ctx.pshapes)}
     return pneed, shared, bool(pneed) and all(shared[n] for n in pneed)
 
 
@@ -129,13 +141,15 @@ class _MPCStep(torch.autograd.Function):
         return (None,) + tuple(grads) + (None,) + tuple(_param_grads(ctx, res, pneed, shared, batch_sum))
 
 
-def mpc_step(controller, x, u_prev=None, xref=None, params=None):
+def mpc_step(controller, x, u_prev=None, xref=None, params=None, bounds=None):
     """``u [B,nu] = K(x [B,nx], u_prev [B,nu], xref [B,nx] or [B,Np+1,nx])`` of a set-up ``BatchMPCController``, differentiable with
     respect to the three tensors (float64 device tensors; ``u_prev`` / ``xref`` None: the controller's own, no gradient) and, with
     ``params`` -- a dict of device tensors under any of the names Ad, Bd, Qx, QxN, Qu, QDu, each [B, ...] or unbatched [...] -- with respect
-    to the model the step is made with: the controller's model is replaced by them first (``update_model``)."""
-    names = _check_args('mpc_step', controller, params)
-    return _MPCStep.apply(controller, x, u_prev, xref, names, *[params[n] for n in names])
+    to the model the step is made with: the controller's model is replaced by them first (``update_model``).  ``bounds``: likewise a dict
+    under any of the names xmin, xmax, umin, umax, Dumin, Dumax, each [B, nx | nu] or unbatched [nx | nu] -- the constraint bounds the step is
+    made with, differentiable too."""
+    names, tensors = _check_args('mpc_step', controller, params, bounds=bounds)
+    return _MPCStep.apply(controller, x, u_prev, xref, names, *tensors)
 
 
 # ---- a closed-loop rollout as one differentiable operation (include/mpcqp_rollout.h, include/mpcqp_rollout_est.h) ----------------------
@@ -207,7 +221,7 @@ class _MPCRollout(torch.autograd.Function):
         return _rollout_backward(ctx, 'mpc_rollout', ('x0', 'u_prev', 'xref', 'w', 'Ap', 'Bp'), dict(g_x=grad_X, g_u=grad_U), False)
 
 
-def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None):
+def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None, bounds=None):
     """``(X [K+1,B,nx], U [K,B,nu])`` of ``nsteps`` = K closed-loop steps of a set-up ``BatchMPCController`` from ``x0`` [B,nx] against the
     plant x_{k+1} = Ap x_k + Bp u_k + w[k] (``Ap`` / ``Bp`` None: the controller's own Ad, Bd; ``w`` [K,B,nx] or None), on ONE controller:
     forward is ``update_model(solve=False, **params)`` where given, ``update(x0, u_prev, xref)`` with its solve, then
@@ -217,9 +231,10 @@ def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None,
     the rollout), ``w``, ``Ap``, ``Bp`` ([B, ., .] or unbatched) and ``params`` (as in ``mpc_step``; with ``Ap`` / ``Bp`` None the gradients
     of ``params['Ad']`` / ``['Bd']`` include the plant path).  A step whose solve does not end 'solved' applies ``u_failure`` = uref and
     passes the gradient through the plant alone.  The tape is a copy: stepping or solving the controller between forward and backward is
-    fine, another rollout is not -- the backward then raises."""
-    names = _check_args('mpc_rollout', controller, params, Ap, Bp)
-    return _MPCRollout.apply(controller, int(nsteps), x0, u_prev, xref, w, Ap, Bp, names, *[params[n] for n in names])
+    fine, another rollout is not -- the backward then raises.  ``bounds`` as in ``mpc_step``: constant over the rollout, their gradient the
+    sum over its steps."""
+    names, tensors = _check_args('mpc_rollout', controller, params, Ap, Bp, bounds)
+    return _MPCRollout.apply(controller, int(nsteps), x0, u_prev, xref, w, Ap, Bp, names, *tensors)
 
 
 class _MPCRolloutEst(torch.autograd.Function):
@@ -242,7 +257,7 @@ class _MPCRolloutEst(torch.autograd.Function):
                                  dict(g_x=grad_X, g_u=grad_U, g_xhat=grad_XH, g_y=grad_Y), True)
 
 
-def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None):
+def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None, bounds=None):
     """``(X [K+1,B,nx], Xhat [K+1,B,nx], Y [K,B,ny], U [K,B,nu])`` of ``nsteps`` = K steps of the OUTPUT-FEEDBACK loop of a set-up
     ``BatchMPCController``: the plant x_{k+1} = Ap x_k + Bp u_k + w[k] starts at ``x0`` [B,nx], the controller sees the estimate only, which
     starts at ``xhat0`` [B,nx] and follows xhat_{k+1} = Ad (xhat_k + L (y_k - C xhat_k)) + Bd u_k with y_k = C x_k + v[k] (``C`` [B,ny,nx] or
@@ -251,12 +266,12 @@ def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xr
     ``mpcqp_rollout_adjoint_est`` call with the four seeds ``grad_X, grad_Xhat, grad_Y, grad_U``.  Differentiable with respect to ``x0``,
     ``xhat0``, ``C``, ``L``, ``v``, ``u_prev``, ``xref``, ``w``, ``Ap``, ``Bp`` and ``params`` (as in ``mpc_rollout``); the gradients of
     ``params['Ad']`` / ``['Bd']`` include the estimator's path and, with ``Ap`` / ``Bp`` None, the plant's.  ``mpc_rollout`` is the loop
-    without an estimator."""
-    names = _check_args('mpc_rollout_est', controller, params, Ap, Bp)
+    without an estimator.  ``bounds`` as in ``mpc_rollout``."""
+    names, tensors = _check_args('mpc_rollout_est', controller, params, Ap, Bp, bounds)
     for n, t in (('C', C), ('L', L)):
         if not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (2, 3):
             raise ValueError('mpc_rollout_est: %s must be a device tensor [B, ., .] or [., .]' % n)
-    return _MPCRolloutEst.apply(controller, int(nsteps), x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, names, *[params[n] for n in names])
+    return _MPCRolloutEst.apply(controller, int(nsteps), x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, names, *tensors)
 
 
 # ---- the discrete algebraic Riccati equation as a differentiable operation (include/mpcqp_riccati.h) ------------------------------------

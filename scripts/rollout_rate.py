@@ -13,7 +13,9 @@ is part of the result.  Per (batch, shape, K):
   (c) the factor reuse       no_reuse = 1 against 0, with the mean n_factor / K beside it.
 One JSON line per (batch, shape, K).
 
-    python scripts/rollout_rate.py [--reps 5] [--eps 1e-6] [--sizes 1024:12,4,30 256:4,2,10] [--steps 20 100] [--no-route-b]"""
+``--bounds``: the sweeps of (b) and (c) are asked for the six bound gradients too (include/mpcqp_adjoint_bounds.h).
+
+    python scripts/rollout_rate.py [--reps 5] [--eps 1e-6] [--sizes 1024:12,4,30 256:4,2,10] [--steps 20 100] [--no-route-b] [--bounds]"""
 import argparse
 import json
 import os
@@ -42,6 +44,7 @@ def main():
     ap.add_argument('--sizes', nargs='+', default=['1024:12,4,30', '256:4,2,10'])
     ap.add_argument('--steps', nargs='+', type=int, default=[20, 100])
     ap.add_argument('--no-route-b', action='store_true', help='skip the K-controller route (it builds K handles)')
+    ap.add_argument('--bounds', action='store_true', help='ask the sweep for xmin, xmax, umin, umax, Dumin, Dumax as well')
     a = ap.parse_args()
     import torch
     from pympc_amd import fixtures
@@ -69,7 +72,7 @@ def main():
         x0, um1 = t(np.stack([kw['x0'] for kw in kws])), t(np.zeros((B, nu)))
         Ad, Bd = t(np.stack([kw['Ad'] for kw in kws])), t(np.stack([kw['Bd'] for kw in kws]))
         for K in a.steps:
-            res = dict(batch=B, shape=[nx, nu, Np], K=K, eps=a.eps, reps=a.reps)
+            res = dict(batch=B, shape=[nx, nu, Np], K=K, eps=a.eps, reps=a.reps, bounds=bool(a.bounds))
             m0 = used()
             C = controller(kws, Np, a.eps, stream)
             bp = C.prob
@@ -77,7 +80,7 @@ def main():
             out = [torch.empty((K + 1, B, nx), dtype=torch.float64, device=dev), torch.empty((K, B, nu), dtype=torch.float64, device=dev),
                    torch.empty((K, B), dtype=torch.int32, device=dev), torch.empty((K, B), dtype=torch.int32, device=dev)]
             gx, gu = torch.randn((K + 1, B, nx), dtype=torch.float64, device=dev), torch.randn((K, B, nu), dtype=torch.float64, device=dev)
-            want = ('lam', 'uminus1', 'Ad', 'Bd', 'Ap', 'Bp')
+            want = ('lam', 'uminus1', 'Ad', 'Bd', 'Ap', 'Bp') + (('xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax') if a.bounds else ())
 
             def reset():
                 bp.update(x0, um1)

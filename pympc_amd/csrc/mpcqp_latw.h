@@ -163,8 +163,10 @@ constexpr int latw_kept_input(int N, int W, int L, int e) {
 }
 constexpr int latw_atleast1(int n) { return n > 0 ? n : 1; }
 
-// forward tasks of level L that wave W owns: every input of the phase requested up front, in the order the tasks consume them, each distinct vector once
-template <int N, int W, int L>
+// forward tasks of level L that wave W owns: every input of the phase requested up front, in the order the tasks consume them, each distinct vector once.
+// LEAVES false: without the products c_e = D^-1(e) b'(e) of its eliminated stages, which nobody reads in the next phase (fused schedule: they run at the
+// head of the top, latw_top_own)
+template <int N, int W, int L, bool LEAVES = true>
 __device__ __forceinline__ void latw_fwd(const d4 *fr, const LatwVecs &v) {
     constexpr int h = 1 << L, NK = latw_mine(N, W, L, 0), NE = latw_mine(N, W, L, 1);
     double p0[latw_atleast1(NK)];
@@ -181,7 +183,7 @@ __device__ __forceinline__ void latw_fwd(const d4 *fr, const LatwVecs &v) {
     });
     static_for<0, lat_count(N, L, 1)>([&](auto tc) {
         constexpr int t = decltype(tc)::value, e = lat_stage(L, 1, t);
-        if constexpr (latw_owner(N, L, 1, t) == W && latw_kept_input(N, W, L, e) < 0) xe[latw_ord(N, W, L, 1, t)] = latw_in<false, e>(v);
+        if constexpr (LEAVES && latw_owner(N, L, 1, t) == W && latw_kept_input(N, W, L, e) < 0) xe[latw_ord(N, W, L, 1, t)] = latw_in<false, e>(v);
     });
     static_for<0, lat_count(N, L, 0)>([&](auto tc) {
         constexpr int t = decltype(tc)::value, i = lat_stage(L, 0, t);
@@ -198,7 +200,7 @@ __device__ __forceinline__ void latw_fwd(const d4 *fr, const LatwVecs &v) {
     });
     static_for<0, lat_count(N, L, 1)>([&](auto tc) {
         constexpr int t = decltype(tc)::value, e = lat_stage(L, 1, t);
-        if constexpr (latw_owner(N, L, 1, t) == W) {
+        if constexpr (LEAVES && latw_owner(N, L, 1, t) == W) {
             constexpr int s1 = latw_slot(N, W, L, 1, t), ki = latw_kept_input(N, W, L, e);
             double p = 0.0, q = 0.0;
             if constexpr (ki >= 0) latw_mv_lds(fr[s1], xk[ki], p, q);
@@ -322,8 +324,10 @@ __device__ __forceinline__ double latw_dpp(double x) {
 // group's reads are issued before the current group's FMAs (two groups of registers in flight).  (Requesting a wave's first group of matrix
 // pairs on the other side of the barrier, at the start of level 1 forward -- they depend on nothing the iteration computes -- took 80 cycles off
 // this phase and, through 16 more live registers, added 300 to the owner passes: 7 572 against 7 352 cycles per iteration; not kept.)
-template <int N, int W>
-__device__ __forceinline__ void latw_top_valu(const double *TopL, const double *Xt, double *Cc, int lane) {
+// head(): what the wave issues between the requests of its first matrix group and that group's first FMAs, where it would otherwise only wait (latw_top_own)
+struct LatwNone { __device__ __forceinline__ void operator()() const {} };
+template <int N, int W, class Head = LatwNone>
+__device__ __forceinline__ void latw_top_valu(const double *TopL, const double *Xt, double *Cc, int lane, Head head = Head{}) {
     constexpr int NTOP = BcrFmt::top_count(N), H = 2;
     static_for<0, NTOP>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
@@ -350,6 +354,7 @@ __device__ __forceinline__ void latw_top_valu(const double *TopL, const double *
             __builtin_amdgcn_sched_barrier(0);
             load(std::integral_constant<int, 0>{});
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (r == W && !std::is_same<Head, LatwNone>::value) { head(); __builtin_amdgcn_sched_barrier(0); }
             static_for<0, NG>([&](auto gc) {
                 constexpr int g = decltype(gc)::value;
                 if constexpr (g + 1 < NG) load(std::integral_constant<int, g + 1>{});
@@ -370,6 +375,31 @@ __device__ __forceinline__ void latw_top_valu(const double *TopL, const double *
     });
 }
 
+// The top of the fused schedule with level 1's leaf of wave W at its head: c_e = D^-1(e) b'(e) of the eliminated stage e = 4r+1 the wave owns at level 1.
+// The product is read by nobody before the back substitution, behind the top's barrier; in level 1 forward it stood behind the wave's dependent chain, in
+// front of the barrier every wave waits at.  Here its vector is requested first, and the four MFMAs (from p = q = 0 as before: no summand and no order of
+// a sum moves) are issued while the wave waits for its first group of matrix pairs with nothing else to issue.  tb(e) is b'(e) from level 0 forward until the back
+// substitution, the top writes cb at the stages 4r+3 only.  A wave without a top row (wave 7 of 31 stages) just runs it.  Level 0's leaves D^-1(4w) b(4w),
+// D^-1(4w+2) b(4w+2) stay behind the right-hand side: deferred to level 1 forward they cost that phase what they save the first (LAB_NOTES.md).
+template <int N, int W>
+__device__ __forceinline__ void latw_top_own(const d4 *fr, const LatwVecs &v, const double *TopL, double *Cc, int lane) {
+    constexpr int NTOP = BcrFmt::top_count(N);
+    static_assert(latw_mine(N, W, 1, 1) <= 1, "one group of four stages per wave");
+    LatwIn xe{};
+    static_for<0, lat_count(N, 1, 1)>([&](auto tc) {
+        constexpr int t = decltype(tc)::value, e = lat_stage(1, 1, t);
+        if constexpr (latw_owner(N, 1, 1, t) == W) xe = latw_in<false, e>(v);
+    });
+    auto leaf = [&]() {
+        static_for<0, lat_count(N, 1, 1)>([&](auto tc) {
+            constexpr int t = decltype(tc)::value, e = lat_stage(1, 1, t);
+            if constexpr (latw_owner(N, 1, 1, t) == W) { double p = 0.0, q = 0.0; latw_mv_lds(fr[latw_slot(N, W, 1, 1, t)], xe, p, q); v.cb[e * 16] = p + q; }
+        });
+    };
+    if constexpr (W < NTOP) latw_top_valu<N, W>(TopL, TopL + LATW_TOP_LDS(N) - 32 * NTOP, Cc, lane, leaf);
+    else leaf();
+}
+
 // Tc <- K^-1 Tc.  All threads call; four barriers inside, none after the last phase (the caller's follows).
 template <int N>
 __device__ __forceinline__ void latw_solve(const d4 *fr, const double *TopL, const LatwVecs &v, double *Cc, int wv, int lane) {
@@ -380,16 +410,20 @@ __device__ __forceinline__ void latw_solve(const d4 *fr, const double *TopL, con
         __syncthreads();
     }
     TICK(1)
-    LATW_DISPATCH(wv, (latw_fwd<N, W, 1>(fr, v)))
+    LATW_DISPATCH(wv, (latw_fwd<N, W, 1, !latw_fused(N)>(fr, v)))      // (fused: its leaves wait for the head of the top)
+    WTICK(1)
     __syncthreads();
     TICK(2)
-    LATW_DISPATCH(wv, (latw_top_valu<N, W>(TopL, TopL + LATW_TOP_LDS(N) - 32 * NTOP, Cc, lane)))
+    if constexpr (latw_fused(N)) { LATW_DISPATCH(wv, (latw_top_own<N, W>(fr, v, TopL, Cc, lane))) }
+    else { LATW_DISPATCH(wv, (latw_top_valu<N, W>(TopL, TopL + LATW_TOP_LDS(N) - 32 * NTOP, Cc, lane))) }
+    WTICK(2)
     __syncthreads();
     TICK(3)
     // level 1 back reads the top's solution from cb; on the way every top row's owner moves its stage into tb, where level 0 back (and the
     // owner passes) look for it -- nobody reads tb at a top stage during this phase
     if constexpr (latw_fused(N)) {
         LATW_DISPATCH(wv, (latw_bwd_own<N, W>(fr, v)))
+        WTICK(3)
         TICK(4)
     } else {
         LATW_DISPATCH(wv, (latw_bwd1<N, W>(fr, v)))
@@ -540,6 +574,7 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
     for (int it = 1; it <= iters; ++it) {
         const bool keep_delta = it == iters;
         TICK_START
+        WTICK_START
         // ---- right-hand side  s x - c q + A'W  with the slack eliminated; A'W = own rows' W + G' W_dyn of the next stage (MFMA, four stages a group)
         {
             double g[QN], h2[QN];
@@ -557,6 +592,7 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
             }
         }
         if constexpr (latw_fused(N)) { LATW_DISPATCH(wv, (latw_fwd0_own<N, W>(fr, vec))) }      // (level 0 forward of the wave's own stages: no barrier in between)
+        WTICK(0)
         __syncthreads();
         TICK(0)
         latw_solve<N>(fr, TopL, vec, Cc, wv, lane);
@@ -589,6 +625,7 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
                 WA[sl[q]] = ok[q] ? rA[q].w : 0.0; WB[sl[q]] = ok[q] ? rB[q].w : 0.0;      // (a slot without a variable contributes nothing)
             }
         }
+        WTICK(4)
         __syncthreads();
         TICK(6)
     }

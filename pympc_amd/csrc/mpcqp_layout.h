@@ -118,11 +118,21 @@ __device__ unsigned long long g_ticks[16];
 __device__ __forceinline__ unsigned long long *tick_slots() { __shared__ unsigned long long s[16]; return s; }
 #define TICK(i) { if (threadIdx.x == 0) { unsigned long long *s_ = tick_slots(); const unsigned long long t_ = clock64(); s_[i] += t_ - s_[15]; s_[15] = t_; } }
 #define TICK_START { if (threadIdx.x == 0) tick_slots()[15] = clock64(); }
-#define TICK_RESET { if (threadIdx.x < 16) tick_slots()[threadIdx.x] = 0; __syncthreads(); }
-#define TICK_FLUSH { __syncthreads(); if (threadIdx.x < 15) atomicAdd(&g_ticks[threadIdx.x], tick_slots()[threadIdx.x]); }
+// Per wave (the latency round, mpcqp_latw.h): when lane 0 of EVERY wave reaches each of an iteration's barriers, in cycles since that wave left the
+// previous iteration's last one -- thread 0 is the lightest wave's and says nothing about which wave ends a phase.  Slot 8 k + w: barrier k, wave w;
+// 48 + w: the wave's start.
+__device__ unsigned long long g_wticks[48];
+__device__ __forceinline__ unsigned long long *wtick_slots() { __shared__ unsigned long long s[64]; return s; }
+#define WTICK_START { if ((threadIdx.x & 63) == 0) wtick_slots()[48 + (threadIdx.x >> 6)] = clock64(); }
+#define WTICK(k) { if ((threadIdx.x & 63) == 0) { unsigned long long *s_ = wtick_slots(); s_[8 * (k) + (threadIdx.x >> 6)] += clock64() - s_[48 + (threadIdx.x >> 6)]; } }
+#define TICK_RESET { if (threadIdx.x < 16) tick_slots()[threadIdx.x] = 0; if (threadIdx.x < 64) wtick_slots()[threadIdx.x] = 0; __syncthreads(); }
+#define TICK_FLUSH { __syncthreads(); if (threadIdx.x < 15) atomicAdd(&g_ticks[threadIdx.x], tick_slots()[threadIdx.x]); \
+                     if (threadIdx.x < 48 && wtick_slots()[threadIdx.x]) atomicAdd(&g_wticks[threadIdx.x], wtick_slots()[threadIdx.x]); }
 #else
 #define TICK(i)
 #define TICK_START
 #define TICK_RESET
 #define TICK_FLUSH
+#define WTICK(k)
+#define WTICK_START
 #endif

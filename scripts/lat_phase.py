@@ -1,7 +1,8 @@
 """Phase clocks of ONE instance alone on its compute unit, -DMPCQP_RUN_TIMING builds:  python scripts/lat_phase.py <lib.so> [backend] [iters] [tuning]
 Prints cycles per ADMM iteration by phase (thread 0 of the workgroup: rhs | level 0 fwd | level 1 fwd | top | level 1 back | level 0 back | update)
 and per round / per check outside the iterations; per step, the wall clock of begin, the rounds, the generic checks and the loop body (output,
-plant, update -- inside the round too where it carries a solve into the next step; libraries that predate that clock print no body).  The library writes its counters to stderr; this script reads them back through a pipe."""
+plant, update -- inside the round too where it carries a solve into the next step; libraries that predate that clock print no body); for the
+latency round a table per WAVE as well: when lane 0 of each wave reaches each barrier of the iteration and which wave ends each phase.  The library writes its counters to stderr; this script reads them back through a pipe."""
 import os, sys, re, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -39,6 +40,20 @@ print('%s %s: %d iterations, %d rounds in 20 steps; %.0f cycles per iteration = 
 print('   whole admm function (thread 0): %.0f cycles per step; sum of its slots: %.0f; before the first tick %.0f' % (chk[1] / 20.0, (tot + sum(outside)) / 20.0, chk[2] / 20.0))
 print('   per round: load %.0f  owner regs %.0f  write-back %.0f cycles;  per check: setup+tail %.0f vars %.0f reduce %.0f decide %.0f cycles;  wall (10 ns ticks) per step: begin %.0f admm %.0f check %.0f'
       % tuple([o / rounds for o in outside] + [chk[0] / rounds, chk[2] / rounds, chk[3] / rounds, chk[4] / rounds] + [x / 20.0 for x in wall]))
+wl = [l for l in txt.splitlines() if l.startswith('wave barrier cycles')]
+if wl:                                        # (libraries with per-wave clocks: when lane 0 of each wave reaches each barrier of the iteration, cycles since the wave's start)
+    g = re.findall(r' b\d((?: \d+)+)', wl[-1])
+    arr = np.array([[int(x) for x in s.split()] for s in g], dtype=float) / its          # [barrier, wave]
+    if arr.any():
+        nwv = max(w for w in range(arr.shape[1]) if arr[:, w].any()) + 1
+        bars = ['rhs+L0fwd', 'L1fwd', 'top', 'back', 'update'] if arr[3].any() else ['b0', 'b1', 'b2', 'b3', 'b4']
+        print('   per wave: arrival at the barrier that ends each phase, cycles since the iteration started (* = last to arrive) | work in the phase since the previous arrival of the last wave')
+        print('   %-10s' % 'phase' + ''.join('%8s' % ('w%d' % w) for w in range(nwv)) + ' |' + ''.join('%8s' % ('w%d' % w) for w in range(nwv)))
+        prev = 0.0
+        for k, nm in enumerate(bars):
+            row = arr[k, :nwv]; last = row.max()
+            print('   %-10s' % nm + ''.join('%7.0f%s' % (x, '*' if x == last else ' ') for x in row) + ' |' + ''.join('%8.0f' % (x - prev) for x in row))
+            prev = last
 print('   per step: cycles of the admm function outside the iterations %.0f;  wall (10 ns ticks): begin %.0f%s  begin+check+body %s'
       % ((chk[1] - tot) / 20.0, wall[0] / 20.0, ('  body %.0f' % (int(body.group(1)) / 20.0)) if body else '',
          ('%.0f' % ((wall[0] + wall[2] + int(body.group(1))) / 20.0)) if body else 'n/a'))

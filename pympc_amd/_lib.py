@@ -43,6 +43,9 @@ ROLLOUT_EST_SYMBOLS = ['mpcqp_rollout_est', 'mpcqp_rollout_est_tape_bytes', 'mpc
 ADJOINT_BOUNDS_SYMBOLS = ['mpcqp_adjoint_bounds', 'mpcqp_rollout_adjoint_bounds']
 ADJOINT_BOUNDS_NAMES = ('xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')      # the outputs of mpcqp_adjoint_bounds_io, in its order
 
+# include_ext/mpcqp_rollout_tv.h: likewise -- the taped rollout under a model schedule, and its reverse sweep with per-slot model gradients
+ROLLOUT_TV_SYMBOLS = ['mpcqp_rollout_tv', 'mpcqp_rollout_tv_tape_bytes', 'mpcqp_rollout_adjoint_tv', 'mpcqp_rollout_tv_get_slot']
+
 # include/mpcqp_riccati.h: likewise -- batched discrete algebraic Riccati equations and their adjoint, without a handle
 RICCATI_SYMBOLS = ['mpcqp_riccati_default_settings', 'mpcqp_dare', 'mpcqp_dare_adjoint']
 
@@ -94,6 +97,12 @@ class RolloutEstIO(C.Structure):
     """mpcqp_rollout_est_io (include/mpcqp_rollout_est.h): the estimator's seeds in, gradients out; host or device pointers, None = not given / not wanted."""
     _fields_ = [('struct_size', C.c_int32), ('G_xhat', C.c_void_p), ('G_y', C.c_void_p), ('eta', C.c_void_p), ('d_C', C.c_void_p),
                 ('d_L', C.c_void_p), ('d_v', C.c_void_p), ('d_Ae', C.c_void_p), ('d_Be', C.c_void_p)]
+
+
+class RolloutTVIO(C.Structure):
+    """mpcqp_rollout_tv_io (include_ext/mpcqp_rollout_tv.h): the per-slot and per-entry model gradients out; host or device pointers, None = not wanted."""
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('d_Ad_slots', C.c_void_p), ('d_Bd_slots', C.c_void_p),
+                ('d_Ap_entries', C.c_void_p), ('d_Bp_entries', C.c_void_p)]
 
 
 class Settings(C.Structure):
@@ -258,6 +267,13 @@ def load():
         L.mpcqp_rollout_adjoint_bounds.argtypes = [H, C.POINTER(RolloutAdjointIO), C.POINTER(RolloutEstIO), C.POINTER(AdjointModelIO), C.POINTER(AdjointBoundsIO)]
         for name in ADJOINT_BOUNDS_SYMBOLS:
             getattr(L, name).restype = C.c_int
+    if has_rollout_tv(L):
+        L.mpcqp_rollout_tv.argtypes = [H, C.c_int, C.POINTER(Loop), C.POINTER(ModelTraj)]
+        L.mpcqp_rollout_tv_tape_bytes.argtypes = [H, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        L.mpcqp_rollout_adjoint_tv.argtypes = [H, C.POINTER(RolloutAdjointIO), C.POINTER(AdjointModelIO), C.POINTER(AdjointBoundsIO), C.POINTER(RolloutTVIO)]
+        L.mpcqp_rollout_tv_get_slot.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ROLLOUT_TV_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     if has_riccati(L):
         L.mpcqp_riccati_default_settings.argtypes = [C.POINTER(RiccatiSettings)]
         L.mpcqp_riccati_default_settings.restype = None
@@ -308,6 +324,11 @@ def has_rollout_est(L=None):
 def has_adjoint_bounds(L=None):
     """True if the library exports include/mpcqp_adjoint_bounds.h."""
     return _has(L, ADJOINT_BOUNDS_SYMBOLS)
+
+
+def has_rollout_tv(L=None):
+    """True if the library exports include_ext/mpcqp_rollout_tv.h."""
+    return _has(L, ROLLOUT_TV_SYMBOLS)
 
 
 def has_riccati(L=None):

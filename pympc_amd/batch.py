@@ -199,13 +199,17 @@ class BatchMPCController:
         self.solve_count += int(nsteps)
         out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=_est_dict(estimator), model_traj=model_traj)
         if model_traj is not None:
-            last = (int(nsteps) - 1) // int(model_traj[2])
-            host = lambda a: np.array(a[last].cpu() if hasattr(a, 'data_ptr') else a[last], dtype=float).reshape((self.B,) + tuple(a.shape[-2:]))
-            if model_traj[0] is not None:
-                self.Ad = host(model_traj[0])
-            if model_traj[1] is not None:
-                self.Bd = host(model_traj[1])
+            self._after_schedule(nsteps, model_traj)
         return self._after_loop(out, xref_traj, estimator)
+
+    def _after_schedule(self, nsteps, model_traj):
+        """The controller's Ad, Bd after a loop under a schedule: the last entry used."""
+        last = (int(nsteps) - 1) // int(model_traj[2])
+        host = lambda a: np.array(a[last].detach().cpu() if hasattr(a, 'data_ptr') else a[last], dtype=float).reshape((self.B,) + tuple(a.shape[-2:]))
+        if model_traj[0] is not None:
+            self.Ad = host(model_traj[0])
+        if model_traj[1] is not None:
+            self.Bd = host(model_traj[1])
 
     def _after_loop(self, out, xref_traj, estimator=None, count=0):
         """The controller's books after a device loop of any kind, and its result dict: the controller stands at the last state (with an
@@ -234,6 +238,15 @@ class BatchMPCController:
         out = self.prob.rollout(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
         return self._after_loop(out, xref_traj, count=int(nsteps))
 
+    def rollout_tv(self, nsteps, model_traj, w=None, Ap=None, Bp=None, xref_traj=None):
+        """``run(model_traj=)`` that keeps a tape (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h): the same loop under the same schedule
+        ``model_traj = (Ad [nmodels,B,nx,nx] or None, Bd [nmodels,B,nx,nu] or None, hold)``, the same dict, the controller left with the last
+        entry used -- and a tape that remembers every model it was made under, so that ``rollout_adjoint`` can differentiate a loss on the
+        trajectory with respect to each schedule entry ('Ad_traj', 'Bd_traj', 'Ap_traj', 'Bp_traj') beside everything else."""
+        out = self.prob.rollout_tv(nsteps, model_traj, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
+        self._after_schedule(nsteps, model_traj)
+        return self._after_loop(out, xref_traj, count=int(nsteps))
+
     def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None):
         """``run(estimator=...)`` that keeps a tape (mpcqp_rollout_est, include/mpcqp_rollout_est.h): the output-feedback loop with a
         ``BatchLinearStateEstimator`` -- the same dict (``x, u, status, iter, xhat, y``), ``estimator.x_true`` advanced in place -- and afterwards
@@ -250,7 +263,10 @@ class BatchMPCController:
         [B,nu] (mpcqp_rollout_adjoint_bounds: the bounds are constant over the tape) -- plus ``n_weak`` [K,B], ``status`` [K,B] per step and ``n_factor`` [B], the
         factorizations the sweep made.  numpy in, numpy out; torch device tensors in, device tensors out.  After ``rollout_est``: ``g_xhat``
         [K+1,B,nx] = dL/dxhat_k and ``g_y`` [K,B,ny] = dL/dy_k seed the sweep too, and ``want`` may name 'eta' [K+1,B,nx] (eta[0] = dL/dxhat_0),
-        'C' [B,ny,nx], 'L' [B,nx,ny], 'v' [K,B,ny] and 'Ae' [B,nx,nx], 'Be' [B,nx,nu], the estimator path alone (add them to 'Ad', 'Bd')."""
+        'C' [B,ny,nx], 'L' [B,nx,ny], 'v' [K,B,ny] and 'Ae' [B,nx,nx], 'Be' [B,nx,nu], the estimator path alone (add them to 'Ad', 'Bd').
+        After ``rollout_tv``: ``want`` may name 'Ad_traj' [nseg,B,nx,nx], 'Bd_traj' [nseg,B,nx,nu] (entry e: through the solves made under
+        schedule entry e) and 'Ap_traj', 'Bp_traj' (entry e: through the plant while entry e was in force; where the plant followed the
+        schedule, add them); 'Ad', 'Bd' are then the share of the model the rollout began with."""
         res = self.prob.rollout_adjoint(g_x=g_x, g_u=g_u, want=want, batch_sum=batch_sum, no_reuse=no_reuse, g_xhat=g_xhat, g_y=g_y)
         _, n_weak, status, n_factor = self.prob.rollout_info()
         res.update(n_weak=n_weak, status=status, n_factor=n_factor)

@@ -50,6 +50,7 @@
 #include "../../include/mpcqp_adjoint_model.h"
 #include "../../include/mpcqp_rollout.h"
 #include "../../include/mpcqp_rollout_est.h"
+#include "../../include_ext/mpcqp_rollout_tv.h"
 #include "../../include/mpcqp_adjoint_bounds.h"
 
 #include "mpcqp_defs.h"
@@ -153,6 +154,7 @@ struct mpcqp_handle : Plan {       // the plan (mpcqp_plan.h: ncu, batch, L, lds
     double *adjb_out = nullptr, *adjb_sum = nullptr;   // mpcqp_adjoint_bounds: the per-instance bound gradients (field-major, AdjointBoundsArgs::out: the tail of adjm_out's block, where the sweep expects them) and their batch sum; null until first use
     RolloutTape tape = {}; void *tape_buf = nullptr; size_t tape_bytes = 0;      // mpcqp_rollout (include/mpcqp_rollout.h): the tape, one device block (null until the first rollout)
     int tape_ny = 0;                                           // > 0: the tape is one of the output-feedback loop (mpcqp_rollout_est, include/mpcqp_rollout_est.h)
+    RolloutSlots tape_slots = {};                              // nslots > 0: the tape is one of the loop under a model schedule (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h) and carries its models
     int tape_xref_rows = 1; bool tape_valid = false;           // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
     bool has_solve = false;              // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
@@ -1360,7 +1362,8 @@ extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *
 // The tape and the sweep's staging are ONE device block: a rollout that cannot get it changes nothing, and releasing it is one call.
 // base null: sizes only.  Returns the bytes of the block.
 // ny > 0: a tape of the output-feedback loop -- the plant states, measurements, C, L and the estimator's seeds and gradients behind the rest.
-static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int ny, char *base, RolloutTape *T) {
+// nslots > 0: a tape of the loop under a model schedule -- the model slots and their gradients behind the rest (V).
+static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int ny, char *base, RolloutTape *T, int nslots = 0, int hold = 0, RolloutSlots *V = nullptr) {
     const size_t B = (size_t)batch, K = (size_t)nsteps, nx = L.nx, nu = L.nu, xw = (size_t)xref_rows * nx, db = sizeof(double);
     size_t off = 0;
     auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~size_t(255); return q; };
@@ -1384,7 +1387,16 @@ static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int
         t.dC = (double *)take(B * q * nx * db); t.dL = (double *)take(B * nx * q * db);
         t.dAe = (double *)take(B * nx * nx * db); t.dBe = (double *)take(B * nx * nu * db);
     }
+    RolloutSlots v; memset(&v, 0, sizeof(v));
+    if (nslots > 0) {
+        const size_t S = (size_t)nslots;
+        v.nslots = nslots; v.hold = hold;
+        v.model = (double *)take(S * B * L.model_sz * db); v.D = (double *)take(S * B * L.n * db); v.E = (double *)take(S * B * L.m * db); v.c = (double *)take(S * B * db);
+        v.dAd = (double *)take(S * B * nx * nx * db); v.dBd = (double *)take(S * B * nx * nu * db);
+        v.dAp = (double *)take((S - 1) * B * nx * nx * db); v.dBp = (double *)take((S - 1) * B * nx * nu * db);
+    }
     if (T) *T = t;
+    if (V) *V = v;
     return off;
 }
 extern "C" int mpcqp_rollout_tape_bytes(mpcqp_handle *h, int nsteps, int64_t *bytes) {
@@ -1397,7 +1409,7 @@ extern "C" int mpcqp_rollout_release(mpcqp_handle *h) {
     HIPCHK(hipSetDevice(h->device));
     if (h->tape_buf) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->tape_buf); }
     h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_valid = false; h->tape_ny = 0;
-    memset(&h->tape, 0, sizeof(h->tape));
+    memset(&h->tape, 0, sizeof(h->tape)); memset(&h->tape_slots, 0, sizeof(h->tape_slots));
     return MPCQP_OK;
 }
 // What the calls that read the tape back refuse: no tape, for the estimator's part a tape without one, an entry k (null: the call takes none) out of range.
@@ -1410,7 +1422,19 @@ static int tape_guard(const mpcqp_handle *h, const std::string &fn, bool est, co
 // The taped loop behind mpcqp_rollout (io->ny == 0) and mpcqp_rollout_est (io->ny > 0): the refusals, the tape's one allocation and its
 // invalidation, k_rollout_tape and one closed-loop launch per step with the trajectory buffers advanced to that step.  With an estimator C, L,
 // the plant and x_true are read from the tape's copies, and x_k, x_{k+1}, y_k are written straight onto the tape (x_traj, y_traj of the step).
-static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const std::string &what) {
+// mt (mpcqp_rollout_tv): the loop is mpcqp_mpc_loop_tv's -- at a boundary step the tape's copy, then mpcqp_update_model with the entry, then a
+// copy of what the handle holds now (model blob, D, E, c) into the entry's slot, then the step; slot 0 is what it held when the call began.
+static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const std::string &what, const mpcqp_model_traj *mt = nullptr) {
+    int nseg = 0;
+    if (mt) {                                       // (the refusals of mpcqp_mpc_loop_tv, in its order)
+        if (mt->struct_size != (int32_t)sizeof(mpcqp_model_traj)) return fail(MPCQP_ERR_ARG, what + ": struct_size is not sizeof(mpcqp_model_traj)");
+        if (mt->hold < 1) return fail(MPCQP_ERR_ARG, what + ": hold must be >= 1");
+        nseg = (nsteps + mt->hold - 1) / mt->hold;
+        if (mt->nmodels < nseg) return fail(MPCQP_ERR_ARG, what + ": fewer than ceil(nsteps / hold) model entries");
+        if (!mt->Ad && !mt->Bd) return fail(MPCQP_ERR_ARG, what + ": give Ad, Bd or both");
+        if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, what + ": output feedback with a model schedule is not implemented");
+    }
+    const int nslots = mt ? nseg + 1 : 0, hold = mt ? mt->hold : 0;
     int rc = loop_check(h, nsteps, io);
     if (rc) return rc;
     if (!h->has_solve) return fail(MPCQP_ERR_STATE, what + ": no solve since the last setup, update, model update or warm start: the iterate does not belong to the step data of tape entry 0");
@@ -1418,7 +1442,7 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, co
         return fail(MPCQP_ERR_UNSUPPORTED, what + ": xref_traj must have the reference shape of the last upload (the entries of a tape have one shape)");
     const Lay &L = h->L;
     const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu, ny = (size_t)io->ny, db = sizeof(double);
-    const size_t bytes = tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, nullptr, nullptr);
+    const size_t bytes = tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, nullptr, nullptr, nslots, hold);
     if (!h->tape_buf || bytes > h->tape_bytes) {
         void *q = nullptr;
         if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MPCQP_ERR_HIP, what + ": the tape could not be allocated (" + what + "_tape_bytes says how much it takes)"); }
@@ -1426,8 +1450,17 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, co
         h->tape_buf = q; h->tape_bytes = bytes;
     }
     h->tape_valid = false;
-    RolloutTape T;
-    tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, (char *)h->tape_buf, &T);
+    RolloutTape T; RolloutSlots V;
+    tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, (char *)h->tape_buf, &T, nslots, hold, &V);
+    auto keep_slot = [&](int s) -> int {                   // what the handle holds now, as slot s
+        const size_t sB = (size_t)s * B;
+        HIPCHK(hipMemcpyAsync(const_cast<double *>(V.model) + sB * L.model_sz, h->P.model, B * L.model_sz * db, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(const_cast<double *>(V.D) + sB * L.n, h->P.D, B * L.n * db, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(const_cast<double *>(V.E) + sB * L.m, h->P.E, B * L.m * db, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(const_cast<double *>(V.c) + sB, h->P.c, B * db, hipMemcpyDeviceToDevice, h->stream));
+        return MPCQP_OK;
+    };
+    if (mt && (rc = keep_slot(0))) return rc;
     if (io->Ap) {
         HIPCHK(hipMemcpyAsync(T.Ap, io->Ap, B * nx * nx * db, hipMemcpyDefault, h->stream));
         HIPCHK(hipMemcpyAsync(T.Bp, io->Bp, B * nx * nu * db, hipMemcpyDefault, h->stream));
@@ -1438,13 +1471,20 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, co
         HIPCHK(hipMemcpyAsync(T.xt, io->x_true, B * nx * db, hipMemcpyDefault, h->stream));
     }
     HIPCHK(hipMemsetAsync(T.nact, 0, (3 * (size_t)nsteps * B + B) * sizeof(int), h->stream));      // (mpcqp_get_rollout_info before a sweep: all zero)
-    h->tape = T; h->tape_xref_rows = L.xref_rows; h->tape_ny = io->ny;
+    h->tape = T; h->tape_slots = V; h->tape_xref_rows = L.xref_rows; h->tape_ny = io->ny;
     const size_t per = (size_t)L.n + 2 * (size_t)L.m + L.step_sz + nu + 1;
     const unsigned grid = (unsigned)std::min<size_t>(1024, (B * per + 255) / 256);
     for (int k = 0; k < nsteps; ++k) {
         hipLaunchKernelGGL(k_rollout_tape, dim3(grid), dim3(256), 0, h->stream, h->L, h->P, T, k, (const double *)(h->um1_moved ? h->um1_used : nullptr));
         HIPCHK(hipGetLastError());
         const size_t k0 = (size_t)k;
+        if (mt && k % hold == 0) {                  // a boundary step: the entry replaces the model under the iterate the tape has just copied
+            const size_t e = (size_t)(k / hold);
+            mpcqp_model M; memset(&M, 0, sizeof(M));
+            if (mt->Ad) M.Ad = mt->Ad + e * B * nx * nx;
+            if (mt->Bd) M.Bd = mt->Bd + e * B * nx * nu;
+            if ((rc = mpcqp_update_model(h, &M)) || (rc = keep_slot((int)e + 1))) return rc;
+        }
         mpcqp_loop seg = loop_at(h, io, k0);
         if (ny) {                                   // (the estimator's loop reads and writes the tape's own copies)
             seg.Ap = T.Ap; seg.Bp = T.Bp; seg.C = T.C; seg.Lgain = T.Lg; seg.x_true = T.xt;
@@ -1461,6 +1501,32 @@ extern "C" int mpcqp_rollout(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) 
     if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout: bad argument");
     if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout: output feedback in a taped rollout is mpcqp_rollout_est (include/mpcqp_rollout_est.h)");
     return rollout_forward(h, nsteps, io, "mpcqp_rollout");
+}
+// ---- the taped rollout of the loop under a model schedule (include_ext/mpcqp_rollout_tv.h) ------------------------------------------
+extern "C" int mpcqp_rollout_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt) {
+    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tv: bad argument");
+    if (!mt) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tv: no model schedule given (mpcqp_rollout is the taped loop on one model)");
+    return rollout_forward(h, nsteps, io, "mpcqp_rollout_tv", mt);
+}
+extern "C" int mpcqp_rollout_tv_tape_bytes(mpcqp_handle *h, int nsteps, int hold, int64_t *bytes) {
+    if (!h || !bytes || nsteps < 1 || hold < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tv_tape_bytes: bad argument");
+    *bytes = (int64_t)tape_carve(h->L, h->batch, nsteps, h->L.xref_rows, 0, nullptr, nullptr, (nsteps + hold - 1) / hold + 1, hold);
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_rollout_tv_get_slot(mpcqp_handle *h, int s, double *model, double *D, double *E, double *c) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    const int rc = tape_guard(h, "mpcqp_rollout_tv_get_slot", false, nullptr);
+    if (rc) return rc;
+    const RolloutSlots &V = h->tape_slots;
+    if (V.nslots < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_tv_get_slot: the tape is not one of mpcqp_rollout_tv (no model schedule, no slots)");
+    if (s < 0 || s >= V.nslots) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tv_get_slot: s must be in 0 .. nseg");
+    HIPCHK(hipSetDevice(h->device));
+    const Lay &L = h->L;
+    const size_t B = (size_t)h->batch, sB = (size_t)s * B, db = sizeof(double);
+    if (get(h, model, V.model + sB * L.model_sz, B * L.model_sz * db) || get(h, D, V.D + sB * L.n, B * L.n * db) ||
+        get(h, E, V.E + sB * L.m, B * L.m * db) || get(h, c, V.c + sB, B * db)) return MPCQP_ERR_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
 }
 // ---- the taped rollout of the output-feedback loop (include/mpcqp_rollout_est.h) ---------------------------------------------------
 extern "C" int mpcqp_rollout_est_tape_bytes(mpcqp_handle *h, int nsteps, int ny, int64_t *bytes) {
@@ -1492,9 +1558,13 @@ static int put_seed(mpcqp_handle *h, double *dst, const double *src, size_t byte
 }
 // eo: the estimator's seeds and gradients (mpcqp_rollout_adjoint_est), or null.  est: the call is mpcqp_rollout_adjoint_est.
 // bo: the bound gradients (mpcqp_rollout_adjoint_bounds), or null.
+// tv: the call is mpcqp_rollout_adjoint_tv; to: its per-slot outputs, or null.
 static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo, bool est,
-                         const mpcqp_adjoint_bounds_io *bo = nullptr) {
+                         const mpcqp_adjoint_bounds_io *bo = nullptr, bool tv = false, const mpcqp_rollout_tv_io *to = nullptr) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
+    if (to && to->struct_size != (int32_t)sizeof(mpcqp_rollout_tv_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_tv: struct_size is not sizeof(mpcqp_rollout_tv_io)");
+    if (tv && (io->d_Ap || io->d_Bp || (mo && (mo->d_Ad || mo->d_Bd))))
+        return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_tv: d_Ap, d_Bp, d_Ad, d_Bd are per slot under a schedule: ask for them in mpcqp_rollout_tv_io");
     if (io->struct_size != (int32_t)sizeof(mpcqp_rollout_adjoint_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: struct_size is not sizeof(mpcqp_rollout_adjoint_io)");
     ModelOut m;                                     // (its refusals say mpcqp_rollout_adjoint on the _est path too)
     if (model_out(mo, "mpcqp_rollout_adjoint", &m)) return MPCQP_ERR_ARG;
@@ -1503,7 +1573,7 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (bo) {
         const bool other = io->lam || io->d_uminus1 || io->d_uref || io->d_xref || io->d_Ap || io->d_Bp || m.any ||
                            (eo && (eo->eta || eo->d_C || eo->d_L || eo->d_v || eo->d_Ae || eo->d_Be));
-        if (!bd.any && !other) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_bounds: no output asked for");
+        if (!tv && !bd.any && !other) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_bounds: no output asked for");
         if (bd.any && m.any && bd.batch_sum != m.batch_sum) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_bounds: batch_sum of mo and of bo differ");
     }
     if (eo && eo->struct_size != (int32_t)sizeof(mpcqp_rollout_est_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_est: struct_size is not sizeof(mpcqp_rollout_est_io)");
@@ -1514,6 +1584,9 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint before mpcqp_setup");
     if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the handle holds no tape (call mpcqp_rollout first)");
     if (!h->tape_valid) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the model or the scaling the tape was made under has been replaced (mpcqp_setup*, mpcqp_update_model, mpcqp_update_vectors with l, u) or its rollout failed: roll out again");
+    const RolloutSlots &V = h->tape_slots;
+    if (!tv && V.nslots > 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the tape is one of mpcqp_rollout_tv (a model schedule); use mpcqp_rollout_adjoint_tv");
+    if (tv && V.nslots < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_tv: the tape is not one of mpcqp_rollout_tv (no model schedule); use mpcqp_rollout_adjoint");
     if (est && h->tape_ny == 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_est: the tape is one of mpcqp_rollout (no estimator); use mpcqp_rollout_adjoint");
     HIPCHK(hipSetDevice(h->device));
     int rc = adjoint_alloc(h);
@@ -1531,16 +1604,29 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (ny && (put_seed(h, T.gxh, eo ? eo->G_xhat : nullptr, (K + 1) * B * nx * db) || put_seed(h, T.gy, eo ? eo->G_y : nullptr, K * B * ny * db))) return MPCQP_ERR_HIP;
     AdjointArgs Q = adjoint_args(h);
     Q.nseeds = 1; Q.gw = nullptr; Q.gu0 = nullptr; Q.chain = 1; Q.ncol = 1; Q.cs = 0;
-    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = (m.any ? ROLLOUT_WANT_MODEL : 0) | (bd.any ? ROLLOUT_WANT_BOUNDS : 0);
+    const bool slot_model = tv && to && (to->d_Ad_slots || to->d_Bd_slots);      // (the Ad, Bd gradients of a scheduled tape are asked for in `to`, not in mo)
+    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = ((m.any || slot_model) ? ROLLOUT_WANT_MODEL : 0) | (bd.any ? ROLLOUT_WANT_BOUNDS : 0);
     const size_t with_carry = v.smem + db * (size_t)rollout_carry_doubles(G, (int)ny);
     W.carry_lds = with_carry <= 160 * 1024 ? 1 : 0;         // (lam, mu, g behind the common block, or in the tape's few doubles of global memory)
     const size_t smem = W.carry_lds ? with_carry : v.smem;
-    DISPATCH_NB(G.NB, {
-        const auto kernel = ny ? k_rollout_adjoint_est<NB> : k_rollout_adjoint<NB>;      // (one sweep, with and without the estimator: mpcqp_rollout.h)
-        if (set_smem(kernel, smem)) return MPCQP_ERR_HIP;
-        hipLaunchKernelGGL(kernel, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
-    });
+    if (tv) {
+        DISPATCH_NB(G.NB, {
+            if (set_smem(k_rollout_adjoint_tv<NB>, smem)) return MPCQP_ERR_HIP;
+            hipLaunchKernelGGL(k_rollout_adjoint_tv<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W, V);
+        });
+    } else {
+        DISPATCH_NB(G.NB, {
+            const auto kernel = ny ? k_rollout_adjoint_est<NB> : k_rollout_adjoint<NB>;      // (one sweep, with and without the estimator: mpcqp_rollout.h)
+            if (set_smem(kernel, smem)) return MPCQP_ERR_HIP;
+            hipLaunchKernelGGL(kernel, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W);
+        });
+    }
     HIPCHK(hipGetLastError());
+    if (tv && to) {
+        const size_t S = (size_t)V.nslots;
+        if (get(h, to->d_Ad_slots, V.dAd, S * B * nx * nx * db) || get(h, to->d_Bd_slots, V.dBd, S * B * nx * nu * db) ||
+            get(h, to->d_Ap_entries, V.dAp, (S - 1) * B * nx * nx * db) || get(h, to->d_Bp_entries, V.dBp, (S - 1) * B * nx * nu * db)) return MPCQP_ERR_HIP;
+    }
     const size_t xw = (size_t)G.xref_rows * nx;
     if (get(h, io->lam, T.lam, (K + 1) * B * nx * db) || get(h, io->d_uminus1, T.dum1, B * nu * db) || get(h, io->d_uref, T.duref, B * nu * db) ||
         get(h, io->d_xref, T.dxref, K * B * xw * db) || get(h, io->d_Ap, T.dAp, B * nx * nx * db) || get(h, io->d_Bp, T.dBp, B * nx * nu * db)) return MPCQP_ERR_HIP;
@@ -1554,7 +1640,12 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (any_host(bd)) HIPCHK(hipStreamSynchronize(h->stream));
     return sync_unless_all_device(h, {io->G_x, io->G_u, io->lam, io->d_uminus1, io->d_uref, io->d_xref, io->d_Ap, io->d_Bp,
                                       eo ? eo->G_xhat : nullptr, eo ? eo->G_y : nullptr, eo ? eo->eta : nullptr, eo ? eo->d_C : nullptr, eo ? eo->d_L : nullptr,
-                                      eo ? eo->d_v : nullptr, eo ? eo->d_Ae : nullptr, eo ? eo->d_Be : nullptr}, &m);
+                                      eo ? eo->d_v : nullptr, eo ? eo->d_Ae : nullptr, eo ? eo->d_Be : nullptr,
+                                      to ? to->d_Ad_slots : nullptr, to ? to->d_Bd_slots : nullptr, to ? to->d_Ap_entries : nullptr, to ? to->d_Bp_entries : nullptr}, &m);
+}
+extern "C" int mpcqp_rollout_adjoint_tv(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo,
+                                        const mpcqp_adjoint_bounds_io *bo, const mpcqp_rollout_tv_io *to) {
+    return rollout_sweep(h, io, nullptr, mo, false, bo, true, to);
 }
 extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
     return rollout_sweep(h, io, nullptr, mo, false);

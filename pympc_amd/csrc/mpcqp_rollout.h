@@ -14,6 +14,12 @@
 //   reuse     the metric of K_pol is s = delta / D^2 (fixed) and omega = E^2 / delta on the active rows: it follows from the active set alone.
 //             The rows whose state differs from the one in place are counted while the set is written; where there is none and a factor
 //             is in place, kpol_factor is skipped.  The factorization is deterministic: the same bits either way.
+//   schedule  TV = true (k_rollout_adjoint_tv<NB>, include_ext/mpcqp_rollout_tv.h): the loop ran under a model schedule and the tape holds every model
+//             it was made under, with its scaling, as slots (RolloutSlots).  Entry k then reads model, D, E, c of slot sigma(k) = 0 for k = 0,
+//             1 + (k - 1) / hold beyond; on a change of slot the fixed half of the metric is formed again and the factor in place is dropped.
+//             Without a plant of its own the step reads Ad, Bd of the slot in force, 1 + k / hold, from global memory (S.hot holds the solve's
+//             slot, another one at a boundary step).  The Ad, Bd gradients land in the slot's buffer, the plant's in the schedule entry's.
+//             TV = false compiles to the code without any of it.
 //   estimator EST = true (k_rollout_adjoint_est<NB>, include/mpcqp_rollout_est.h): the loop ran output feedback, the entry's x0 is the estimate
 //             xh_k and the tape holds the plant state x_k, the measurement y_k, C and L beside it.  The step prologue then carries eta
 //             (the gradient at xh) beside lam and forms s = Ad' eta, t = L' s, r = G_y + t in three more barrier-separated phases; the
@@ -55,6 +61,14 @@ struct RolloutSweep {
                                   // kernel arguments: the sweep has no scalar register to spare, and one that is not asked for bounds must cost what it did.)
 };
 constexpr int ROLLOUT_WANT_MODEL = 1, ROLLOUT_WANT_BOUNDS = 2;
+// The model slots of a scheduled tape (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h): slot 0 is the model the call began under, slot e + 1
+// schedule entry e.  An argument of k_rollout_adjoint_tv alone: the other two sweeps neither take nor read it.
+struct RolloutSlots {
+    const double *model, *D, *E, *c;      // [nslots][batch][model_sz], [..][n], [..][m], [nslots][batch]: what the handle held under slot s
+    double *dAd, *dBd;                    // [nslots][batch][nx nx], [..][nx nu] the solve path of the entries made under slot s
+    double *dAp, *dBp;                    // [nslots - 1][batch][nx nx], [..][nx nu] the plant path of the steps schedule entry e was in force
+    int hold, nslots;
+};
 
 // lam | lam as the plant alone gives it | d_x0 of the step | g | mu | d_uref of the step | d_uref so far
 // with an estimator (ny > 0), behind them: eta | eta before d_x0 | s | xhat[k|k] | t | r | innovation
@@ -84,8 +98,9 @@ __global__ __launch_bounds__(256) void k_rollout_tape(Lay L, Ptrs P, RolloutTape
 // The sweep's body.  The estimator is a template parameter of this force-inlined function and not of the kernel: k_rollout_adjoint<NB> keeps the
 // name and the one template argument it had (the build's resource remarks are read by that name, tests/test_rollout_resources.py), and is the
 // EST = false instantiation; k_rollout_adjoint_est<NB> is the EST = true one.
-template <int NB, bool EST>
-__device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P, const AdjointArgs &Q, const RolloutTape &T, const RolloutSweep &W) {
+template <int NB, bool EST, bool TV>
+__device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P, const AdjointArgs &Q, const RolloutTape &T, const RolloutSweep &W, const RolloutSlots &V) {
+    static_assert(!(EST && TV), "a schedule together with an estimator is not a loop the library runs");
     extern __shared__ __attribute__((aligned(16))) double sh[];
     double *p = sh; Smem S; smem_common(L, P, p, S);       // (P.perm is null: workgroup b works on instance b)
     const int b = blockIdx.x, tid = threadIdx.x, B = T.batch, K = T.nsteps;
@@ -99,7 +114,9 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
     double *dAe = EST ? T.dAe + (size_t)b * nx * nx : nullptr, *dBe = EST ? T.dBe + (size_t)b * nx * nu : nullptr;
     const double *model = P.model + (size_t)b * L.model_sz;
     const double *D = P.D + (size_t)b * L.n, *E = P.E + (size_t)b * L.m;
-    const double cc = P.c[b], delta = Q.delta;
+    double cc = TV ? 0.0 : P.c[b];                        // (TV: all four are aimed at the entry's slot inside the loop)
+    const double delta = Q.delta;
+    int slot = -1;                                       // (TV) the slot model, D, E, cc, sv belong to
     double *om = Q.K.om + (size_t)b * L.m, *sv = Q.K.s + (size_t)b * L.n;
     int *act = Q.K.act + (size_t)b * L.m;
     const size_t vn = (size_t)b * ADJOINT_COLS * L.n, vm = (size_t)b * ADJOINT_COLS * L.m;      // (column 0 of the adjoint's work area)
@@ -112,12 +129,19 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
     auto mdst = [&](int e) -> double & {
         int f = 0;
         while (e >= W.off[f + 1]) ++f;
+        if constexpr (TV) if (f < 2) return (f == 0 ? V.dAd : V.dBd)[((size_t)slot * B + b) * (W.off[f + 1] - W.off[f]) + (e - W.off[f])];      // (Ad, Bd: per slot)
         return W.mout[(size_t)B * W.off[f] + (size_t)b * (W.off[f + 1] - W.off[f]) + (e - W.off[f])];
     };
     // lam_K = G_x[K], mu = 0, every sum 0; the fixed half of K_pol's metric
     for (int i = tid; i < nx; i += NT) { const double v = T.gx[((size_t)K * B + b) * nx + i]; lam[i] = v; T.lam[((size_t)K * B + b) * nx + i] = v; }
     for (int j = tid; j < nu; j += NT) { mu[j] = 0.0; dur[j] = 0.0; }
-    for (int e = tid; e < EN; e += NT) mdst(e) = 0.0;
+    if constexpr (TV) {
+        for (int s = 0; s < V.nslots; ++s) {
+            for (int e = tid; e < nx * nx; e += NT) { V.dAd[((size_t)s * B + b) * nx * nx + e] = 0.0; if (s) V.dAp[((size_t)(s - 1) * B + b) * nx * nx + e] = 0.0; }
+            for (int e = tid; e < nx * nu; e += NT) { V.dBd[((size_t)s * B + b) * nx * nu + e] = 0.0; if (s) V.dBp[((size_t)(s - 1) * B + b) * nx * nu + e] = 0.0; }
+        }
+    }
+    for (int e = tid + (TV ? W.off[2] : 0); e < EN; e += NT) mdst(e) = 0.0;
     auto bdst = [&](int e) -> double & {                 // (called under ROLLOUT_WANT_BOUNDS only)
         const int f = e < 2 * nx ? e / nx : 2 + (e - 2 * nx) / nu, sz = f < 2 ? nx : nu, off = f < 2 ? f * nx : 2 * nx + (f - 2) * nu;
         return W.mout[(size_t)B * (EN + off) + (size_t)b * sz + (e - off)];
@@ -131,7 +155,7 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
         for (int e = tid; e < nx * nu; e += NT) dBe[e] = 0.0;
         for (int e = tid; e < nx * ny; e += NT) { dC[e] = 0.0; dL[e] = 0.0; }
     }
-    for (int j = tid; j < L.n; j += NT) sv[j] = delta / (D[j] * D[j]);
+    if constexpr (!TV) for (int j = tid; j < L.n; j += NT) sv[j] = delta / (D[j] * D[j]);
     __syncthreads();
     Kpol kp = {};
     bool have = false;                                   // a factor of the active set in act[] is in place
@@ -139,9 +163,21 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
     for (int k = K - 1; k >= 0; --k) {
         const size_t kb = (size_t)k * B + b;
         const double *step = T.step + kb * L.step_sz;
+        if constexpr (TV) {                              // the slot this entry's solve was made under: its model, its scaling, its metric, and no factor of another's
+            const int s = k == 0 ? 0 : 1 + (k - 1) / V.hold;
+            if (s != slot) {
+                const size_t sb = (size_t)s * B + b;
+                slot = s;
+                model = V.model + sb * L.model_sz; D = V.D + sb * L.n; E = V.E + sb * L.m; cc = V.c[sb];
+                for (int j = tid; j < L.n; j += NT) sv[j] = delta / (D[j] * D[j]);
+                have = false;
+            }
+        }
         load_common(L, model, step, S);                  // (x_k, u_{-1} and the first Delta-u bounds of this entry; ends with a barrier)
         {   // g = G_u[k] + Bp' lam_{k+1} + mu;  lam_k = G_x[k] + Ap' lam_{k+1} (+ d_x0 below);  d_Ap += lam_{k+1} x_k',  d_Bp += lam_{k+1} u_k'
-            const double *Ap = T.Ap ? T.Ap + (size_t)b * nx * nx : S.hot + L.oAd, *Bp = T.Bp ? T.Bp + (size_t)b * nx * nu : S.hot + L.oBd;
+            const double *inforce = TV ? V.model + ((size_t)(1 + k / V.hold) * B + b) * L.model_sz : S.hot;      // (TV: the plant follows the schedule entry in force)
+            const double *Ap = T.Ap ? T.Ap + (size_t)b * nx * nx : inforce + L.oAd, *Bp = T.Bp ? T.Bp + (size_t)b * nx * nu : inforce + L.oBd;
+            double *dApk = TV ? V.dAp + ((size_t)(k / V.hold) * B + b) * nx * nx : dAp, *dBpk = TV ? V.dBp + ((size_t)(k / V.hold) * B + b) * nx * nu : dBp;
             const double *uk = T.u + kb * nu;
             const double *xk = EST ? T.xp + kb * nx : S.x0s;      // (the plant state; with an estimator the entry's x0 is the estimate)
             for (int j = tid; j < nu; j += NT) {
@@ -155,8 +191,8 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
                 for (int r = 0; r < nx; ++r) a += Ap[r * nx + i] * lam[r];
                 lamn[i] = a;
             }
-            for (int e = tid; e < nx * nx; e += NT) { const int r = e / nx; dAp[e] += lam[r] * xk[e - r * nx]; }
-            for (int e = tid; e < nx * nu; e += NT) { const int r = e / nu; dBp[e] += lam[r] * uk[e - r * nu]; }
+            for (int e = tid; e < nx * nx; e += NT) { const int r = e / nx; dApk[e] += lam[r] * xk[e - r * nx]; }
+            for (int e = tid; e < nx * nu; e += NT) { const int r = e / nu; dBpk[e] += lam[r] * uk[e - r * nu]; }
             if (EST) {
                 // s = Ad' eta_{k+1};  d_Be += eta_{k+1} u_k'
                 const double *Ad = S.hot + L.oAd, *yk = T.ym + kb * ny;
@@ -257,7 +293,10 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
 }
 
 template <int NB>
-__global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, false>(L, P, Q, T, W); }
+__global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, false, false>(L, P, Q, T, W, RolloutSlots{}); }
 // the same sweep over a tape of the output-feedback loop (mpcqp_rollout_est)
 template <int NB>
-__global__ __launch_bounds__(NT) void k_rollout_adjoint_est(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, true>(L, P, Q, T, W); }
+__global__ __launch_bounds__(NT) void k_rollout_adjoint_est(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, true, false>(L, P, Q, T, W, RolloutSlots{}); }
+// the same sweep over a tape of the loop under a model schedule (mpcqp_rollout_tv)
+template <int NB>
+__global__ __launch_bounds__(NT) void k_rollout_adjoint_tv(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W, RolloutSlots V) { rollout_adjoint_body<NB, false, true>(L, P, Q, T, W, V); }

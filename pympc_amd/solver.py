@@ -36,6 +36,7 @@ _FEATURES = dict(
     adjoint_bounds=(_lib.has_adjoint_bounds, 'no bound gradients (include/mpcqp_adjoint_bounds.h)'),
     rollout=(_lib.has_rollout, 'no taped rollout (include/mpcqp_rollout.h)'),
     rollout_est=(_lib.has_rollout_est, 'no taped output-feedback rollout (include/mpcqp_rollout_est.h)'),
+    rollout_tv=(_lib.has_rollout_tv, 'no taped rollout under a model schedule (include_ext/mpcqp_rollout_tv.h)'),
     model_update=(_lib.has_model_update, 'no in-place model update (include/mpcqp_model.h)'),
     model_traj=(_lib.has_model_update, 'no model schedule for the device loop (include/mpcqp_model.h)'))
 
@@ -391,6 +392,7 @@ class BatchProblem:
     # -- a rollout with a tape and its reverse sweep (include/mpcqp_rollout.h) ---------------------
     _rollout_shape = None      # (nsteps, xref rows) of the tape the handle holds
     _rollout_ny = 0            # > 0: the tape is one of the output-feedback loop (rollout_est)
+    _rollout_tv = None         # (hold, nseg, schedule gave Ad, schedule gave Bd): the tape is one of the loop under a model schedule (rollout_tv)
     rollout_count = 0          # rollouts made so far (pympc_amd.torch_layer: is the tape still the one of a forward?)
 
     def rollout(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
@@ -400,6 +402,7 @@ class BatchProblem:
         res = self._loop('mpcqp_rollout', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj)
         self._rollout_shape = (int(nsteps), self._xref_rows_last)
         self._rollout_ny = 0
+        self._rollout_tv = None
         self.rollout_count += 1
         return res
 
@@ -413,8 +416,40 @@ class BatchProblem:
         res = self._loop('mpcqp_rollout_est', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator)
         self._rollout_shape = (int(nsteps), self._xref_rows_last)
         self._rollout_ny = int(tuple(estimator['C'].shape)[-2])
+        self._rollout_tv = None
         self.rollout_count += 1
         return res
+
+    def rollout_tv(self, nsteps, model_traj, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
+        """``mpc_run(model_traj=)`` that keeps a tape (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h): the same arguments and results, one
+        closed-loop launch per step, and a tape that remembers every model it was made under -- slot 0: the model the call began with, slot
+        e + 1: schedule entry e.  Afterwards ``rollout_adjoint`` differentiates the loop with respect to every one of them."""
+        self._need('rollout_tv')
+        if model_traj is None:
+            raise ValueError('rollout_tv: a model_traj = (Ad, Bd, hold) is needed (rollout is the taped loop on one model)')
+        res = self._loop('mpcqp_rollout_tv', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, model_traj=model_traj)
+        hold = int(model_traj[2])
+        self._rollout_shape = (int(nsteps), self._xref_rows_last)
+        self._rollout_ny = 0
+        self._rollout_tv = (hold, (int(nsteps) + hold - 1) // hold, model_traj[0] is not None, model_traj[1] is not None)
+        self.rollout_count += 1
+        return res
+
+    def rollout_tv_tape_bytes(self, nsteps, hold):
+        """Device memory the tape of ``nsteps`` steps under a schedule with this ``hold`` takes (mpcqp_rollout_tv_tape_bytes)."""
+        self._need('rollout_tv')
+        v = C.c_int64()
+        _lib.check(self._L.mpcqp_rollout_tv_tape_bytes(self._h, int(nsteps), int(hold), C.byref(v)), 'mpcqp_rollout_tv_tape_bytes')
+        return v.value
+
+    def rollout_tv_slot(self, s):
+        """Model slot s of a scheduled tape as the sweep reads it (mpcqp_rollout_tv_get_slot; verification): dict(model [B, model doubles] the
+        blob (Ad | Bd | xmin | xmax | umin | umax | Dumin | Dumax | uref | eps_feas | Qx | QxN | Qu | QDu), D [B, n], E [B, m], c [B])."""
+        self._need('rollout_tv')
+        B, nx, nu = self.batch, self.nx, self.nu
+        r = dict(model=np.empty((B, 3 * nx * nx + nx * nu + 2 * nu * nu + 2 * nx + 5 * nu + 1)), D=np.empty((B, self.n)), E=np.empty((B, self.m)), c=np.empty(B))
+        _lib.check(self._L.mpcqp_rollout_tv_get_slot(self._h, int(s), *[_ptr(r[n]) for n in ('model', 'D', 'E', 'c')]), 'mpcqp_rollout_tv_get_slot')
+        return r
 
     def rollout_tape_bytes(self, nsteps, ny=0):
         """Device memory a tape of ``nsteps`` steps takes (mpcqp_rollout_tape_bytes; with ``ny`` outputs: mpcqp_rollout_est_tape_bytes)."""
@@ -433,6 +468,7 @@ class BatchProblem:
         _lib.check(self._L.mpcqp_rollout_release(self._h), 'mpcqp_rollout_release')
         self._rollout_shape = None
         self._rollout_ny = 0
+        self._rollout_tv = None
 
     def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), out=None, batch_sum=False, no_reuse=False, g_xhat=None, g_y=None):
         """The reverse sweep over the tape of the last ``rollout`` (mpcqp_rollout_adjoint): for ``g_x`` [K+1, B, nx] = dL/dx_k and / or
@@ -444,9 +480,21 @@ class BatchProblem:
         numpy in, numpy out; torch device tensors in, device tensors out (stream-ordered, no wait).
         On the tape of a ``rollout_est`` (mpcqp_rollout_adjoint_est): ``g_xhat`` [K+1, B, nx] = dL/dxhat_k and ``g_y`` [K, B, ny] = dL/dy_k are
         seeds too (any one of the four is enough), and ``want`` may name 'eta' [K+1, B, nx] (eta[0] = dL/dxhat_0), 'C' [B, ny, nx],
-        'L' [B, nx, ny], 'v' [K, B, ny], 'Ae' [B, nx, nx], 'Be' [B, nx, nu] (the estimator path alone); on a state-feedback tape they raise."""
+        'L' [B, nx, ny], 'v' [K, B, ny], 'Ae' [B, nx, nx], 'Be' [B, nx, nu] (the estimator path alone); on a state-feedback tape they raise.
+        On the tape of a ``rollout_tv`` (mpcqp_rollout_adjoint_tv): ``want`` may name 'Ad_traj' [nseg, B, nx, nx], 'Bd_traj' [nseg, B, nx, nu] --
+        entry e: the solve path of the solves made under schedule entry e -- and 'Ap_traj', 'Bp_traj' of the same shapes: the plant path of
+        the steps entry e was in force.  'Ad', 'Bd' are then the solve path of the model the call began with, plus that of all entries for a
+        matrix the schedule did not give (it never changed); 'Ap', 'Bp' the sum over the entries.  ``batch_sum`` sums these over the
+        instances too ([nseg, 1, ..] and [1, ..]).  On any other tape the four ``_traj`` names raise."""
         self._need('rollout')
         ny = self._rollout_ny
+        tv_names = ('Ad_traj', 'Bd_traj', 'Ap_traj', 'Bp_traj')
+        if self._rollout_shape is not None and self._rollout_tv is None and any(k in tv_names for k in want):
+            raise RuntimeError('rollout_adjoint: the gradients %s need the tape of a rollout_tv (this one was made on one model)' % ', '.join(tv_names))
+        if self._rollout_shape is not None and self._rollout_tv is not None:
+            if g_xhat is not None or g_y is not None:
+                raise RuntimeError('rollout_adjoint: g_xhat, g_y need the tape of a rollout_est (this one has no estimator)')
+            return self._rollout_adjoint_tv(g_x, g_u, want, out, batch_sum, no_reuse)
         est_names = ('eta', 'C', 'L', 'v', 'Ae', 'Be')
         if self._rollout_shape is not None and not ny and (g_xhat is not None or g_y is not None or any(k in est_names for k in want)):
             raise RuntimeError('rollout_adjoint: g_xhat, g_y and the gradients %s need the tape of a rollout_est (this one has no estimator)' % ', '.join(est_names))
@@ -490,6 +538,51 @@ class BatchProblem:
             _lib.check(self._L.mpcqp_rollout_adjoint_est(self._h, C.byref(io), C.byref(eo), C.byref(mo)), 'mpcqp_rollout_adjoint_est')
         else:
             _lib.check(self._L.mpcqp_rollout_adjoint(self._h, C.byref(io), C.byref(mo)), 'mpcqp_rollout_adjoint')
+        return res
+
+    def _rollout_adjoint_tv(self, g_x, g_u, want, out, batch_sum, no_reuse):
+        """``rollout_adjoint`` on the tape of a ``rollout_tv``: one mpcqp_rollout_adjoint_tv, then the per-slot gradients put together
+        (views and sums of the call's own buffers: ``out`` serves the other names only)."""
+        self._need('rollout_tv')
+        if g_x is None and g_u is None:
+            raise ValueError('rollout_adjoint: give g_x, g_u or both')
+        K, rows = self._rollout_shape
+        hold, nseg, gave_Ad, gave_Bd = self._rollout_tv
+        B, nx, nu = self.batch, self.nx, self.nu
+        like = g_x if g_x is not None else g_u
+        gx = _prep(g_x, (K + 1, B, nx), 'g_x') if g_x is not None else None
+        gu = _prep(g_u, (K, B, nu), 'g_u') if g_u is not None else None
+        io = _lib.RolloutAdjointIO()
+        io.struct_size, io.no_reuse = C.sizeof(_lib.RolloutAdjointIO), int(bool(no_reuse))
+        io.G_x, io.G_u = _ptr(gx), _ptr(gu)
+        table = dict(lam=(io, 'lam', (K + 1, B, nx)), uminus1=(io, 'd_uminus1', (B, nu)), uref=(io, 'd_uref', (B, nu)), xref=(io, 'd_xref', (K, B, rows * nx)))
+        mo, mtable = self._model_grads(batch_sum)
+        table.update({k: v for k, v in mtable.items() if k not in ('Ad', 'Bd')})
+        bo, btable = self._bound_grads(batch_sum)
+        table.update(btable)
+        if any(k in btable for k in want):
+            self._need('adjoint_bounds')
+        # what the schedule splits: name -> (field of mpcqp_rollout_tv_io, its leading dimension, how the answer is read from it)
+        whole = lambda gave: (lambda a: a[0] if gave else a.sum(0))
+        split = dict(Ad_traj=('d_Ad_slots', nseg + 1, nx, lambda a: a[1:]), Bd_traj=('d_Bd_slots', nseg + 1, nu, lambda a: a[1:]),
+                     Ap_traj=('d_Ap_entries', nseg, nx, lambda a: a), Bp_traj=('d_Bp_entries', nseg, nu, lambda a: a),
+                     Ad=('d_Ad_slots', nseg + 1, nx, whole(gave_Ad)), Bd=('d_Bd_slots', nseg + 1, nu, whole(gave_Bd)),
+                     Ap=('d_Ap_entries', nseg, nx, lambda a: a.sum(0)), Bp=('d_Bp_entries', nseg, nu, lambda a: a.sum(0)))
+        to = _lib.RolloutTVIO()
+        to.struct_size = C.sizeof(_lib.RolloutTVIO)
+        bufs = {}
+        for k in want:
+            if k in split and split[k][0] not in bufs:
+                field, lead, cols, _ = split[k]
+                bufs[field] = self._out(like, (lead, B, nx, cols))
+                setattr(to, field, _ptr(bufs[field]))
+        res = self._grads_out([k for k in want if k not in split], table, out, like)
+        self._keep = [gx, gu, res, bufs]
+        _lib.check(self._L.mpcqp_rollout_adjoint_tv(self._h, C.byref(io), C.byref(mo), C.byref(bo), C.byref(to)), 'mpcqp_rollout_adjoint_tv')
+        for k in want:
+            if k in split:
+                a = bufs[split[k][0]]
+                res[k] = split[k][3](a.sum(1)[:, None] if batch_sum else a)
         return res
 
     def rollout_info(self):
@@ -782,8 +875,8 @@ class BatchProblem:
             mt = _lib.ModelTraj()
             mt.struct_size, mt.hold, mt.nmodels = C.sizeof(_lib.ModelTraj), hold, nm
             mt.Ad = inp(Adt, (nm, B, nx, nx), 'model_traj Ad'); mt.Bd = inp(Bdt, (nm, B, nx, nu), 'model_traj Bd')
-            entry = 'mpcqp_mpc_loop_tv'
-            rc = self._L.mpcqp_mpc_loop_tv(self._h, K, C.byref(io), C.byref(mt))
+            entry = 'mpcqp_rollout_tv' if entry == 'mpcqp_rollout_tv' else 'mpcqp_mpc_loop_tv'
+            rc = getattr(self._L, entry)(self._h, K, C.byref(io), C.byref(mt))
         else:
             rc = getattr(self._L, entry)(self._h, K, C.byref(io))
         if rc == -4:

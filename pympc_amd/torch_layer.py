@@ -237,6 +237,93 @@ def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None,
     return _MPCRollout.apply(controller, int(nsteps), x0, u_prev, xref, w, Ap, Bp, names, *tensors)
 
 
+class _MPCRolloutTV(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, K, nsteps, hold, x0, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, names, *params):
+        if not x0.is_cuda:
+            raise ValueError('mpc_rollout_tv works on device tensors (x0 is on %s)' % x0.device)
+        nseg = (nsteps + hold - 1) // hold
+
+        def roll(new, st, it):
+            X, U = new(nsteps + 1, K.nx), new(nsteps, K.nu)
+            # (entry e of an unbatched schedule is one model for the whole batch)
+            sched = [None if t is None else _det(t)[:nseg].reshape((nseg, -1) + tuple(t.shape[-2:])).expand((nseg, K.B) + tuple(t.shape[-2:])).contiguous()
+                     for t in (Ad_traj, Bd_traj)]
+            K.prob.rollout_tv(nsteps, (sched[0], sched[1], hold), w=_det(w), Ap=_bc(Ap, (K.B, K.nx, K.nx)), Bp=_bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it])
+            for n, t in zip(('Ad', 'Bd'), sched):             # the controller is left with the last entry used: read back when somebody asks (update_model's way)
+                if t is not None:
+                    K.__dict__.pop(n, None)
+                    K._on_device[n] = t[nseg - 1]
+            return X[-1], U, (X, U)
+        ctx.nseg = nseg
+        return _rollout_forward(ctx, K, nsteps, x0, u_prev, xref, names, params, roll, (x0, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj))
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_U):
+        K = ctx.K
+        if K.prob.rollout_count != ctx.count:
+            raise RuntimeError('mpc_rollout_tv: the controller has been rolled out again since this forward (rollout %d then, %d now); '
+                               'its tape is no longer the one to differentiate.' % (ctx.count, K.prob.rollout_count))
+        inputs = ('x0', 'u_prev', 'xref', 'w', 'Ap', 'Bp', 'Ad_traj', 'Bd_traj')
+        ni = 3 + len(inputs)
+        need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[3:ni], ctx.shapes)}
+        shape = dict(zip(inputs, ctx.shapes))
+        pneed, shared, _ = _param_want(ctx, ctx.needs_input_grad[ni + 1:])
+        if not any(need.values()) and not pneed:
+            return (None,) * (ni + 1 + len(ctx.names))
+        follows = shape['Ap'] is None                        # the plant followed the schedule: its path belongs to the model in force
+        # a matrix the schedule gave gets the plant's path entry by entry; one it did not give never changed: params' matrix gets all of it
+        plant = {'Ad_traj': 'Ap_traj', 'Bd_traj': 'Bp_traj', 'Ad': 'Ap', 'Bd': 'Bp'}
+        left = {'Ad': shape['Ad_traj'] is None, 'Bd': shape['Bd_traj'] is None}
+        split = [n for n in ('Ad_traj', 'Bd_traj', 'Ap', 'Bp') if need[n]] + [n for n in ('Ad', 'Bd') if n in pneed]
+        unbatched = lambda n: len(shape[n]) == (3 if n.endswith('_traj') else 2) if n in shape else shared[n]
+        batch_sum = bool(split or pneed) and all(unbatched(n) for n in split) and all(shared[n] for n in pneed)
+        want = list(dict.fromkeys(_ROLLOUT_INPUTS[n][0] for n in inputs[:6] if need[n]))
+        want += [n for n in ('Ad_traj', 'Bd_traj') if need[n]] + pneed
+        if follows:
+            want += [plant[n] for n in ('Ad_traj', 'Bd_traj') if need[n]] + [plant[n] for n in ('Ad', 'Bd') if n in pneed and left[n]]
+        want = list(dict.fromkeys(want))
+        with _ordered(K):
+            res = K.prob.rollout_adjoint(g_x=grad_X.to(torch.float64).contiguous(), g_u=grad_U.to(torch.float64).contiguous(), want=want, batch_sum=batch_sum)
+        grads = [_ROLLOUT_INPUTS[n][1](res[_ROLLOUT_INPUTS[n][0]], shape[n]).reshape(shape[n]) if need[n] else None for n in inputs[:6]]
+        for n in ('Ad_traj', 'Bd_traj'):
+            v = None
+            if need[n]:
+                v = res[n] + res[plant[n]] if follows else res[n]
+                v = (v.sum(dim=1) if len(shape[n]) == 3 else v)[:ctx.nseg]
+                if shape[n][0] > ctx.nseg:                   # entries beyond ceil(nsteps / hold) were never in force
+                    v = torch.cat([v, v.new_zeros((shape[n][0] - ctx.nseg,) + tuple(v.shape[1:]))])
+                v = v.reshape(shape[n])
+            grads.append(v)
+        pgrads = _param_grads(ctx, res, pneed, shared, batch_sum)
+        for i, (n, shp) in enumerate(zip(ctx.names, ctx.pshapes)):
+            if follows and n in ('Ad', 'Bd') and n in pneed and left[n]:
+                p = res[plant[n]]
+                pgrads[i] = pgrads[i] + ((p[0] if batch_sum else p.sum(dim=0)) if shared[n] else p).reshape(shp)
+        return (None, None, None) + tuple(grads) + (None,) + tuple(pgrads)
+
+
+def mpc_rollout_tv(controller, x0, nsteps, Ad_traj, Bd_traj, hold, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None, bounds=None):
+    """``mpc_rollout`` under a model schedule: ``(X [K+1,B,nx], U [K,B,nu])`` of ``nsteps`` = K closed-loop steps in which entry ``k // hold``
+    of ``Ad_traj`` [nseg,B,nx,nx] / ``Bd_traj`` [nseg,B,nx,nu] (or unbatched [nseg,nx,nx] / [nseg,nx,nu]; either may be None, not both;
+    nseg >= ceil(K / hold)) replaces the controller's model at the start of step k, as ``BatchMPCController.run(model_traj=)`` does -- a
+    controller tracking a relinearised plant.  Forward is ``update_model(solve=False, **params)`` where given, ``update(x0, u_prev, xref)``
+    with its solve (made under the model the controller holds then: tape entry 0), then ONE ``mpcqp_rollout_tv``; backward is ONE
+    ``mpcqp_rollout_adjoint_tv`` on torch's current stream.  Differentiable with respect to every tensor argument: the gradient of
+    ``Ad_traj[e]`` is that of the solves made under entry e plus, where ``Ap`` is None (the plant follows the schedule), that of the plant
+    steps it was in force; ``params['Ad']`` is the model the rollout begins with and gets the first solve's share (and, where the schedule
+    leaves Ad alone, everything).  An unbatched schedule's gradient is the sum over the batch, formed on the device.  Everything else as
+    in ``mpc_rollout``."""
+    names, tensors = _check_args('mpc_rollout_tv', controller, params, Ap, Bp, bounds)
+    if Ad_traj is None and Bd_traj is None:
+        raise ValueError('mpc_rollout_tv: give Ad_traj, Bd_traj or both (mpc_rollout is the loop on one model)')
+    nseg = (int(nsteps) + int(hold) - 1) // int(hold)
+    for n, t in (('Ad_traj', Ad_traj), ('Bd_traj', Bd_traj)):
+        if t is not None and (not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (3, 4) or t.shape[0] < nseg):
+            raise ValueError('mpc_rollout_tv: %s must be a device tensor [nseg, B, ., .] or [nseg, ., .] with nseg >= ceil(nsteps / hold)' % n)
+    return _MPCRolloutTV.apply(controller, int(nsteps), int(hold), x0, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, names, *tensors)
+
+
 class _MPCRolloutEst(torch.autograd.Function):
     @staticmethod
     def forward(ctx, K, nsteps, x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, names, *params):

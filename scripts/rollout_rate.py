@@ -14,8 +14,12 @@ is part of the result.  Per (batch, shape, K):
 One JSON line per (batch, shape, K).
 
 ``--bounds``: the sweeps of (b) and (c) are asked for the six bound gradients too (include/mpcqp_adjoint_bounds.h).
+``--schedule HOLD ..``: per hold, the loop under a model schedule (include_ext/mpcqp_rollout_tv.h; every entry a smooth 3 % perturbation of
+the instance's Ad, Bd) in the same alternation: run(model_traj=) against rollout_tv, and the scheduled sweep ('Ad_traj', 'Bd_traj',
+'Ap_traj', 'Bp_traj' in place of 'Ad', 'Bd', 'Ap', 'Bp') with its n_factor / K, beside the constant-model figures of the same repetition.
+Every timed loop starts from the same model, state and solve (update_model + update + solve before it, not timed).
 
-    python scripts/rollout_rate.py [--reps 5] [--eps 1e-6] [--sizes 1024:12,4,30 256:4,2,10] [--steps 20 100] [--no-route-b] [--bounds]"""
+    python scripts/rollout_rate.py [--reps 5] [--eps 1e-6] [--sizes 1024:12,4,30 256:4,2,10] [--steps 20 100] [--no-route-b] [--bounds] [--schedule 1 5]"""
 import argparse
 import json
 import os
@@ -45,6 +49,7 @@ def main():
     ap.add_argument('--steps', nargs='+', type=int, default=[20, 100])
     ap.add_argument('--no-route-b', action='store_true', help='skip the K-controller route (it builds K handles)')
     ap.add_argument('--bounds', action='store_true', help='ask the sweep for xmin, xmax, umin, umax, Dumin, Dumax as well')
+    ap.add_argument('--schedule', nargs='*', type=int, default=[], help='holds of a model schedule to time the scheduled loop and sweep under')
     a = ap.parse_args()
     import torch
     from pympc_amd import fixtures
@@ -83,8 +88,19 @@ def main():
             want = ('lam', 'uminus1', 'Ad', 'Bd', 'Ap', 'Bp') + (('xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax') if a.bounds else ())
 
             def reset():
+                if a.schedule:                             # (a scheduled loop leaves its last entry under the handle)
+                    bp.update_model(Ad=Ad, Bd=Bd)
                 bp.update(x0, um1)
                 bp.solve_async()
+
+            scheds = {}
+            for hold in a.schedule:
+                nseg = (K + hold - 1) // hold
+                rng = np.random.default_rng(3)
+                e = np.arange(nseg).reshape(-1, 1, 1, 1)
+                wave = lambda M: t(M.cpu().numpy()[None] * (1.0 + 0.03 * np.sin(0.7 * e + rng.uniform(0, 2 * np.pi, (1,) + tuple(M.shape)))))
+                scheds[hold] = (wave(Ad), wave(Bd), hold)
+            want_tv = tuple(k + '_traj' if k in ('Ad', 'Bd', 'Ap', 'Bp') else k for k in want)
 
             # (a) taping, (c) reuse: warm up, then alternate
             reset(); bp.mpc_run(K, out=out); reset(); bp.rollout(K, out=out)
@@ -94,12 +110,28 @@ def main():
             bufs = bp.rollout_adjoint(g_x=gx, g_u=gu, want=want)
             bp.rollout_adjoint(g_x=gx, g_u=gu, want=want, out=bufs, no_reuse=True)
             run_ms, roll_ms, sweep_ms, noreuse_ms = [], [], [], []
+            tv = {hold: dict(run_tv_ms=[], rollout_tv_ms=[], sweep_tv_ms=[]) for hold in scheds}
+            for hold, sc in scheds.items():                # warm up
+                reset(); bp.mpc_run(K, out=out, model_traj=sc); reset(); bp.rollout_tv(K, sc, out=out)
+                bp.rollout_adjoint(g_x=gx, g_u=gu, want=want_tv)
+                tv[hold]['tape_bytes'] = bp.rollout_tv_tape_bytes(K, hold)
+            if scheds:
+                reset(); bp.rollout(K, out=out)
             for _ in range(a.reps):
                 reset(); run_ms.append(timed(lambda: bp.mpc_run(K, out=out))[0])
                 reset(); roll_ms.append(timed(lambda: bp.rollout(K, out=out))[0])
                 sweep_ms.append(timed(lambda: bp.rollout_adjoint(g_x=gx, g_u=gu, want=want, out=bufs))[0])
                 nfac = bp.rollout_info()[3]
                 noreuse_ms.append(timed(lambda: bp.rollout_adjoint(g_x=gx, g_u=gu, want=want, out=bufs, no_reuse=True))[0])
+                for hold, sc in scheds.items():
+                    reset(); tv[hold]['run_tv_ms'].append(timed(lambda: bp.mpc_run(K, out=out, model_traj=sc))[0])
+                    reset(); tv[hold]['rollout_tv_ms'].append(timed(lambda: bp.rollout_tv(K, sc, out=out))[0])
+                    tv[hold]['sweep_tv_ms'].append(timed(lambda: bp.rollout_adjoint(g_x=gx, g_u=gu, want=want_tv))[0])
+                    info = bp.rollout_info()
+                    tv[hold].update(n_factor_per_step=float(info[3].mean()) / K, steps_differentiated=float((info[2] == 1).mean()))
+            if scheds:                                     # (the constant-model tape again, for the status read below)
+                reset(); bp.rollout(K, out=out); bp.rollout_adjoint(g_x=gx, g_u=gu, want=want, out=bufs)
+                res['schedule'] = {str(hold): v for hold, v in tv.items()}
             _, _, status, _ = bp.rollout_info()
             res.update(run_ms=run_ms, rollout_ms=roll_ms, sweep_ms=sweep_ms, sweep_no_reuse_ms=noreuse_ms,
                        n_factor_per_step=float(nfac.mean()) / K, steps_differentiated=float((status == 1).mean()))

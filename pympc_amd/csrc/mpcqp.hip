@@ -104,7 +104,7 @@ int mpcqp_set_error(int code, const char *msg) { return fail(code, msg); }      
 // mpcqp_w8.hip: the second translation unit (NT = 512).  kargs: this unit's RunKArgs, byte for byte the other's.
 int mpcqp_w8_launch(const void *kargs, size_t kargs_bytes, const RunKernelId &id, int loop, int grid, size_t smem, hipStream_t stream);
 #ifdef MPCQP_RUN_TIMING
-void mpcqp_w8_ticks(unsigned long long *out16, unsigned long long *outw48);
+void mpcqp_w8_ticks(unsigned long long *out16, unsigned long long *outw48, unsigned long long *outb128);
 #endif
 constexpr int BALANCE_EVERY = 16;  // solves between two rebuilds of the workgroup -> instance map
 constexpr int QUEUE_ITEMS_PER_SLOT = 16;   // persistent closed-loop launches: queue items per resident workgroup slot (run_kernel_args)
@@ -1857,7 +1857,12 @@ extern "C" int mpcqp_get_stats(mpcqp_handle *h, uint64_t *out4, int reset) {
     { uint64_t t[4]; hipMemcpy(t, h->P.stats + 4, sizeof(t), hipMemcpyDeviceToHost); fprintf(stderr, "phase wall-clock ticks: begin %llu admm %llu check %llu body %llu\n", (unsigned long long)t[0], (unsigned long long)t[1], (unsigned long long)t[2], (unsigned long long)t[3]);
       unsigned long long g[16]; hipMemcpyFromSymbol(g, HIP_SYMBOL(g_ticks), sizeof(g)); unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_ticks), z, sizeof(z));
       unsigned long long gw[48]; hipMemcpyFromSymbol(gw, HIP_SYMBOL(g_wticks), sizeof(gw)); unsigned long long zw[48] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_wticks), zw, sizeof(zw));
-      if (h->L.nw == 8) mpcqp_w8_ticks(g, gw);      // (the 512-thread kernels count in their own translation unit)
+      unsigned long long gb[128]; hipMemcpyFromSymbol(gb, HIP_SYMBOL(g_bticks), sizeof(gb)); unsigned long long zb[128] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_bticks), zb, sizeof(zb));
+      if (h->L.nw == 8) mpcqp_w8_ticks(g, gw, gb);      // (the 512-thread kernels count in their own translation unit)
+      // the boundary between two rounds of the latency round, section by section (mpcqp_layout.h: BTICK): one group per section, one number per wave
+      { char line[2048]; int n = snprintf(line, sizeof line, "boundary cycles (lane 0 of each wave, summed over rounds):");
+        for (int k = 0; k < 10; ++k) { n += snprintf(line + n, sizeof line - n, " s%d", k); for (int w = 0; w < 8; ++w) n += snprintf(line + n, sizeof line - n, " %llu", gb[8 * k + w]); }
+        fprintf(stderr, "%s\n", line); }
       // the latency round's barriers as every wave's lane 0 reaches them (mpcqp_layout.h: WTICK): one group per barrier, one number per wave
       { char line[1024]; int n = snprintf(line, sizeof line, "wave barrier cycles (lane 0 of each wave, summed over iterations):");
         for (int k = 0; k < 5; ++k) { n += snprintf(line + n, sizeof line - n, " b%d", k); for (int w = 0; w < 8; ++w) n += snprintf(line + n, sizeof line - n, " %llu", gw[8 * k + w]); }

@@ -15,13 +15,15 @@
 
 struct RunSmem { Smem S; double *X, *Z, *Y; };
 template <bool LDSSTATE>
-__device__ __forceinline__ RunSmem run_smem(const Lay &L, const Ptrs &P) {
+__device__ __forceinline__ RunSmem run_smem(const Lay &L, const Ptrs &P, int b) {      // (b: the instance, by value -- the latency round's check holds it)
     extern __shared__ __attribute__((aligned(16))) double sh[];
-    RunSmem r; double *p = sh; smem_common(L, P, p, r.S);
+    RunSmem r; double *p = sh; smem_common(L, P, p, r.S, b);
     r.X = r.Z = r.Y = nullptr;
     if (LDSSTATE) { r.X = carve(p, L.n); r.Z = carve(p, L.m); r.Y = carve(p, L.m); }
     return r;
 }
+template <bool LDSSTATE>
+__device__ __forceinline__ RunSmem run_smem(const Lay &L, const Ptrs &P) { return run_smem<LDSSTATE>(L, P, inst_of(P.perm)); }
 
 // (OCC: workgroups per CU of the calling kernel -- a tag only: it keeps the phases of kernels with different launch bounds apart,
 //  so that the register budget of the one-workgroup-per-CU kernels does not leak into the four-per-CU ones through a shared callee)

@@ -434,19 +434,18 @@ __device__ __forceinline__ void latw_solve(const d4 *fr, const double *TopL, con
 }
 
 // ---- the round (as admm_lat, with ceil(NG / NWAVES) groups of four stages per wave) -----------------------------------------------------
-enum { LATW_CONTINUE = 0, LATW_SOLVED = 1, LATW_GENERIC = 2 };
+enum { LATW_CONTINUE = 0, LATW_SOLVED = 1, LATW_GENERIC = 2, LATW_CARRIED = 3 };      // (CARRIED: solved, and the queue item's next step begun in the same call)
 template <int NXT, int NUT, int NST>
 __device__ int latw_check(double pv, double pv2, double ncq, double zA, double ysA, double omA, double zB, double ysB, double omB, double z0, double ys0, double om0,
-                          double loA, double hiA, double loB, double hiB, double cc, int iter, int *frame_pin);      // (mpcqp_latw_check.h)
-template <int NXT, int NUT, int NST>
-__device__ int latw_carry(int iter, int *frame_pin);      // (mpcqp_latw_check.h)
+                          double loA, double hiA, double loB, double hiB, double cc, int iter, int binst, int *frame_pin);      // (mpcqp_latw_check.h)
 
 // FAST (iter0 >= 0): the round does not end with its iterations.  The termination test of OSQP (update_info + check_termination, mpcqp_phases.h:
 // check_body) is evaluated right here in the OWNER layout -- A x and A'y are the two MFMA groups of the iteration applied to x and y, P x a 16-long
 // dot product per lane against the weight matrices' LDS copy, the norms one block reduction (latw_check, a NON-INLINED function: compiled into this
 // one, its temporaries and the 220 registers that live across it fought for the same file, and the spill reloads -- each a memory round trip --
 // cost more than the generic check it replaced; as a call only the registers the callee really uses are saved around it) -- and
-//   * converged: the solve is finished here (solution, iterate, mpcqp_info, statistics: what check_body's tail writes), return 1;
+//   * converged: the solve is finished here (solution, iterate, mpcqp_info, statistics: what check_body's tail writes), return 1 -- or, where the queue
+//     item has another step, that step's transition is made in the same call (latw_carry) and its solve starts from the owner registers;
 //   * not converged, and the cheap halves of both infeasibility certificates rule them out (|dy| or the support-function sum, |dx| or q'dx): the
 //     next round starts at once, with the fragments and the owner registers where they are -- no write-back, no generic check, no reload;
 //   * anything else (a rho estimate is due, the iteration limit, a certificate that needs its operator product, a non-finite residual, the first
@@ -638,22 +637,21 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
         const RunArgs &R = run_kargs().R;
         if (stop_mode(iter, R.max_iter, R.chk, R.rho_every, R.plain != 0) != COLD_CHECK) break;      // (rho estimate / iteration limit / plain iterations: the generic check)
         int verdict;
+        BTICK_START
         { FramePin pin; verdict = latw_check<NXT, NUT, NST>(pv[0], pv2[0], ncq[0], rA[0].z, rA[0].ys, rA[0].om, rB[0].z, rB[0].ys, rB[0].om, r0.z, r0.ys, r0.om,
-                                                               loA[0], hiA[0], loB[0], hiB[0], cc, iter, &pin.v); }
+                                                               loA[0], hiA[0], loB[0], hiB[0], cc, iter, b, &pin.v); }
         verdict = __builtin_amdgcn_readfirstlane(verdict);
-        if (verdict == LATW_SOLVED) {
-            // the closed loop on the device: the queue item's next step -- output, plant, update, q -- without leaving this function
-            // (latw_carry), and its solve warm-started from the owner registers, as a write-back, begin and this prologue would start it
-            const int kc = __builtin_amdgcn_readfirstlane(S.iflag[6]), ke = __builtin_amdgcn_readfirstlane(S.iflag[7]);
-            if (!(R.nsteps > 0 && kc >= 0 && ke <= R.nsteps && kc + 1 < ke)) { term = 1; break; }      // (iflag[6], [7]: run_instance's)
-            int carried;
-            { FramePin pin; carried = latw_carry<NXT, NUT, NST>(iter, &pin.v); }
-            if (!__builtin_amdgcn_readfirstlane(carried)) { term = 1; break; }      // (a constraint type changed: the kernel's begin refactors)
+        // (solved, and no next step of the queue item to carry the solve into -- or its transition made and a constraint type changed: the kernel's begin refactors)
+        if (verdict == LATW_SOLVED) { BTICK(4) term = 1; break; }
+        if (verdict == LATW_CARRIED) {
+            BTICK(7)
+            // the closed loop on the device: the queue item's next step -- output, plant, update, q -- was made by the same call (latw_carry);
+            // its solve is warm-started from the owner registers, as a write-back, begin and this prologue would start it.
             // what changed in the owned coefficients -- q of stage 0's inputs, the bounds of stage 0's dynamics rows: where latw_carry left them
             if (u0v) ncq[0] = Tc[sl[0]];
             if (is_x && wv == 0 && (lane & 3) == 0) { loA[0] = Cc[sl[0]]; hiA[0] = loA[0]; }
             iter = 0;
-        } else if (verdict != LATW_CONTINUE) break;
+        } else { BTICK(9) if (verdict != LATW_CONTINUE) break; }
         iters = next_stop(iter, R.max_iter, R.chk, R.rho_every) - iter;
         // The next round starts from exactly the state a write-back and a reload would give it -- y leaves as ys (om / c) and comes back as c y / om:
         // the same two roundings here -- so that an instance's iterates do not depend on whether a round boundary was crossed in this function or through
@@ -663,6 +661,7 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
         if (u0v) rt(r0);
         WA[sl[0]] = ok[0] ? rA[0].w : 0.0; WB[sl[0]] = ok[0] ? rB[0].w : 0.0;      // (a slot without a variable contributes nothing)
         __syncthreads();
+        BTICK(8)
     }
     TICK(9)
     }

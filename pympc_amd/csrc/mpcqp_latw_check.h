@@ -7,6 +7,8 @@
 //     (|c dy| clipped by the infinite bounds and the support function of [l, u]; |dx| and q'dx) meet in ONE block reduction;
 //   * LATW_SOLVED: the solve is finished here -- iterate for the next warm start, reported solution, mpcqp_info, statistics, first input and status
 //     for the closed loop on the device: everything check_body's tail writes;
+//   * LATW_CARRIED: solved, and the queue item has another step: its transition (latw_carry below, inline) is made in the same call -- one entry, one
+//     return, one set of kernel-argument loads, and everything the transition reads from memory was requested behind the check's first barrier;
 //   * LATW_CONTINUE: not converged and neither certificate can hold: the caller starts the next round at once, fragments and owner registers
 //     where they are;
 //   * LATW_GENERIC: anything else (a certificate that needs its operator product, a non-finite residual, the first launch of a two-launch
@@ -16,17 +18,21 @@
 #pragma once
 
 template <int NXT, int NUT, int NST>
+__device__ __forceinline__ int latw_carry(const RunKArgs &KA, Smem &S, int b, int k, int iter, double cc, double wn, double Er, int ct, int r, mpcqp_info inf);      // (below)
+
+template <int NXT, int NUT, int NST>
 __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double zA, double ysA, double omA, double zB, double ysB, double omB, double z0, double ys0, double om0,
-                                       double loA, double hiA, double loB, double hiB, double cc, int iter, int *frame_pin) {
+                                       double loA, double hiA, double loB, double hiB, double cc, int iter, int binst, int *frame_pin) {
     PHASE_PIN_USE(frame_pin);
     constexpr int NB = 16, N = NST, NG = (N + 3) / 4, VS = LAT_VS(N), NTOP = BcrFmt::top_count(N);
     static_assert(NG <= NWAVES, "one group of four stages per wave");
     const RunKArgs &KA = run_kargs();
     const Lay &L = KA.L; const Ptrs &PP = KA.P; const RunArgs &R = KA.R;
-    RunSmem rs = run_smem<true>(L, PP);
+    const int b = __builtin_amdgcn_readfirstlane(binst);      // (the instance travels by value: the map entry is not loaded again)
+    RunSmem rs = run_smem<true>(L, PP, b);
     Smem &S = rs.S;
     const int nx = NXT ? NXT : L.nx, nu = NUT ? NUT : L.nu, NR = L.N;
-    const int b = inst_of(PP.perm), tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const double cinv = 1.0 / cc;
     const double *hot = S.hot;
     double *Tc = S.T + NB, *Cc = Tc + VS;
@@ -55,6 +61,19 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     const double yA = ysA * (omA * cinv), yB = ysB * (omB * cinv), y0 = u0v ? ys0 * (om0 * cinv) : 0.0;
     Tc[sl] = ok ? pv : 0.0; Cc[sl] = ok ? yA : 0.0;
     __syncthreads();
+    BTICK(0)
+    // the closed loop on the device: may a converged solve be carried into the item's next step right here (Smem::iflag[6], [7]: run_instance's, written
+    // before the round began)?  Then what that transition reads from memory -- the next step's disturbance, scaling and current type of the row this
+    // thread re-types, rho -- is requested here, before the verdict is known, and consumed in latw_carry: no round trip of its own -- behind the first barrier, where the two
+    // flags arrive with the exchange's own LDS reads (in front of it, at the function's entry, waiting for them cost every check 900 cycles).  (w[k + 1] only
+    // where step k + 1 is inside the item: no address out of range; the other addresses are the instance's own whatever the verdict.)
+    const int kc = __builtin_amdgcn_readfirstlane(S.iflag[6]), ke = __builtin_amdgcn_readfirstlane(S.iflag[7]);
+    const bool more = R.nsteps > 0 && kc >= 0 && ke <= R.nsteps && kc + 1 < ke;
+    const int rc = tid < nx ? tid : (tid < nx + nu ? L.rdu + (tid - nx) : -1);
+    const double wn = (more && tid < nx && R.w) ? ((cgdouble *)R.w)[((size_t)(kc + 1) * R.batch + b) * nx + tid] : 0.0;
+    const double Erc = Eg[rc >= 0 ? rc : 0];
+    const int ctc = ((const __attribute__((address_space(1))) int *)(PP.ctype + (size_t)b * L.m))[rc >= 0 ? rc : 0];
+    const double rho = PP.rho[b];
     int infbits = !ok ? 0 : (eA * hiA > lim ? 1 : 0) | (eA * loA < -lim ? 2 : 0) | (eB * hiB > lim ? 4 : 0) | (eB * loB < -lim ? 8 : 0);
     if (u0v) infbits |= (e0 * S.du0[nu + jj] > lim ? 16 : 0) | (e0 * S.du0[jj] < -lim ? 32 : 0);
     const Ctx c{L, hot, hot + L.hot_sz};
@@ -82,6 +101,7 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     __syncthreads();
     Cc[sl] = ok ? yB : 0.0;
     __syncthreads();
+    BTICK(1)
     if (ok) {
         const double xj = pv, qj = -ncq * cinv, yprev = Cc[sl + oprev];
         const double *xs = Tc + s * NB;
@@ -109,7 +129,10 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
         }
         cert(ddA, loA, hiA, infbits); cert(ddB, loB, hiB, infbits >> 2);
     }
+    if (u0v) S.uo[jj] = pv;      // (the first input, should the verdict be 'solved' -- nobody reads it otherwise: published by the reduction's barriers, for latw_carry)
+    BTICK(2)
     block_reduce<9, 3>(nrm, vsum, S.red);
+    BTICK(3)
     const double ea = KA.S.eps_abs, er = KA.S.eps_rel, epi = KA.S.eps_prim_inf, edi = KA.S.eps_dual_inf;
     const double pri_res = nrm[0], dua_res = nrm[3], obj_val = vsum[0];
     if (!(pri_res <= QP_INFTY) || !(dua_res <= QP_INFTY) || obj_val != obj_val) return LATW_GENERIC;      // (non-finite: the generic check reports it)
@@ -124,19 +147,20 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
             gz[aidx] = zA; gy[aidx] = yA; yo[aidx] = yA;
             gz[bidx] = zB; gy[bidx] = yB; yo[bidx] = yB;
         }
-        if (u0v) { gz[L.rdu + jj] = z0; gy[L.rdu + jj] = y0; yo[L.rdu + jj] = y0; S.uo[jj] = pv; }
+        if (u0v) { gz[L.rdu + jj] = z0; gy[L.rdu + jj] = y0; yo[L.rdu + jj] = y0; }
+        mpcqp_info inf;                                    // (thread 0's: stored ONCE, here or by the carry)
+        inf.status = MPCQP_SOLVED; inf.iter = iter; inf.rho_updates = 0; inf.reserved = 0;
+        inf.obj_val = obj_val; inf.pri_res = pri_res; inf.dua_res = dua_res; inf.rho = rho;
         if (tid == 0) {
-            mpcqp_info inf;
-            inf.status = MPCQP_SOLVED; inf.iter = iter; inf.rho_updates = S.iflag[1]; inf.reserved = (S.iflag[3] += 1);
-            inf.obj_val = obj_val; inf.pri_res = pri_res; inf.dua_res = dua_res; inf.rho = PP.rho[b];
+            inf.rho_updates = S.iflag[1];
+            const int checks = (S.iflag[3] += 1);
             S.iflag[4] = MPCQP_SOLVED;
-            atomicAdd(&PP.stats[0], (unsigned long long)iter); atomicAdd(&PP.stats[1], (unsigned long long)inf.reserved);
+            atomicAdd(&PP.stats[0], (unsigned long long)iter); atomicAdd(&PP.stats[1], (unsigned long long)checks);
             atomicAdd(&PP.stats[2], (unsigned long long)inf.rho_updates); atomicAdd(&PP.stats[3], 1ULL);
-            PP.work[b] += (unsigned)iter;
-            inf.reserved = 0;
-            PP.info[b] = inf;
+            atomicAdd(&PP.work[b], (unsigned)iter);      // (one writer per instance: the sum a load, an addition and a store gave, without the round trip)
         }
-        return LATW_SOLVED;
+        if (!more) { if (tid == 0) PP.info[b] = inf; return LATW_SOLVED; }
+        return latw_carry<NXT, NUT, NST>(KA, S, b, kc, iter, cc, wn, Erc, ctc, rc, inf);
     }
     // not converged: may the next round start at once?  Only if neither certificate can hold -- decided from their cheap halves
     if (R.nsteps == 0 && R.part == 1) return LATW_GENERIC;                       // (the first launch of a two-launch solve hands over after ONE round)
@@ -146,60 +170,52 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     return LATW_CONTINUE;
 }
 
-// The closed loop on the device, between two steps of one queue item, without leaving the latency round (admm_latw, after latw_check has
-// returned LATW_SOLVED; Smem::iflag[6] = the step whose solve just ended, [7] = the end of the item, 0 where the carry does not apply -- the kernel
-// decides: no estimator, no reference trajectory, warm start on, not MPCQP_TUNE_NO_CARRY).  What the kernel's loop body and begin_body would do,
-// in their arithmetic and summation order: the records of step k, output (u_0 of the converged solve), plant step, update of x0 / u_{-1} / the
-// first Delta-u bounds and the step blob, and of what these enter -- q of stage 0's inputs (the only entries of q that change with a constant
-// reference), the types of stage 0's dynamics rows and the first Delta-u rows (the only bounds that move).  Every global request of the
-// function is issued before its first barrier: one memory round trip.
-// Returns 1: carried -- the caller starts step k + 1's solve from its owner registers, iflag[6] = k + 1, with the new -c q of stage 0's inputs
+// The closed loop on the device, between two steps of one queue item, without leaving the latency round: the tail of latw_check where the solve has
+// converged and the item has another step (Smem::iflag[6] = k, the step whose solve just ended, [7] = the end of the item, 0 where the carry does not
+// apply -- the kernel decides: no estimator, no reference trajectory, warm start on, not MPCQP_TUNE_NO_CARRY).  What the kernel's loop body and
+// begin_body would do, in their arithmetic and summation order: the records of step k, output (u_0 of the converged solve), plant step, update of
+// x0 / u_{-1} / the first Delta-u bounds and the step blob, and of what these enter -- q of stage 0's inputs (the only entries of q that change with
+// a constant reference), the types of stage 0's dynamics rows and the first Delta-u rows (the only bounds that move).  It loads NOTHING from memory
+// where the plant is the model's (the LDS copy): the disturbance wn, the scaling Er and type ct of row r, rho (in inf) were requested early in
+// the check; S.uo was published by the check's block reduction.  Called in line, forward declared for the check above.
+// Returns LATW_CARRIED: the caller starts step k + 1's solve from its owner registers, iflag[6] = k + 1, with the new -c q of stage 0's inputs
 // in Tc and the new bound of stage 0's dynamics rows in Cc at their owners' slots (both vectors are rewritten by the iteration before it reads
-// them).  Returns 0: a type changed -- the step's transition is done, its begin (refactorization) is not: iflag[7] = -1 tells the kernel to run
-// begin for step iflag[6] = k + 1.
-// A function of its own for the reason latw_check is one: nothing of it lives across the iterations.
+// them).  Returns LATW_SOLVED: a type changed -- the step's transition is done, its begin (refactorization) is not: iflag[7] = -1 tells the kernel
+// to run begin for step iflag[6] = k + 1.
 template <int NXT, int NUT, int NST>
-__device__ __noinline__ int latw_carry(int iter, int *frame_pin) {
-    PHASE_PIN_USE(frame_pin);
+__device__ __forceinline__ int latw_carry(const RunKArgs &KA, Smem &S, int b, int k, int iter, double cc, double wn, double Er, int ct, int r, mpcqp_info inf) {
+    BTICK(4)
 #ifdef MPCQP_RUN_TIMING
     const unsigned long long tw0_ = wall_clock64();
 #endif
     constexpr int NB = 16, VS = LAT_VS(NST);
-    const RunKArgs &KA = run_kargs();
     const Lay &L = KA.L; const Ptrs &P = KA.P; const RunArgs &R = KA.R;
-    RunSmem rs = run_smem<true>(L, P);
-    Smem &S = rs.S;
     const int nx = NXT ? NXT : L.nx, nu = NUT ? NUT : L.nu;
-    const int b = inst_of(P.perm), tid = threadIdx.x;
+    const int tid = threadIdx.x, k1 = k + 1;
+    const unsigned long long tstep = wall_clock64();      // (the end of step k: asked for here, stored with the record below)
     double *step = P.step + (size_t)b * L.step_sz;
-    const int k = S.iflag[6], k1 = k + 1;                  // (written before the round began)
     const size_t kb = (size_t)k1 * R.batch + b;
-    // the requests: disturbance, scaling and current type of the row this thread checks, rho and c
-    const int r = tid < nx ? tid : (tid < nx + nu ? L.rdu + (tid - nx) : -1);
-    const double v = (tid < nx && R.w) ? R.w[kb * nx + tid] : 0.0;
-    const double Er = r >= 0 ? P.E[(size_t)b * L.m + r] : 0.0;
-    const int ct = r >= 0 ? P.ctype[(size_t)b * L.m + r] : 0;
-    const double rho = P.rho[b], cc = P.c[b];
-    __syncthreads();                                       // (S.uo, S.iflag[4]: latw_check's)
-    if (tid == 0) {
-        R.status_traj[(size_t)k * R.batch + b] = S.iflag[4];
-        R.iter_traj[(size_t)k * R.batch + b] = iter;
-        if (k < TS_STEPS) P.tstamp[(size_t)TS_STRIDE * b + 2 + k] = wall_clock64();
-    }
     // ---- output (solved: the first input), plant step, update -- mpcqp_kernels.h run_instance, ny = 0
     const double *un = S.uo, *xt = S.x0s;
     double xn = 0.0;
     if (tid < nx) {
-        const double *Ap = R.Ap ? R.Ap + (size_t)b * nx * nx : S.hot + L.oAd;
-        const double *Bp = R.Bp ? R.Bp + (size_t)b * nx * nu : S.hot + L.oBd;
         double acc = 0.0;
-        for (int j = 0; j < nx; ++j) acc += Ap[tid * nx + j] * xt[j];
-        for (int j = 0; j < nu; ++j) acc += Bp[tid * nu + j] * un[j];
-        xn = acc + v;
+        if (!R.Ap && !R.Bp) {                              // (the model's own matrices: LDS, read as LDS)
+            const double *Ad = S.hot + L.oAd, *Bd = S.hot + L.oBd;
+            for (int j = 0; j < nx; ++j) acc += Ad[tid * nx + j] * xt[j];
+            for (int j = 0; j < nu; ++j) acc += Bd[tid * nu + j] * un[j];
+        } else {
+            const double *Ap = R.Ap ? R.Ap + (size_t)b * nx * nx : S.hot + L.oAd;
+            const double *Bp = R.Bp ? R.Bp + (size_t)b * nx * nu : S.hot + L.oBd;
+            for (int j = 0; j < nx; ++j) acc += Ap[tid * nx + j] * xt[j];
+            for (int j = 0; j < nu; ++j) acc += Bp[tid * nu + j] * un[j];
+        }
+        xn = acc + wn;
         R.x_traj[kb * nx + tid] = xt[tid];
     }
     if (tid < nu) R.u_traj[kb * nu + tid] = un[tid];
     __syncthreads();
+    BTICK(6)
     if (tid < nx) { S.x0s[tid] = xn; step[tid] = xn; }
     if (tid < nu) { const double u = un[tid]; S.um1s[tid] = u; step[nx + tid] = u; S.du0[tid] = S.hot[L.oDumin + tid] + u; S.du0[nu + tid] = S.hot[L.oDumax + tid] + u; }
     __syncthreads();
@@ -212,18 +228,21 @@ __device__ __noinline__ int latw_carry(int iter, int *frame_pin) {
     if (r >= 0) { double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi); changed = row_type(Er, lo, hi) != ct; }
     changed = __syncthreads_or(changed);
     if (tid == 0) {
+        R.status_traj[(size_t)k * R.batch + b] = MPCQP_SOLVED;      // (Smem::iflag[4]: the check's, a moment ago)
+        R.iter_traj[(size_t)k * R.batch + b] = iter;
+        if (k < TS_STEPS) P.tstamp[(size_t)TS_STRIDE * b + 2 + k] = tstep;
         S.iflag[6] = k1;
         atomicAdd(&P.stats[8], 1ULL);                      // (mpcqp_dev_carry_stats: steps carried, and of those handed back)
-        if (changed) { S.iflag[7] = -1; atomicAdd(&P.stats[9], 1ULL); }
+        if (changed) { S.iflag[7] = -1; atomicAdd(&P.stats[9], 1ULL); }      // (the record stays the solved step's)
         else {
-            mpcqp_info *inf = P.info + b;                  // (begin_body's record, field by field: no frame for a local copy)
-            inf->status = MPCQP_UNSOLVED; inf->iter = 0; inf->rho_updates = 0; inf->reserved = 0;
-            inf->obj_val = 0.0; inf->pri_res = 0.0; inf->dua_res = 0.0; inf->rho = rho;
+            inf.status = MPCQP_UNSOLVED; inf.iter = 0; inf.rho_updates = 0;      // (begin_body's record)
+            inf.obj_val = 0.0; inf.pri_res = 0.0; inf.dua_res = 0.0;
             S.iflag[1] = 0; S.iflag[3] = 0;
         }
+        P.info[b] = inf;
     }
 #ifdef MPCQP_RUN_TIMING
     if (tid == 0) atomicAdd(&P.stats[7], wall_clock64() - tw0_);      // (the loop body's clock: transitions inside the round count there too)
 #endif
-    return changed ? 0 : 1;
+    return changed ? LATW_SOLVED : LATW_CARRIED;
 }

@@ -125,9 +125,21 @@ __device__ unsigned long long g_wticks[48];
 __device__ __forceinline__ unsigned long long *wtick_slots() { __shared__ unsigned long long s[64]; return s; }
 #define WTICK_START { if ((threadIdx.x & 63) == 0) wtick_slots()[48 + (threadIdx.x >> 6)] = clock64(); }
 #define WTICK(k) { if ((threadIdx.x & 63) == 0) { unsigned long long *s_ = wtick_slots(); s_[8 * (k) + (threadIdx.x >> 6)] += clock64() - s_[48 + (threadIdx.x >> 6)]; } }
-#define TICK_RESET { if (threadIdx.x < 16) tick_slots()[threadIdx.x] = 0; if (threadIdx.x < 64) wtick_slots()[threadIdx.x] = 0; __syncthreads(); }
+// The boundary between two rounds of the latency round (everything slot 9 covers: termination test, carried transition, hand-over), cut into
+// sections the same way: lane 0 of EVERY wave, cycles since that wave passed the previous section's end.  Slot 8 k + w: section k, wave w; 128 + w:
+// the wave's last clock.  Sections: 0 check entry -> first barrier, 1 the three exchanges, 2 rows and variables, 3 block reduction, 4 solved tail
+// (-> back in the caller where nothing is carried), 5 free (the carry's own entry and first barrier while it was a second call), 6 plant, 7 update
+// and types -> back in the caller, 8 hand-over up to the barrier in front of the next round, 9 a verdict other than 'solved' -> back in the caller.
+__device__ unsigned long long g_bticks[128];
+__device__ __forceinline__ unsigned long long *btick_slots() { __shared__ unsigned long long s[136]; return s; }
+#define BTICK_START { if ((threadIdx.x & 63) == 0) btick_slots()[128 + (threadIdx.x >> 6)] = clock64(); }
+#define BTICK(k) { if ((threadIdx.x & 63) == 0) { unsigned long long *s_ = btick_slots(); const unsigned long long t_ = clock64(); const int w_ = threadIdx.x >> 6; \
+                                                  s_[8 * (k) + w_] += t_ - s_[128 + w_]; s_[128 + w_] = t_; } }
+#define TICK_RESET { if (threadIdx.x < 16) tick_slots()[threadIdx.x] = 0; if (threadIdx.x < 64) wtick_slots()[threadIdx.x] = 0; \
+                     if (threadIdx.x < 136) btick_slots()[threadIdx.x] = 0; __syncthreads(); }
 #define TICK_FLUSH { __syncthreads(); if (threadIdx.x < 15) atomicAdd(&g_ticks[threadIdx.x], tick_slots()[threadIdx.x]); \
-                     if (threadIdx.x < 48 && wtick_slots()[threadIdx.x]) atomicAdd(&g_wticks[threadIdx.x], wtick_slots()[threadIdx.x]); }
+                     if (threadIdx.x < 48 && wtick_slots()[threadIdx.x]) atomicAdd(&g_wticks[threadIdx.x], wtick_slots()[threadIdx.x]); \
+                     if (threadIdx.x < 128 && btick_slots()[threadIdx.x]) atomicAdd(&g_bticks[threadIdx.x], btick_slots()[threadIdx.x]); }
 #else
 #define TICK(i)
 #define TICK_START
@@ -135,4 +147,6 @@ __device__ __forceinline__ unsigned long long *wtick_slots() { __shared__ unsign
 #define TICK_FLUSH
 #define WTICK(k)
 #define WTICK_START
+#define BTICK(k)
+#define BTICK_START
 #endif

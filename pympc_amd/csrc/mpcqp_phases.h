@@ -38,9 +38,10 @@ __device__ __forceinline__ double *carve(double *&p, int n) { double *r = p; p +
 // LDS layout of a workgroup: [ hot | x0 | um1 | du0 | red | tv | iflag | T (tsz) ] and, behind it, the LDS-resident iterate
 // [ X | Z | Y ] of small problems.  T comes last so that the factorization, which runs while the iterate copy is dead
 // (before a round loads it, after a check has read it), can let its workspace run on into that area.
+// (b: the instance, where the caller holds it -- inst_of(P.perm) is a load of the map entry otherwise)
 template <class PT>
-__device__ __forceinline__ void smem_common(const Lay &L, const PT &P, double *&p, Smem &S) {
-    S.Qv = (double *)P.qv + (size_t)inst_of(P.perm) * (L.n_x + L.n_u);
+__device__ __forceinline__ void smem_common(const Lay &L, const PT &P, double *&p, Smem &S, int b) {
+    S.Qv = (double *)P.qv + (size_t)b * (L.n_x + L.n_u);
     S.hot = carve(p, L.hot_lds);
     S.x0s = carve(p, L.nx);
     S.um1s = carve(p, L.nu);
@@ -52,6 +53,8 @@ __device__ __forceinline__ void smem_common(const Lay &L, const PT &P, double *&
     S.iflag = (int *)carve(p, 4);
     S.T = carve(p, L.tsz);
 }
+template <class PT>
+__device__ __forceinline__ void smem_common(const Lay &L, const PT &P, double *&p, Smem &S) { smem_common(L, P, p, S, inst_of(P.perm)); }
 __host__ __device__ inline int smem_common_doubles(const Lay &L) { return L.tsz + L.hot_lds + 2 * L.nx + 4 * L.nu + 16 * L.nw + 128 + 4; }
 
 __device__ __forceinline__ void load_common(const Lay &L, const double *model, const double *step, Smem &S) {

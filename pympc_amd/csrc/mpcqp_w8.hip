@@ -63,11 +63,13 @@ int mpcqp_w8_launch(const void *kargs, size_t kargs_bytes, const RunKernelId &id
 
 #ifdef MPCQP_RUN_TIMING
 // development build: this unit's phase clocks (mpcqp_get_stats prints them beside its own)
-void mpcqp_w8_ticks(unsigned long long *out16, unsigned long long *outw48) {
+void mpcqp_w8_ticks(unsigned long long *out16, unsigned long long *outw48, unsigned long long *outb128) {
     hipMemcpyFromSymbol(out16, HIP_SYMBOL(w8::g_ticks), 16 * sizeof(unsigned long long));
     hipMemcpyFromSymbol(outw48, HIP_SYMBOL(w8::g_wticks), 48 * sizeof(unsigned long long));
-    unsigned long long z[48] = {0};
+    hipMemcpyFromSymbol(outb128, HIP_SYMBOL(w8::g_bticks), 128 * sizeof(unsigned long long));
+    unsigned long long z[128] = {0};
     hipMemcpyToSymbol(HIP_SYMBOL(w8::g_ticks), z, 16 * sizeof(unsigned long long));
-    hipMemcpyToSymbol(HIP_SYMBOL(w8::g_wticks), z, sizeof(z));
+    hipMemcpyToSymbol(HIP_SYMBOL(w8::g_wticks), z, 48 * sizeof(unsigned long long));
+    hipMemcpyToSymbol(HIP_SYMBOL(w8::g_bticks), z, sizeof(z));
 }
 #endif

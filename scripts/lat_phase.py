@@ -1,6 +1,7 @@
 """Phase clocks of ONE instance alone on its compute unit, -DMPCQP_RUN_TIMING builds:  python scripts/lat_phase.py <lib.so> [backend] [iters] [tuning]
 Prints cycles per ADMM iteration by phase (thread 0 of the workgroup: rhs | level 0 fwd | level 1 fwd | top | level 1 back | level 0 back | update)
-and per round / per check outside the iterations; per step, the wall clock of begin, the rounds, the generic checks and the loop body (output,
+and per round / per check outside the iterations (slot 9, 'boundary': everything between a round's last iteration and the next round -- termination
+test, carried transition, hand-over -- and, on libraries with boundary clocks, its sections on lane 0 of every wave); per step, the wall clock of begin, the rounds, the generic checks and the loop body (output,
 plant, update -- inside the round too where it carries a solve into the next step; libraries that predate that clock print no body); for the
 latency round a table per WAVE as well: when lane 0 of each wave reaches each barrier of the iteration and which wave ends each phase.  The library writes its counters to stderr; this script reads them back through a pipe."""
 import os, sys, re, tempfile
@@ -38,8 +39,15 @@ names = ['rhs', 'L0fwd', 'L1fwd', 'top', 'L1back', 'L0back', 'update']
 print('%s %s: %d iterations, %d rounds in 20 steps; %.0f cycles per iteration = ' % (os.path.basename(sys.argv[1]), backend, its, rounds, tot / its)
       + ' + '.join('%s %.0f' % (n, p / 100 * tot / its) for n, p in zip(names, pct)))
 print('   whole admm function (thread 0): %.0f cycles per step; sum of its slots: %.0f; before the first tick %.0f' % (chk[1] / 20.0, (tot + sum(outside)) / 20.0, chk[2] / 20.0))
-print('   per round: load %.0f  owner regs %.0f  write-back %.0f cycles;  per check: setup+tail %.0f vars %.0f reduce %.0f decide %.0f cycles;  wall (10 ns ticks) per step: begin %.0f admm %.0f check %.0f'
+print('   per round: load %.0f  owner regs %.0f  boundary %.0f cycles;  per check: setup+tail %.0f vars %.0f reduce %.0f decide %.0f cycles;  wall (10 ns ticks) per step: begin %.0f admm %.0f check %.0f'
       % tuple([o / rounds for o in outside] + [chk[0] / rounds, chk[2] / rounds, chk[3] / rounds, chk[4] / rounds] + [x / 20.0 for x in wall]))
+bl = [l for l in txt.splitlines() if l.startswith('boundary cycles')]
+if bl:                                        # (libraries with boundary clocks, mpcqp_layout.h BTICK: the sections of slot 9, lane 0 of each wave, cycles per round)
+    g = re.findall(r' s\d((?: \d+)+)', bl[-1])
+    arr = np.array([[int(x) for x in s.split()] for s in g], dtype=float) / rounds       # [section, wave]
+    secs = ['check entry', 'exchanges', 'rows+vars', 'reduction', 'solved tail', 'carry entry', 'plant', 'update+types', 'hand-over', 'other verdict']
+    print('   boundary, cycles per round by section (mean over the waves / slowest wave): '
+          + '  '.join('%s %.0f/%.0f' % (n, r.mean(), r.max()) for n, r in zip(secs, arr)) + '  | sum of the means %.0f' % arr.mean(axis=1).sum())
 wl = [l for l in txt.splitlines() if l.startswith('wave barrier cycles')]
 if wl:                                        # (libraries with per-wave clocks: when lane 0 of each wave reaches each barrier of the iteration, cycles since the wave's start)
     g = re.findall(r' b\d((?: \d+)+)', wl[-1])

@@ -6,7 +6,9 @@ header: an instruction belongs to the phase given by the number of s_barrier pas
 eight per-wave cases of LATW_DISPATCH, so the text order alone does not say).  Per phase it prints static counts -- summed over the per-wave cases,
 i.e. what the compute unit's LDS sees per iteration; instructions in front of a wave switch run on all eight waves and count once --
 of ds_read_b64 | ds_read2_b64 + ds_read2st64_b64 | ds_read_b128 | ds_write_b64 | ds_write2_b64 + ds_write2st64_b64 | other ds_* | v_mfma*, and the LDS-array
-cycles these forms cost by MI355X's rates (ds_read_b64 2, ds_read2_b64 8, ds_read_b128 4, ds_write_b64 4, ds_write2_b64 8 per wave instruction)."""
+cycles these forms cost by MI355X's rates (ds_read_b64 2, ds_read2_b64 8, ds_read_b128 4, ds_write_b64 4, ds_write2_b64 8 per wave instruction).
+    python scripts/lds_forms.py --boundary [--inst ...] [--asm w8.s]
+prints instead the static counts of the boundary between two rounds (w8::latw_check<NXT,NUT,NST>, see boundary() below)."""
 import argparse, collections, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -120,8 +122,51 @@ def phases(blocks, header, body, succ):
     return counts, clash, nbar
 
 
+def function_text(lines, name):
+    """Instruction lines (opcode and operands) of the first function whose symbol starts with name; None if there is none."""
+    start = next((i for i, l in enumerate(lines) if l.startswith(name) and ':' in l), None)
+    if start is None:
+        return None
+    out = []
+    for l in lines[start + 1:]:
+        s = l.strip()
+        if s.startswith('.Lfunc_end'): break
+        if s and s[0] not in '.;': out.append(s)
+    return out
+
+
+def boundary(lines, nxt, nut, mode):
+    """The boundary between two rounds: w8::latw_check<NXT,NUT,NST> -- termination test and, inline, the carried transition -- and, in trees where
+    the carry is a call of its own, w8::latw_carry<...> beside it.  Static counts in text order, not weighted by how often a path runs."""
+    nst = int(mode) % 100
+    tot = collections.Counter()
+    for fn in ('latw_check', 'latw_carry'):
+        text = function_text(lines, '_ZN2w8%d%sILi%sELi%sELi%dEEE' % (len(fn), fn, nxt, nut, nst))
+        if text is None:
+            print('w8::%s<%s,%s,%d>: not a function of its own' % (fn, nxt, nut, nst))
+            continue
+        ops = [t.split()[0] for t in text]
+        first = ops.index('s_barrier') if 's_barrier' in ops else len(ops)
+        # (inst_of masks the map entry with PERM_INST_MASK: one 'and' with that literal per load of the map, vector or scalar)
+        c = collections.Counter({
+            'vector loads of the instance map': sum(o == 'v_and_b32' and '0xffffff' in t for o, t in zip(ops, text)),
+            'scalar loads of the instance map': sum(o == 's_and_b32' and '0xffffff' in t for o, t in zip(ops, text)),
+            's_waitcnt vmcnt(0) in front of the first barrier': sum(o == 's_waitcnt' and 'vmcnt(0)' in t for o, t in zip(ops[:first], text[:first])),
+            'barriers': ops.count('s_barrier'),
+            'flat_load': sum(o.startswith('flat_load') for o in ops),
+            'global_load': sum(o.startswith('global_load') for o in ops),
+            's_load': sum(o.startswith('s_load') for o in ops),
+            's_waitcnt': ops.count('s_waitcnt'),
+            'scratch / buffer accesses': sum(o.startswith('scratch_') or o.startswith('buffer_') for o in ops),
+            'instructions': len(ops)})
+        tot.update(c)
+        print('w8::%s<%s,%s,%d>:' % (fn, nxt, nut, nst) + ''.join('\n    %-50s %5d' % kv for kv in c.items()))
+    print('together:' + ''.join('\n    %-50s %5d' % kv for kv in tot.items()))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--boundary', action='store_true', help='instead: static counts of the boundary between two rounds (latw_check with the carry in it)')
     ap.add_argument('--inst', default='16,true,12,4,231', help='template arguments NB,LDSSTATE,NXT,NUT,MODE of run_admm_phase')
     ap.add_argument('--asm', help='read this assembly instead of compiling')
     ap.add_argument('--keep', help='keep the compiled assembly here')
@@ -134,6 +179,8 @@ def main():
         path = args.keep or os.path.join(tempfile.mkdtemp(), 'w8.s')
         compile_asm(os.path.abspath(path), extra)
     lines = open(path).read().splitlines()
+    if args.boundary:
+        return boundary(lines, nxt, nut, mode)
     blocks = function_blocks(lines, name)
     header, body, succ = iteration_loop(blocks)
     counts, clash, nbar = phases(blocks, header, body, succ)

@@ -46,6 +46,10 @@ ADJOINT_BOUNDS_NAMES = ('xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')      #
 # include_ext/mpcqp_rollout_tv.h: likewise -- the taped rollout under a model schedule, and its reverse sweep with per-slot model gradients
 ROLLOUT_TV_SYMBOLS = ['mpcqp_rollout_tv', 'mpcqp_rollout_tv_tape_bytes', 'mpcqp_rollout_adjoint_tv', 'mpcqp_rollout_tv_get_slot']
 
+# include_ext2/mpcqp_rollout_tv_est.h: likewise -- the output-feedback loop under a model (and gain) schedule, its tape and its reverse sweep
+ROLLOUT_TV_EST_SYMBOLS = ['mpcqp_mpc_loop_tv_est', 'mpcqp_rollout_tv_est', 'mpcqp_rollout_tv_est_tape_bytes', 'mpcqp_rollout_adjoint_tv_est',
+                          'mpcqp_rollout_tv_est_get_gain']
+
 # include/mpcqp_riccati.h: likewise -- batched discrete algebraic Riccati equations and their adjoint, without a handle
 RICCATI_SYMBOLS = ['mpcqp_riccati_default_settings', 'mpcqp_dare', 'mpcqp_dare_adjoint']
 
@@ -103,6 +107,17 @@ class RolloutTVIO(C.Structure):
     """mpcqp_rollout_tv_io (include_ext/mpcqp_rollout_tv.h): the per-slot and per-entry model gradients out; host or device pointers, None = not wanted."""
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('d_Ad_slots', C.c_void_p), ('d_Bd_slots', C.c_void_p),
                 ('d_Ap_entries', C.c_void_p), ('d_Bp_entries', C.c_void_p)]
+
+
+class EstTraj(C.Structure):
+    """mpcqp_est_traj (include_ext2/mpcqp_rollout_tv_est.h): entry e of Lgain_traj is the observer gain while model entry e is in force."""
+    _fields_ = [('struct_size', C.c_int32), ('nentries', C.c_int32), ('Lgain_traj', C.c_void_p)]
+
+
+class RolloutTVEstIO(C.Structure):
+    """mpcqp_rollout_tv_est_io (include_ext2/mpcqp_rollout_tv_est.h): the per-entry estimator gradients out; host or device pointers, None = not wanted."""
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('d_Ae_entries', C.c_void_p), ('d_Be_entries', C.c_void_p),
+                ('d_L_entries', C.c_void_p)]
 
 
 class Settings(C.Structure):
@@ -274,6 +289,15 @@ def load():
         L.mpcqp_rollout_tv_get_slot.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ROLLOUT_TV_SYMBOLS:
             getattr(L, name).restype = C.c_int
+    if has_rollout_tv_est(L):
+        L.mpcqp_mpc_loop_tv_est.argtypes = [H, C.c_int, C.POINTER(Loop), C.POINTER(ModelTraj), C.POINTER(EstTraj)]
+        L.mpcqp_rollout_tv_est.argtypes = [H, C.c_int, C.POINTER(Loop), C.POINTER(ModelTraj), C.POINTER(EstTraj)]
+        L.mpcqp_rollout_tv_est_tape_bytes.argtypes = [H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        L.mpcqp_rollout_adjoint_tv_est.argtypes = [H, C.POINTER(RolloutAdjointIO), C.POINTER(RolloutEstIO), C.POINTER(AdjointModelIO), C.POINTER(AdjointBoundsIO),
+                                                   C.POINTER(RolloutTVIO), C.POINTER(RolloutTVEstIO)]
+        L.mpcqp_rollout_tv_est_get_gain.argtypes = [H, C.c_int, C.c_void_p]
+        for name in ROLLOUT_TV_EST_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     if has_riccati(L):
         L.mpcqp_riccati_default_settings.argtypes = [C.POINTER(RiccatiSettings)]
         L.mpcqp_riccati_default_settings.restype = None
@@ -329,6 +353,11 @@ def has_adjoint_bounds(L=None):
 def has_rollout_tv(L=None):
     """True if the library exports include_ext/mpcqp_rollout_tv.h."""
     return _has(L, ROLLOUT_TV_SYMBOLS)
+
+
+def has_rollout_tv_est(L=None):
+    """True if the library exports include_ext2/mpcqp_rollout_tv_est.h."""
+    return _has(L, ROLLOUT_TV_EST_SYMBOLS)
 
 
 def has_riccati(L=None):

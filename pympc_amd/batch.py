@@ -184,7 +184,7 @@ class BatchMPCController:
         self._u_last = None
         return uMPC
 
-    def run(self, nsteps, w=None, Ap=None, Bp=None, xref_traj=None, estimator=None, model_traj=None):
+    def run(self, nsteps, w=None, Ap=None, Bp=None, xref_traj=None, estimator=None, model_traj=None, L_traj=None):
         """``nsteps`` closed-loop steps on the device, equivalent to
         ``for k in range(nsteps): u = K.output(); x = Ap @ x + Bp @ u + w[k]; K.update(x, u, xref_traj[k])``
         (the loop of examples/example_point_mass.py:88-101 with a linear plant; default plant = (Ad, Bd)), or, with
@@ -193,23 +193,40 @@ class BatchMPCController:
         ``estimator.v`` [nsteps,B,ny] (optional) and the true plant state ``estimator.x_true`` [B,nx], advanced in place.
         ``model_traj = (Ad [nmodels,B,nx,nx] or None, Bd [nmodels,B,nx,nu] or None, hold)``: a schedule of models -- entry ``k // hold`` replaces
         Ad / Bd at the start of step k (mpcqp_mpc_loop_tv: ``update_model`` between closed-loop launches, no host round trip); the controller is
-        left with the last entry used.  Not with an estimator.
+        left with the last entry used.  With an estimator too (mpcqp_mpc_loop_tv_est, include_ext2/mpcqp_rollout_tv_est.h): the estimator steps
+        under the entry in force, and ``L_traj`` [nentries,B,nx,ny] schedules its gain the same way (entry ``k // hold`` at step k; None: the
+        estimator's own ``L`` throughout); the estimator object is left with the last estimate and, where scheduled, the last gain.
         Returns ``dict(x=[nsteps+1,B,nx], u=[nsteps,B,nu], status=[nsteps,B] (OSQP status values), iter=[nsteps,B])``
         plus ``xhat`` and ``y`` with an estimator."""
+        if L_traj is not None and (estimator is None or model_traj is None):
+            raise ValueError('run: L_traj schedules the gain of an estimator beside a model_traj: give both')
+        if estimator is not None and model_traj is not None:
+            out = self.prob.mpc_run_tv_est(nsteps, model_traj, _est_dict(estimator), L_traj=L_traj, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
+            self.solve_count += int(nsteps)               # (a library without the call has raised: the controller is not moved on)
+            self._after_schedule(nsteps, model_traj, estimator, L_traj)
+            return self._after_loop(out, xref_traj, estimator)
         self.solve_count += int(nsteps)
         out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=_est_dict(estimator), model_traj=model_traj)
         if model_traj is not None:
             self._after_schedule(nsteps, model_traj)
         return self._after_loop(out, xref_traj, estimator)
 
-    def _after_schedule(self, nsteps, model_traj):
-        """The controller's Ad, Bd after a loop under a schedule: the last entry used."""
+    def _after_schedule(self, nsteps, model_traj, estimator=None, L_traj=None):
+        """The controller's Ad, Bd after a loop under a schedule: the last entry used.  With an estimator: its model is that entry too, and its
+        gain the last entry of ``L_traj`` where there is one."""
         last = (int(nsteps) - 1) // int(model_traj[2])
         host = lambda a: np.array(a[last].detach().cpu() if hasattr(a, 'data_ptr') else a[last], dtype=float).reshape((self.B,) + tuple(a.shape[-2:]))
         if model_traj[0] is not None:
             self.Ad = host(model_traj[0])
         if model_traj[1] is not None:
             self.Bd = host(model_traj[1])
+        if estimator is not None:
+            if model_traj[0] is not None:
+                estimator.A = self.Ad.copy()
+            if model_traj[1] is not None:
+                estimator.Bm = self.Bd.copy()
+            if L_traj is not None:
+                estimator.L = host(L_traj)
 
     def _after_loop(self, out, xref_traj, estimator=None, count=0):
         """The controller's books after a device loop of any kind, and its result dict: the controller stands at the last state (with an
@@ -247,6 +264,17 @@ class BatchMPCController:
         self._after_schedule(nsteps, model_traj)
         return self._after_loop(out, xref_traj, count=int(nsteps))
 
+    def rollout_tv_est(self, nsteps, model_traj, estimator, L_traj=None, w=None, Ap=None, Bp=None, xref_traj=None):
+        """``run(estimator=, model_traj=, L_traj=)`` that keeps a tape (mpcqp_rollout_tv_est, include_ext2/mpcqp_rollout_tv_est.h): the same
+        output-feedback loop under the same schedule of models and, optionally, gains, the same dict, the controller left with the last entry
+        used, the estimator object with the last estimate and, where scheduled, the last gain -- and a tape from which ``rollout_adjoint``
+        differentiates a loss on states, estimates, inputs and measurements with respect to every schedule entry through its three paths:
+        its solves ('Ad_traj', 'Bd_traj'), the plant ('Ap_traj', 'Bp_traj') and the estimator ('Ae_traj', 'Be_traj'), and to every gain
+        entry ('L_traj')."""
+        out = self.prob.rollout_tv_est(nsteps, model_traj, _est_dict(estimator), L_traj=L_traj, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
+        self._after_schedule(nsteps, model_traj, estimator, L_traj)
+        return self._after_loop(out, xref_traj, estimator, count=int(nsteps))
+
     def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None):
         """``run(estimator=...)`` that keeps a tape (mpcqp_rollout_est, include/mpcqp_rollout_est.h): the output-feedback loop with a
         ``BatchLinearStateEstimator`` -- the same dict (``x, u, status, iter, xhat, y``), ``estimator.x_true`` advanced in place -- and afterwards
@@ -266,7 +294,9 @@ class BatchMPCController:
         'C' [B,ny,nx], 'L' [B,nx,ny], 'v' [K,B,ny] and 'Ae' [B,nx,nx], 'Be' [B,nx,nu], the estimator path alone (add them to 'Ad', 'Bd').
         After ``rollout_tv``: ``want`` may name 'Ad_traj' [nseg,B,nx,nx], 'Bd_traj' [nseg,B,nx,nu] (entry e: through the solves made under
         schedule entry e) and 'Ap_traj', 'Bp_traj' (entry e: through the plant while entry e was in force; where the plant followed the
-        schedule, add them); 'Ad', 'Bd' are then the share of the model the rollout began with."""
+        schedule, add them); 'Ad', 'Bd' are then the share of the model the rollout began with.
+        After ``rollout_tv_est``: all of both, and 'Ae_traj' [nseg,B,nx,nx], 'Be_traj' [nseg,B,nx,nu], 'L_traj' [nseg,B,nx,ny] (entry e: through
+        the estimator while entry e was in force); 'Ae', 'Be', 'L' are their sums over the entries."""
         res = self.prob.rollout_adjoint(g_x=g_x, g_u=g_u, want=want, batch_sum=batch_sum, no_reuse=no_reuse, g_xhat=g_xhat, g_y=g_y)
         _, n_weak, status, n_factor = self.prob.rollout_info()
         res.update(n_weak=n_weak, status=status, n_factor=n_factor)

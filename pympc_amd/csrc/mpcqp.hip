@@ -51,6 +51,7 @@
 #include "../../include/mpcqp_rollout.h"
 #include "../../include/mpcqp_rollout_est.h"
 #include "../../include_ext/mpcqp_rollout_tv.h"
+#include "../../include_ext2/mpcqp_rollout_tv_est.h"
 #include "../../include/mpcqp_adjoint_bounds.h"
 
 #include "mpcqp_defs.h"
@@ -155,6 +156,7 @@ struct mpcqp_handle : Plan {       // the plan (mpcqp_plan.h: ncu, batch, L, lds
     RolloutTape tape = {}; void *tape_buf = nullptr; size_t tape_bytes = 0;      // mpcqp_rollout (include/mpcqp_rollout.h): the tape, one device block (null until the first rollout)
     int tape_ny = 0;                                           // > 0: the tape is one of the output-feedback loop (mpcqp_rollout_est, include/mpcqp_rollout_est.h)
     RolloutSlots tape_slots = {};                              // nslots > 0: the tape is one of the loop under a model schedule (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h) and carries its models
+    RolloutGains tape_gains = {};                              // Lg non-null: the tape is one of the output-feedback loop under a schedule (mpcqp_rollout_tv_est, include_ext2/mpcqp_rollout_tv_est.h): nslots > 0 and tape_ny > 0 both
     int tape_xref_rows = 1; bool tape_valid = false;           // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
     bool has_solve = false;              // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
@@ -1332,18 +1334,31 @@ static mpcqp_loop loop_at(const mpcqp_handle *h, const mpcqp_loop *io, size_t k0
     }
     return seg;
 }
+// The refusals a schedule adds to a loop's, in mpcqp_mpc_loop_tv's order.  est: the call is one of include_ext2/mpcqp_rollout_tv_est.h (an
+// estimator is expected, et: its gain schedule or null); otherwise an estimator is refused.  Sets *nseg.
+static int schedule_check(const std::string &what, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt, bool est, const mpcqp_est_traj *et, int *nseg) {
+    if (mt->struct_size != (int32_t)sizeof(mpcqp_model_traj)) return fail(MPCQP_ERR_ARG, what + ": struct_size is not sizeof(mpcqp_model_traj)");
+    if (mt->hold < 1) return fail(MPCQP_ERR_ARG, what + ": hold must be >= 1");
+    *nseg = (nsteps + mt->hold - 1) / mt->hold;
+    if (mt->nmodels < *nseg) return fail(MPCQP_ERR_ARG, what + ": fewer than ceil(nsteps / hold) model entries");
+    if (!mt->Ad && !mt->Bd) return fail(MPCQP_ERR_ARG, what + ": give Ad, Bd or both");
+    if (!est && io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, what + ": output feedback with a model schedule is " + what + "_est (include_ext2/mpcqp_rollout_tv_est.h)");
+    if (est && io->ny == 0) return fail(MPCQP_ERR_ARG, what + ": ny must be > 0 (without an estimator the call is the one without _est)");
+    if (et && et->struct_size != (int32_t)sizeof(mpcqp_est_traj)) return fail(MPCQP_ERR_ARG, what + ": struct_size is not sizeof(mpcqp_est_traj)");
+    if (et && et->nentries < *nseg) return fail(MPCQP_ERR_ARG, what + ": fewer than ceil(nsteps / hold) gain entries");
+    return MPCQP_OK;
+}
 // The device loop under a schedule of models (include/mpcqp_model.h): per entry, mpcqp_update_model and one closed-loop launch of the steps it holds for.
-extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt) {
-    if (!mt) return mpcqp_mpc_loop(h, nsteps, io);
-    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: bad argument");
-    if (mt->struct_size != (int32_t)sizeof(mpcqp_model_traj)) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: struct_size is not sizeof(mpcqp_model_traj)");
-    if (mt->hold < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: hold must be >= 1");
-    const int nseg = (nsteps + mt->hold - 1) / mt->hold;
-    if (mt->nmodels < nseg) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: fewer than ceil(nsteps / hold) model entries");
-    if (!mt->Ad && !mt->Bd) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: give Ad, Bd or both");
-    if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_mpc_loop_tv: output feedback with a model schedule is not implemented");
-    int rc = loop_check(h, nsteps, io);
+// et (mpcqp_mpc_loop_tv_est): the gain of entry s, where the schedule has gains, is the estimator's during segment s.
+static int loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in, const mpcqp_model_traj *mt, const std::string &what, bool est, const mpcqp_est_traj *et) {
+    int nseg = 0;
+    int rc = schedule_check(what, nsteps, io_in, mt, est, et, &nseg);
     if (rc) return rc;
+    const double *Lt = et ? et->Lgain_traj : nullptr;
+    mpcqp_loop first = *io_in;
+    if (Lt) first.Lgain = Lt;                       // (a gain schedule stands in for io->Lgain, which may then be null)
+    const mpcqp_loop *io = &first;
+    if ((rc = loop_check(h, nsteps, io))) return rc;
     const Lay &L = h->L;
     const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu;
     for (int s = 0; s < nseg; ++s) {
@@ -1352,10 +1367,21 @@ extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *
         if (mt->Ad) M.Ad = mt->Ad + (size_t)s * B * nx * nx;
         if (mt->Bd) M.Bd = mt->Bd + (size_t)s * B * nx * nu;
         if ((rc = mpcqp_update_model(h, &M))) return rc;
-        const mpcqp_loop seg = loop_at(h, io, k0);
+        mpcqp_loop seg = loop_at(h, io, k0);
+        if (Lt) seg.Lgain = Lt + (size_t)s * B * nx * (size_t)io->ny;
         if ((rc = loop_run(h, std::min(mt->hold, nsteps - (int)k0), &seg, s == nseg - 1))) return rc;
     }
     return MPCQP_OK;
+}
+extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt) {
+    if (!mt) return mpcqp_mpc_loop(h, nsteps, io);
+    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv: bad argument");
+    return loop_tv(h, nsteps, io, mt, "mpcqp_mpc_loop_tv", false, nullptr);
+}
+// The output-feedback loop under a schedule of models and, optionally, of observer gains (include_ext2/mpcqp_rollout_tv_est.h).
+extern "C" int mpcqp_mpc_loop_tv_est(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt, const mpcqp_est_traj *et) {
+    if (!h || !io || !mt || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv_est: bad argument");
+    return loop_tv(h, nsteps, io, mt, "mpcqp_mpc_loop_tv_est", true, et);
 }
 
 // ---- a rollout with a tape and its reverse sweep (include/mpcqp_rollout.h, mpcqp_rollout.h) ------------------------------------
@@ -1363,7 +1389,9 @@ extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *
 // base null: sizes only.  Returns the bytes of the block.
 // ny > 0: a tape of the output-feedback loop -- the plant states, measurements, C, L and the estimator's seeds and gradients behind the rest.
 // nslots > 0: a tape of the loop under a model schedule -- the model slots and their gradients behind the rest (V).
-static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int ny, char *base, RolloutTape *T, int nslots = 0, int hold = 0, RolloutSlots *V = nullptr) {
+// both: the gain of every schedule entry and the estimator path's per-entry gradients behind those (X).
+static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int ny, char *base, RolloutTape *T, int nslots = 0, int hold = 0, RolloutSlots *V = nullptr,
+                         RolloutGains *X = nullptr) {
     const size_t B = (size_t)batch, K = (size_t)nsteps, nx = L.nx, nu = L.nu, xw = (size_t)xref_rows * nx, db = sizeof(double);
     size_t off = 0;
     auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~size_t(255); return q; };
@@ -1395,8 +1423,15 @@ static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int
         v.dAd = (double *)take(S * B * nx * nx * db); v.dBd = (double *)take(S * B * nx * nu * db);
         v.dAp = (double *)take((S - 1) * B * nx * nx * db); v.dBp = (double *)take((S - 1) * B * nx * nu * db);
     }
+    RolloutGains x; memset(&x, 0, sizeof(x));
+    if (nslots > 0 && ny > 0) {
+        const size_t S1 = (size_t)nslots - 1, q = (size_t)ny;
+        x.Lg = (double *)take(S1 * B * nx * q * db); x.dL = (double *)take(S1 * B * nx * q * db);
+        x.dAe = (double *)take(S1 * B * nx * nx * db); x.dBe = (double *)take(S1 * B * nx * nu * db);
+    }
     if (T) *T = t;
     if (V) *V = v;
+    if (X) *X = x;
     return off;
 }
 extern "C" int mpcqp_rollout_tape_bytes(mpcqp_handle *h, int nsteps, int64_t *bytes) {
@@ -1409,7 +1444,7 @@ extern "C" int mpcqp_rollout_release(mpcqp_handle *h) {
     HIPCHK(hipSetDevice(h->device));
     if (h->tape_buf) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->tape_buf); }
     h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_valid = false; h->tape_ny = 0;
-    memset(&h->tape, 0, sizeof(h->tape)); memset(&h->tape_slots, 0, sizeof(h->tape_slots));
+    memset(&h->tape, 0, sizeof(h->tape)); memset(&h->tape_slots, 0, sizeof(h->tape_slots)); memset(&h->tape_gains, 0, sizeof(h->tape_gains));
     return MPCQP_OK;
 }
 // What the calls that read the tape back refuse: no tape, for the estimator's part a tape without one, an entry k (null: the call takes none) out of range.
@@ -1424,19 +1459,18 @@ static int tape_guard(const mpcqp_handle *h, const std::string &fn, bool est, co
 // the plant and x_true are read from the tape's copies, and x_k, x_{k+1}, y_k are written straight onto the tape (x_traj, y_traj of the step).
 // mt (mpcqp_rollout_tv): the loop is mpcqp_mpc_loop_tv's -- at a boundary step the tape's copy, then mpcqp_update_model with the entry, then a
 // copy of what the handle holds now (model blob, D, E, c) into the entry's slot, then the step; slot 0 is what it held when the call began.
-static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const std::string &what, const mpcqp_model_traj *mt = nullptr) {
-    int nseg = 0;
-    if (mt) {                                       // (the refusals of mpcqp_mpc_loop_tv, in its order)
-        if (mt->struct_size != (int32_t)sizeof(mpcqp_model_traj)) return fail(MPCQP_ERR_ARG, what + ": struct_size is not sizeof(mpcqp_model_traj)");
-        if (mt->hold < 1) return fail(MPCQP_ERR_ARG, what + ": hold must be >= 1");
-        nseg = (nsteps + mt->hold - 1) / mt->hold;
-        if (mt->nmodels < nseg) return fail(MPCQP_ERR_ARG, what + ": fewer than ceil(nsteps / hold) model entries");
-        if (!mt->Ad && !mt->Bd) return fail(MPCQP_ERR_ARG, what + ": give Ad, Bd or both");
-        if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, what + ": output feedback with a model schedule is not implemented");
-    }
+// est (mpcqp_rollout_tv_est): both at once -- the tape keeps the gain of every entry too (et's, or io->Lgain over and over), and the step of
+// entry e runs with its gain.
+static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in, const std::string &what, const mpcqp_model_traj *mt = nullptr,
+                           bool est = false, const mpcqp_est_traj *et = nullptr) {
+    int nseg = 0, rc = 0;
+    if (mt && (rc = schedule_check(what, nsteps, io_in, mt, est, et, &nseg))) return rc;      // (the refusals of mpcqp_mpc_loop_tv, in its order)
     const int nslots = mt ? nseg + 1 : 0, hold = mt ? mt->hold : 0;
-    int rc = loop_check(h, nsteps, io);
-    if (rc) return rc;
+    const double *Lt = et ? et->Lgain_traj : nullptr;
+    mpcqp_loop first = *io_in;
+    if (Lt) first.Lgain = Lt;                       // (a gain schedule stands in for io->Lgain, which may then be null)
+    const mpcqp_loop *io = &first;
+    if ((rc = loop_check(h, nsteps, io))) return rc;
     if (!h->has_solve) return fail(MPCQP_ERR_STATE, what + ": no solve since the last setup, update, model update or warm start: the iterate does not belong to the step data of tape entry 0");
     if (io->xref_traj && io->xref_rows && io->xref_rows != h->L.xref_rows)
         return fail(MPCQP_ERR_UNSUPPORTED, what + ": xref_traj must have the reference shape of the last upload (the entries of a tape have one shape)");
@@ -1450,8 +1484,8 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, co
         h->tape_buf = q; h->tape_bytes = bytes;
     }
     h->tape_valid = false;
-    RolloutTape T; RolloutSlots V;
-    tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, (char *)h->tape_buf, &T, nslots, hold, &V);
+    RolloutTape T; RolloutSlots V; RolloutGains X;
+    tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, (char *)h->tape_buf, &T, nslots, hold, &V, &X);
     auto keep_slot = [&](int s) -> int {                   // what the handle holds now, as slot s
         const size_t sB = (size_t)s * B;
         HIPCHK(hipMemcpyAsync(const_cast<double *>(V.model) + sB * L.model_sz, h->P.model, B * L.model_sz * db, hipMemcpyDeviceToDevice, h->stream));
@@ -1469,9 +1503,11 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, co
         HIPCHK(hipMemcpyAsync(T.C, io->C, B * ny * nx * db, hipMemcpyDefault, h->stream));
         HIPCHK(hipMemcpyAsync(T.Lg, io->Lgain, B * nx * ny * db, hipMemcpyDefault, h->stream));
         HIPCHK(hipMemcpyAsync(T.xt, io->x_true, B * nx * db, hipMemcpyDefault, h->stream));
+        if (mt && Lt) HIPCHK(hipMemcpyAsync(const_cast<double *>(X.Lg), Lt, (size_t)nseg * B * nx * ny * db, hipMemcpyDefault, h->stream));
+        else if (mt) for (int e = 0; e < nseg; ++e) HIPCHK(hipMemcpyAsync(const_cast<double *>(X.Lg) + (size_t)e * B * nx * ny, T.Lg, B * nx * ny * db, hipMemcpyDeviceToDevice, h->stream));
     }
     HIPCHK(hipMemsetAsync(T.nact, 0, (3 * (size_t)nsteps * B + B) * sizeof(int), h->stream));      // (mpcqp_get_rollout_info before a sweep: all zero)
-    h->tape = T; h->tape_slots = V; h->tape_xref_rows = L.xref_rows; h->tape_ny = io->ny;
+    h->tape = T; h->tape_slots = V; h->tape_gains = X; h->tape_xref_rows = L.xref_rows; h->tape_ny = io->ny;
     const size_t per = (size_t)L.n + 2 * (size_t)L.m + L.step_sz + nu + 1;
     const unsigned grid = (unsigned)std::min<size_t>(1024, (B * per + 255) / 256);
     for (int k = 0; k < nsteps; ++k) {
@@ -1489,13 +1525,14 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, co
         if (ny) {                                   // (the estimator's loop reads and writes the tape's own copies)
             seg.Ap = T.Ap; seg.Bp = T.Bp; seg.C = T.C; seg.Lgain = T.Lg; seg.x_true = T.xt;
             seg.x_traj = T.xp + k0 * B * nx; seg.y_traj = T.ym + k0 * B * ny;
+            if (mt) seg.Lgain = X.Lg + (size_t)(k / hold) * B * nx * ny;
         }
         if ((rc = loop_run(h, 1, &seg, k == nsteps - 1))) return rc;
     }
     if (ny && (get(h, io->x_traj, T.xp, ((size_t)nsteps + 1) * B * nx * db) || get(h, io->y_traj, T.ym, (size_t)nsteps * B * ny * db) ||
                get(h, io->x_true, T.xt, B * nx * db))) return MPCQP_ERR_HIP;
     h->tape_valid = true;
-    return ny ? sync_unless_all_device(h, {io->x_traj, io->y_traj, io->x_true, io->C, io->Lgain, io->Ap, io->Bp}) : MPCQP_OK;
+    return ny ? sync_unless_all_device(h, {io->x_traj, io->y_traj, io->x_true, io->C, io->Lgain, io->Ap, io->Bp}) : MPCQP_OK;      // (io->Lgain: the gain schedule where there is one)
 }
 extern "C" int mpcqp_rollout(mpcqp_handle *h, int nsteps, const mpcqp_loop *io) {
     if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout: bad argument");
@@ -1525,6 +1562,29 @@ extern "C" int mpcqp_rollout_tv_get_slot(mpcqp_handle *h, int s, double *model, 
     const size_t B = (size_t)h->batch, sB = (size_t)s * B, db = sizeof(double);
     if (get(h, model, V.model + sB * L.model_sz, B * L.model_sz * db) || get(h, D, V.D + sB * L.n, B * L.n * db) ||
         get(h, E, V.E + sB * L.m, B * L.m * db) || get(h, c, V.c + sB, B * db)) return MPCQP_ERR_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+// ---- the taped rollout of the output-feedback loop under a model schedule (include_ext2/mpcqp_rollout_tv_est.h) --------------------------
+extern "C" int mpcqp_rollout_tv_est(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt, const mpcqp_est_traj *et) {
+    if (!h || !io || !mt || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tv_est: bad argument");
+    return rollout_forward(h, nsteps, io, "mpcqp_rollout_tv_est", mt, true, et);
+}
+extern "C" int mpcqp_rollout_tv_est_tape_bytes(mpcqp_handle *h, int nsteps, int hold, int ny, int64_t *bytes) {
+    if (!h || !bytes || nsteps < 1 || hold < 1 || ny < 1 || ny > 64) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tv_est_tape_bytes: bad argument");
+    *bytes = (int64_t)tape_carve(h->L, h->batch, nsteps, h->L.xref_rows, ny, nullptr, nullptr, (nsteps + hold - 1) / hold + 1, hold);
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_rollout_tv_est_get_gain(mpcqp_handle *h, int e, double *Lg) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    const int rc = tape_guard(h, "mpcqp_rollout_tv_est_get_gain", false, nullptr);
+    if (rc) return rc;
+    const RolloutGains &X = h->tape_gains;
+    if (!X.Lg) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_tv_est_get_gain: the tape is not one of mpcqp_rollout_tv_est (no gain entries)");
+    if (e < 0 || e >= h->tape_slots.nslots - 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_tv_est_get_gain: e must be in 0 .. nseg - 1");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t per = (size_t)h->batch * h->L.nx * (size_t)h->tape_ny;
+    if (get(h, Lg, X.Lg + (size_t)e * per, per * sizeof(double))) return MPCQP_ERR_HIP;
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
@@ -1559,9 +1619,14 @@ static int put_seed(mpcqp_handle *h, double *dst, const double *src, size_t byte
 // eo: the estimator's seeds and gradients (mpcqp_rollout_adjoint_est), or null.  est: the call is mpcqp_rollout_adjoint_est.
 // bo: the bound gradients (mpcqp_rollout_adjoint_bounds), or null.
 // tv: the call is mpcqp_rollout_adjoint_tv; to: its per-slot outputs, or null.
+// tve: the call is mpcqp_rollout_adjoint_tv_est (tv and est are set too); xo: its per-entry estimator outputs, or null.
 static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo, bool est,
-                         const mpcqp_adjoint_bounds_io *bo = nullptr, bool tv = false, const mpcqp_rollout_tv_io *to = nullptr) {
+                         const mpcqp_adjoint_bounds_io *bo = nullptr, bool tv = false, const mpcqp_rollout_tv_io *to = nullptr,
+                         bool tve = false, const mpcqp_rollout_tv_est_io *xo = nullptr) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
+    if (xo && xo->struct_size != (int32_t)sizeof(mpcqp_rollout_tv_est_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_tv_est: struct_size is not sizeof(mpcqp_rollout_tv_est_io)");
+    if (tve && eo && (eo->d_L || eo->d_Ae || eo->d_Be))
+        return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_tv_est: d_L, d_Ae, d_Be are per entry under a schedule: ask for them in mpcqp_rollout_tv_est_io");
     if (to && to->struct_size != (int32_t)sizeof(mpcqp_rollout_tv_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_tv: struct_size is not sizeof(mpcqp_rollout_tv_io)");
     if (tv && (io->d_Ap || io->d_Bp || (mo && (mo->d_Ad || mo->d_Bd))))
         return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_tv: d_Ap, d_Bp, d_Ad, d_Bd are per slot under a schedule: ask for them in mpcqp_rollout_tv_io");
@@ -1585,6 +1650,9 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the handle holds no tape (call mpcqp_rollout first)");
     if (!h->tape_valid) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the model or the scaling the tape was made under has been replaced (mpcqp_setup*, mpcqp_update_model, mpcqp_update_vectors with l, u) or its rollout failed: roll out again");
     const RolloutSlots &V = h->tape_slots;
+    const RolloutGains &X = h->tape_gains;
+    if (!tve && X.Lg) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the tape is one of mpcqp_rollout_tv_est (an estimator under a model schedule); use mpcqp_rollout_adjoint_tv_est");
+    if (tve && !X.Lg) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_tv_est: the tape is not one of mpcqp_rollout_tv_est; use the sweep of the call that made it");
     if (!tv && V.nslots > 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the tape is one of mpcqp_rollout_tv (a model schedule); use mpcqp_rollout_adjoint_tv");
     if (tv && V.nslots < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_tv: the tape is not one of mpcqp_rollout_tv (no model schedule); use mpcqp_rollout_adjoint");
     if (est && h->tape_ny == 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_est: the tape is one of mpcqp_rollout (no estimator); use mpcqp_rollout_adjoint");
@@ -1609,7 +1677,12 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     const size_t with_carry = v.smem + db * (size_t)rollout_carry_doubles(G, (int)ny);
     W.carry_lds = with_carry <= 160 * 1024 ? 1 : 0;         // (lam, mu, g behind the common block, or in the tape's few doubles of global memory)
     const size_t smem = W.carry_lds ? with_carry : v.smem;
-    if (tv) {
+    if (tve) {
+        DISPATCH_NB(G.NB, {
+            if (set_smem(k_rollout_adjoint_tv_est<NB>, smem)) return MPCQP_ERR_HIP;
+            hipLaunchKernelGGL(k_rollout_adjoint_tv_est<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W, V, X);
+        });
+    } else if (tv) {
         DISPATCH_NB(G.NB, {
             if (set_smem(k_rollout_adjoint_tv<NB>, smem)) return MPCQP_ERR_HIP;
             hipLaunchKernelGGL(k_rollout_adjoint_tv<NB>, dim3(h->batch), dim3(NT), smem, h->stream, G, v.P, Q, T, W, V);
@@ -1627,6 +1700,11 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
         if (get(h, to->d_Ad_slots, V.dAd, S * B * nx * nx * db) || get(h, to->d_Bd_slots, V.dBd, S * B * nx * nu * db) ||
             get(h, to->d_Ap_entries, V.dAp, (S - 1) * B * nx * nx * db) || get(h, to->d_Bp_entries, V.dBp, (S - 1) * B * nx * nu * db)) return MPCQP_ERR_HIP;
     }
+    if (tve && xo) {
+        const size_t S1 = (size_t)V.nslots - 1;
+        if (get(h, xo->d_Ae_entries, X.dAe, S1 * B * nx * nx * db) || get(h, xo->d_Be_entries, X.dBe, S1 * B * nx * nu * db) ||
+            get(h, xo->d_L_entries, X.dL, S1 * B * nx * ny * db)) return MPCQP_ERR_HIP;
+    }
     const size_t xw = (size_t)G.xref_rows * nx;
     if (get(h, io->lam, T.lam, (K + 1) * B * nx * db) || get(h, io->d_uminus1, T.dum1, B * nu * db) || get(h, io->d_uref, T.duref, B * nu * db) ||
         get(h, io->d_xref, T.dxref, K * B * xw * db) || get(h, io->d_Ap, T.dAp, B * nx * nx * db) || get(h, io->d_Bp, T.dBp, B * nx * nu * db)) return MPCQP_ERR_HIP;
@@ -1641,11 +1719,16 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     return sync_unless_all_device(h, {io->G_x, io->G_u, io->lam, io->d_uminus1, io->d_uref, io->d_xref, io->d_Ap, io->d_Bp,
                                       eo ? eo->G_xhat : nullptr, eo ? eo->G_y : nullptr, eo ? eo->eta : nullptr, eo ? eo->d_C : nullptr, eo ? eo->d_L : nullptr,
                                       eo ? eo->d_v : nullptr, eo ? eo->d_Ae : nullptr, eo ? eo->d_Be : nullptr,
-                                      to ? to->d_Ad_slots : nullptr, to ? to->d_Bd_slots : nullptr, to ? to->d_Ap_entries : nullptr, to ? to->d_Bp_entries : nullptr}, &m);
+                                      to ? to->d_Ad_slots : nullptr, to ? to->d_Bd_slots : nullptr, to ? to->d_Ap_entries : nullptr, to ? to->d_Bp_entries : nullptr,
+                                      xo ? xo->d_Ae_entries : nullptr, xo ? xo->d_Be_entries : nullptr, xo ? xo->d_L_entries : nullptr}, &m);
 }
 extern "C" int mpcqp_rollout_adjoint_tv(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo,
                                         const mpcqp_adjoint_bounds_io *bo, const mpcqp_rollout_tv_io *to) {
     return rollout_sweep(h, io, nullptr, mo, false, bo, true, to);
+}
+extern "C" int mpcqp_rollout_adjoint_tv_est(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo,
+                                            const mpcqp_adjoint_bounds_io *bo, const mpcqp_rollout_tv_io *to, const mpcqp_rollout_tv_est_io *xo) {
+    return rollout_sweep(h, io, eo, mo, true, bo, true, to, true, xo);
 }
 extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
     return rollout_sweep(h, io, nullptr, mo, false);

@@ -24,6 +24,10 @@
 //             xh_k and the tape holds the plant state x_k, the measurement y_k, C and L beside it.  The step prologue then carries eta
 //             (the gradient at xh) beside lam and forms s = Ad' eta, t = L' s, r = G_y + t in three more barrier-separated phases; the
 //             step's d_x0 lands on eta instead of lam.  EST = false compiles to the code without any of it.
+//   both      EST and TV (k_rollout_adjoint_tv_est<NB>, include_ext2/mpcqp_rollout_tv_est.h): the output-feedback loop ran under a schedule of
+//             models and, where given, of observer gains.  The estimator stepped under the slot in force, pi(k) = 1 + k / hold, so its phases
+//             read Ad, Bd of that slot's blob from global memory (S.hot holds the solve's slot sigma(k), another one at every boundary step)
+//             and the gain of entry k / hold (RolloutGains); d_Ae, d_Be, d_L are re-aimed per entry as the plant's d_Ap, d_Bp are.
 // Every sum over the steps is formed by the thread that owns the entry, in the order K-1 .. 0: no atomics, the same bits every time.
 #pragma once
 
@@ -69,6 +73,12 @@ struct RolloutSlots {
     double *dAp, *dBp;                    // [nslots - 1][batch][nx nx], [..][nx nu] the plant path of the steps schedule entry e was in force
     int hold, nslots;
 };
+// The observer gains of a scheduled output-feedback tape (mpcqp_rollout_tv_est, include_ext2/mpcqp_rollout_tv_est.h) and the estimator path's
+// per-entry sums.  An argument of k_rollout_adjoint_tv_est alone: the other three sweeps neither take nor read it.
+struct RolloutGains {
+    const double *Lg;                     // [nslots - 1][batch][nx ny] the gain of schedule entry e
+    double *dAe, *dBe, *dL;               // [nslots - 1][batch][nx nx], [..][nx nu], [..][nx ny] the steps schedule entry e was in force
+};
 
 // lam | lam as the plant alone gives it | d_x0 of the step | g | mu | d_uref of the step | d_uref so far
 // with an estimator (ny > 0), behind them: eta | eta before d_x0 | s | xhat[k|k] | t | r | innovation
@@ -99,8 +109,8 @@ __global__ __launch_bounds__(256) void k_rollout_tape(Lay L, Ptrs P, RolloutTape
 // name and the one template argument it had (the build's resource remarks are read by that name, tests/test_rollout_resources.py), and is the
 // EST = false instantiation; k_rollout_adjoint_est<NB> is the EST = true one.
 template <int NB, bool EST, bool TV>
-__device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P, const AdjointArgs &Q, const RolloutTape &T, const RolloutSweep &W, const RolloutSlots &V) {
-    static_assert(!(EST && TV), "a schedule together with an estimator is not a loop the library runs");
+__device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P, const AdjointArgs &Q, const RolloutTape &T, const RolloutSweep &W, const RolloutSlots &V,
+                                                     const RolloutGains &X) {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     double *p = sh; Smem S; smem_common(L, P, p, S);       // (P.perm is null: workgroup b works on instance b)
     const int b = blockIdx.x, tid = threadIdx.x, B = T.batch, K = T.nsteps;
@@ -109,9 +119,9 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
     double *lam = W.carry_lds ? p : T.carry + (size_t)b * rollout_carry_doubles(L, ny);
     double *lamn = lam + nx, *dx0 = lamn + nx, *g = dx0 + nx, *mu = g + nu, *durk = mu + nu, *dur = durk + nu;
     double *eta = dur + nu, *etan = eta + nx, *sv_e = etan + nx, *xu = sv_e + nx, *tv = xu + nx, *rv = tv + ny, *inn = rv + ny;      // (EST only)
-    const double *Cm = EST ? T.C + (size_t)b * ny * nx : nullptr, *Lg = EST ? T.Lg + (size_t)b * nx * ny : nullptr;
-    double *dC = EST ? T.dC + (size_t)b * ny * nx : nullptr, *dL = EST ? T.dL + (size_t)b * nx * ny : nullptr;
-    double *dAe = EST ? T.dAe + (size_t)b * nx * nx : nullptr, *dBe = EST ? T.dBe + (size_t)b * nx * nu : nullptr;
+    const double *Cm = EST ? T.C + (size_t)b * ny * nx : nullptr, *Lg = EST && !TV ? T.Lg + (size_t)b * nx * ny : nullptr;
+    double *dC = EST ? T.dC + (size_t)b * ny * nx : nullptr, *dL = EST && !TV ? T.dL + (size_t)b * nx * ny : nullptr;      // (EST and TV: Lg, dL, dAe, dBe are
+    double *dAe = EST && !TV ? T.dAe + (size_t)b * nx * nx : nullptr, *dBe = EST && !TV ? T.dBe + (size_t)b * nx * nu : nullptr;      // aimed at the schedule entry in force inside the loop)
     const double *model = P.model + (size_t)b * L.model_sz;
     const double *D = P.D + (size_t)b * L.n, *E = P.E + (size_t)b * L.m;
     double cc = TV ? 0.0 : P.c[b];                        // (TV: all four are aimed at the entry's slot inside the loop)
@@ -151,9 +161,19 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
     for (int e = tid; e < nx * nu; e += NT) dBp[e] = 0.0;
     if (EST) {                                           // eta_K = G_xh[K]
         for (int i = tid; i < nx; i += NT) { const double v = T.gxh[((size_t)K * B + b) * nx + i]; eta[i] = v; T.eta[((size_t)K * B + b) * nx + i] = v; }
-        for (int e = tid; e < nx * nx; e += NT) dAe[e] = 0.0;
-        for (int e = tid; e < nx * nu; e += NT) dBe[e] = 0.0;
-        for (int e = tid; e < nx * ny; e += NT) { dC[e] = 0.0; dL[e] = 0.0; }
+        if constexpr (TV) {
+            for (int s = 0; s + 1 < V.nslots; ++s) {
+                const size_t sb = (size_t)s * B + b;
+                for (int e = tid; e < nx * nx; e += NT) X.dAe[sb * nx * nx + e] = 0.0;
+                for (int e = tid; e < nx * nu; e += NT) X.dBe[sb * nx * nu + e] = 0.0;
+                for (int e = tid; e < nx * ny; e += NT) X.dL[sb * nx * ny + e] = 0.0;
+            }
+            for (int e = tid; e < nx * ny; e += NT) dC[e] = 0.0;
+        } else {
+            for (int e = tid; e < nx * nx; e += NT) dAe[e] = 0.0;
+            for (int e = tid; e < nx * nu; e += NT) dBe[e] = 0.0;
+            for (int e = tid; e < nx * ny; e += NT) { dC[e] = 0.0; dL[e] = 0.0; }
+        }
     }
     if constexpr (!TV) for (int j = tid; j < L.n; j += NT) sv[j] = delta / (D[j] * D[j]);
     __syncthreads();
@@ -180,10 +200,15 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
             double *dApk = TV ? V.dAp + ((size_t)(k / V.hold) * B + b) * nx * nx : dAp, *dBpk = TV ? V.dBp + ((size_t)(k / V.hold) * B + b) * nx * nu : dBp;
             const double *uk = T.u + kb * nu;
             const double *xk = EST ? T.xp + kb * nx : S.x0s;      // (the plant state; with an estimator the entry's x0 is the estimate)
+            const double *estm = TV ? inforce : S.hot;            // (EST: the model the estimator stepped under, the slot in force)
+            if constexpr (EST && TV) {                            // the gain and the estimator path's sums of the schedule entry in force
+                const size_t eb = (size_t)(k / V.hold) * B + b;
+                Lg = X.Lg + eb * nx * ny; dL = X.dL + eb * nx * ny; dAe = X.dAe + eb * nx * nx; dBe = X.dBe + eb * nx * nu;
+            }
             for (int j = tid; j < nu; j += NT) {
                 double a = T.gu[kb * nu + j] + mu[j];
                 for (int i = 0; i < nx; ++i) a += Bp[i * nu + j] * lam[i];
-                if (EST) { const double *Bd = S.hot + L.oBd; for (int i = 0; i < nx; ++i) a += Bd[i * nu + j] * eta[i]; }
+                if (EST) { const double *Bd = estm + L.oBd; for (int i = 0; i < nx; ++i) a += Bd[i * nu + j] * eta[i]; }
                 g[j] = a;
             }
             for (int i = tid; i < nx; i += NT) {
@@ -195,7 +220,7 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
             for (int e = tid; e < nx * nu; e += NT) { const int r = e / nu; dBpk[e] += lam[r] * uk[e - r * nu]; }
             if (EST) {
                 // s = Ad' eta_{k+1};  d_Be += eta_{k+1} u_k'
-                const double *Ad = S.hot + L.oAd, *yk = T.ym + kb * ny;
+                const double *Ad = estm + L.oAd, *yk = T.ym + kb * ny;
                 for (int i = tid; i < nx; i += NT) {
                     double a = 0.0;
                     for (int r = 0; r < nx; ++r) a += Ad[r * nx + i] * eta[r];
@@ -293,10 +318,13 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
 }
 
 template <int NB>
-__global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, false, false>(L, P, Q, T, W, RolloutSlots{}); }
+__global__ __launch_bounds__(NT) void k_rollout_adjoint(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, false, false>(L, P, Q, T, W, RolloutSlots{}, RolloutGains{}); }
 // the same sweep over a tape of the output-feedback loop (mpcqp_rollout_est)
 template <int NB>
-__global__ __launch_bounds__(NT) void k_rollout_adjoint_est(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, true, false>(L, P, Q, T, W, RolloutSlots{}); }
+__global__ __launch_bounds__(NT) void k_rollout_adjoint_est(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W) { rollout_adjoint_body<NB, true, false>(L, P, Q, T, W, RolloutSlots{}, RolloutGains{}); }
 // the same sweep over a tape of the loop under a model schedule (mpcqp_rollout_tv)
 template <int NB>
-__global__ __launch_bounds__(NT) void k_rollout_adjoint_tv(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W, RolloutSlots V) { rollout_adjoint_body<NB, false, true>(L, P, Q, T, W, V); }
+__global__ __launch_bounds__(NT) void k_rollout_adjoint_tv(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W, RolloutSlots V) { rollout_adjoint_body<NB, false, true>(L, P, Q, T, W, V, RolloutGains{}); }
+// the same sweep over a tape of the output-feedback loop under a model schedule (mpcqp_rollout_tv_est)
+template <int NB>
+__global__ __launch_bounds__(NT) void k_rollout_adjoint_tv_est(Lay L, Ptrs P, AdjointArgs Q, RolloutTape T, RolloutSweep W, RolloutSlots V, RolloutGains X) { rollout_adjoint_body<NB, true, true>(L, P, Q, T, W, V, X); }

@@ -37,6 +37,7 @@ _FEATURES = dict(
     rollout=(_lib.has_rollout, 'no taped rollout (include/mpcqp_rollout.h)'),
     rollout_est=(_lib.has_rollout_est, 'no taped output-feedback rollout (include/mpcqp_rollout_est.h)'),
     rollout_tv=(_lib.has_rollout_tv, 'no taped rollout under a model schedule (include_ext/mpcqp_rollout_tv.h)'),
+    rollout_tv_est=(_lib.has_rollout_tv_est, 'no output-feedback loop under a model schedule (include_ext2/mpcqp_rollout_tv_est.h)'),
     model_update=(_lib.has_model_update, 'no in-place model update (include/mpcqp_model.h)'),
     model_traj=(_lib.has_model_update, 'no model schedule for the device loop (include/mpcqp_model.h)'))
 
@@ -435,6 +436,46 @@ class BatchProblem:
         self.rollout_count += 1
         return res
 
+    def mpc_run_tv_est(self, nsteps, model_traj, estimator, L_traj=None, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
+        """``mpc_run`` with an estimator AND a model schedule (mpcqp_mpc_loop_tv_est, include_ext2/mpcqp_rollout_tv_est.h): the output-feedback
+        loop in which entry ``k // hold`` of ``model_traj`` replaces Ad / Bd at the start of step k -- for the controller, the estimator and,
+        without ``Ap``/``Bp``, the plant -- and, with ``L_traj`` [nentries, B, nx, ny], entry ``k // hold`` of it is the observer gain of step k
+        (``estimator['L']`` may then be None).  Results as ``mpc_run`` with an estimator."""
+        self._need('rollout_tv_est')
+        if model_traj is None or estimator is None:
+            raise ValueError('mpc_run_tv_est: a model_traj = (Ad, Bd, hold) and an estimator dict(C=, L=, x_true=, v=) are both needed')
+        return self._loop('mpcqp_mpc_loop_tv_est', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj, L_traj=L_traj)
+
+    def rollout_tv_est(self, nsteps, model_traj, estimator, L_traj=None, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
+        """``mpc_run_tv_est`` that keeps a tape (mpcqp_rollout_tv_est): the same arguments and results, one closed-loop launch per step, and a
+        tape with the model slots of ``rollout_tv``, the plant states and measurements of ``rollout_est`` and the gain of every entry.
+        Afterwards ``rollout_adjoint`` differentiates the loop through controller, plant and estimator, entry by entry."""
+        self._need('rollout_tv_est')
+        if model_traj is None or estimator is None:
+            raise ValueError('rollout_tv_est: a model_traj = (Ad, Bd, hold) and an estimator dict(C=, L=, x_true=, v=) are both needed')
+        res = self._loop('mpcqp_rollout_tv_est', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj, L_traj=L_traj)
+        hold = int(model_traj[2])
+        self._rollout_shape = (int(nsteps), self._xref_rows_last)
+        self._rollout_ny = int(tuple(estimator['C'].shape)[-2])
+        self._rollout_tv = (hold, (int(nsteps) + hold - 1) // hold, model_traj[0] is not None, model_traj[1] is not None)
+        self.rollout_count += 1
+        return res
+
+    def rollout_tv_est_tape_bytes(self, nsteps, hold, ny):
+        """Device memory the tape of ``rollout_tv_est`` takes (mpcqp_rollout_tv_est_tape_bytes)."""
+        self._need('rollout_tv_est')
+        v = C.c_int64()
+        _lib.check(self._L.mpcqp_rollout_tv_est_tape_bytes(self._h, int(nsteps), int(hold), int(ny), C.byref(v)), 'mpcqp_rollout_tv_est_tape_bytes')
+        return v.value
+
+    def rollout_tv_est_gain(self, e):
+        """The observer gain of schedule entry e on the tape of a ``rollout_tv_est`` as the sweep reads it [B, nx, ny]
+        (mpcqp_rollout_tv_est_get_gain; verification)."""
+        self._need('rollout_tv_est')
+        Lg = np.empty((self.batch, self.nx, max(self._rollout_ny, 1)))
+        _lib.check(self._L.mpcqp_rollout_tv_est_get_gain(self._h, int(e), _ptr(Lg)), 'mpcqp_rollout_tv_est_get_gain')
+        return Lg
+
     def rollout_tv_tape_bytes(self, nsteps, hold):
         """Device memory the tape of ``nsteps`` steps under a schedule with this ``hold`` takes (mpcqp_rollout_tv_tape_bytes)."""
         self._need('rollout_tv')
@@ -485,16 +526,22 @@ class BatchProblem:
         entry e: the solve path of the solves made under schedule entry e -- and 'Ap_traj', 'Bp_traj' of the same shapes: the plant path of
         the steps entry e was in force.  'Ad', 'Bd' are then the solve path of the model the call began with, plus that of all entries for a
         matrix the schedule did not give (it never changed); 'Ap', 'Bp' the sum over the entries.  ``batch_sum`` sums these over the
-        instances too ([nseg, 1, ..] and [1, ..]).  On any other tape the four ``_traj`` names raise."""
+        instances too ([nseg, 1, ..] and [1, ..]).  On any other tape the four ``_traj`` names raise.
+        On the tape of a ``rollout_tv_est`` (mpcqp_rollout_adjoint_tv_est): everything the scheduled sweep and the estimator sweep take, and
+        'Ae_traj' [nseg, B, nx, nx], 'Be_traj' [nseg, B, nx, nu], 'L_traj' [nseg, B, nx, ny] -- the estimator path of the steps entry e was in
+        force; 'Ae', 'Be', 'L' are their sums over the entries."""
         self._need('rollout')
         ny = self._rollout_ny
         tv_names = ('Ad_traj', 'Bd_traj', 'Ap_traj', 'Bp_traj')
+        tv_est_names = ('Ae_traj', 'Be_traj', 'L_traj')
+        if self._rollout_shape is not None and not (self._rollout_tv is not None and ny) and any(k in tv_est_names for k in want):
+            raise RuntimeError('rollout_adjoint: the gradients %s need the tape of a rollout_tv_est' % ', '.join(tv_est_names))
         if self._rollout_shape is not None and self._rollout_tv is None and any(k in tv_names for k in want):
             raise RuntimeError('rollout_adjoint: the gradients %s need the tape of a rollout_tv (this one was made on one model)' % ', '.join(tv_names))
         if self._rollout_shape is not None and self._rollout_tv is not None:
-            if g_xhat is not None or g_y is not None:
+            if not ny and (g_xhat is not None or g_y is not None):
                 raise RuntimeError('rollout_adjoint: g_xhat, g_y need the tape of a rollout_est (this one has no estimator)')
-            return self._rollout_adjoint_tv(g_x, g_u, want, out, batch_sum, no_reuse)
+            return self._rollout_adjoint_tv(g_x, g_u, want, out, batch_sum, no_reuse, g_xhat, g_y)
         est_names = ('eta', 'C', 'L', 'v', 'Ae', 'Be')
         if self._rollout_shape is not None and not ny and (g_xhat is not None or g_y is not None or any(k in est_names for k in want)):
             raise RuntimeError('rollout_adjoint: g_xhat, g_y and the gradients %s need the tape of a rollout_est (this one has no estimator)' % ', '.join(est_names))
@@ -540,22 +587,31 @@ class BatchProblem:
             _lib.check(self._L.mpcqp_rollout_adjoint(self._h, C.byref(io), C.byref(mo)), 'mpcqp_rollout_adjoint')
         return res
 
-    def _rollout_adjoint_tv(self, g_x, g_u, want, out, batch_sum, no_reuse):
+    def _rollout_adjoint_tv(self, g_x, g_u, want, out, batch_sum, no_reuse, g_xhat=None, g_y=None):
         """``rollout_adjoint`` on the tape of a ``rollout_tv``: one mpcqp_rollout_adjoint_tv, then the per-slot gradients put together
-        (views and sums of the call's own buffers: ``out`` serves the other names only)."""
-        self._need('rollout_tv')
-        if g_x is None and g_u is None:
-            raise ValueError('rollout_adjoint: give g_x, g_u or both')
+        (views and sums of the call's own buffers: ``out`` serves the other names only).  On the tape of a ``rollout_tv_est``: one
+        mpcqp_rollout_adjoint_tv_est, with the estimator's seeds and its per-entry gradients handled the same way."""
+        ny = self._rollout_ny
+        self._need('rollout_tv_est' if ny else 'rollout_tv')
+        if g_x is None and g_u is None and g_xhat is None and g_y is None:
+            raise ValueError('rollout_adjoint: give g_x, g_u or both' + (', or g_xhat, g_y' if ny else ''))
         K, rows = self._rollout_shape
         hold, nseg, gave_Ad, gave_Bd = self._rollout_tv
         B, nx, nu = self.batch, self.nx, self.nu
-        like = g_x if g_x is not None else g_u
+        like = next(g for g in (g_x, g_u, g_xhat, g_y) if g is not None)
         gx = _prep(g_x, (K + 1, B, nx), 'g_x') if g_x is not None else None
         gu = _prep(g_u, (K, B, nu), 'g_u') if g_u is not None else None
+        gxh = _prep(g_xhat, (K + 1, B, nx), 'g_xhat') if g_xhat is not None else None
+        gy = _prep(g_y, (K, B, ny), 'g_y') if g_y is not None else None
         io = _lib.RolloutAdjointIO()
         io.struct_size, io.no_reuse = C.sizeof(_lib.RolloutAdjointIO), int(bool(no_reuse))
         io.G_x, io.G_u = _ptr(gx), _ptr(gu)
         table = dict(lam=(io, 'lam', (K + 1, B, nx)), uminus1=(io, 'd_uminus1', (B, nu)), uref=(io, 'd_uref', (B, nu)), xref=(io, 'd_xref', (K, B, rows * nx)))
+        eo = _lib.RolloutEstIO()
+        eo.struct_size = C.sizeof(_lib.RolloutEstIO)
+        eo.G_xhat, eo.G_y = _ptr(gxh), _ptr(gy)
+        if ny:
+            table.update(eta=(eo, 'eta', (K + 1, B, nx)), C=(eo, 'd_C', (B, ny, nx)), v=(eo, 'd_v', (K, B, ny)))
         mo, mtable = self._model_grads(batch_sum)
         table.update({k: v for k, v in mtable.items() if k not in ('Ad', 'Bd')})
         bo, btable = self._bound_grads(batch_sum)
@@ -570,15 +626,23 @@ class BatchProblem:
                      Ap=('d_Ap_entries', nseg, nx, lambda a: a.sum(0)), Bp=('d_Bp_entries', nseg, nu, lambda a: a.sum(0)))
         to = _lib.RolloutTVIO()
         to.struct_size = C.sizeof(_lib.RolloutTVIO)
+        xo = _lib.RolloutTVEstIO()
+        xo.struct_size = C.sizeof(_lib.RolloutTVEstIO)
+        if ny:                                    # (the estimator path, per entry: the names of rollout_est are the sums over the entries)
+            split.update(Ae_traj=('d_Ae_entries', nseg, nx, lambda a: a), Be_traj=('d_Be_entries', nseg, nu, lambda a: a), L_traj=('d_L_entries', nseg, ny, lambda a: a),
+                         Ae=('d_Ae_entries', nseg, nx, lambda a: a.sum(0)), Be=('d_Be_entries', nseg, nu, lambda a: a.sum(0)), L=('d_L_entries', nseg, ny, lambda a: a.sum(0)))
         bufs = {}
         for k in want:
             if k in split and split[k][0] not in bufs:
                 field, lead, cols, _ = split[k]
                 bufs[field] = self._out(like, (lead, B, nx, cols))
-                setattr(to, field, _ptr(bufs[field]))
+                setattr(xo if hasattr(xo, field) else to, field, _ptr(bufs[field]))
         res = self._grads_out([k for k in want if k not in split], table, out, like)
-        self._keep = [gx, gu, res, bufs]
-        _lib.check(self._L.mpcqp_rollout_adjoint_tv(self._h, C.byref(io), C.byref(mo), C.byref(bo), C.byref(to)), 'mpcqp_rollout_adjoint_tv')
+        self._keep = [gx, gu, gxh, gy, res, bufs]
+        if ny:
+            _lib.check(self._L.mpcqp_rollout_adjoint_tv_est(self._h, C.byref(io), C.byref(eo), C.byref(mo), C.byref(bo), C.byref(to), C.byref(xo)), 'mpcqp_rollout_adjoint_tv_est')
+        else:
+            _lib.check(self._L.mpcqp_rollout_adjoint_tv(self._h, C.byref(io), C.byref(mo), C.byref(bo), C.byref(to)), 'mpcqp_rollout_adjoint_tv')
         for k in want:
             if k in split:
                 a = bufs[split[k][0]]
@@ -819,9 +883,10 @@ class BatchProblem:
         numpy arrays (plus ``xhat_traj, y_traj`` with an estimator), or fills the arrays/tensors given in ``out``."""
         return self._loop('mpcqp_mpc_loop', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj)
 
-    def _loop(self, entry, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None):
+    def _loop(self, entry, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None, L_traj=None):
         """``mpc_run`` through the C entry point ``entry`` -- mpcqp_mpc_loop, or mpcqp_rollout / mpcqp_rollout_est: the same loop, and a tape
-        of it; with a ``model_traj``, mpcqp_mpc_loop_tv."""
+        of it; with a ``model_traj``, mpcqp_mpc_loop_tv (or mpcqp_rollout_tv; mpcqp_mpc_loop_tv_est / mpcqp_rollout_tv_est take an estimator
+        and a gain schedule ``L_traj`` too)."""
         K, B, nx, nu = int(nsteps), self.batch, self.nx, self.nu
         io = _lib.Loop()
         keep = []
@@ -849,7 +914,7 @@ class BatchProblem:
             Cm = estimator['C']
             ny = int(tuple(Cm.shape)[-2])
             io.ny = ny
-            io.C = inp(Cm, (B, ny, nx), 'C'); io.Lgain = inp(estimator['L'], (B, nx, ny), 'L')
+            io.C = inp(Cm, (B, ny, nx), 'C'); io.Lgain = inp(estimator.get('L'), (B, nx, ny), 'L')
             io.v = inp(estimator.get('v'), (K, B, ny), 'v')
             xt = estimator['x_true']
             if hasattr(xt, 'ctypes') and not (xt.dtype == np.float64 and xt.flags['C_CONTIGUOUS'] and xt.shape == (B, nx)):
@@ -875,8 +940,17 @@ class BatchProblem:
             mt = _lib.ModelTraj()
             mt.struct_size, mt.hold, mt.nmodels = C.sizeof(_lib.ModelTraj), hold, nm
             mt.Ad = inp(Adt, (nm, B, nx, nx), 'model_traj Ad'); mt.Bd = inp(Bdt, (nm, B, nx, nu), 'model_traj Bd')
-            entry = 'mpcqp_rollout_tv' if entry == 'mpcqp_rollout_tv' else 'mpcqp_mpc_loop_tv'
-            rc = getattr(self._L, entry)(self._h, K, C.byref(io), C.byref(mt))
+            if entry in ('mpcqp_mpc_loop_tv_est', 'mpcqp_rollout_tv_est'):
+                et = None
+                if L_traj is not None:
+                    ne = int(tuple(L_traj.shape)[0])
+                    et = _lib.EstTraj()
+                    et.struct_size, et.nentries = C.sizeof(_lib.EstTraj), ne
+                    et.Lgain_traj = inp(L_traj, (ne, B, nx, ny), 'L_traj')
+                rc = getattr(self._L, entry)(self._h, K, C.byref(io), C.byref(mt), None if et is None else C.byref(et))
+            else:
+                entry = 'mpcqp_rollout_tv' if entry == 'mpcqp_rollout_tv' else 'mpcqp_mpc_loop_tv'
+                rc = getattr(self._L, entry)(self._h, K, C.byref(io), C.byref(mt))
         else:
             rc = getattr(self._L, entry)(self._h, K, C.byref(io))
         if rc == -4:

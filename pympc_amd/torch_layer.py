@@ -152,7 +152,7 @@ def mpc_step(controller, x, u_prev=None, xref=None, params=None, bounds=None):
     return _MPCStep.apply(controller, x, u_prev, xref, names, *tensors)
 
 
-# ---- a closed-loop rollout as one differentiable operation (include/mpcqp_rollout.h, include/mpcqp_rollout_est.h) ----------------------
+# ---- a closed-loop rollout as one differentiable operation (include/mpcqp_rollout.h, include/mpcqp_rollout_est.h, include_ext*/) ------------
 _per = lambda v, shp: v.sum(dim=0) if len(shp) == 2 else v      # (an unbatched matrix input: summed over the batch)
 # input of a rollout -> (the gradient of rollout_adjoint it is made from, how; its own shape is put on last)
 _ROLLOUT_INPUTS = dict(
@@ -359,6 +359,113 @@ def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xr
         if not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (2, 3):
             raise ValueError('mpc_rollout_est: %s must be a device tensor [B, ., .] or [., .]' % n)
     return _MPCRolloutEst.apply(controller, int(nsteps), x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, names, *tensors)
+
+
+class _MPCRolloutTVEst(torch.autograd.Function):
+    INPUTS = ('x0', 'xhat0', 'C', 'L', 'v', 'u_prev', 'xref', 'w', 'Ap', 'Bp', 'Ad_traj', 'Bd_traj', 'L_traj')
+
+    @staticmethod
+    def forward(ctx, K, nsteps, hold, x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, L_traj, names, *params):
+        if not x0.is_cuda:
+            raise ValueError('mpc_rollout_tv_est works on device tensors (x0 is on %s)' % x0.device)
+        nseg = (nsteps + hold - 1) // hold
+
+        def roll(new, st, it):
+            ny = int(C.shape[-2])
+            X, XH, U, Y = new(nsteps + 1, K.nx), new(nsteps + 1, K.nx), new(nsteps, K.nu), new(nsteps, ny)
+            # (entry e of an unbatched schedule is one model, one gain, for the whole batch)
+            sched = [None if t is None else _det(t)[:nseg].reshape((nseg, -1) + tuple(t.shape[-2:])).expand((nseg, K.B) + tuple(t.shape[-2:])).contiguous()
+                     for t in (Ad_traj, Bd_traj, L_traj)]
+            est = dict(C=_bc(C, (K.B, ny, K.nx)), L=_bc(L, (K.B, K.nx, ny)), x_true=_det(x0).clone(), v=_det(v))
+            K.prob.rollout_tv_est(nsteps, (sched[0], sched[1], hold), est, L_traj=sched[2], w=_det(w), Ap=_bc(Ap, (K.B, K.nx, K.nx)), Bp=_bc(Bp, (K.B, K.nx, K.nu)),
+                                  out=[X, U, st, it, XH, Y])
+            for n, t in zip(('Ad', 'Bd'), sched):             # the controller is left with the last entry used: read back when somebody asks (update_model's way)
+                if t is not None:
+                    K.__dict__.pop(n, None)
+                    K._on_device[n] = t[nseg - 1]
+            return XH[-1], U, (X, XH, Y, U)
+        ctx.nseg = nseg
+        return _rollout_forward(ctx, K, nsteps, xhat0, u_prev, xref, names, params, roll,
+                                (x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, L_traj))
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_XH, grad_Y, grad_U):
+        K = ctx.K
+        if K.prob.rollout_count != ctx.count:
+            raise RuntimeError('mpc_rollout_tv_est: the controller has been rolled out again since this forward (rollout %d then, %d now); '
+                               'its tape is no longer the one to differentiate.' % (ctx.count, K.prob.rollout_count))
+        inputs = _MPCRolloutTVEst.INPUTS
+        simple, traj = inputs[:10], inputs[10:]
+        ni = 3 + len(inputs)
+        need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[3:ni], ctx.shapes)}
+        shape = dict(zip(inputs, ctx.shapes))
+        pneed, shared, _ = _param_want(ctx, ctx.needs_input_grad[ni + 1:])
+        if not any(need.values()) and not pneed:
+            return (None,) * (ni + 1 + len(ctx.names))
+        follows = shape['Ap'] is None                        # the plant followed the schedule: its path belongs to the model in force
+        # Ad, Bd of an entry have up to three paths: its solves, the estimator (always) and the plant (where it followed); a matrix the schedule
+        # did not give never changed: params' matrix gets all of them
+        plant = {'Ad_traj': 'Ap_traj', 'Bd_traj': 'Bp_traj', 'Ad': 'Ap', 'Bd': 'Bp'}
+        estim = {'Ad_traj': 'Ae_traj', 'Bd_traj': 'Be_traj', 'Ad': 'Ae', 'Bd': 'Be'}
+        left = {'Ad': shape['Ad_traj'] is None, 'Bd': shape['Bd_traj'] is None}
+        split = [n for n in traj + ('Ap', 'Bp', 'L') if need[n]] + [n for n in ('Ad', 'Bd') if n in pneed]
+        unbatched = lambda n: len(shape[n]) == (3 if n.endswith('_traj') else 2) if n in shape else shared[n]
+        batch_sum = bool(split or pneed) and all(unbatched(n) for n in split) and all(shared[n] for n in pneed)
+        paths = lambda n: [estim[n]] + ([plant[n]] if follows else [])
+        want = list(dict.fromkeys(_ROLLOUT_INPUTS[n][0] for n in simple if need[n]))
+        want += [n for n in traj if need[n]] + pneed
+        want += [g for n in ('Ad_traj', 'Bd_traj') if need[n] for g in paths(n)] + [g for n in ('Ad', 'Bd') if n in pneed and left[n] for g in paths(n)]
+        want = list(dict.fromkeys(want))
+        seeds = dict(g_x=grad_X, g_u=grad_U, g_xhat=grad_XH, g_y=grad_Y)
+        with _ordered(K):
+            res = K.prob.rollout_adjoint(want=want, batch_sum=batch_sum, **{k: g.to(torch.float64).contiguous() for k, g in seeds.items()})
+        grads = [_ROLLOUT_INPUTS[n][1](res[_ROLLOUT_INPUTS[n][0]], shape[n]).reshape(shape[n]) if need[n] else None for n in simple]
+        for n in traj:
+            v = None
+            if need[n]:
+                v = res[n] if n == 'L_traj' else sum((res[g] for g in paths(n)), res[n])
+                v = (v.sum(dim=1) if len(shape[n]) == 3 else v)[:ctx.nseg]
+                if shape[n][0] > ctx.nseg:                   # entries beyond ceil(nsteps / hold) were never in force
+                    v = torch.cat([v, v.new_zeros((shape[n][0] - ctx.nseg,) + tuple(v.shape[1:]))])
+                v = v.reshape(shape[n])
+            grads.append(v)
+        pgrads = _param_grads(ctx, res, pneed, shared, batch_sum)
+        for i, (n, shp) in enumerate(zip(ctx.names, ctx.pshapes)):
+            if n in ('Ad', 'Bd') and n in pneed and left[n]:
+                for g in paths(n):
+                    p = res[g]
+                    pgrads[i] = pgrads[i] + ((p[0] if batch_sum else p.sum(dim=0)) if shared[n] else p).reshape(shp)
+        return (None, None, None) + tuple(grads) + (None,) + tuple(pgrads)
+
+
+def mpc_rollout_tv_est(controller, x0, xhat0, nsteps, Ad_traj, Bd_traj, hold, C, L=None, L_traj=None, v=None, u_prev=None, xref=None, w=None, Ap=None, Bp=None,
+                       params=None, bounds=None):
+    """``mpc_rollout_est`` under a model schedule: ``(X [K+1,B,nx], Xhat [K+1,B,nx], Y [K,B,ny], U [K,B,nu])`` of ``nsteps`` = K steps of the
+    output-feedback loop in which entry ``k // hold`` of ``Ad_traj`` / ``Bd_traj`` (as in ``mpc_rollout_tv``) replaces the model at the start of
+    step k -- for the controller, for the estimator xhat_{k+1} = Ad_e (xhat_k + L_e (y_k - C xhat_k)) + Bd_e u_k and, with ``Ap`` / ``Bp`` None,
+    for the plant -- as ``BatchMPCController.run(estimator=, model_traj=, L_traj=)`` does.  Exactly one of ``L`` ([B,nx,ny] or [nx,ny]: one
+    gain throughout) and ``L_traj`` ([nseg,B,nx,ny] or [nseg,nx,ny]: a gain per entry, e.g. ``kalman_gain(Ad_traj[e], C, Qn, Rn)``) is given.
+    Forward is ``update_model(solve=False, **params)`` where given, ``update(xhat0, u_prev, xref)`` with its solve, then ONE
+    ``mpcqp_rollout_tv_est`` (include_ext2/mpcqp_rollout_tv_est.h); backward is ONE ``mpcqp_rollout_adjoint_tv_est`` with the four seeds.
+    Differentiable with respect to every tensor argument: the gradient of ``Ad_traj[e]`` is that of the solves made under entry e plus that of
+    the estimator steps it was in force plus, where ``Ap`` is None, that of the plant steps; ``params['Ad']`` is the model the rollout
+    begins with and gets the first solve's share (and, where the schedule leaves Ad alone, everything).  An unbatched schedule's or gain
+    schedule's gradient is the sum over the batch.  Everything else as in ``mpc_rollout_est`` and ``mpc_rollout_tv``."""
+    names, tensors = _check_args('mpc_rollout_tv_est', controller, params, Ap, Bp, bounds)
+    if Ad_traj is None and Bd_traj is None:
+        raise ValueError('mpc_rollout_tv_est: give Ad_traj, Bd_traj or both (mpc_rollout_est is the loop on one model)')
+    if (L is None) == (L_traj is None):
+        raise ValueError('mpc_rollout_tv_est: give exactly one of L and L_traj')
+    nseg = (int(nsteps) + int(hold) - 1) // int(hold)
+    for n, t in (('Ad_traj', Ad_traj), ('Bd_traj', Bd_traj), ('L_traj', L_traj)):
+        if t is not None and (not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (3, 4) or t.shape[0] < nseg):
+            raise ValueError('mpc_rollout_tv_est: %s must be a device tensor [nseg, B, ., .] or [nseg, ., .] with nseg >= ceil(nsteps / hold)' % n)
+    for n, t in (('C', C), ('L', L)):
+        if t is not None and (not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (2, 3)):
+            raise ValueError('mpc_rollout_tv_est: %s must be a device tensor [B, ., .] or [., .]' % n)
+    if C is None:
+        raise ValueError('mpc_rollout_tv_est: C is needed')
+    return _MPCRolloutTVEst.apply(controller, int(nsteps), int(hold), x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, L_traj, names, *tensors)
 
 
 # ---- the discrete algebraic Riccati equation as a differentiable operation (include/mpcqp_riccati.h) ------------------------------------

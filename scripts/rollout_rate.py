@@ -18,8 +18,12 @@ One JSON line per (batch, shape, K).
 the instance's Ad, Bd) in the same alternation: run(model_traj=) against rollout_tv, and the scheduled sweep ('Ad_traj', 'Bd_traj',
 'Ap_traj', 'Bp_traj' in place of 'Ad', 'Bd', 'Ap', 'Bp') with its n_factor / K, beside the constant-model figures of the same repetition.
 Every timed loop starts from the same model, state and solve (update_model + update + solve before it, not timed).
+``--estimator`` (with ``--schedule``): the output-feedback legs in the same repetition loop -- random C with ny = 3 outputs, stationary Kalman
+gains from pympc_amd.torch_layer.kalman_gain (one per instance; under a schedule one per entry) -- run(estimator=) against rollout_est and
+its sweep, and per hold run(estimator=, model_traj=, L_traj=) against rollout_tv_est (include_ext2/mpcqp_rollout_tv_est.h) and its sweep, with
+the plain sweep and the scheduled state-feedback sweep timed again beside them, so that the four sweeps of one repetition can be compared.
 
-    python scripts/rollout_rate.py [--reps 5] [--eps 1e-6] [--sizes 1024:12,4,30 256:4,2,10] [--steps 20 100] [--no-route-b] [--bounds] [--schedule 1 5]"""
+    python scripts/rollout_rate.py [--reps 5] [--eps 1e-6] [--sizes 1024:12,4,30 256:4,2,10] [--steps 20 100] [--no-route-b] [--bounds] [--schedule 1 5] [--estimator]"""
 import argparse
 import json
 import os
@@ -41,6 +45,49 @@ def controller(kws, Np, eps, stream):
     return K
 
 
+def estimator_leg(a, torch, t, bp, K, B, nx, nu, Ad, x0, out, gx, gu, want, want_tv, scheds, reset, timed):
+    """The output-feedback legs of one (batch, shape, K): dict of lists of milliseconds, one entry per repetition; per hold under 'schedule'."""
+    from pympc_amd.torch_layer import kalman_gain
+    ny, dev = 3, x0.device
+    rng = np.random.default_rng(5)
+    Cm = t(rng.standard_normal((B, ny, nx)))
+    Qn, Rn = t(0.01 * np.eye(nx)), t(0.01 * np.eye(ny))
+    Lg = kalman_gain(Ad, Cm, Qn, Rn)[0]
+    assert bool((Lg.status == 1).all())
+    Lts = {}
+    for hold, sc in scheds.items():                        # a gain per schedule entry
+        nseg = sc[0].shape[0]
+        Lt = kalman_gain(sc[0].reshape(nseg * B, nx, nx), Cm.repeat(nseg, 1, 1), Qn, Rn)[0]
+        assert bool((Lt.status == 1).all())
+        Lts[hold] = Lt.reshape(nseg, B, nx, ny).contiguous()
+    oute = out + [torch.empty((K + 1, B, nx), dtype=torch.float64, device=dev), torch.empty((K, B, ny), dtype=torch.float64, device=dev)]
+    seeds = dict(g_x=gx, g_u=gu, g_xhat=torch.randn((K + 1, B, nx), dtype=torch.float64, device=dev), g_y=torch.randn((K, B, ny), dtype=torch.float64, device=dev))
+    est = lambda: dict(C=Cm, L=Lg, x_true=x0.clone(), v=None)
+    want_e = want + ('eta', 'C', 'L', 'Ae', 'Be')
+    want_x = want_tv + ('eta', 'C', 'L_traj', 'Ae_traj', 'Be_traj')
+    r = dict(ny=ny, run_est_ms=[], rollout_est_ms=[], sweep_est_ms=[], sweep_plain_ms=[], tape_bytes=bp.rollout_tape_bytes(K, ny=ny))
+    tv = {hold: dict(run_tv_est_ms=[], rollout_tv_est_ms=[], sweep_tv_est_ms=[], sweep_tv_ms=[], tape_bytes=bp.rollout_tv_est_tape_bytes(K, hold, ny)) for hold in scheds}
+    for rep in range(a.reps + 1):                          # (repetition 0 warms every call up and is not kept)
+        keep = (lambda lst, v: lst.append(v)) if rep else (lambda lst, v: None)
+        reset(); e = est(); keep(r['run_est_ms'], timed(lambda: bp.mpc_run(K, out=oute, estimator=e))[0])
+        reset(); e = est(); keep(r['rollout_est_ms'], timed(lambda: bp.rollout_est(K, e, out=oute))[0])
+        keep(r['sweep_est_ms'], timed(lambda: bp.rollout_adjoint(want=want_e, **seeds))[0])
+        info = bp.rollout_info()
+        r.update(n_factor_per_step=float(info[3].mean()) / K, steps_differentiated=float((info[2] == 1).mean()))
+        reset(); bp.rollout(K, out=out)
+        keep(r['sweep_plain_ms'], timed(lambda: bp.rollout_adjoint(g_x=gx, g_u=gu, want=want))[0])
+        for hold, sc in scheds.items():
+            reset(); e = est(); keep(tv[hold]['run_tv_est_ms'], timed(lambda: bp.mpc_run_tv_est(K, sc, e, L_traj=Lts[hold], out=oute))[0])
+            reset(); e = est(); keep(tv[hold]['rollout_tv_est_ms'], timed(lambda: bp.rollout_tv_est(K, sc, e, L_traj=Lts[hold], out=oute))[0])
+            keep(tv[hold]['sweep_tv_est_ms'], timed(lambda: bp.rollout_adjoint(want=want_x, **seeds))[0])
+            info = bp.rollout_info()
+            tv[hold].update(n_factor_per_step=float(info[3].mean()) / K, steps_differentiated=float((info[2] == 1).mean()))
+            reset(); bp.rollout_tv(K, sc, out=out)
+            keep(tv[hold]['sweep_tv_ms'], timed(lambda: bp.rollout_adjoint(g_x=gx, g_u=gu, want=want_tv))[0])
+    r['schedule'] = {str(hold): v for hold, v in tv.items()}
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
@@ -50,7 +97,10 @@ def main():
     ap.add_argument('--no-route-b', action='store_true', help='skip the K-controller route (it builds K handles)')
     ap.add_argument('--bounds', action='store_true', help='ask the sweep for xmin, xmax, umin, umax, Dumin, Dumax as well')
     ap.add_argument('--schedule', nargs='*', type=int, default=[], help='holds of a model schedule to time the scheduled loop and sweep under')
+    ap.add_argument('--estimator', action='store_true', help='time the output-feedback loops and sweeps too, under every hold of --schedule')
     a = ap.parse_args()
+    if a.estimator and not a.schedule:
+        ap.error('--estimator times the scheduled output-feedback loop: give --schedule HOLD ..')
     import torch
     from pympc_amd import fixtures
     dev = torch.device('cuda:0')
@@ -135,6 +185,8 @@ def main():
             _, _, status, _ = bp.rollout_info()
             res.update(run_ms=run_ms, rollout_ms=roll_ms, sweep_ms=sweep_ms, sweep_no_reuse_ms=noreuse_ms,
                        n_factor_per_step=float(nfac.mean()) / K, steps_differentiated=float((status == 1).mean()))
+            if a.estimator:
+                res['estimator'] = estimator_leg(a, torch, t, bp, K, B, nx, nu, Ad, x0, out, gx, gu, want, want_tv, scheds, reset, timed)
             # (b) the route without a tape: K controllers
             if not a.no_route_b:
                 m2 = used()

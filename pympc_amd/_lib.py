@@ -53,6 +53,9 @@ ROLLOUT_TV_EST_SYMBOLS = ['mpcqp_mpc_loop_tv_est', 'mpcqp_rollout_tv_est', 'mpcq
 # include/mpcqp_riccati.h: likewise -- batched discrete algebraic Riccati equations and their adjoint, without a handle
 RICCATI_SYMBOLS = ['mpcqp_riccati_default_settings', 'mpcqp_dare', 'mpcqp_dare_adjoint']
 
+# include_ext3/mpcqp_riccati_traj.h: likewise -- batched Riccati difference equations (a recursion over a model trajectory) and their adjoint
+RICCATI_TRAJ_SYMBOLS = ['mpcqp_dre', 'mpcqp_dre_adjoint']
+
 
 class RiccatiSettings(C.Structure):
     """mpcqp_riccati_settings (include/mpcqp_riccati.h)."""
@@ -305,6 +308,12 @@ def load():
         L.mpcqp_dare_adjoint.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RiccatiSettings)] + [C.c_void_p] * 14
         for name in RICCATI_SYMBOLS[1:]:
             getattr(L, name).restype = C.c_int
+    if has_riccati_traj(L):
+        head = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RiccatiSettings), C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.mpcqp_dre.argtypes = head + [C.c_void_p] * 7
+        L.mpcqp_dre_adjoint.argtypes = head + [C.c_void_p] * 12
+        for name in RICCATI_TRAJ_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -363,6 +372,11 @@ def has_rollout_tv_est(L=None):
 def has_riccati(L=None):
     """True if the library exports include/mpcqp_riccati.h."""
     return _has(L, RICCATI_SYMBOLS)
+
+
+def has_riccati_traj(L=None):
+    """True if the library exports include_ext3/mpcqp_riccati_traj.h."""
+    return _has(L, RICCATI_TRAJ_SYMBOLS)
 
 
 def check(rc, what):

@@ -520,3 +520,76 @@ def kalman_gain(A, C, Qn, Rn, type='filter'):
     L = G.transpose(-1, -2).contiguous()
     L.status = P.status
     return L, P
+
+
+# ---- the Riccati difference equation as a differentiable operation (include_ext3/mpcqp_riccati_traj.h) ---------------------------------
+class _Dre(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gain_form, a_traj, b_traj, T, A, B, Q, R, X0):
+        from . import riccati
+        X, K, status, bad = riccati.dre_flagged(A, a_traj, B, b_traj, Q, R, X0, gain_form=gain_form, T=T)
+        ctx.save_for_backward(A, B, Q, R, X0, X)
+        ctx.conf, ctx.status = (gain_form, a_traj, b_traj, T), status
+        ctx.mark_non_differentiable(status, bad)
+        return X, K, status, bad
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_K, _s, _b):
+        from . import riccati
+        A, B, Q, R, X0, X = ctx.saved_tensors
+        gain_form, a_traj, b_traj, T = ctx.conf
+        names = ('A', 'B', 'Q', 'R', 'X0')
+        want = [n for n, need in zip(names, ctx.needs_input_grad[4:]) if need]
+        if not want:
+            return (None,) * 9
+        g = riccati.dre_adjoint_flagged(A, a_traj, B, b_traj, Q, R, X0, X, status=ctx.status, G_X=grad_X, G_K=grad_K, gain_form=gain_form, T=T, want=want)
+        # (an unbatched input beside batched ones: one matrix or trajectory shared by the batch, its gradient the sum over it)
+        out = []
+        for n, p, tr in zip(names, (A, B, Q, R, X0), (a_traj, b_traj, False, False, False)):
+            out.append(None if n not in g else (g[n].sum(dim=1 if tr else 0) if g[n].dim() == p.dim() + 1 else g[n]))
+        return (None,) * 4 + tuple(out)
+
+
+def _dre_flagged(A, a_traj, B, b_traj, Q, R, X0, gain_form=0, T=None, stream=None):
+    """``riccati.dre_flagged`` as the differentiable operation (``stream`` is torch's current one)."""
+    return _Dre.apply(int(gain_form), bool(a_traj), bool(b_traj), None if T is None else int(T), A, B, Q, R, X0)
+
+
+def _traj_args(fn, mats, trajs):
+    for n, t in mats.items():
+        if not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (2, 3):
+            raise ValueError('%s: %s must be a device tensor [B, ., .] or [., .]' % (fn, n))
+    for n, t in trajs.items():
+        if not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (2, 3, 4):
+            raise ValueError('%s: %s must be a device tensor, one matrix ([B, ., .] or [., .]) or a trajectory ([T, B, ., .] or [T, ., .])' % (fn, n))
+
+
+def dre(A, B, Q, R, X0, gain_form=0, T=None):
+    """``(X_traj, K_traj)`` of the Riccati difference equation from X0 over T steps for device tensors (``pympc_amd.riccati.dre``, which
+    says how A and B are read as one matrix or as a trajectory): forward is ONE mpcqp_dre call, backward ONE mpcqp_dre_adjoint call, both on
+    torch's current stream.  Differentiable with respect to A, B, Q, R and X0; the gradients of Q, R and X0 are those of a symmetric
+    perturbation, a trajectory gets a gradient per entry and one matrix the sum over the steps, an unbatched input beside batched ones the
+    sum over the batch; an instance that did not run through returns zeros and contributes a zero gradient.  ``X_traj.status``
+    ( = ``K_traj.status``) and ``.first_bad``: per instance, as in ``riccati.dre``."""
+    from . import riccati
+    _traj_args('dre', dict(Q=Q, R=R, X0=X0), dict(A=A, B=B))
+    a_traj, b_traj = riccati.traj_flags('dre', A, B, (Q, R, X0))
+    X, K, status, bad = _dre_flagged(A, a_traj, B, b_traj, Q, R, X0, gain_form=gain_form, T=T)
+    X.status = K.status = status
+    X.first_bad = K.first_bad = bad
+    return X, K
+
+
+def kalman_gain_traj(A_traj, C, Qn, Rn, P0, hold=1):
+    """``(L_traj [nentries, B, nx, ny], P_traj [nentries + 1, B, nx, nx])`` of the Kalman filter of a time-varying system, with the meaning
+    and the indexing of ``pympc_amd.riccati.kalman_gain_traj`` (entry e: the gain and the covariance at the first step of schedule entry
+    e; ``mpc_rollout_tv_est(.., L_traj=L_traj)`` under the same ``hold`` is that filter): ONE mpcqp_dre call forward, ONE
+    mpcqp_dre_adjoint call backward.  Differentiable with respect to every entry of ``A_traj``, C, the noise covariances Qn, Rn and the
+    initial covariance P0.  ``L_traj.status``, ``P_traj.status`` as in ``dre``."""
+    from . import riccati
+    _traj_args('kalman_gain_traj', dict(C=C, Qn=Qn, Rn=Rn, P0=P0), {})
+    if not hasattr(A_traj, 'data_ptr') or not A_traj.is_cuda or A_traj.dim() not in (3, 4):
+        raise ValueError('kalman_gain_traj: A_traj must be a device tensor [nentries, B, nx, nx] or [nentries, nx, nx]')
+    L, P, status = riccati._dre_dual(_dre_flagged, A_traj, C, Qn, Rn, P0, riccati._hold(hold), None)
+    L.status = P.status = status
+    return L, P

@@ -3,8 +3,9 @@
 // layout of the latency round (mpcqp_latw.h: lane (I, B, J) of wave w owns slot a = 4B + I of stage s = 4w + J -- one group of four stages per
 // wave), called by admm_latw between two rounds with the owned values BY VALUE:
 //   * A x and A'y are the two MFMA groups of the iteration (G v of the previous stage, G' y_dyn of the next) applied to x and y, P x a 16-long dot
-//     product per lane against the weight matrices' LDS copy; seven max-norms, the objective and the cheap halves of both infeasibility certificates
-//     (|c dy| clipped by the infinite bounds and the support function of [l, u]; |dx| and q'dx) meet in ONE block reduction;
+//     product per lane against the weight matrices' LDS copy; the residuals, their scales and the objective meet in one block reduction of five
+//     values, and ONLY where the solve has not converged the cheap halves of both infeasibility certificates (|c dy| clipped by the infinite bounds
+//     and the support function of [l, u]; |dx| and q'dx) in a second one of four;
 //   * LATW_SOLVED: the solve is finished here -- iterate for the next warm start, reported solution, mpcqp_info, statistics, first input and status
 //     for the closed loop on the device: everything check_body's tail writes;
 //   * LATW_CARRIED: solved, and the queue item has another step: its transition (latw_carry below, inline) is made in the same call -- one entry, one
@@ -47,15 +48,9 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     const int pidx = is_x ? e : L.ou + cu, aidx = is_x ? e : L.ri + cu, bidx = is_x ? L.rs + e : L.rdu + nu + cu;
     const bool u0v = wv == 0 && J == 0 && !is_x && a < nx + nu;
     const int onext = (jj + 1 < nu) ? 1 : NB - nu + 1, oprev = (jj > 0) ? -1 : -(NB - nu + 1);
-    // (the last iteration's increments: each lane reads back what it stored itself for the generic check -- requested first, consumed last)
     cgdouble *dxg = (cgdouble *)(PP.dx + (size_t)b * L.n), *dyg = (cgdouble *)(PP.dy + (size_t)b * L.m);
-    const int ip = ok ? pidx : 0;
-    const double ddx = dxg[ip], dde = dxg[(ok && is_x && L.soft) ? ip + L.oe : 0], ddA = dyg[ok ? aidx : 0], ddB = dyg[ok ? bidx : 0];
-    const double dd0 = dyg[L.rdu + ((jj >= 0 && jj < nu) ? jj : 0)];
-    // which of the owned rows' bounds are infinite on OSQP's scaled test (E hi > 1e26, E lo < -1e26: the primal infeasibility certificate clips the
-    // dual increment by them) -- two bits per row: rA 0,1  rB 2,3  r0 4,5
     cgdouble *Eg = (cgdouble *)(PP.E + (size_t)b * L.m);
-    const double eA = Eg[ok ? aidx : 0], eB = Eg[ok ? bidx : 0], e0 = Eg[L.rdu + ((jj >= 0 && jj < nu) ? jj : 0)], lim = QP_INFTY * MIN_SCALING;
+    const double lim = QP_INFTY * MIN_SCALING;
     // x in Tc, the first rows' multipliers in Cc -- and, once G'y has been formed, the second rows' in Cc again (every slot 0 .. 4 NG - 1 has an
     // owner that writes it; slots -1 and 4 NG stay zero throughout; the iteration rewrites both vectors before it reads them)
     const double yA = ysA * (omA * cinv), yB = ysB * (omB * cinv), y0 = u0v ? ys0 * (om0 * cinv) : 0.0;
@@ -74,25 +69,18 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     const double Erc = Eg[rc >= 0 ? rc : 0];
     const int ctc = ((const __attribute__((address_space(1))) int *)(PP.ctype + (size_t)b * L.m))[rc >= 0 ? rc : 0];
     const double rho = PP.rho[b];
-    int infbits = !ok ? 0 : (eA * hiA > lim ? 1 : 0) | (eA * loA < -lim ? 2 : 0) | (eB * hiB > lim ? 4 : 0) | (eB * loB < -lim ? 8 : 0);
-    if (u0v) infbits |= (e0 * S.du0[nu + jj] > lim ? 16 : 0) | (e0 * S.du0[jj] < -lim ? 32 : 0);
     const Ctx c{L, hot, hot + L.hot_sz};
-    // 0 pri, 1 |Ax|, 2 |z|, 3 dua, 4 |Px|, 5 |A'y|, 6 |q|, 7 |c dy| clipped, 8 |dx|;  sums: objective, support function of [l, u] at c dy, q'dx
-    double nrm[9], vsum[3];
+    // STAGE 1, every check: what a verdict 'solved' needs and no more.  0 pri, 1 max(|Ax|, |z|), 2 dua, 3 max(|Px|, |A'y|, |q|); sum: the objective.
+    // (|Ax| and |z| enter the test only as their maximum, |Px|, |A'y| and |q| only as theirs; a maximum of non-negative numbers is the same in any
+    //  grouping, and block_reduce forms every value on its own: pri_res, dua_res, obj_val and every verdict keep their bits.)
+    double nrm[4], vsum[1];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) nrm[i] = 0.0;
-    vsum[0] = vsum[1] = vsum[2] = 0.0;
-    auto row = [&](double ax, double z) { nrm[0] = fmax(nrm[0], fabs(ax - z)); nrm[1] = fmax(nrm[1], fabs(ax)); nrm[2] = fmax(nrm[2], fabs(z)); };
-    auto var = [&](double px, double aty, double qj, double xj, double dxj) {
-        nrm[3] = fmax(nrm[3], fabs(px + qj + aty)); nrm[4] = fmax(nrm[4], fabs(px)); nrm[5] = fmax(nrm[5], fabs(aty)); nrm[6] = fmax(nrm[6], fabs(qj));
+    for (int i = 0; i < 4; ++i) nrm[i] = 0.0;
+    vsum[0] = 0.0;
+    auto row = [&](double ax, double z) { nrm[0] = fmax(nrm[0], fabs(ax - z)); nrm[1] = fmax(nrm[1], fmax(fabs(z), fabs(ax))); };
+    auto var = [&](double px, double aty, double qj, double xj) {
+        nrm[2] = fmax(nrm[2], fabs(px + qj + aty)); nrm[3] = fmax(nrm[3], fmax(fmax(fabs(qj), fabs(aty)), fabs(px)));
         vsum[0] += xj * (0.5 * px + qj);
-        nrm[8] = fmax(nrm[8], fabs(dxj)); vsum[2] += qj * dxj;
-    };
-    auto cert = [&](double dy, double lo, double hi, int bits) {      // OSQP is_primal_infeasible: c dy projected on the polar of the recession cone of [l, u]
-        double v = cc * dy;
-        if (bits & 1) v = (bits & 2) ? 0.0 : fmin(v, 0.0);
-        else if (bits & 2) v = fmax(v, 0.0);
-        nrm[7] = fmax(nrm[7], fabs(v)); vsum[1] += hi * fmax(v, 0.0) + lo * fmin(v, 0.0);
     };
     double g = 0.0, h2 = 0.0, gt = 0.0, ht = 0.0;
     lat_mv(latw_top_frag(TopL, NTOP * NTOP, lane), Tc[sl - NB], g, h2);            // G v of the previous stage
@@ -102,8 +90,9 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     Cc[sl] = ok ? yB : 0.0;
     __syncthreads();
     BTICK(1)
+    const double qj = -ncq * cinv;
     if (ok) {
-        const double xj = pv, qj = -ncq * cinv, yprev = Cc[sl + oprev];
+        const double xj = pv, yprev = Cc[sl + oprev];
         const double *xs = Tc + s * NB;
         if (is_x) {
             row((g + h2) - xj, zA);
@@ -112,8 +101,8 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
             double px = 0.0;
 #pragma unroll 4
             for (int l = 0; l < nx; ++l) px += Q[min(a, l) * nx + max(a, l)] * xs[l];
-            var(px, (gt + ht) - yA + yB, qj, xj, ddx);
-            if (L.soft) var(c.eps_feas() * pv2, yB, 0.0, pv2, dde);
+            var(px, (gt + ht) - yA + yB, qj, xj);
+            if (L.soft) var(c.eps_feas() * pv2, yB, 0.0, pv2);
         } else {
             row(xj, zA);
             row(un - xj, zB);
@@ -124,19 +113,18 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
             if (s + 1 < L.Nc) for (int l = 0; l < nu; ++l) px += -QDu[jj * nu + l] * us[NB + l];
             if (s > 0) for (int l = 0; l < nu; ++l) px += -QDu[l * nu + jj] * us[l - NB];
             double aty = (gt + ht) + yA - yB + yprev;
-            if (u0v) { aty += y0; row(xj, z0); cert(dd0, S.du0[jj], S.du0[nu + jj], infbits >> 4); }
-            var(px, aty, qj, xj, ddx);
+            if (u0v) { aty += y0; row(xj, z0); }
+            var(px, aty, qj, xj);
         }
-        cert(ddA, loA, hiA, infbits); cert(ddB, loB, hiB, infbits >> 2);
     }
     if (u0v) S.uo[jj] = pv;      // (the first input, should the verdict be 'solved' -- nobody reads it otherwise: published by the reduction's barriers, for latw_carry)
     BTICK(2)
-    block_reduce<9, 3>(nrm, vsum, S.red);
+    block_reduce<4, 1>(nrm, vsum, S.red);
     BTICK(3)
-    const double ea = KA.S.eps_abs, er = KA.S.eps_rel, epi = KA.S.eps_prim_inf, edi = KA.S.eps_dual_inf;
-    const double pri_res = nrm[0], dua_res = nrm[3], obj_val = vsum[0];
+    const double ea = KA.S.eps_abs, er = KA.S.eps_rel;
+    const double pri_res = nrm[0], dua_res = nrm[2], obj_val = vsum[0];
     if (!(pri_res <= QP_INFTY) || !(dua_res <= QP_INFTY) || obj_val != obj_val) return LATW_GENERIC;      // (non-finite: the generic check reports it)
-    const bool pc = pri_res < ea + er * fmax(nrm[2], nrm[1]), dc = dua_res < ea + er * fmax(fmax(nrm[6], nrm[5]), nrm[4]);
+    const bool pc = pri_res < ea + er * nrm[1], dc = dua_res < ea + er * nrm[3];
     if (pc && dc) {
         // ---- solved: what check_body's tail writes (the iterate for the next warm start, the reported solution, the record)
         gdouble *gx = (gdouble *)(PP.x + (size_t)b * L.n), *gz = (gdouble *)(PP.z + (size_t)b * L.m), *gy = (gdouble *)(PP.y + (size_t)b * L.m);
@@ -164,8 +152,42 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     }
     // not converged: may the next round start at once?  Only if neither certificate can hold -- decided from their cheap halves
     if (R.nsteps == 0 && R.part == 1) return LATW_GENERIC;                       // (the first launch of a two-launch solve hands over after ONE round)
-    if (!pc && nrm[7] > epi && vsum[1] < -epi * nrm[7]) return LATW_GENERIC;     // primal infeasibility would need |A' dy|
-    if (!dc && nrm[8] > edi && vsum[2] < -edi * nrm[8]) return LATW_GENERIC;     // dual infeasibility would need |P dx| and A dx
+    // STAGE 2, only here: the cheap halves of both certificates.  0 |c dy| clipped by the infinite bounds, 1 |dx|;  sums: the support function of
+    // [l, u] at c dy, q'dx -- each lane's terms in the order the one-stage check added them.
+    double cn[2] = {0.0, 0.0}, cs[2] = {0.0, 0.0};
+    auto cert = [&](double dy, double lo, double hi, int bits) {      // OSQP is_primal_infeasible: c dy projected on the polar of the recession cone of [l, u]
+        double v = cc * dy;
+        if (bits & 1) v = (bits & 2) ? 0.0 : fmin(v, 0.0);
+        else if (bits & 2) v = fmax(v, 0.0);
+        cn[0] = fmax(cn[0], fabs(v)); cs[0] += hi * fmax(v, 0.0) + lo * fmin(v, 0.0);
+    };
+    auto dvar = [&](double qv, double dxj) { cn[1] = fmax(cn[1], fabs(dxj)); cs[1] += qv * dxj; };
+    // (the last iteration's increments -- each lane reads back what it stored itself for the generic check -- and the owned rows' scaling: requested
+    //  HERE, by every lane at clamped addresses in one go.  Requested at the function's entry they cost every check 900 cycles of entry and this stage
+    //  300 less; seven checks in ten end solved and never come here.)
+    const int ip = ok ? pidx : 0;
+    const double ddx = dxg[ip], dde = dxg[(ok && is_x && L.soft) ? ip + L.oe : 0], ddA = dyg[ok ? aidx : 0], ddB = dyg[ok ? bidx : 0];
+    const double dd0 = dyg[L.rdu + ((jj >= 0 && jj < nu) ? jj : 0)];
+    const double eA = Eg[ok ? aidx : 0], eB = Eg[ok ? bidx : 0], e0 = Eg[L.rdu + ((jj >= 0 && jj < nu) ? jj : 0)];
+    if (ok) {
+        // which of the owned rows' bounds are infinite on OSQP's scaled test (E hi > 1e26, E lo < -1e26: the primal infeasibility certificate clips the
+        // dual increment by them) -- two bits per row: rA 0,1  rB 2,3
+        int infbits = (eA * hiA > lim ? 1 : 0) | (eA * loA < -lim ? 2 : 0) | (eB * hiB > lim ? 4 : 0) | (eB * loB < -lim ? 8 : 0);
+        if (u0v) cert(dd0, S.du0[jj], S.du0[nu + jj], (e0 * S.du0[nu + jj] > lim ? 1 : 0) | (e0 * S.du0[jj] < -lim ? 2 : 0));
+        dvar(qj, ddx);
+        if (is_x && L.soft) dvar(0.0, dde);
+        cert(ddA, loA, hiA, infbits); cert(ddB, loB, hiB, infbits >> 2);
+    }
+    block_reduce<2, 2>(cn, cs, S.red);
+    BTICK(5)
+    // (pc and dc formed again from the first stage's values: kept across the second reduction they are two scalar register pairs more than the
+    //  function has, and the spill lane that takes them is a register of the caller's to save and restore around every check)
+    const double epi = KA.S.eps_prim_inf, edi = KA.S.eps_dual_inf;
+    double s0 = nrm[0], s1 = nrm[1], s2 = nrm[2], s3 = nrm[3];
+    asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3));
+    const bool pc2 = s0 < ea + er * s1, dc2 = s2 < ea + er * s3;
+    if (!pc2 && cn[0] > epi && cs[0] < -epi * cn[0]) return LATW_GENERIC;     // primal infeasibility would need |A' dy|
+    if (!dc2 && cn[1] > edi && cs[1] < -edi * cn[1]) return LATW_GENERIC;     // dual infeasibility would need |P dx| and A dx
     if (tid == 0) S.iflag[3] += 1;
     return LATW_CONTINUE;
 }

@@ -128,7 +128,7 @@ __device__ __forceinline__ unsigned long long *wtick_slots() { __shared__ unsign
 // The boundary between two rounds of the latency round (everything slot 9 covers: termination test, carried transition, hand-over), cut into
 // sections the same way: lane 0 of EVERY wave, cycles since that wave passed the previous section's end.  Slot 8 k + w: section k, wave w; 128 + w:
 // the wave's last clock.  Sections: 0 check entry -> first barrier, 1 the three exchanges, 2 rows and variables, 3 block reduction, 4 solved tail
-// (-> back in the caller where nothing is carried), 5 free (the carry's own entry and first barrier while it was a second call), 6 plant, 7 update
+// (-> back in the caller where nothing is carried), 5 the check's second stage (certificates; unconverged solves only), 6 plant, 7 update
 // and types -> back in the caller, 8 hand-over up to the barrier in front of the next round, 9 a verdict other than 'solved' -> back in the caller.
 __device__ unsigned long long g_bticks[128];
 __device__ __forceinline__ unsigned long long *btick_slots() { __shared__ unsigned long long s[136]; return s; }

@@ -45,7 +45,7 @@ bl = [l for l in txt.splitlines() if l.startswith('boundary cycles')]
 if bl:                                        # (libraries with boundary clocks, mpcqp_layout.h BTICK: the sections of slot 9, lane 0 of each wave, cycles per round)
     g = re.findall(r' s\d((?: \d+)+)', bl[-1])
     arr = np.array([[int(x) for x in s.split()] for s in g], dtype=float) / rounds       # [section, wave]
-    secs = ['check entry', 'exchanges', 'rows+vars', 'reduction', 'solved tail', 'carry entry', 'plant', 'update+types', 'hand-over', 'other verdict']
+    secs = ['check entry', 'exchanges', 'rows+vars', 'reduction', 'solved tail', 'check stage 2', 'plant', 'update+types', 'hand-over', 'other verdict']
     print('   boundary, cycles per round by section (mean over the waves / slowest wave): '
           + '  '.join('%s %.0f/%.0f' % (n, r.mean(), r.max()) for n, r in zip(secs, arr)) + '  | sum of the means %.0f' % arr.mean(axis=1).sum())
 wl = [l for l in txt.splitlines() if l.startswith('wave barrier cycles')]

@@ -248,21 +248,30 @@ class BatchMPCController:
         self._u_last = None
         return res
 
+    def _rollout(self, nsteps, w, Ap, Bp, xref_traj, **form):
+        """The taped loop of every form: the ``prob.rollout*`` that takes the options of ``form`` -- ``model_traj``, ``estimator``, ``L_traj``
+        as the public method has them: which are there says which loop, so that the loop refuses one that is None -- then the controller's books."""
+        model_traj, estimator = form.get('model_traj'), form.get('estimator')
+        if 'estimator' in form:
+            form['estimator'] = _est_dict(estimator)
+        roll = getattr(self.prob, 'rollout' + ('_tv' if 'model_traj' in form else '') + ('_est' if 'estimator' in form else ''))
+        out = roll(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, **form)
+        if model_traj is not None:
+            self._after_schedule(nsteps, model_traj, estimator, form.get('L_traj'))
+        return self._after_loop(out, xref_traj, estimator, count=int(nsteps))
+
     def rollout(self, nsteps, w=None, Ap=None, Bp=None, xref_traj=None):
         """``run`` that keeps a tape (mpcqp_rollout, include/mpcqp_rollout.h): the same loop, the same dict, one closed-loop launch per
         step -- and afterwards ``rollout_adjoint`` differentiates a loss on the whole trajectory in one reverse sweep on the device.  No
         estimator and no model schedule in a taped rollout."""
-        out = self.prob.rollout(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
-        return self._after_loop(out, xref_traj, count=int(nsteps))
+        return self._rollout(nsteps, w, Ap, Bp, xref_traj)
 
     def rollout_tv(self, nsteps, model_traj, w=None, Ap=None, Bp=None, xref_traj=None):
         """``run(model_traj=)`` that keeps a tape (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h): the same loop under the same schedule
         ``model_traj = (Ad [nmodels,B,nx,nx] or None, Bd [nmodels,B,nx,nu] or None, hold)``, the same dict, the controller left with the last
         entry used -- and a tape that remembers every model it was made under, so that ``rollout_adjoint`` can differentiate a loss on the
         trajectory with respect to each schedule entry ('Ad_traj', 'Bd_traj', 'Ap_traj', 'Bp_traj') beside everything else."""
-        out = self.prob.rollout_tv(nsteps, model_traj, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
-        self._after_schedule(nsteps, model_traj)
-        return self._after_loop(out, xref_traj, count=int(nsteps))
+        return self._rollout(nsteps, w, Ap, Bp, xref_traj, model_traj=model_traj)
 
     def rollout_tv_est(self, nsteps, model_traj, estimator, L_traj=None, w=None, Ap=None, Bp=None, xref_traj=None):
         """``run(estimator=, model_traj=, L_traj=)`` that keeps a tape (mpcqp_rollout_tv_est, include_ext2/mpcqp_rollout_tv_est.h): the same
@@ -271,16 +280,13 @@ class BatchMPCController:
         differentiates a loss on states, estimates, inputs and measurements with respect to every schedule entry through its three paths:
         its solves ('Ad_traj', 'Bd_traj'), the plant ('Ap_traj', 'Bp_traj') and the estimator ('Ae_traj', 'Be_traj'), and to every gain
         entry ('L_traj')."""
-        out = self.prob.rollout_tv_est(nsteps, model_traj, _est_dict(estimator), L_traj=L_traj, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
-        self._after_schedule(nsteps, model_traj, estimator, L_traj)
-        return self._after_loop(out, xref_traj, estimator, count=int(nsteps))
+        return self._rollout(nsteps, w, Ap, Bp, xref_traj, model_traj=model_traj, estimator=estimator, L_traj=L_traj)
 
     def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None):
         """``run(estimator=...)`` that keeps a tape (mpcqp_rollout_est, include/mpcqp_rollout_est.h): the output-feedback loop with a
         ``BatchLinearStateEstimator`` -- the same dict (``x, u, status, iter, xhat, y``), ``estimator.x_true`` advanced in place -- and afterwards
         ``rollout_adjoint`` differentiates a loss on states, estimates, inputs and measurements through controller, plant and estimator."""
-        out = self.prob.rollout_est(nsteps, _est_dict(estimator), w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj)
-        return self._after_loop(out, xref_traj, estimator, count=int(nsteps))
+        return self._rollout(nsteps, w, Ap, Bp, xref_traj, estimator=estimator)
 
     def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), batch_sum=False, no_reuse=False, g_xhat=None, g_y=None):
         """Push a loss on the trajectory of the last ``rollout`` back through the closed loop (mpcqp_rollout_adjoint): ``g_x`` [K+1,B,nx] =

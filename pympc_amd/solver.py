@@ -9,6 +9,7 @@
 Arrays may be numpy ndarrays (host) or torch CUDA tensors (device-resident); both are passed as
 raw pointers, PyTorch being used only as a device-memory container.
 """
+import collections
 import ctypes as C
 import math
 
@@ -27,6 +28,10 @@ _POLISH_SETTINGS = ('polish', 'delta', 'polish_refine_iter')
 _FIXED_AT_CREATE = ('rho', 'sigma', 'scaling', 'soft_constraints', 'backend', 'tuning')
 
 _STATUS_STRINGS = {}       # status code -> OSQP's string (filled from mpcqp_status_string on first use)
+
+# the tape a handle holds: its steps, the rows of its references, the outputs of its estimator (0: state feedback), and None or
+# (hold, nseg, the schedule gave Ad, the schedule gave Bd) of the model schedule it was made under
+_Tape = collections.namedtuple('_Tape', 'K rows ny sched')
 
 # the extensions beside include/mpcqp.h: feature -> (is it in the loaded library, what BatchProblem._need says where it is not)
 _FEATURES = dict(
@@ -391,21 +396,26 @@ class BatchProblem:
         return tuple(out)
 
     # -- a rollout with a tape and its reverse sweep (include/mpcqp_rollout.h) ---------------------
-    _rollout_shape = None      # (nsteps, xref rows) of the tape the handle holds
-    _rollout_ny = 0            # > 0: the tape is one of the output-feedback loop (rollout_est)
-    _rollout_tv = None         # (hold, nseg, schedule gave Ad, schedule gave Bd): the tape is one of the loop under a model schedule (rollout_tv)
+    _tape = None               # the _Tape the handle holds (None: none)
     rollout_count = 0          # rollouts made so far (pympc_amd.torch_layer: is the tape still the one of a forward?)
+
+    def _taped_loop(self, nsteps, w, Ap, Bp, out, xref_traj, model_traj=None, estimator=None, L_traj=None):
+        """The taped loop of every form: ``_loop`` through mpcqp_rollout, _est, _tv or _tv_est as the options say, then the record of the tape."""
+        entry = 'mpcqp_rollout' + ('_tv' if model_traj is not None else '') + ('_est' if estimator is not None else '')
+        res = self._loop(entry, nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj, L_traj=L_traj)
+        sched = None
+        if model_traj is not None:
+            hold = int(model_traj[2])
+            sched = (hold, (int(nsteps) + hold - 1) // hold, model_traj[0] is not None, model_traj[1] is not None)
+        self._tape = _Tape(int(nsteps), self._xref_rows_last, int(tuple(estimator['C'].shape)[-2]) if estimator is not None else 0, sched)
+        self.rollout_count += 1
+        return res
 
     def rollout(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
         """``mpc_run`` that keeps a tape (mpcqp_rollout): the same arguments and results, one closed-loop launch per step, and afterwards
         ``rollout_adjoint`` can push a loss on the trajectory back through the loop.  No estimator, no model schedule."""
         self._need('rollout')
-        res = self._loop('mpcqp_rollout', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj)
-        self._rollout_shape = (int(nsteps), self._xref_rows_last)
-        self._rollout_ny = 0
-        self._rollout_tv = None
-        self.rollout_count += 1
-        return res
+        return self._taped_loop(nsteps, w, Ap, Bp, out, xref_traj)
 
     def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None, out=None):
         """``mpc_run(estimator=dict(C=, L=, x_true=, v=))`` that keeps a tape (mpcqp_rollout_est): the same arguments and results
@@ -414,12 +424,7 @@ class BatchProblem:
         self._need('rollout_est')
         if estimator is None:
             raise ValueError('rollout_est: an estimator dict(C=, L=, x_true=, v=) is needed (rollout is the taped loop without one)')
-        res = self._loop('mpcqp_rollout_est', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator)
-        self._rollout_shape = (int(nsteps), self._xref_rows_last)
-        self._rollout_ny = int(tuple(estimator['C'].shape)[-2])
-        self._rollout_tv = None
-        self.rollout_count += 1
-        return res
+        return self._taped_loop(nsteps, w, Ap, Bp, out, xref_traj, estimator=estimator)
 
     def rollout_tv(self, nsteps, model_traj, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
         """``mpc_run(model_traj=)`` that keeps a tape (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h): the same arguments and results, one
@@ -428,13 +433,7 @@ class BatchProblem:
         self._need('rollout_tv')
         if model_traj is None:
             raise ValueError('rollout_tv: a model_traj = (Ad, Bd, hold) is needed (rollout is the taped loop on one model)')
-        res = self._loop('mpcqp_rollout_tv', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, model_traj=model_traj)
-        hold = int(model_traj[2])
-        self._rollout_shape = (int(nsteps), self._xref_rows_last)
-        self._rollout_ny = 0
-        self._rollout_tv = (hold, (int(nsteps) + hold - 1) // hold, model_traj[0] is not None, model_traj[1] is not None)
-        self.rollout_count += 1
-        return res
+        return self._taped_loop(nsteps, w, Ap, Bp, out, xref_traj, model_traj=model_traj)
 
     def mpc_run_tv_est(self, nsteps, model_traj, estimator, L_traj=None, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
         """``mpc_run`` with an estimator AND a model schedule (mpcqp_mpc_loop_tv_est, include_ext2/mpcqp_rollout_tv_est.h): the output-feedback
@@ -453,35 +452,31 @@ class BatchProblem:
         self._need('rollout_tv_est')
         if model_traj is None or estimator is None:
             raise ValueError('rollout_tv_est: a model_traj = (Ad, Bd, hold) and an estimator dict(C=, L=, x_true=, v=) are both needed')
-        res = self._loop('mpcqp_rollout_tv_est', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj, L_traj=L_traj)
-        hold = int(model_traj[2])
-        self._rollout_shape = (int(nsteps), self._xref_rows_last)
-        self._rollout_ny = int(tuple(estimator['C'].shape)[-2])
-        self._rollout_tv = (hold, (int(nsteps) + hold - 1) // hold, model_traj[0] is not None, model_traj[1] is not None)
-        self.rollout_count += 1
-        return res
+        return self._taped_loop(nsteps, w, Ap, Bp, out, xref_traj, model_traj=model_traj, estimator=estimator, L_traj=L_traj)
+
+    def _tape_bytes(self, fn, *sizes):
+        """What the library's ``fn`` says a tape of these sizes takes."""
+        v = C.c_int64()
+        _lib.check(getattr(self._L, fn)(self._h, *[int(s) for s in sizes], C.byref(v)), fn)
+        return v.value
 
     def rollout_tv_est_tape_bytes(self, nsteps, hold, ny):
         """Device memory the tape of ``rollout_tv_est`` takes (mpcqp_rollout_tv_est_tape_bytes)."""
         self._need('rollout_tv_est')
-        v = C.c_int64()
-        _lib.check(self._L.mpcqp_rollout_tv_est_tape_bytes(self._h, int(nsteps), int(hold), int(ny), C.byref(v)), 'mpcqp_rollout_tv_est_tape_bytes')
-        return v.value
+        return self._tape_bytes('mpcqp_rollout_tv_est_tape_bytes', nsteps, hold, ny)
 
     def rollout_tv_est_gain(self, e):
         """The observer gain of schedule entry e on the tape of a ``rollout_tv_est`` as the sweep reads it [B, nx, ny]
         (mpcqp_rollout_tv_est_get_gain; verification)."""
         self._need('rollout_tv_est')
-        Lg = np.empty((self.batch, self.nx, max(self._rollout_ny, 1)))
+        Lg = np.empty((self.batch, self.nx, max(self._tape.ny if self._tape else 0, 1)))
         _lib.check(self._L.mpcqp_rollout_tv_est_get_gain(self._h, int(e), _ptr(Lg)), 'mpcqp_rollout_tv_est_get_gain')
         return Lg
 
     def rollout_tv_tape_bytes(self, nsteps, hold):
         """Device memory the tape of ``nsteps`` steps under a schedule with this ``hold`` takes (mpcqp_rollout_tv_tape_bytes)."""
         self._need('rollout_tv')
-        v = C.c_int64()
-        _lib.check(self._L.mpcqp_rollout_tv_tape_bytes(self._h, int(nsteps), int(hold), C.byref(v)), 'mpcqp_rollout_tv_tape_bytes')
-        return v.value
+        return self._tape_bytes('mpcqp_rollout_tv_tape_bytes', nsteps, hold)
 
     def rollout_tv_slot(self, s):
         """Model slot s of a scheduled tape as the sweep reads it (mpcqp_rollout_tv_get_slot; verification): dict(model [B, model doubles] the
@@ -495,21 +490,16 @@ class BatchProblem:
     def rollout_tape_bytes(self, nsteps, ny=0):
         """Device memory a tape of ``nsteps`` steps takes (mpcqp_rollout_tape_bytes; with ``ny`` outputs: mpcqp_rollout_est_tape_bytes)."""
         self._need('rollout')
-        v = C.c_int64()
         if ny:
             self._need('rollout_est')
-            _lib.check(self._L.mpcqp_rollout_est_tape_bytes(self._h, int(nsteps), int(ny), C.byref(v)), 'mpcqp_rollout_est_tape_bytes')
-            return v.value
-        _lib.check(self._L.mpcqp_rollout_tape_bytes(self._h, int(nsteps), C.byref(v)), 'mpcqp_rollout_tape_bytes')
-        return v.value
+            return self._tape_bytes('mpcqp_rollout_est_tape_bytes', nsteps, ny)
+        return self._tape_bytes('mpcqp_rollout_tape_bytes', nsteps)
 
     def rollout_release(self):
         """Free the tape (mpcqp_rollout_release)."""
         self._need('rollout')
         _lib.check(self._L.mpcqp_rollout_release(self._h), 'mpcqp_rollout_release')
-        self._rollout_shape = None
-        self._rollout_ny = 0
-        self._rollout_tv = None
+        self._tape = None
 
     def rollout_adjoint(self, g_x=None, g_u=None, want=('lam', 'uminus1', 'uref', 'xref'), out=None, batch_sum=False, no_reuse=False, g_xhat=None, g_y=None):
         """The reverse sweep over the tape of the last ``rollout`` (mpcqp_rollout_adjoint): for ``g_x`` [K+1, B, nx] = dL/dx_k and / or
@@ -531,25 +521,27 @@ class BatchProblem:
         'Ae_traj' [nseg, B, nx, nx], 'Be_traj' [nseg, B, nx, nu], 'L_traj' [nseg, B, nx, ny] -- the estimator path of the steps entry e was in
         force; 'Ae', 'Be', 'L' are their sums over the entries."""
         self._need('rollout')
-        ny = self._rollout_ny
-        tv_names = ('Ad_traj', 'Bd_traj', 'Ap_traj', 'Bp_traj')
-        tv_est_names = ('Ae_traj', 'Be_traj', 'L_traj')
-        if self._rollout_shape is not None and not (self._rollout_tv is not None and ny) and any(k in tv_est_names for k in want):
-            raise RuntimeError('rollout_adjoint: the gradients %s need the tape of a rollout_tv_est' % ', '.join(tv_est_names))
-        if self._rollout_shape is not None and self._rollout_tv is None and any(k in tv_names for k in want):
-            raise RuntimeError('rollout_adjoint: the gradients %s need the tape of a rollout_tv (this one was made on one model)' % ', '.join(tv_names))
-        if self._rollout_shape is not None and self._rollout_tv is not None:
-            if not ny and (g_xhat is not None or g_y is not None):
-                raise RuntimeError('rollout_adjoint: g_xhat, g_y need the tape of a rollout_est (this one has no estimator)')
-            return self._rollout_adjoint_tv(g_x, g_u, want, out, batch_sum, no_reuse, g_xhat, g_y)
-        est_names = ('eta', 'C', 'L', 'v', 'Ae', 'Be')
-        if self._rollout_shape is not None and not ny and (g_xhat is not None or g_y is not None or any(k in est_names for k in want)):
-            raise RuntimeError('rollout_adjoint: g_xhat, g_y and the gradients %s need the tape of a rollout_est (this one has no estimator)' % ', '.join(est_names))
-        if g_x is None and g_u is None and g_xhat is None and g_y is None:
+        tape = self._tape
+        ny, sched = (tape.ny, tape.sched) if tape is not None else (0, None)
+        est_seeds = g_xhat is not None or g_y is not None
+        tv_est_names, tv_names, est_names = ('Ae_traj', 'Be_traj', 'L_traj'), ('Ad_traj', 'Bd_traj', 'Ap_traj', 'Bp_traj'), ('eta', 'C', 'L', 'v', 'Ae', 'Be')
+        named = lambda names: any(k in names for k in want)
+        # (what was asked for, what the tape must have for it, what is said where it has not); on a scheduled tape without an estimator the
+        # estimator's gradients are unknown names like any other
+        refusals = ((named(tv_est_names), sched is not None and ny, 'the gradients %s need the tape of a rollout_tv_est' % ', '.join(tv_est_names)),
+                    (named(tv_names), sched is not None, 'the gradients %s need the tape of a rollout_tv (this one was made on one model)' % ', '.join(tv_names)),
+                    (est_seeds and sched is not None, ny, 'g_xhat, g_y need the tape of a rollout_est (this one has no estimator)'),
+                    ((est_seeds or named(est_names)) and sched is None, ny,
+                     'g_xhat, g_y and the gradients %s need the tape of a rollout_est (this one has no estimator)' % ', '.join(est_names)))
+        for asked, has, msg in refusals:
+            if tape is not None and asked and not has:
+                raise RuntimeError('rollout_adjoint: ' + msg)
+        if g_x is None and g_u is None and not est_seeds:
             raise ValueError('rollout_adjoint: give g_x, g_u or both' + (', or g_xhat, g_y' if ny else ''))
-        if self._rollout_shape is None:
+        if tape is None:
             raise RuntimeError('rollout_adjoint: no rollout has been made (mpcqp_rollout)')
-        K, rows = self._rollout_shape
+        self._need('rollout' + ('_tv' if sched is not None else '') + ('_est' if ny else ''))
+        K, rows = tape.K, tape.rows
         B, nx, nu = self.batch, self.nx, self.nu
         like = next(g for g in (g_x, g_u, g_xhat, g_y) if g is not None)
         gx = _prep(g_x, (K + 1, B, nx), 'g_x') if g_x is not None else None
@@ -574,63 +566,18 @@ class BatchProblem:
         bounds = any(k in btable for k in want)
         if bounds:
             self._need('adjoint_bounds')
-        res = self._grads_out(want, table, out, like)
-        self._keep = [gx, gu, gxh, gy, res]
-        if bounds:
-            if ny:
-                self._need('rollout_est')
-            _lib.check(self._L.mpcqp_rollout_adjoint_bounds(self._h, C.byref(io), C.byref(eo) if ny else None, C.byref(mo), C.byref(bo)), 'mpcqp_rollout_adjoint_bounds')
-        elif ny:
-            self._need('rollout_est')
-            _lib.check(self._L.mpcqp_rollout_adjoint_est(self._h, C.byref(io), C.byref(eo), C.byref(mo)), 'mpcqp_rollout_adjoint_est')
-        else:
-            _lib.check(self._L.mpcqp_rollout_adjoint(self._h, C.byref(io), C.byref(mo)), 'mpcqp_rollout_adjoint')
-        return res
-
-    def _rollout_adjoint_tv(self, g_x, g_u, want, out, batch_sum, no_reuse, g_xhat=None, g_y=None):
-        """``rollout_adjoint`` on the tape of a ``rollout_tv``: one mpcqp_rollout_adjoint_tv, then the per-slot gradients put together
-        (views and sums of the call's own buffers: ``out`` serves the other names only).  On the tape of a ``rollout_tv_est``: one
-        mpcqp_rollout_adjoint_tv_est, with the estimator's seeds and its per-entry gradients handled the same way."""
-        ny = self._rollout_ny
-        self._need('rollout_tv_est' if ny else 'rollout_tv')
-        if g_x is None and g_u is None and g_xhat is None and g_y is None:
-            raise ValueError('rollout_adjoint: give g_x, g_u or both' + (', or g_xhat, g_y' if ny else ''))
-        K, rows = self._rollout_shape
-        hold, nseg, gave_Ad, gave_Bd = self._rollout_tv
-        B, nx, nu = self.batch, self.nx, self.nu
-        like = next(g for g in (g_x, g_u, g_xhat, g_y) if g is not None)
-        gx = _prep(g_x, (K + 1, B, nx), 'g_x') if g_x is not None else None
-        gu = _prep(g_u, (K, B, nu), 'g_u') if g_u is not None else None
-        gxh = _prep(g_xhat, (K + 1, B, nx), 'g_xhat') if g_xhat is not None else None
-        gy = _prep(g_y, (K, B, ny), 'g_y') if g_y is not None else None
-        io = _lib.RolloutAdjointIO()
-        io.struct_size, io.no_reuse = C.sizeof(_lib.RolloutAdjointIO), int(bool(no_reuse))
-        io.G_x, io.G_u = _ptr(gx), _ptr(gu)
-        table = dict(lam=(io, 'lam', (K + 1, B, nx)), uminus1=(io, 'd_uminus1', (B, nu)), uref=(io, 'd_uref', (B, nu)), xref=(io, 'd_xref', (K, B, rows * nx)))
-        eo = _lib.RolloutEstIO()
-        eo.struct_size = C.sizeof(_lib.RolloutEstIO)
-        eo.G_xhat, eo.G_y = _ptr(gxh), _ptr(gy)
-        if ny:
-            table.update(eta=(eo, 'eta', (K + 1, B, nx)), C=(eo, 'd_C', (B, ny, nx)), v=(eo, 'd_v', (K, B, ny)))
-        mo, mtable = self._model_grads(batch_sum)
-        table.update({k: v for k, v in mtable.items() if k not in ('Ad', 'Bd')})
-        bo, btable = self._bound_grads(batch_sum)
-        table.update(btable)
-        if any(k in btable for k in want):
-            self._need('adjoint_bounds')
-        # what the schedule splits: name -> (field of mpcqp_rollout_tv_io, its leading dimension, how the answer is read from it)
-        whole = lambda gave: (lambda a: a[0] if gave else a.sum(0))
-        split = dict(Ad_traj=('d_Ad_slots', nseg + 1, nx, lambda a: a[1:]), Bd_traj=('d_Bd_slots', nseg + 1, nu, lambda a: a[1:]),
-                     Ap_traj=('d_Ap_entries', nseg, nx, lambda a: a), Bp_traj=('d_Bp_entries', nseg, nu, lambda a: a),
-                     Ad=('d_Ad_slots', nseg + 1, nx, whole(gave_Ad)), Bd=('d_Bd_slots', nseg + 1, nu, whole(gave_Bd)),
-                     Ap=('d_Ap_entries', nseg, nx, lambda a: a.sum(0)), Bp=('d_Bp_entries', nseg, nu, lambda a: a.sum(0)))
-        to = _lib.RolloutTVIO()
-        to.struct_size = C.sizeof(_lib.RolloutTVIO)
-        xo = _lib.RolloutTVEstIO()
-        xo.struct_size = C.sizeof(_lib.RolloutTVEstIO)
-        if ny:                                    # (the estimator path, per entry: the names of rollout_est are the sums over the entries)
-            split.update(Ae_traj=('d_Ae_entries', nseg, nx, lambda a: a), Be_traj=('d_Be_entries', nseg, nu, lambda a: a), L_traj=('d_L_entries', nseg, ny, lambda a: a),
-                         Ae=('d_Ae_entries', nseg, nx, lambda a: a.sum(0)), Be=('d_Be_entries', nseg, nu, lambda a: a.sum(0)), L=('d_L_entries', nseg, ny, lambda a: a.sum(0)))
+        # what a schedule splits: name -> (field of mpcqp_rollout_tv_io / _tv_est_io, its leading dimension, its columns, how the answer is read
+        # from it).  These names are views and sums of the call's own per-slot / per-entry buffers: ``out`` serves the other names only
+        split, to, xo = {}, _lib.RolloutTVIO(), _lib.RolloutTVEstIO()
+        to.struct_size, xo.struct_size = C.sizeof(_lib.RolloutTVIO), C.sizeof(_lib.RolloutTVEstIO)
+        if sched is not None:
+            _, nseg, gave_Ad, gave_Bd = sched
+            entries, total = (lambda a: a), (lambda a: a.sum(0))
+            whole = lambda gave: (lambda a: a[0] if gave else a.sum(0))      # (slot 0: the model the call began with; a matrix the schedule left alone never changed)
+            split = dict(Ad_traj=('d_Ad_slots', nseg + 1, nx, lambda a: a[1:]), Bd_traj=('d_Bd_slots', nseg + 1, nu, lambda a: a[1:]),
+                         Ad=('d_Ad_slots', nseg + 1, nx, whole(gave_Ad)), Bd=('d_Bd_slots', nseg + 1, nu, whole(gave_Bd)))
+            for k, cols in (('Ap', nx), ('Bp', nu)) + ((('Ae', nx), ('Be', nu), ('L', ny)) if ny else ()):      # (per entry; the unsuffixed name: the sum over the entries)
+                split[k + '_traj'], split[k] = ('d_%s_entries' % k, nseg, cols, entries), ('d_%s_entries' % k, nseg, cols, total)
         bufs = {}
         for k in want:
             if k in split and split[k][0] not in bufs:
@@ -639,10 +586,14 @@ class BatchProblem:
                 setattr(xo if hasattr(xo, field) else to, field, _ptr(bufs[field]))
         res = self._grads_out([k for k in want if k not in split], table, out, like)
         self._keep = [gx, gu, gxh, gy, res, bufs]
-        if ny:
-            _lib.check(self._L.mpcqp_rollout_adjoint_tv_est(self._h, C.byref(io), C.byref(eo), C.byref(mo), C.byref(bo), C.byref(to), C.byref(xo)), 'mpcqp_rollout_adjoint_tv_est')
+        # which C function, with which structs (None: not passed)
+        if sched is not None:
+            fn, structs = ('mpcqp_rollout_adjoint_tv_est', (io, eo, mo, bo, to, xo)) if ny else ('mpcqp_rollout_adjoint_tv', (io, mo, bo, to))
+        elif bounds:
+            fn, structs = 'mpcqp_rollout_adjoint_bounds', (io, eo if ny else None, mo, bo)
         else:
-            _lib.check(self._L.mpcqp_rollout_adjoint_tv(self._h, C.byref(io), C.byref(mo), C.byref(bo), C.byref(to)), 'mpcqp_rollout_adjoint_tv')
+            fn, structs = ('mpcqp_rollout_adjoint_est', (io, eo, mo)) if ny else ('mpcqp_rollout_adjoint', (io, mo))
+        _lib.check(getattr(self._L, fn)(self._h, *[None if s is None else C.byref(s) for s in structs]), fn)
         for k in want:
             if k in split:
                 a = bufs[split[k][0]]
@@ -653,9 +604,9 @@ class BatchProblem:
         """(n_active [K, B], n_weak [K, B], status [K, B], n_factor [B]) int32 of the last ``rollout_adjoint`` (mpcqp_get_rollout_info;
         synchronises): per tape entry as ``adjoint_info``; n_factor: the factorizations the sweep made."""
         self._need('rollout')
-        if self._rollout_shape is None:
+        if self._tape is None:
             raise RuntimeError('rollout_info: no rollout has been made (mpcqp_rollout)')
-        K = self._rollout_shape[0]
+        K = self._tape.K
         out = [np.zeros((K, self.batch), dtype=np.int32) for _ in range(3)] + [np.zeros(self.batch, dtype=np.int32)]
         _lib.check(self._L.mpcqp_get_rollout_info(self._h, *[_ptr(o) for o in out]), 'mpcqp_get_rollout_info')
         return tuple(out)
@@ -664,14 +615,14 @@ class BatchProblem:
         """Tape entry k (mpcqp_rollout_get_tape; verification): dict(x [B, n], z, y [B, m], step [B, nx + nu + rows*nx] = (x_k | the u_{-1}
         the solve was made with | xref), status [B])."""
         self._need('rollout')
-        if self._rollout_shape is None:
+        if self._tape is None:
             raise RuntimeError('rollout_tape: no rollout has been made (mpcqp_rollout)')
-        B, rows = self.batch, self._rollout_shape[1]
+        B, rows, ny = self.batch, self._tape.rows, self._tape.ny
         r = dict(x=np.empty((B, self.n)), z=np.empty((B, self.m)), y=np.empty((B, self.m)),
                  step=np.empty((B, self.nx + self.nu + rows * self.nx)), status=np.zeros(B, dtype=np.int32))
         _lib.check(self._L.mpcqp_rollout_get_tape(self._h, int(k), *[_ptr(r[n]) for n in ('x', 'z', 'y', 'step', 'status')]), 'mpcqp_rollout_get_tape')
-        if self._rollout_ny:                      # (a rollout_est: the step data begin with the estimate, the plant state and the measurement are beside it)
-            r.update(x_plant=np.empty((B, self.nx)), y_meas=np.empty((B, self._rollout_ny)))
+        if ny:                                    # (a rollout_est: the step data begin with the estimate, the plant state and the measurement are beside it)
+            r.update(x_plant=np.empty((B, self.nx)), y_meas=np.empty((B, ny)))
             _lib.check(self._L.mpcqp_rollout_get_tape_est(self._h, int(k), _ptr(r['x_plant']), _ptr(r['y_meas'])), 'mpcqp_rollout_get_tape_est')
         return r
 

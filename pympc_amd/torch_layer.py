@@ -24,6 +24,13 @@ is the container of the device buffers and the owner of the graph; no torch oper
   Dumax, each [B, nx | nu] or unbatched [nx | nu].  They go under the controller in the same ``update_model`` call as ``params``; backward
   asks the same one adjoint call (mpcqp_adjoint_bounds / mpcqp_rollout_adjoint_bounds, include/mpcqp_adjoint_bounds.h) for their
   gradients too: the multipliers of the active rows summed onto the bound each sits on, zero for a bound that is nowhere active.
+
+A closed-loop rollout is one differentiable operation in four forms -- ``mpc_rollout`` (state feedback on one model), ``mpc_rollout_est``
+(output feedback), ``mpc_rollout_tv`` (under a model schedule), ``mpc_rollout_tv_est`` (both) -- which are one description: each Function
+states its inputs and which options are present, ``_rollout_forward`` makes the taped loop of ``BatchProblem`` they pick, ``_rollout_backward``
+asks ONE ``rollout_adjoint`` call for exactly the gradients torch needs, and ``_model_paths`` is the rule by which the gradient of a model
+matrix is added up from its solve, estimator and plant paths.  The Riccati equations (``dare``, ``dre``) and the Kalman gains made of them
+are differentiable operations of their own at the end of the file.
 """
 import contextlib
 
@@ -34,7 +41,7 @@ MODEL_PARAMS = ('Ad', 'Bd', 'Qx', 'QxN', 'Qu', 'QDu')
 BOUND_PARAMS = ('xmin', 'xmax', 'umin', 'umax', 'Dumin', 'Dumax')      # (the outputs of mpcqp_adjoint_bounds_io: pympc_amd._lib.ADJOINT_BOUNDS_NAMES)
 
 
-# ---- what the three Functions share ----------------------------------------------------------------------------------------------------
+# ---- what the step and the four rollouts share ------------------------------------------------------------------------------------------
 @contextlib.contextmanager
 def _ordered(K):
     """The library works on the controller's stream: unless that IS torch's current stream, the two are ordered by waiting, torch's work
@@ -85,26 +92,31 @@ def _put_params(ctx, K, names, params):
     ctx.names, ctx.pshapes = names, tuple(tuple(p.shape) for p in params)
 
 
-def _param_want(ctx, needs):
+def _param_want(ctx, needs, also=()):
     """(the parameters, bounds among them, that need a gradient, which parameters are unbatched, batch_sum).  One model for the whole batch: the device adds the
-    instances' gradients up (a mixture of shared and per-instance parameters takes them per instance and adds the shared ones' here)."""
+    instances' gradients up (a mixture of shared and per-instance parameters takes them per instance and adds the shared ones' here).
+    ``also``: is it unbatched, for every other input whose gradient ``batch_sum`` would sum -- under a schedule, whatever ``rollout_adjoint`` puts
+    together from per-entry buffers."""
     pneed = [n for n, need in zip(ctx.names, needs) if need]
     shared = {n: len(shp) == (1 if n in BOUND_PARAMS else 2) for n, shp in zip(ctx.names, ctx.pshapes)}
-    return pneed, shared, bool(pneed) and all(shared[n] for n in pneed)
+    return pneed, shared, bool(pneed or also) and all(shared[n] for n in pneed) and all(also)
 
 
-def _param_grads(ctx, res, pneed, shared, batch_sum, paths=()):
-    """The gradient of every parameter, None where none is needed.  ``paths``: pairs of further gradients of ``res`` -- per instance, an Ad-like
-    and a Bd-like one -- that are paths into Ad / Bd too (the plant where the controller's model is the plant, the estimator): added on."""
+def _param_grads(ctx, res, pneed, shared, batch_sum, paths={}, sched=False):
+    """The gradient of every parameter, None where none is needed.  ``paths``: parameter -> the gradients of ``res`` whose sum, in their order,
+    is its own (Ad and Bd of a rollout: ``_model_paths``); any other parameter's is the one under its name.
+    An unbatched parameter gets the sum over the batch, and which sweep returns what decides how it is read.  With ``batch_sum`` every adjoint
+    call returns the model's and the bounds' gradients summed on the device, [1, ...]: ``p[0]``.  The plant's and the estimator's paths ('Ap',
+    'Ae', ...) come summed only from the sweep under a schedule (``sched``), where ``BatchProblem.rollout_adjoint`` puts them together from
+    per-entry buffers; the unscheduled sweep returns them per instance whatever ``batch_sum`` says: ``p.sum(dim=0)``."""
     pgrads = []
     for n, shp in zip(ctx.names, ctx.pshapes):
-        v = res.get(n) if n in pneed else None
-        if v is not None:
-            v = (v[0] if batch_sum else v.sum(dim=0)) if shared[n] else v
-            for a, b in paths if n in ('Ad', 'Bd') else ():
-                p = res[a if n == 'Ad' else b]
-                v = v + (p.sum(dim=0) if shared[n] else p)
-            v = v.reshape(shp)
+        v = None
+        for g in paths.get(n, [n]) if n in pneed else ():
+            p = res[g]
+            if shared[n]:
+                p = p[0] if batch_sum and (sched or g == n) else p.sum(dim=0)
+            v = p.reshape(shp) if v is None else v + p.reshape(shp)
         pgrads.append(v)
     return pgrads
 
@@ -160,65 +172,116 @@ _ROLLOUT_INPUTS = dict(
     u_prev=('uminus1', lambda v, shp: v), xref=('xref', lambda v, shp: v.sum(dim=0)), C=('C', _per), L=('L', _per), Ap=('Ap', _per), Bp=('Bp', _per))
 
 
-def _rollout_forward(ctx, K, nsteps, x_first, u_prev, xref, names, params, roll, inputs):
-    """``update_model`` of the parameters, ``update(x_first, u_prev, xref)`` with its solve (tape entry 0), then ``roll(new, st, it)`` -- the
-    taped loop, which makes its trajectories with ``new(rows, cols)``, fills the status and iteration tensors and returns (the last state
-    the controller saw, U, what forward returns) -- and the controller's and the context's books.  ``inputs``: forward's tensor inputs."""
+def _model_paths(est, sched, follows, given_Ad=False, given_Bd=False):
+    """Which gradients of ``rollout_adjoint`` add up, in this order, to the gradient of each input that is a model matrix -- a pure rule.
+    Ad (Bd likewise) has up to three paths: the solves made under it ('Ad'), the estimator where there is one (``est``: 'Ae') and the plant
+    where it follows the controller's model (``follows``: 'Ap').  Under a schedule (``sched``) that gave the matrix, entry e of ``Ad_traj``
+    collects the three of the steps it was in force ('Ad_traj', 'Ae_traj', 'Ap_traj'), and ``params['Ad']``, the model the rollout began
+    with, is left with the first solve's share; a matrix the schedule did not give never changed, so the parameter collects all of them,
+    summed over the entries, as it does without a schedule."""
+    paths = {}
+    for m, given in (('A', given_Ad), ('B', given_Bd)):
+        of = lambda suffix: [m + 'd' + suffix] + ([m + 'e' + suffix] if est else []) + ([m + 'p' + suffix] if follows else [])
+        per_entry = bool(sched and given)
+        paths[m + 'd_traj'] = of('_traj') if per_entry else []
+        paths[m + 'd'] = [m + 'd'] if per_entry else of('')
+    return paths
+
+
+def _rollout_forward(ctx, fn, K, nsteps, inputs, names, params, hold=None):
+    """Forward of every form.  ``inputs``: forward's tensor inputs by name, in its order behind (K, nsteps[, hold]) -- keys of _ROLLOUT_INPUTS
+    and, under a schedule (``hold``), 'Ad_traj', 'Bd_traj' and, with an estimator ('C' is among them), 'L_traj'.  ``update_model`` of the
+    parameters, ``update(x0 or xhat0, u_prev, xref)`` with its solve (tape entry 0), then the taped loop of ``BatchProblem`` the options pick,
+    and the controller's and the context's books."""
+    x0 = inputs['x0']
+    if not x0.is_cuda:
+        raise ValueError('%s works on device tensors (x0 is on %s)' % (fn, x0.device))
+    est, sched = 'C' in inputs, hold is not None
+    B, nx, nu = K.B, K.nx, K.nu
     with _ordered(K):
         _put_params(ctx, K, names, params)
-        xr = _det(xref)
-        K.update(_det(x_first), _det(u_prev), None if xr is None else xr.reshape(K.B, -1))
-        new = lambda rows, cols: torch.empty((rows, K.B, cols), dtype=torch.float64, device=x_first.device)
-        st, it = (torch.empty((nsteps, K.B), dtype=torch.int32, device=x_first.device) for _ in range(2))
-        last, U, ret = roll(new, st, it)
+        xr = _det(inputs['xref'])
+        K.update(_det(inputs['xhat0'] if est else x0), _det(inputs['u_prev']), None if xr is None else xr.reshape(B, -1))
+        new = lambda rows, cols: torch.empty((rows, B, cols), dtype=torch.float64, device=x0.device)
+        st, it = (torch.empty((nsteps, B), dtype=torch.int32, device=x0.device) for _ in range(2))
+        X, U = new(nsteps + 1, nx), new(nsteps, nu)
+        out, more = [X, U, st, it], {}
+        if est:
+            ny = int(inputs['C'].shape[-2])
+            XH, Y = new(nsteps + 1, nx), new(nsteps, ny)
+            out += [XH, Y]
+            more['estimator'] = dict(C=_bc(inputs['C'], (B, ny, nx)), L=_bc(inputs['L'], (B, nx, ny)), x_true=_det(x0).clone(), v=_det(inputs['v']))
+        if sched:
+            nseg = ctx.nseg = (nsteps + hold - 1) // hold
+            # [nseg, B, ., .] of the entries in force (entry e of an unbatched schedule is one model, one gain, for the whole batch)
+            entries = lambda t: None if t is None else _det(t)[:nseg].reshape((nseg, -1) + tuple(t.shape[-2:])).expand((nseg, B) + tuple(t.shape[-2:])).contiguous()
+            last = dict(Ad=entries(inputs['Ad_traj']), Bd=entries(inputs['Bd_traj']))
+            more['model_traj'] = (last['Ad'], last['Bd'], hold)
+            if est:
+                more['L_traj'] = entries(inputs['L_traj'])
+        roll = getattr(K.prob, 'rollout' + ('_tv' if sched else '') + ('_est' if est else ''))
+        roll(nsteps, w=_det(inputs['w']), Ap=_bc(inputs['Ap'], (B, nx, nx)), Bp=_bc(inputs['Bp'], (B, nx, nu)), out=out, **more)
+        for n, t in last.items() if sched else ():             # the controller is left with the last entry used: read back when somebody asks (update_model's way)
+            if t is not None:
+                K.__dict__.pop(n, None)
+                K._on_device[n] = t[nseg - 1]
         K.solve_count += nsteps
-        K.x0_rh, K.uminus1_rh, K._um1_on_device, K._u_last = last, U[-1], True, None
+        K.x0_rh, K.uminus1_rh, K._um1_on_device, K._u_last = (XH if est else X)[-1], U[-1], True, None
     ctx.K, ctx.count = K, K.prob.rollout_count
-    ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in inputs)
+    ctx.fn, ctx.est, ctx.sched = fn, est, sched
+    ctx.inputs, ctx.shapes = tuple(inputs), tuple(None if t is None else tuple(t.shape) for t in inputs.values())
     ctx.status, ctx.iters = st, it
-    return ret
+    return (X, XH, Y, U) if est else (X, U)
 
 
-def _rollout_backward(ctx, fn, inputs, seeds, est):
-    """One ``rollout_adjoint`` call for exactly the gradients torch needs.  ``inputs``: the names of the tensor inputs (keys of
-    _ROLLOUT_INPUTS) in forward's order behind (K, nsteps) and before ``names``; ``seeds``: rollout_adjoint's, by name; ``est``: the tape
-    is one of the output-feedback loop."""
-    K = ctx.K
+def _rollout_backward(ctx, **seeds):
+    """Backward of every form: one ``rollout_adjoint`` call, with its ``seeds`` by name, for exactly the gradients torch needs."""
+    K, fn, inputs, est, sched = ctx.K, ctx.fn, ctx.inputs, ctx.est, ctx.sched
     if K.prob.rollout_count != ctx.count:
         raise RuntimeError('%s: the controller has been rolled out again since this forward (rollout %d then, %d now); '
                            'its tape is no longer the one to differentiate.' % (fn, ctx.count, K.prob.rollout_count))
-    ni = 2 + len(inputs)
-    need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[2:ni], ctx.shapes)}
+    first = 3 if sched else 2                              # (K, nsteps[, hold]) stand before the tensor inputs, ``names`` behind them
+    ni = first + len(inputs)
+    need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[first:ni], ctx.shapes)}
     shape = dict(zip(inputs, ctx.shapes))
-    pneed, shared, batch_sum = _param_want(ctx, ctx.needs_input_grad[ni + 1:])
+    traj = [n for n in inputs if n.endswith('_traj')]
+    unbatched = lambda n: len(shape[n]) == (3 if n in traj else 2)
+    # (under a schedule rollout_adjoint puts these together from per-entry buffers, and batch_sum sums them too)
+    split = [n for n in traj + ['Ap', 'Bp', 'L'] if need.get(n)] if sched else []
+    pneed, shared, batch_sum = _param_want(ctx, ctx.needs_input_grad[ni + 1:], [unbatched(n) for n in split])
     if not any(need.values()) and not pneed:
         return (None,) * (ni + 1 + len(ctx.names))
-    # Ad, Bd are the estimator's model too, and without Ap, Bp the plant's: one parameter with up to three paths, of which the estimator's and
-    # the plant's come back on their own
-    paths = ((('Ae', 'Be'),) if est else ()) + ((('Ap', 'Bp'),) if shape['Ap'] is None else ())
-    want = list(dict.fromkeys(_ROLLOUT_INPUTS[n][0] for n in inputs if need[n]))
-    want += [g for pair in paths for g, m in zip(pair, ('Ad', 'Bd')) if m in pneed] + pneed
+    paths = _model_paths(est, sched, shape['Ap'] is None, shape.get('Ad_traj') is not None, shape.get('Bd_traj') is not None)
+    paths['L_traj'] = ['L_traj']
+    want = [_ROLLOUT_INPUTS[n][0] for n in inputs if need[n] and n not in traj]
+    want += [g for n in traj if need[n] for g in paths[n]] + [g for n in pneed for g in paths.get(n, [n])]
     with _ordered(K):
-        res = K.prob.rollout_adjoint(want=want, batch_sum=batch_sum, **{k: g.to(torch.float64).contiguous() for k, g in seeds.items()})
-    grads = [_ROLLOUT_INPUTS[n][1](res[_ROLLOUT_INPUTS[n][0]], shape[n]).reshape(shape[n]) if need[n] else None for n in inputs]
-    return (None, None) + tuple(grads) + (None,) + tuple(_param_grads(ctx, res, pneed, shared, batch_sum, paths))
+        res = K.prob.rollout_adjoint(want=list(dict.fromkeys(want)), batch_sum=batch_sum, **{k: g.to(torch.float64).contiguous() for k, g in seeds.items()})
+    grads = []
+    for n in inputs:
+        v = None
+        if need[n] and n in traj:                          # entry e: its paths added up, then the batch where the schedule is unbatched
+            v = res[paths[n][0]]
+            for g in paths[n][1:]:
+                v = v + res[g]
+            v = (v.sum(dim=1) if unbatched(n) else v)[:ctx.nseg]
+            if shape[n][0] > ctx.nseg:                     # entries beyond ceil(nsteps / hold) were never in force
+                v = torch.cat([v, v.new_zeros((shape[n][0] - ctx.nseg,) + tuple(v.shape[1:]))])
+            v = v.reshape(shape[n])
+        elif need[n]:
+            v = _ROLLOUT_INPUTS[n][1](res[_ROLLOUT_INPUTS[n][0]], shape[n]).reshape(shape[n])
+        grads.append(v)
+    return (None,) * first + tuple(grads) + (None,) + tuple(_param_grads(ctx, res, pneed, shared, batch_sum, paths, sched))
 
 
 class _MPCRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, K, nsteps, x0, u_prev, xref, w, Ap, Bp, names, *params):
-        if not x0.is_cuda:
-            raise ValueError('mpc_rollout works on device tensors (x0 is on %s)' % x0.device)
-
-        def roll(new, st, it):
-            X, U = new(nsteps + 1, K.nx), new(nsteps, K.nu)
-            K.prob.rollout(nsteps, w=_det(w), Ap=_bc(Ap, (K.B, K.nx, K.nx)), Bp=_bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it])
-            return X[-1], U, (X, U)
-        return _rollout_forward(ctx, K, nsteps, x0, u_prev, xref, names, params, roll, (x0, u_prev, xref, w, Ap, Bp))
+        return _rollout_forward(ctx, 'mpc_rollout', K, nsteps, dict(x0=x0, u_prev=u_prev, xref=xref, w=w, Ap=Ap, Bp=Bp), names, params)
 
     @staticmethod
     def backward(ctx, grad_X, grad_U):
-        return _rollout_backward(ctx, 'mpc_rollout', ('x0', 'u_prev', 'xref', 'w', 'Ap', 'Bp'), dict(g_x=grad_X, g_u=grad_U), False)
+        return _rollout_backward(ctx, g_x=grad_X, g_u=grad_U)
 
 
 def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None, bounds=None):
@@ -240,67 +303,12 @@ def mpc_rollout(controller, x0, nsteps, u_prev=None, xref=None, w=None, Ap=None,
 class _MPCRolloutTV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, K, nsteps, hold, x0, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, names, *params):
-        if not x0.is_cuda:
-            raise ValueError('mpc_rollout_tv works on device tensors (x0 is on %s)' % x0.device)
-        nseg = (nsteps + hold - 1) // hold
-
-        def roll(new, st, it):
-            X, U = new(nsteps + 1, K.nx), new(nsteps, K.nu)
-            # (entry e of an unbatched schedule is one model for the whole batch)
-            sched = [None if t is None else _det(t)[:nseg].reshape((nseg, -1) + tuple(t.shape[-2:])).expand((nseg, K.B) + tuple(t.shape[-2:])).contiguous()
-                     for t in (Ad_traj, Bd_traj)]
-            K.prob.rollout_tv(nsteps, (sched[0], sched[1], hold), w=_det(w), Ap=_bc(Ap, (K.B, K.nx, K.nx)), Bp=_bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it])
-            for n, t in zip(('Ad', 'Bd'), sched):             # the controller is left with the last entry used: read back when somebody asks (update_model's way)
-                if t is not None:
-                    K.__dict__.pop(n, None)
-                    K._on_device[n] = t[nseg - 1]
-            return X[-1], U, (X, U)
-        ctx.nseg = nseg
-        return _rollout_forward(ctx, K, nsteps, x0, u_prev, xref, names, params, roll, (x0, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj))
+        inputs = dict(x0=x0, u_prev=u_prev, xref=xref, w=w, Ap=Ap, Bp=Bp, Ad_traj=Ad_traj, Bd_traj=Bd_traj)
+        return _rollout_forward(ctx, 'mpc_rollout_tv', K, nsteps, inputs, names, params, hold)
 
     @staticmethod
     def backward(ctx, grad_X, grad_U):
-        K = ctx.K
-        if K.prob.rollout_count != ctx.count:
-            raise RuntimeError('mpc_rollout_tv: the controller has been rolled out again since this forward (rollout %d then, %d now); '
-                               'its tape is no longer the one to differentiate.' % (ctx.count, K.prob.rollout_count))
-        inputs = ('x0', 'u_prev', 'xref', 'w', 'Ap', 'Bp', 'Ad_traj', 'Bd_traj')
-        ni = 3 + len(inputs)
-        need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[3:ni], ctx.shapes)}
-        shape = dict(zip(inputs, ctx.shapes))
-        pneed, shared, _ = _param_want(ctx, ctx.needs_input_grad[ni + 1:])
-        if not any(need.values()) and not pneed:
-            return (None,) * (ni + 1 + len(ctx.names))
-        follows = shape['Ap'] is None                        # the plant followed the schedule: its path belongs to the model in force
-        # a matrix the schedule gave gets the plant's path entry by entry; one it did not give never changed: params' matrix gets all of it
-        plant = {'Ad_traj': 'Ap_traj', 'Bd_traj': 'Bp_traj', 'Ad': 'Ap', 'Bd': 'Bp'}
-        left = {'Ad': shape['Ad_traj'] is None, 'Bd': shape['Bd_traj'] is None}
-        split = [n for n in ('Ad_traj', 'Bd_traj', 'Ap', 'Bp') if need[n]] + [n for n in ('Ad', 'Bd') if n in pneed]
-        unbatched = lambda n: len(shape[n]) == (3 if n.endswith('_traj') else 2) if n in shape else shared[n]
-        batch_sum = bool(split or pneed) and all(unbatched(n) for n in split) and all(shared[n] for n in pneed)
-        want = list(dict.fromkeys(_ROLLOUT_INPUTS[n][0] for n in inputs[:6] if need[n]))
-        want += [n for n in ('Ad_traj', 'Bd_traj') if need[n]] + pneed
-        if follows:
-            want += [plant[n] for n in ('Ad_traj', 'Bd_traj') if need[n]] + [plant[n] for n in ('Ad', 'Bd') if n in pneed and left[n]]
-        want = list(dict.fromkeys(want))
-        with _ordered(K):
-            res = K.prob.rollout_adjoint(g_x=grad_X.to(torch.float64).contiguous(), g_u=grad_U.to(torch.float64).contiguous(), want=want, batch_sum=batch_sum)
-        grads = [_ROLLOUT_INPUTS[n][1](res[_ROLLOUT_INPUTS[n][0]], shape[n]).reshape(shape[n]) if need[n] else None for n in inputs[:6]]
-        for n in ('Ad_traj', 'Bd_traj'):
-            v = None
-            if need[n]:
-                v = res[n] + res[plant[n]] if follows else res[n]
-                v = (v.sum(dim=1) if len(shape[n]) == 3 else v)[:ctx.nseg]
-                if shape[n][0] > ctx.nseg:                   # entries beyond ceil(nsteps / hold) were never in force
-                    v = torch.cat([v, v.new_zeros((shape[n][0] - ctx.nseg,) + tuple(v.shape[1:]))])
-                v = v.reshape(shape[n])
-            grads.append(v)
-        pgrads = _param_grads(ctx, res, pneed, shared, batch_sum)
-        for i, (n, shp) in enumerate(zip(ctx.names, ctx.pshapes)):
-            if follows and n in ('Ad', 'Bd') and n in pneed and left[n]:
-                p = res[plant[n]]
-                pgrads[i] = pgrads[i] + ((p[0] if batch_sum else p.sum(dim=0)) if shared[n] else p).reshape(shp)
-        return (None, None, None) + tuple(grads) + (None,) + tuple(pgrads)
+        return _rollout_backward(ctx, g_x=grad_X, g_u=grad_U)
 
 
 def mpc_rollout_tv(controller, x0, nsteps, Ad_traj, Bd_traj, hold, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None, bounds=None):
@@ -327,21 +335,12 @@ def mpc_rollout_tv(controller, x0, nsteps, Ad_traj, Bd_traj, hold, u_prev=None, 
 class _MPCRolloutEst(torch.autograd.Function):
     @staticmethod
     def forward(ctx, K, nsteps, x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, names, *params):
-        if not x0.is_cuda:
-            raise ValueError('mpc_rollout_est works on device tensors (x0 is on %s)' % x0.device)
-
-        def roll(new, st, it):
-            ny = int(C.shape[-2])
-            X, XH, U, Y = new(nsteps + 1, K.nx), new(nsteps + 1, K.nx), new(nsteps, K.nu), new(nsteps, ny)
-            est = dict(C=_bc(C, (K.B, ny, K.nx)), L=_bc(L, (K.B, K.nx, ny)), x_true=_det(x0).clone(), v=_det(v))
-            K.prob.rollout_est(nsteps, est, w=_det(w), Ap=_bc(Ap, (K.B, K.nx, K.nx)), Bp=_bc(Bp, (K.B, K.nx, K.nu)), out=[X, U, st, it, XH, Y])
-            return XH[-1], U, (X, XH, Y, U)
-        return _rollout_forward(ctx, K, nsteps, xhat0, u_prev, xref, names, params, roll, (x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp))
+        inputs = dict(x0=x0, xhat0=xhat0, C=C, L=L, v=v, u_prev=u_prev, xref=xref, w=w, Ap=Ap, Bp=Bp)
+        return _rollout_forward(ctx, 'mpc_rollout_est', K, nsteps, inputs, names, params)
 
     @staticmethod
     def backward(ctx, grad_X, grad_XH, grad_Y, grad_U):
-        return _rollout_backward(ctx, 'mpc_rollout_est', ('x0', 'xhat0', 'C', 'L', 'v', 'u_prev', 'xref', 'w', 'Ap', 'Bp'),
-                                 dict(g_x=grad_X, g_u=grad_U, g_xhat=grad_XH, g_y=grad_Y), True)
+        return _rollout_backward(ctx, g_x=grad_X, g_u=grad_U, g_xhat=grad_XH, g_y=grad_Y)
 
 
 def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None, bounds=None):
@@ -362,80 +361,14 @@ def mpc_rollout_est(controller, x0, xhat0, nsteps, C, L, v=None, u_prev=None, xr
 
 
 class _MPCRolloutTVEst(torch.autograd.Function):
-    INPUTS = ('x0', 'xhat0', 'C', 'L', 'v', 'u_prev', 'xref', 'w', 'Ap', 'Bp', 'Ad_traj', 'Bd_traj', 'L_traj')
-
     @staticmethod
     def forward(ctx, K, nsteps, hold, x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, L_traj, names, *params):
-        if not x0.is_cuda:
-            raise ValueError('mpc_rollout_tv_est works on device tensors (x0 is on %s)' % x0.device)
-        nseg = (nsteps + hold - 1) // hold
-
-        def roll(new, st, it):
-            ny = int(C.shape[-2])
-            X, XH, U, Y = new(nsteps + 1, K.nx), new(nsteps + 1, K.nx), new(nsteps, K.nu), new(nsteps, ny)
-            # (entry e of an unbatched schedule is one model, one gain, for the whole batch)
-            sched = [None if t is None else _det(t)[:nseg].reshape((nseg, -1) + tuple(t.shape[-2:])).expand((nseg, K.B) + tuple(t.shape[-2:])).contiguous()
-                     for t in (Ad_traj, Bd_traj, L_traj)]
-            est = dict(C=_bc(C, (K.B, ny, K.nx)), L=_bc(L, (K.B, K.nx, ny)), x_true=_det(x0).clone(), v=_det(v))
-            K.prob.rollout_tv_est(nsteps, (sched[0], sched[1], hold), est, L_traj=sched[2], w=_det(w), Ap=_bc(Ap, (K.B, K.nx, K.nx)), Bp=_bc(Bp, (K.B, K.nx, K.nu)),
-                                  out=[X, U, st, it, XH, Y])
-            for n, t in zip(('Ad', 'Bd'), sched):             # the controller is left with the last entry used: read back when somebody asks (update_model's way)
-                if t is not None:
-                    K.__dict__.pop(n, None)
-                    K._on_device[n] = t[nseg - 1]
-            return XH[-1], U, (X, XH, Y, U)
-        ctx.nseg = nseg
-        return _rollout_forward(ctx, K, nsteps, xhat0, u_prev, xref, names, params, roll,
-                                (x0, xhat0, C, L, v, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, L_traj))
+        inputs = dict(x0=x0, xhat0=xhat0, C=C, L=L, v=v, u_prev=u_prev, xref=xref, w=w, Ap=Ap, Bp=Bp, Ad_traj=Ad_traj, Bd_traj=Bd_traj, L_traj=L_traj)
+        return _rollout_forward(ctx, 'mpc_rollout_tv_est', K, nsteps, inputs, names, params, hold)
 
     @staticmethod
     def backward(ctx, grad_X, grad_XH, grad_Y, grad_U):
-        K = ctx.K
-        if K.prob.rollout_count != ctx.count:
-            raise RuntimeError('mpc_rollout_tv_est: the controller has been rolled out again since this forward (rollout %d then, %d now); '
-                               'its tape is no longer the one to differentiate.' % (ctx.count, K.prob.rollout_count))
-        inputs = _MPCRolloutTVEst.INPUTS
-        simple, traj = inputs[:10], inputs[10:]
-        ni = 3 + len(inputs)
-        need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[3:ni], ctx.shapes)}
-        shape = dict(zip(inputs, ctx.shapes))
-        pneed, shared, _ = _param_want(ctx, ctx.needs_input_grad[ni + 1:])
-        if not any(need.values()) and not pneed:
-            return (None,) * (ni + 1 + len(ctx.names))
-        follows = shape['Ap'] is None                        # the plant followed the schedule: its path belongs to the model in force
-        # Ad, Bd of an entry have up to three paths: its solves, the estimator (always) and the plant (where it followed); a matrix the schedule
-        # did not give never changed: params' matrix gets all of them
-        plant = {'Ad_traj': 'Ap_traj', 'Bd_traj': 'Bp_traj', 'Ad': 'Ap', 'Bd': 'Bp'}
-        estim = {'Ad_traj': 'Ae_traj', 'Bd_traj': 'Be_traj', 'Ad': 'Ae', 'Bd': 'Be'}
-        left = {'Ad': shape['Ad_traj'] is None, 'Bd': shape['Bd_traj'] is None}
-        split = [n for n in traj + ('Ap', 'Bp', 'L') if need[n]] + [n for n in ('Ad', 'Bd') if n in pneed]
-        unbatched = lambda n: len(shape[n]) == (3 if n.endswith('_traj') else 2) if n in shape else shared[n]
-        batch_sum = bool(split or pneed) and all(unbatched(n) for n in split) and all(shared[n] for n in pneed)
-        paths = lambda n: [estim[n]] + ([plant[n]] if follows else [])
-        want = list(dict.fromkeys(_ROLLOUT_INPUTS[n][0] for n in simple if need[n]))
-        want += [n for n in traj if need[n]] + pneed
-        want += [g for n in ('Ad_traj', 'Bd_traj') if need[n] for g in paths(n)] + [g for n in ('Ad', 'Bd') if n in pneed and left[n] for g in paths(n)]
-        want = list(dict.fromkeys(want))
-        seeds = dict(g_x=grad_X, g_u=grad_U, g_xhat=grad_XH, g_y=grad_Y)
-        with _ordered(K):
-            res = K.prob.rollout_adjoint(want=want, batch_sum=batch_sum, **{k: g.to(torch.float64).contiguous() for k, g in seeds.items()})
-        grads = [_ROLLOUT_INPUTS[n][1](res[_ROLLOUT_INPUTS[n][0]], shape[n]).reshape(shape[n]) if need[n] else None for n in simple]
-        for n in traj:
-            v = None
-            if need[n]:
-                v = res[n] if n == 'L_traj' else sum((res[g] for g in paths(n)), res[n])
-                v = (v.sum(dim=1) if len(shape[n]) == 3 else v)[:ctx.nseg]
-                if shape[n][0] > ctx.nseg:                   # entries beyond ceil(nsteps / hold) were never in force
-                    v = torch.cat([v, v.new_zeros((shape[n][0] - ctx.nseg,) + tuple(v.shape[1:]))])
-                v = v.reshape(shape[n])
-            grads.append(v)
-        pgrads = _param_grads(ctx, res, pneed, shared, batch_sum)
-        for i, (n, shp) in enumerate(zip(ctx.names, ctx.pshapes)):
-            if n in ('Ad', 'Bd') and n in pneed and left[n]:
-                for g in paths(n):
-                    p = res[g]
-                    pgrads[i] = pgrads[i] + ((p[0] if batch_sum else p.sum(dim=0)) if shared[n] else p).reshape(shp)
-        return (None, None, None) + tuple(grads) + (None,) + tuple(pgrads)
+        return _rollout_backward(ctx, g_x=grad_X, g_u=grad_U, g_xhat=grad_XH, g_y=grad_Y)
 
 
 def mpc_rollout_tv_est(controller, x0, xhat0, nsteps, Ad_traj, Bd_traj, hold, C, L=None, L_traj=None, v=None, u_prev=None, xref=None, w=None, Ap=None, Bp=None,

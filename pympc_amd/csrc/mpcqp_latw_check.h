@@ -4,8 +4,8 @@
 // wave), called by admm_latw between two rounds with the owned values BY VALUE:
 //   * A x and A'y are the two MFMA groups of the iteration (G v of the previous stage, G' y_dyn of the next) applied to x and y, P x a 16-long dot
 //     product per lane against the weight matrices' LDS copy; the residuals, their scales and the objective meet in one block reduction of five
-//     values, and ONLY where the solve has not converged the cheap halves of both infeasibility certificates (|c dy| clipped by the infinite bounds
-//     and the support function of [l, u]; |dx| and q'dx) in a second one of four;
+//     values (latw_reduce below: one barrier), and ONLY where the solve has not converged the cheap halves of both infeasibility certificates
+//     (|c dy| clipped by the infinite bounds and the support function of [l, u]; |dx| and q'dx) in a second one of four;
 //   * LATW_SOLVED: the solve is finished here -- iterate for the next warm start, reported solution, mpcqp_info, statistics, first input and status
 //     for the closed loop on the device: everything check_body's tail writes;
 //   * LATW_CARRIED: solved, and the queue item has another step: its transition (latw_carry below, inline) is made in the same call -- one entry, one
@@ -14,12 +14,61 @@
 //     where they are;
 //   * LATW_GENERIC: anything else (a certificate that needs its operator product, a non-finite residual, the first launch of a two-launch
 //     solve): the caller writes the iterate back and the generic check does what it always did.
-// A function of its own on purpose: see the head of admm_latw.  Per check of one (12,4,30) instance ~ 4 k cycles against 15 k of the generic one
-// plus 10 k of write-back and reload around it.
+// A function of its own on purpose: see the head of admm_latw.  Its budget is the caller's: what the function clobbers the caller saves around the
+// call.  It has 80 VGPRs; the (12,4,30) kernel's scratch stays at its 320 bytes up to 106 and is 356 at 117.  Per check of one (12,4,30) instance,
+// on the boundary clocks (BTICK, scripts/lat_phase.py; mean over the waves): entry 2.6 k, exchanges 2.0 k, rows and variables 4.1 k, reduction
+// 2.1 k, solved tail 1.2 k cycles -- 12 k where the solve ends, not the 4 k this comment used to claim -- and 3.4 k more for a carried transition,
+// against 15 k of the generic check plus 10 k of write-back and reload around it.
 #pragma once
 
 template <int NXT, int NUT, int NST>
 __device__ __forceinline__ int latw_carry(const RunKArgs &KA, Smem &S, int b, int k, int iter, double cc, double wn, double Er, int ct, int r, mpcqp_info inf);      // (below)
+
+// The check's own block reduction: ONE barrier where block_reduce (mpcqp_qp.h) has four.  Each wave's partial results (wave_reduce_last, as there)
+// go to red[G i + wv], value by value, G = NWAVES (eight in the 512-thread unit; four in the 256-thread one, which runs the check on schedules of up
+// to sixteen stages); behind the barrier lane G i + w of EVERY wave reads value i of wave w -- one LDS read per wave -- and the waves' values meet
+// inside the wave: a maximum over its group of G lanes in DPP steps (lane ^ 1, lane ^ 2 and, for eight, the mirror of the half row; a maximum has no
+// order), a sum in wave order, v = red[w = 0]; v += red[w], w = 1 .. G - 1, by G - 1 shifts of one lane -- the order block_reduce's thread i uses:
+// the same bits; v_readlane hands the K results to every lane.  (Every thread reading all G K values itself was tried first: 160 broadcast reads a
+// workgroup through one LDS pipe cost 500 cycles MORE than block_reduce.)  No barrier in front and none behind: red is this reduction's alone (the
+// check's two stages use disjoint parts of Smem::red), and between its last read here and its next write lie the barriers of a whole round, of the
+// carried transition or of the generic check's own reduction.
+typedef __attribute__((address_space(3))) double ldsw;      // (ldsd of mpcqp_phases.h, writable)
+template <int KMAX, int KSUM>
+__device__ __forceinline__ void latw_reduce(double *vmax, double *vsum, double *red) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    constexpr int K = KMAX + KSUM, G = NWAVES;
+    static_assert((G == 8 || G == 4) && G * K <= 64, "a group of G lanes per value, a lane per wave");
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) vmax[i] = wave_reduce_last<true>(vmax[i]);
+#pragma unroll
+    for (int i = 0; i < KSUM; ++i) vsum[i] = wave_reduce_last<false>(vsum[i]);
+    ldsd *rl = as_lds(red);
+    ldsw *rw = (ldsw *)rl;
+    if (lane == 63) {
+#pragma unroll
+        for (int i = 0; i < KMAX; ++i) rw[G * i + wv] = vmax[i];
+#pragma unroll
+        for (int i = 0; i < KSUM; ++i) rw[G * (KMAX + i) + wv] = vsum[i];
+    }
+    __syncthreads();
+    const double x = rl[lane < G * K ? lane : 0];
+    double m = x;
+    m = fmax(m, dpp_move_f64<0xB1>(m));             // quad_perm [1,0,3,2]
+    m = fmax(m, dpp_move_f64<0x4E>(m));             // quad_perm [2,3,0,1]
+    if constexpr (G == 8) m = fmax(m, dpp_move_f64<0x141>(m));      // row_half_mirror: the other quad of the group
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) { vmax[i] = readlane_f64(m, G * i); asm volatile("" : "+v"(vmax[i])); }      // (in a vector register from here on: the function has no scalar pair to spare)
+    // (the sums: G - 1 shifts by one lane, acc = acc of the lane below + own value in EVERY lane -- lane k of a group holds the sum of the group's lanes
+    //  0 .. k in that order after step k and its last lane the whole sum after the last step; what the other lanes hold meanwhile is never read)
+    double acc = x;
+#pragma unroll
+    for (int w = 1; w < G; ++w) acc = dpp_move_f64<0x111>(acc) + x;      // row_shr:1
+#pragma unroll
+    for (int i = 0; i < KSUM; ++i) { vsum[i] = readlane_f64(acc, G * (KMAX + i) + G - 1); asm volatile("" : "+v"(vsum[i])); }
+}
+constexpr int LATW_RED1 = 0, LATW_RED2 = 5 * NWAVES, LATW_FLAG = 16 * NWAVES - 8;      // Smem::red: stage 1 (5 values a wave), stage 2 (4), latw_carry's flag word
+static_assert(LATW_RED2 + 4 * NWAVES <= LATW_FLAG, "Smem::red holds 16 doubles per wave");
 
 template <int NXT, int NUT, int NST>
 __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double zA, double ysA, double omA, double zB, double ysB, double omB, double z0, double ys0, double om0,
@@ -119,13 +168,17 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
     }
     if (u0v) S.uo[jj] = pv;      // (the first input, should the verdict be 'solved' -- nobody reads it otherwise: published by the reduction's barriers, for latw_carry)
     BTICK(2)
-    block_reduce<4, 1>(nrm, vsum, S.red);
+    latw_reduce<4, 1>(nrm, vsum, S.red + LATW_RED1);
     BTICK(3)
     const double ea = KA.S.eps_abs, er = KA.S.eps_rel;
     const double pri_res = nrm[0], dua_res = nrm[2], obj_val = vsum[0];
     if (!(pri_res <= QP_INFTY) || !(dua_res <= QP_INFTY) || obj_val != obj_val) return LATW_GENERIC;      // (non-finite: the generic check reports it)
     const bool pc = pri_res < ea + er * nrm[1], dc = dua_res < ea + er * nrm[3];
     if (pc && dc) {
+        // (what was requested behind the first barrier for the carry arrived long ago.  Its wait is taken HERE, in front of the tail's global stores:
+        //  taken at the first use, behind them, it is a vmcnt count that the stores' divergent branches make the compiler put at 3 -- the plant
+        //  product then waits until all but three of a dozen stores are acknowledged.)
+        asm volatile("" :: "v"(wn), "v"(Erc), "v"(ctc), "v"(rho));
         // ---- solved: what check_body's tail writes (the iterate for the next warm start, the reported solution, the record)
         gdouble *gx = (gdouble *)(PP.x + (size_t)b * L.n), *gz = (gdouble *)(PP.z + (size_t)b * L.m), *gy = (gdouble *)(PP.y + (size_t)b * L.m);
         gdouble *xo = (gdouble *)(PP.xo + (size_t)b * L.n), *yo = (gdouble *)(PP.yo + (size_t)b * L.m);
@@ -178,7 +231,7 @@ __device__ __noinline__ int latw_check(double pv, double pv2, double ncq, double
         if (is_x && L.soft) dvar(0.0, dde);
         cert(ddA, loA, hiA, infbits); cert(ddB, loB, hiB, infbits >> 2);
     }
-    block_reduce<2, 2>(cn, cs, S.red);
+    latw_reduce<2, 2>(cn, cs, S.red + LATW_RED2);
     BTICK(5)
     // (pc and dc formed again from the first stage's values: kept across the second reduction they are two scalar register pairs more than the
     //  function has, and the spill lane that takes them is a register of the caller's to save and restore around every check)
@@ -222,10 +275,13 @@ __device__ __forceinline__ int latw_carry(const RunKArgs &KA, Smem &S, int b, in
     double xn = 0.0;
     if (tid < nx) {
         double acc = 0.0;
-        if (!R.Ap && !R.Bp) {                              // (the model's own matrices: LDS, read as LDS)
-            const double *Ad = S.hot + L.oAd, *Bd = S.hot + L.oBd;
-            for (int j = 0; j < nx; ++j) acc += Ad[tid * nx + j] * xt[j];
-            for (int j = 0; j < nu; ++j) acc += Bd[tid * nu + j] * un[j];
+        if (!R.Ap && !R.Bp) {
+            // (the model's own matrices: LDS, read THROUGH LDS POINTERS.  Left generic, the compiler joins the input part of this branch with the other
+            //  one's and reads Bd with FLAT loads; a FLAT load is waited for with vmcnt(0), and that wait stood right behind the solved tail's ten
+            //  global stores: the plant product paid their whole acknowledgement.)
+            ldsd *Ad = as_lds(S.hot + L.oAd), *Bd = as_lds(S.hot + L.oBd), *xl = as_lds(xt), *ul = as_lds(un);
+            for (int j = 0; j < nx; ++j) acc += Ad[tid * nx + j] * xl[j];
+            for (int j = 0; j < nu; ++j) acc += Bd[tid * nu + j] * ul[j];
         } else {
             const double *Ap = R.Ap ? R.Ap + (size_t)b * nx * nx : S.hot + L.oAd;
             const double *Bp = R.Bp ? R.Bp + (size_t)b * nx * nu : S.hot + L.oBd;
@@ -236,6 +292,11 @@ __device__ __forceinline__ int latw_carry(const RunKArgs &KA, Smem &S, int b, in
         R.x_traj[kb * nx + tid] = xt[tid];
     }
     if (tid < nu) R.u_traj[kb * nu + tid] = un[tid];
+    // has a re-typed row changed its type?  An OR has no order: the lanes that see a change store 1 into a word of Smem::red that thread 0 cleared
+    // two barriers earlier, everybody reads it behind one more (__syncthreads_or is three barriers and three loads of the block's dimensions from memory)
+    typedef __attribute__((address_space(3))) int ldsi;
+    ldsi *chg = (ldsi *)(size_t)(unsigned)(unsigned long long)(S.red + LATW_FLAG);      // (as_lds for an int)
+    if (tid == 0) *chg = 0;
     __syncthreads();
     BTICK(6)
     if (tid < nx) { S.x0s[tid] = xn; step[tid] = xn; }
@@ -246,9 +307,9 @@ __device__ __forceinline__ int latw_carry(const RunKArgs &KA, Smem &S, int b, in
     double *Tc = S.T + NB, *Cc = Tc + VS;                  // (owner slot of stage 0's slot a: a)
     if (tid < nu) { const double qj = q_input(c, 0, tid, S.um1s, S.hot + L.ouref); S.Qv[L.n_x + tid] = qj; Tc[nx + tid] = -cc * qj; }
     if (tid < nx) Cc[tid] = -S.x0s[tid];
-    int changed = 0;
-    if (r >= 0) { double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi); changed = row_type(Er, lo, hi) != ct; }
-    changed = __syncthreads_or(changed);
+    if (r >= 0) { double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi); if (row_type(Er, lo, hi) != ct) *chg = 1; }
+    __syncthreads();
+    const int changed = *chg;
     if (tid == 0) {
         R.status_traj[(size_t)k * R.batch + b] = MPCQP_SOLVED;      // (Smem::iflag[4]: the check's, a moment ago)
         R.iter_traj[(size_t)k * R.batch + b] = iter;

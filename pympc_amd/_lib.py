@@ -56,6 +56,9 @@ RICCATI_SYMBOLS = ['mpcqp_riccati_default_settings', 'mpcqp_dare', 'mpcqp_dare_a
 # include_ext3/mpcqp_riccati_traj.h: likewise -- batched Riccati difference equations (a recursion over a model trajectory) and their adjoint
 RICCATI_TRAJ_SYMBOLS = ['mpcqp_dre', 'mpcqp_dre_adjoint']
 
+# include_ext4/mpcqp_affine.h: likewise -- an affine term d in the prediction model x+ = Ad x + Bd u + d, its schedule in the device loop and its gradient
+AFFINE_SYMBOLS = ['mpcqp_set_affine', 'mpcqp_get_affine', 'mpcqp_mpc_loop_affine', 'mpcqp_adjoint_affine']
+
 
 class RiccatiSettings(C.Structure):
     """mpcqp_riccati_settings (include/mpcqp_riccati.h)."""
@@ -168,6 +171,11 @@ class ModelTraj(C.Structure):
     """mpcqp_model_traj (include/mpcqp_model.h): entry e of Ad / Bd is in force during steps e * hold .. e * hold + hold - 1."""
     _fields_ = [('struct_size', C.c_int32), ('hold', C.c_int32), ('nmodels', C.c_int32), ('reserved', C.c_int32),
                 ('Ad', C.c_void_p), ('Bd', C.c_void_p)]
+
+
+class AffineTraj(C.Structure):
+    """mpcqp_affine_traj (include_ext4/mpcqp_affine.h): entry e of d is the affine term of the solves after steps e * hold .. e * hold + hold - 1."""
+    _fields_ = [('struct_size', C.c_int32), ('hold', C.c_int32), ('nentries', C.c_int32), ('rows', C.c_int32), ('d', C.c_void_p)]
 
 
 _lib = None
@@ -314,6 +322,13 @@ def load():
         L.mpcqp_dre_adjoint.argtypes = head + [C.c_void_p] * 12
         for name in RICCATI_TRAJ_SYMBOLS:
             getattr(L, name).restype = C.c_int
+    if has_affine(L):
+        L.mpcqp_set_affine.argtypes = [H, C.c_void_p, C.c_int]
+        L.mpcqp_get_affine.argtypes = [H, C.c_void_p, C.POINTER(C.c_int)]
+        L.mpcqp_mpc_loop_affine.argtypes = [H, C.c_int, C.POINTER(Loop), C.POINTER(ModelTraj), C.POINTER(AffineTraj)]
+        L.mpcqp_adjoint_affine.argtypes = [H, C.POINTER(AdjointIO), C.c_void_p]
+        for name in AFFINE_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -377,6 +392,11 @@ def has_riccati(L=None):
 def has_riccati_traj(L=None):
     """True if the library exports include_ext3/mpcqp_riccati_traj.h."""
     return _has(L, RICCATI_TRAJ_SYMBOLS)
+
+
+def has_affine(L=None):
+    """True if the library exports include_ext4/mpcqp_affine.h."""
+    return _has(L, AFFINE_SYMBOLS)
 
 
 def check(rc, what):

@@ -151,7 +151,21 @@ class BatchMPCController:
         if solve:
             self.solve()
 
-    def update(self, x, u=None, xref=None, solve=True):
+    def set_affine(self, d):
+        """The affine term of every instance's prediction model, x_{k+1} = Ad x_k + Bd u_k + d_k (``BatchProblem.set_affine``, include_ext4/mpcqp_affine.h):
+        ``d`` [B, nx] (one offset for every stage) or [B, Np, nx] (row k: the step k -> k+1), numpy or a torch device tensor; ``None`` clears
+        it.  It stays in force across update(), step(), run() and update_model() until it is replaced or cleared; setup() clears it."""
+        if self.prob is None:
+            raise RuntimeError('set_affine() needs a controller that has been set up')
+        self.prob.set_affine(d)
+
+    def affine(self):
+        """The affine term in force [B, rows, nx] (rows: 1 or Np), or None."""
+        return self.prob.affine()
+
+    def update(self, x, u=None, xref=None, solve=True, d=None):
+        if d is not None:
+            self.set_affine(d)
         self.x0_rh = x
         if u is not None:
             self.uminus1_rh = u
@@ -167,9 +181,12 @@ class BatchMPCController:
         self.solve_count += 1
         self._u_last = None
 
-    def step(self, x, u=None, xref=None, out=None):
+    def step(self, x, u=None, xref=None, out=None, d=None):
         """``u = K(x, u_{-1})``: ``update(x, u, xref)`` followed by ``output()`` in one library call
-        (MPCController.__controller_function__, mpc.py:377-384).  ``out``: an array or torch device tensor [B,nu] to write the inputs into."""
+        (MPCController.__controller_function__, mpc.py:377-384).  ``out``: an array or torch device tensor [B,nu] to write the inputs into.
+        ``d``: a new affine term first (``set_affine``); None leaves the one in force."""
+        if d is not None:
+            self.set_affine(d)
         self.x0_rh = x
         if u is not None:
             self.uminus1_rh = u
@@ -184,7 +201,7 @@ class BatchMPCController:
         self._u_last = None
         return uMPC
 
-    def run(self, nsteps, w=None, Ap=None, Bp=None, xref_traj=None, estimator=None, model_traj=None, L_traj=None):
+    def run(self, nsteps, w=None, Ap=None, Bp=None, xref_traj=None, estimator=None, model_traj=None, L_traj=None, d_traj=None, d_hold=1):
         """``nsteps`` closed-loop steps on the device, equivalent to
         ``for k in range(nsteps): u = K.output(); x = Ap @ x + Bp @ u + w[k]; K.update(x, u, xref_traj[k])``
         (the loop of examples/example_point_mass.py:88-101 with a linear plant; default plant = (Ad, Bd)), or, with
@@ -196,8 +213,14 @@ class BatchMPCController:
         left with the last entry used.  With an estimator too (mpcqp_mpc_loop_tv_est, include_ext2/mpcqp_rollout_tv_est.h): the estimator steps
         under the entry in force, and ``L_traj`` [nentries,B,nx,ny] schedules its gain the same way (entry ``k // hold`` at step k; None: the
         estimator's own ``L`` throughout); the estimator object is left with the last estimate and, where scheduled, the last gain.
+        ``d_traj`` [nentries,B,nx] or [nentries,B,Np,nx]: a schedule of affine terms (mpcqp_mpc_loop_affine) -- the solve after step k uses entry
+        ``k // d_hold``, the indexing of ``model_traj`` and, at ``d_hold = 1``, of ``xref_traj[k]``; the plant does not get the offset (put it into
+        ``w``); the controller is left with the last entry used.  Without it a term set with ``set_affine`` stays in force over the run.  Not
+        with an estimator.
         Returns ``dict(x=[nsteps+1,B,nx], u=[nsteps,B,nu], status=[nsteps,B] (OSQP status values), iter=[nsteps,B])``
         plus ``xhat`` and ``y`` with an estimator."""
+        if d_traj is not None and estimator is not None:
+            raise NotImplementedError('run: output feedback under a schedule of affine terms is not implemented (include_ext4/mpcqp_affine.h)')
         if L_traj is not None and (estimator is None or model_traj is None):
             raise ValueError('run: L_traj schedules the gain of an estimator beside a model_traj: give both')
         if estimator is not None and model_traj is not None:
@@ -206,7 +229,8 @@ class BatchMPCController:
             self._after_schedule(nsteps, model_traj, estimator, L_traj)
             return self._after_loop(out, xref_traj, estimator)
         self.solve_count += int(nsteps)
-        out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=_est_dict(estimator), model_traj=model_traj)
+        out = self.prob.mpc_run(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, estimator=_est_dict(estimator), model_traj=model_traj,
+                                d_traj=d_traj, d_hold=d_hold)
         if model_traj is not None:
             self._after_schedule(nsteps, model_traj)
         return self._after_loop(out, xref_traj, estimator)
@@ -323,7 +347,8 @@ class BatchMPCController:
         ``dict(x0 [B,nx], uminus1 [B,nu], xref [B,rows*nx], uref [B,nu], n_weak [B], status [B])`` = dL/d(x0, u_{-1}, xref, uref).  ``want`` may
         also name the model gradients 'Ad' [B,nx,nx], 'Bd' [B,nx,nu], 'Qx', 'QxN' [B,nx,nx], 'Qu', 'QDu' [B,nu,nu], 'eps_feas' [B]
         (mpcqp_adjoint_model; ``batch_sum``: summed over the batch, leading dimension 1 -- see ``BatchProblem.adjoint``) and the bound
-        gradients 'xmin', 'xmax' [B,nx], 'umin', 'umax', 'Dumin', 'Dumax' [B,nu] (mpcqp_adjoint_bounds; ``batch_sum`` likewise).  numpy in,
+        gradients 'xmin', 'xmax' [B,nx], 'umin', 'umax', 'Dumin', 'Dumax' [B,nu] (mpcqp_adjoint_bounds; ``batch_sum`` likewise) and 'd'
+        [B,rows*nx], the gradient of the affine term in force (mpcqp_adjoint_affine).  numpy in,
         numpy out; torch device tensors in, device tensors out."""
         res = self.prob.adjoint(g_w=g_w, g_u0=g_u0, want=want, batch_sum=batch_sum)
         _, n_weak, status = self.prob.adjoint_info()

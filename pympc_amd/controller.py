@@ -147,6 +147,7 @@ class MPCController:
         self.P_X = None
         self.x0_rh = None
         self.uminus1_rh = None
+        self.d = None                 # the affine term of the prediction model in force, [nx] or [Np, nx] (set_affine / update(d=)); None: none
 
     # ------------------------------------------------------------------------------------
     def _model_data(self):
@@ -175,6 +176,7 @@ class MPCController:
         """Build the QP and set the solver up (mpc.py:254-269); optionally solve it."""
         self.x0_rh = np.copy(self.x0)
         self.uminus1_rh = np.copy(self.uminus1)
+        self.d = None                         # (a new setup starts without an affine term)
         self._compute_QP_matrices_()
         if self.prob is None:
             from .solver import DeviceProblem   # raises loudly without the HIP library / a GPU
@@ -210,8 +212,31 @@ class MPCController:
         self.uminus1_rh = uMPC
         return uMPC if len(info) == 0 else (uMPC, info)
 
-    def update(self, x, u=None, xref=None, solve=True):
-        """New measurement (and optionally u_{-1}, xref): refresh q,l,u and re-solve (mpc.py:338-364)."""
+    def set_affine(self, d):
+        """The affine term of the prediction model, x_{k+1} = Ad x_k + Bd u_k + d_k (mpcqp_set_affine, include_ext4/mpcqp_affine.h): ``d`` [nx] -- the
+        offset c = f(xbar, ubar) - Ad xbar - Bd ubar of a linearisation away from an equilibrium, used at every stage -- or [Np, nx], row k for the
+        step k -> k+1 (a previewed disturbance); ``None`` clears it.  It stays in force across update(), update_model() and solve() until it
+        is replaced or cleared; setup() clears it.  The dynamics rows of ``l``, ``u`` become -d; no factorization is made.  The next solve uses
+        it (this call does not solve).  An addition to the reference's class; it needs the device solver behind ``prob``."""
+        if not hasattr(self.prob, 'set_affine'):
+            raise NotImplementedError('set_affine() needs the device solver behind prob (pympc_amd.solver.DeviceProblem)')
+        nx, Np = self.nx, self.Np
+        if d is not None:
+            d = np.array(d, dtype=float)
+            if d.shape not in ((nx,), (Np, nx)):
+                raise ValueError('d should be a vector of dimension nx or a matrix of dimension (Np, nx)!')
+        self.prob.set_affine(d)
+        self.d = d
+        if self._l is not None:                   # (the public l, u: rows (k+1) nx .. of the dynamics block carry 0.0 - d_k)
+            rows = np.zeros(Np * nx) if d is None else 0.0 - np.broadcast_to(d, (Np, nx)).ravel()
+            self._l[nx:(Np + 1) * nx] = rows
+            self._u[nx:(Np + 1) * nx] = rows
+
+    def update(self, x, u=None, xref=None, solve=True, d=None):
+        """New measurement (and optionally u_{-1}, xref): refresh q,l,u and re-solve (mpc.py:338-364).  ``d``: a new affine term of the
+        prediction model for this and the following solves (``set_affine``); None leaves the one in force as it is."""
+        if d is not None:
+            self.set_affine(d)
         self.x0_rh = x
         if u is not None:
             self.uminus1_rh = u
@@ -304,7 +329,8 @@ class MPCController:
     def unconstrained_gains(self, tol=1e-13):
         """Gain matrices of this controller's law without inequality constraints, U* = K_x0 x0 + K_xref xref + K_uref uref + K_um1 u_{-1}
         (test_scripts/alternative/unconstrained.py:170-183), computed on the device (pympc_amd/unconstrained.py: one KKT factorization, a
-        few batched solves).  An addition to the reference's class; output() does not use it."""
+        few batched solves).  An addition to the reference's class; output() does not use it.  An affine term (``set_affine``) is ignored:
+        these are the gains of the linear part of the law, the term only adds a constant to U*."""
         from .unconstrained import unconstrained_gains, GainSolver
         d = lambda M: np.asarray(M.toarray() if hasattr(M, 'toarray') else M, dtype=float)        # (scipy.sparse inputs are accepted like in the reference)
         gs = getattr(self, '_gain_solver', None)
@@ -330,7 +356,8 @@ class MPCController:
         """Vector-Jacobian products of the last solve for the seed ``g_u0`` [nu] = dL/du_0 and / or ``g_w`` [n] = dL/dw (mpcqp_adjoint,
         mpcqp_adjoint_model): a dict with the gradients named in ``want`` -- 'x0', 'uminus1', 'xref', 'uref', 'q', 'l', 'u' and the model
         gradients 'Ad' [nx, nx], 'Bd' [nx, nu], 'Qx', 'QxN' [nx, nx], 'Qu', 'QDu' [nu, nu], 'eps_feas' (weights: with respect to a symmetric
-        perturbation) and the bound gradients 'xmin', 'xmax' [nx], 'umin', 'umax', 'Dumin', 'Dumax' [nu] (mpcqp_adjoint_bounds) -- plus
+        perturbation) and the bound gradients 'xmin', 'xmax' [nx], 'umin', 'umax', 'Dumin', 'Dumax' [nu] (mpcqp_adjoint_bounds) and 'd', the
+        gradient of the affine term in the shape it was set in (mpcqp_adjoint_affine) -- plus
         ``n_weak`` and ``status`` as in ``gains()``.  A weight whose cost term this controller runs without (the
         switches JX_ON, JU_ON, JDU_ON) gets zero.  An addition to the reference's class."""
         bp = getattr(self.prob, 'batch_problem', None)
@@ -340,6 +367,8 @@ class MPCController:
         res = bp.adjoint(g_w=one(g_w), g_u0=one(g_u0), want=want)
         _, n_weak, status = bp.adjoint_info()
         res = {k: v[0] for k, v in res.items()}
+        if 'd' in res and self.d is not None:
+            res['d'] = res['d'].reshape(self.d.shape)
         off = {'Qx': self.JX_ON, 'QxN': self.JX_ON, 'Qu': self.JU_ON, 'QDu': self.JDU_ON}
         for k, on in off.items():
             if k in res and not on:

@@ -53,6 +53,7 @@
 #include "../../include_ext/mpcqp_rollout_tv.h"
 #include "../../include_ext2/mpcqp_rollout_tv_est.h"
 #include "../../include/mpcqp_adjoint_bounds.h"
+#include "../../include_ext4/mpcqp_affine.h"
 
 #include "mpcqp_defs.h"
 
@@ -97,6 +98,7 @@ int mpcqp_set_error(int code, const char *msg) { return fail(code, msg); }      
 #include "mpcqp_adjoint_model.h"
 #include "mpcqp_adjoint_bounds.h"
 #include "mpcqp_rollout.h"
+#include "mpcqp_affine.h"
 #include "mpcqp_csc.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -158,6 +160,8 @@ struct mpcqp_handle : Plan {       // the plan (mpcqp_plan.h: ncu, batch, L, lds
     RolloutSlots tape_slots = {};                              // nslots > 0: the tape is one of the loop under a model schedule (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h) and carries its models
     RolloutGains tape_gains = {};                              // Lg non-null: the tape is one of the output-feedback loop under a schedule (mpcqp_rollout_tv_est, include_ext2/mpcqp_rollout_tv_est.h): nslots > 0 and tape_ny > 0 both
     int tape_xref_rows = 1; bool tape_valid = false;           // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
+    const mpcqp_affine_traj *loop_aff = nullptr; size_t loop_aff_k0 = 0;      // mpcqp_mpc_loop_affine: the schedule of affine terms of the call in progress and the first step of its next launch (loop_run)
+    double *aff_out = nullptr;           // mpcqp_adjoint_affine: the gradient of the term [batch][Np * nx] (null until first use)
     bool has_solve = false;              // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
 
@@ -417,6 +421,7 @@ extern "C" int mpcqp_setup(mpcqp_handle *h, const mpcqp_model *M, const double *
     rc |= put(h, mb, ms, L.oQx, M->Qx, nx * nx); rc |= put(h, mb, ms, L.oQxN, M->QxN, nx * nx);
     rc |= put(h, mb, ms, L.oQu, M->Qu, nu * nu); rc |= put(h, mb, ms, L.oQDu, M->QDu, nu * nu);
     if (rc) return MPCQP_ERR_HIP;
+    h->L.d_rows = 0;                                // (no affine term until mpcqp_set_affine: include_ext4/mpcqp_affine.h)
     if ((rc = step_upload(h, x0, um1, xref, xref_rows))) return rc;
     if ((rc = launch_setup(h))) return rc;
     h->is_setup = true;
@@ -488,6 +493,7 @@ extern "C" int mpcqp_update_vectors(mpcqp_handle *h, const double *q, const doub
     if ((l == nullptr) != (u == nullptr)) return fail(MPCQP_ERR_ARG, "mpcqp_update_vectors: give l and u together (the equality rows l[:nx] == u[:nx] carry x0)");
     HIPCHK(hipSetDevice(h->device));
     h->has_solve = false;                           // (as in step_upload)
+    if (l) h->L.d_rows = 0;                         // (the caller's l, u replace the bounds, an affine term with them: include_ext4/mpcqp_affine.h)
     if (l) h->tape_valid = false;                   // (k_decode_vectors writes the boxes of l, u into the model blob, which a rollout's reverse sweep reads from the handle)
     if (!h->L.raw) {
         // entering raw mode: the vectors that are NOT given now must keep describing the current problem, so the
@@ -520,7 +526,7 @@ extern "C" int mpcqp_setup_qp(mpcqp_handle *h, const mpcqp_model *M, const doubl
     rc |= put(h, mb, ms, L.oQx, M->Qx, nx * nx); rc |= put(h, mb, ms, L.oQxN, M->QxN, nx * nx);
     rc |= put(h, mb, ms, L.oQu, M->Qu, nu * nu); rc |= put(h, mb, ms, L.oQDu, M->QDu, nu * nu);
     if (rc) return MPCQP_ERR_HIP;
-    h->L.raw = 1; h->step_blank = true;
+    h->L.raw = 1; h->step_blank = true; h->L.d_rows = 0;
     if ((rc = upload_vectors(h, q, l, u))) return rc;
     if ((rc = launch_setup(h))) return rc;
     h->is_setup = true;
@@ -1260,7 +1266,7 @@ static int loop_run(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, bool bala
     // stream-ordered and returns without waiting); host buffers go through one staging block on the device: inputs are
     // copied in before the launch, outputs copied out after it, and the call returns when they have arrived.
     struct Part { const void *src; void *dst; size_t bytes; size_t off; bool direct; };
-    Part parts[16]; int np = 0; size_t total = 0; bool any_host = false;
+    Part parts[16]; int np = 0; size_t total = 0; bool any_host = false;      // (fifteen parts are added below)
     auto add = [&](const void *src, void *dst, size_t bytes) {
         const void *user = src ? src : dst;
         const bool direct = bytes && user && is_device_ptr(user);
@@ -1271,6 +1277,10 @@ static int loop_run(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, bool bala
     const int iw = add(io->w, nullptr, io->w ? 8 * K * B * nx : 0);
     const int iA = add(io->Ap, nullptr, io->Ap ? 8 * B * nx * nx : 0), iB = add(io->Bp, nullptr, io->Bp ? 8 * B * nx * nu : 0);
     const int ir = add(io->xref_traj, nullptr, io->xref_traj ? 8 * K * B * xblk : 0);
+    // mpcqp_mpc_loop_affine: the entries this launch's steps k0 .. k0 + K - 1 use, e0 .. e1 of the schedule
+    const mpcqp_affine_traj *at = h->loop_aff;
+    const size_t dblk = at ? (size_t)at->rows * nx : 0, e0 = at ? h->loop_aff_k0 / (size_t)at->hold : 0, e1 = at ? (h->loop_aff_k0 + K - 1) / (size_t)at->hold : 0;
+    const int id = add(at ? at->d + e0 * B * dblk : nullptr, nullptr, at ? 8 * (e1 - e0 + 1) * B * dblk : 0);
     const int iC = add(io->C, nullptr, ny ? 8 * B * ny * nx : 0), iL = add(io->Lgain, nullptr, ny ? 8 * B * nx * ny : 0);
     const int iv = add(io->v, nullptr, (ny && io->v) ? 8 * K * B * ny : 0);
     const int ixt = add(io->x_true, io->x_true, ny ? 8 * B * nx : 0);
@@ -1296,11 +1306,16 @@ static int loop_run(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, bool bala
     R.nsteps = nsteps;
     R.w = (const double *)dev(iw); R.Ap = (const double *)dev(iA); R.Bp = (const double *)dev(iB);
     R.xref_traj = (const double *)dev(ir); R.xref_blk = (int)xblk;
+    R.d_traj = (const double *)dev(id); R.d_blk = (int)dblk; R.d_hold = at ? at->hold : 1; R.d_k0 = at ? (int)(h->loop_aff_k0 - e0 * (size_t)at->hold) : 0;
     R.ny = ny; R.C = (const double *)dev(iC); R.Lg = (const double *)dev(iL); R.v = (const double *)dev(iv); R.x_true = (double *)dev(ixt);
     R.x_traj = (double *)dev(ox); R.xhat_traj = (double *)dev(oxh); R.y_traj = (double *)dev(oy); R.u_traj = (double *)dev(ou);
     R.status_traj = (int *)dev(os); R.iter_traj = (int *)dev(oi);
+    // a schedule's shape is the handle's from this launch on (every solve of the launch follows a step: none is made with the term the handle held
+    // before) -- set once the staging above has succeeded, and taken back if the launch is refused: a call that fails changes nothing
+    const int d_rows_before = h->L.d_rows;
+    if (at) h->L.d_rows = at->rows;
     int rc = launch_run(h, R, 0);
-    if (rc) return rc;
+    if (rc) { h->L.d_rows = d_rows_before; return rc; }
     if (h->pq.status) HIPCHK(hipMemsetAsync(h->pq.status, 0, sizeof(int) * B, h->stream));      // (the last solve of the loop: not polished)
     for (int i = 0; i < np; ++i)
         if (parts[i].dst && parts[i].bytes && !parts[i].direct && get(h, parts[i].dst, dev(i), parts[i].bytes)) return MPCQP_ERR_HIP;
@@ -1368,6 +1383,7 @@ static int loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in, const m
         if (mt->Bd) M.Bd = mt->Bd + (size_t)s * B * nx * nu;
         if ((rc = mpcqp_update_model(h, &M))) return rc;
         mpcqp_loop seg = loop_at(h, io, k0);
+        h->loop_aff_k0 = k0;
         if (Lt) seg.Lgain = Lt + (size_t)s * B * nx * (size_t)io->ny;
         if ((rc = loop_run(h, std::min(mt->hold, nsteps - (int)k0), &seg, s == nseg - 1))) return rc;
     }
@@ -1382,6 +1398,60 @@ extern "C" int mpcqp_mpc_loop_tv(mpcqp_handle *h, int nsteps, const mpcqp_loop *
 extern "C" int mpcqp_mpc_loop_tv_est(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt, const mpcqp_est_traj *et) {
     if (!h || !io || !mt || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_tv_est: bad argument");
     return loop_tv(h, nsteps, io, mt, "mpcqp_mpc_loop_tv_est", true, et);
+}
+
+// ---- the affine term of the prediction model (include_ext4/mpcqp_affine.h; device side: affine_bound in mpcqp_qp.h, mpcqp_affine.h) ----
+// The term lives in the step blob behind du0 (Lay::od, Np nx doubles) and is in force while Lay::d_rows > 0.
+extern "C" int mpcqp_set_affine(mpcqp_handle *h, const double *d, int d_rows) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_set_affine before mpcqp_setup");
+    if (h->L.raw || h->step_blank || h->csc) return fail(MPCQP_ERR_STATE, "mpcqp_set_affine: the handle works from raw q, l, u (mpcqp_setup_qp / _csc, mpcqp_update_vectors): the dynamics rows' bounds are the caller's there");
+    if (d_rows != 0 && d_rows != 1 && d_rows != h->L.Np) return fail(MPCQP_ERR_ARG, "mpcqp_set_affine: d_rows must be 0 (clear), 1 or Np");
+    HIPCHK(hipSetDevice(h->device));
+    h->has_solve = false;                           // (the bounds no longer belong to the iterate: mpcqp_adjoint waits for the next solve)
+    if (!d || d_rows == 0) { h->L.d_rows = 0; return MPCQP_OK; }
+    h->pack.n = 0;
+    if (put(h, h->P.step, h->L.step_sz, h->L.od, d, d_rows * h->L.nx)) return MPCQP_ERR_HIP;
+    h->L.d_rows = d_rows;
+    return flush_puts(h) ? MPCQP_ERR_HIP : MPCQP_OK;
+}
+extern "C" int mpcqp_get_affine(mpcqp_handle *h, double *d, int *d_rows) {
+    if (!h || !d_rows) return fail(MPCQP_ERR_ARG, "mpcqp_get_affine: null argument");
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_get_affine before mpcqp_setup");
+    *d_rows = h->L.d_rows;
+    if (!d || !h->L.d_rows) return MPCQP_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t w = sizeof(double) * (size_t)h->L.d_rows * h->L.nx;
+    HIPCHK(hipMemcpy2DAsync(d, w, h->P.step + h->L.od, sizeof(double) * (size_t)h->L.step_sz, w, (size_t)h->batch, hipMemcpyDefault, h->stream));
+    return sync_unless_all_device(h, {d});
+}
+extern "C" int mpcqp_mpc_loop_affine(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt, const mpcqp_affine_traj *at) {
+    if (!at) return mpcqp_mpc_loop_tv(h, nsteps, io, mt);
+    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_affine: bad argument");
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_mpc_loop_affine before mpcqp_setup");
+    if (at->struct_size != (int32_t)sizeof(mpcqp_affine_traj)) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_affine: struct_size is not sizeof(mpcqp_affine_traj)");
+    if (at->hold < 1) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_affine: hold must be >= 1");
+    if (at->nentries < (nsteps + at->hold - 1) / at->hold) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_affine: fewer than ceil(nsteps / hold) entries");
+    if (at->rows != 1 && at->rows != h->L.Np) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_affine: rows must be 1 or Np");
+    if (!at->d) return fail(MPCQP_ERR_ARG, "mpcqp_mpc_loop_affine: no entries given (at == NULL runs the loop with the handle's own term)");
+    if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_mpc_loop_affine: output feedback under a schedule of affine terms is not implemented");
+    h->loop_aff = at; h->loop_aff_k0 = 0;           // (read by loop_run; what mt's schedule and the loop refuse, they refuse before anything is launched or changed)
+    int rc = mt ? loop_tv(h, nsteps, io, mt, "mpcqp_mpc_loop_affine", false, nullptr) : loop_check(h, nsteps, io);
+    if (!mt && !rc) rc = loop_run(h, nsteps, io, true);
+    h->loop_aff = nullptr; h->loop_aff_k0 = 0;
+    return rc;
+}
+extern "C" int mpcqp_adjoint_affine(mpcqp_handle *h, const mpcqp_adjoint_io *io, double *d_d) {
+    if (!h || !io || !d_d) return fail(MPCQP_ERR_ARG, "mpcqp_adjoint_affine: null argument");
+    if (h->is_setup && !h->L.d_rows) return fail(MPCQP_ERR_STATE, "mpcqp_adjoint_affine: the handle has no affine term (mpcqp_set_affine)");
+    int rc = adjoint_call(h, io, nullptr, "mpcqp_adjoint_affine");
+    if (rc) return rc;
+    const Lay &L = h->L; const size_t B = (size_t)h->batch, w = (size_t)L.d_rows * L.nx;
+    if (!h->aff_out && dalloc(h, &h->aff_out, B * (size_t)L.Np * L.nx)) return MPCQP_ERR_HIP;
+    hipLaunchKernelGGL(k_affine_grad, dim3(h->batch), dim3(NT), 0, h->stream, L, (const double *)h->aq.y, (const int *)h->aq.status, h->aff_out);      // (behind k_adjoint: r_y of seed 0 as it left it)
+    HIPCHK(hipGetLastError());
+    if (get(h, d_d, h->aff_out, B * w * sizeof(double))) return MPCQP_ERR_HIP;
+    return sync_unless_all_device(h, {d_d});
 }
 
 // ---- a rollout with a tape and its reverse sweep (include/mpcqp_rollout.h, mpcqp_rollout.h) ------------------------------------
@@ -1471,6 +1541,7 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in,
     if (Lt) first.Lgain = Lt;                       // (a gain schedule stands in for io->Lgain, which may then be null)
     const mpcqp_loop *io = &first;
     if ((rc = loop_check(h, nsteps, io))) return rc;
+    if (h->L.d_rows) return fail(MPCQP_ERR_UNSUPPORTED, what + ": the handle has an affine term (include_ext4/mpcqp_affine.h: mpcqp_set_affine), which the taped rollouts and their reverse sweeps do not carry; clear it (mpcqp_set_affine(h, NULL, 0)) or run mpcqp_mpc_loop_affine");
     if (!h->has_solve) return fail(MPCQP_ERR_STATE, what + ": no solve since the last setup, update, model update or warm start: the iterate does not belong to the step data of tape entry 0");
     if (io->xref_traj && io->xref_rows && io->xref_rows != h->L.xref_rows)
         return fail(MPCQP_ERR_UNSUPPORTED, what + ": xref_traj must have the reference shape of the last upload (the entries of a tape have one shape)");
@@ -1647,6 +1718,7 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (io->no_reuse != 0 && io->no_reuse != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: no_reuse is 0 or 1");
     if (m.batch_sum != 0 && m.batch_sum != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: batch_sum is 0 or 1");
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint before mpcqp_setup");
+    if (h->L.d_rows) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout_adjoint: the handle has an affine term (include_ext4/mpcqp_affine.h: mpcqp_set_affine), which the taped rollouts and their reverse sweeps do not carry");
     if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the handle holds no tape (call mpcqp_rollout first)");
     if (!h->tape_valid) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the model or the scaling the tape was made under has been replaced (mpcqp_setup*, mpcqp_update_model, mpcqp_update_vectors with l, u) or its rollout failed: roll out again");
     const RolloutSlots &V = h->tape_slots;

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(NT) void k_adjoint(Lay L, Ptrs P, AdjointArgs Q) {
         block_reduce<1, 2>(ymx, cnt, S.red);
         const double ytol = Q.weak_tol * fmax(1.0, ymx[0]);
         for (int i = tid; i < L.m; i += NT) {
-            double lo, hi; row_bounds(c, S.x0s, S.du0, i, lo, hi);
+            double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), i, lo, hi);
             const double zv = za[i], yv = ya[i];
             const int a = kpol_row(E[i], zv, yv, lo, hi, cc, delta, true, om[i]);
             act[i] = a;

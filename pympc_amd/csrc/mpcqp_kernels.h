@@ -148,8 +148,8 @@ __device__ __forceinline__ void run_instance(const int k0, const int k1) {
     }
     const int nx = L.nx, nu = L.nu;
     // The latency round carries a converged solve into the item's next step itself (admm_latw, latw_carry) where nothing but x0, u_{-1} and the
-    // bounds and q entries they enter changes from step to step: no estimator, no reference trajectory, a warm start
-    const bool carry = LOOP && MODE >= MODE_BCRT && !(A.S.tuning & MPCQP_TUNE_NO_CARRY) && R.ny == 0 && !R.xref_traj && !R.plain && A.S.warm_start && !L.raw;
+    // bounds and q entries they enter changes from step to step: no estimator, no reference trajectory, no schedule of affine terms (a term that is constant over the launch sits in the owners' bound registers), a warm start
+    const bool carry = LOOP && MODE >= MODE_BCRT && !(A.S.tuning & MPCQP_TUNE_NO_CARRY) && R.ny == 0 && !R.xref_traj && !R.d_traj && !R.plain && A.S.warm_start && !L.raw;
     bool stepped = false;                        // (the step's transition was made inside the round, its begin was not: latw_carry)
     for (int k = k0; k < k1; ++k) {              // (LOOP = false: [0, 1), one solve of the current data -- mpcqp_solve)
 #ifdef MPCQP_RUN_TIMING
@@ -208,6 +208,10 @@ __device__ __forceinline__ void run_instance(const int k0, const int k1) {
             if (tid < nx) { S.x0s[tid] = xn[tid]; step[tid] = xn[tid]; }
             if (tid < nu) { S.um1s[tid] = un[tid]; step[nx + tid] = un[tid]; S.du0[tid] = S.hot[L.oDumin + tid] + un[tid]; S.du0[nu + tid] = S.hot[L.oDumax + tid] + un[tid]; }
             if (R.xref_traj) for (int i = tid; i < R.xref_blk; i += NT) { const double xr = R.xref_traj[kb * R.xref_blk + i]; step[nx + nu + i] = xr; if (i < nx) S.xrs[i] = xr; }
+            if (R.d_traj) {                                  // ... and the affine term of the schedule's entry (the phases read it from the step blob: global memory, behind the barrier and,
+                const size_t eb = (size_t)((R.d_k0 + k) / R.d_hold) * R.batch + b;      // for the phases' scalar and vector caches, written and read by this workgroup alone)
+                for (int i = tid; i < R.d_blk; i += NT) step[L.od + i] = R.d_traj[eb * R.d_blk + i];
+            }
             __syncthreads();
         }
         stepped = false;
@@ -352,7 +356,7 @@ __global__ __launch_bounds__(NT) void k_export(Lay L, Ptrs P, double *Pd, double
     if (Pd) { double *o = Pd + (size_t)b * L.n * L.n; for (int j = tid; j < L.n; j += NT) P_row(c, j, [&](double co, int idx) { o[(size_t)j * L.n + idx] = co; }); }
     if (Ad_) { double *o = Ad_ + (size_t)b * L.m * L.n; for (int r = tid; r < L.m; r += NT) A_row(c, r, [&](double co, int idx) { o[(size_t)r * L.n + idx] = co; }); }
     if (q) for (int j = tid; j < L.n; j += NT) q[(size_t)b * L.n + j] = (j < L.oe) ? S.Qv[j] : 0.0;
-    if (l && u) for (int r = tid; r < L.m; r += NT) { double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi); l[(size_t)b * L.m + r] = lo; u[(size_t)b * L.m + r] = hi; }
+    if (l && u) for (int r = tid; r < L.m; r += NT) { double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), r, lo, hi); l[(size_t)b * L.m + r] = lo; u[(size_t)b * L.m + r] = hi; }
 }
 
 template <int NB>
@@ -445,7 +449,7 @@ __global__ __launch_bounds__(NT) void k_eq_solve(Lay L, Ptrs P, int sweeps, int 
     int done = 0;
     bool settled = false;
     bool broken = P.info[b].status == MPCQP_NON_CVX && P.info[b].iter == 0;      // (k_setup's verdict on its factorization: a non-positive pivot)
-    auto dyn = [&](int i, double &lo) { double hi; row_bounds(c, S.x0s, S.du0, i, lo, hi); return true; };      // the dynamics rows, target lo (= hi)
+    auto dyn = [&](int i, double &lo) { double hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), i, lo, hi); return true; };      // the dynamics rows, target lo (= hi)
     for (int sw = 0; sw <= sweeps && !broken; ++sw) {
         nrm[0] = nrm[1] = nrm[2] = nrm[3] = 0.0;
         mm_row_residual(c, L.n_x, dyn, x, y, om, cc, g, nrm);

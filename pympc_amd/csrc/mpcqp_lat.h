@@ -267,7 +267,11 @@ __device__ __forceinline__ void admm_lat(const Lay &L, const HotPtrs &P, Smem &S
             lat_row_load(rB[q], gz, gy, om, cc, bidx[q]);
             if (is_x) {
                 if (L.soft) { pv2[q] = gx[L.oe + e]; sve[q] = sv[L.oe + e]; kap[q] = 1.0 / (cef + sve[q] + rB[q].om); okap[q] = rB[q].om * kap[q]; }
-                loA[q] = hiA[q] = s == 0 ? -S.x0s[a] : 0.0;
+                // (the affine term of the row, affine_bound's rule: requested with the loads above at an address that is valid with or without a term -- the
+                //  step blob always holds the Np nx doubles -- and kept by select, no branch on d_rows; without a term the value read is whatever the blob holds there,
+                //  zeros or a stale term, possibly NaN: the select discards it)
+                const double g_d = affine_ptr(L, P, b)[affine_index(L, max(s, 1), a)];
+                loA[q] = hiA[q] = s == 0 ? -S.x0s[a] : (L.d_rows ? 0.0 - g_d : 0.0);
                 loB[q] = hot[L.oxmin + a]; hiB[q] = hot[L.oxmax + a];
             } else {
                 loA[q] = hot[L.oumin + jj]; hiA[q] = hot[L.oumax + jj]; loB[q] = hot[L.oDumin + jj]; hiB[q] = hot[L.oDumax + jj];

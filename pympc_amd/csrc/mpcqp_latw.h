@@ -536,7 +536,11 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
         const double g_pv = gx[ip], g_sv = sv[ip], g_q = qv[iq], g_oA = om[ia], g_zA = gz[ia], g_yA = gy[ia], g_oB = om[ib], g_zB = gz[ib], g_yB = gy[ib];
         const double g_pe = gx[ie], g_se = sv[ie];
         const int jc = (jj >= 0 && jj < nu) ? jj : 0, ac = a < nx ? a : 0;
+        // (the affine term of the dynamics row, mpcqp_qp.h affine_bound: requested with the rest at a clamped address of the step blob, kept by select;
+        //  without a term the value read is whatever the blob holds there -- zeros or a stale term, possibly NaN -- and the select discards it)
+        const double g_d = affine_ptr(L, P, b)[affine_index(L, min(max(s, 1), L.Np), ac)];
         const double b_x0 = S.x0s[ac], b_xlo = hot[L.oxmin + ac], b_xhi = hot[L.oxmax + ac];
+        const double b_dyn = s == 0 ? -b_x0 : (L.d_rows ? 0.0 - g_d : 0.0);
         const double b_ulo = hot[L.oumin + jc], b_uhi = hot[L.oumax + jc], b_dlo = hot[L.oDumin + jc], b_dhi = hot[L.oDumax + jc];
         pv[q] = live ? g_pv : 0.0; svp[q] = live ? g_sv : 0.0; ncq[q] = live ? -cc * g_q : 0.0;
         rA[q] = LatRow{0.0, 0.0, 0.0, 1.0}; rB[q] = LatRow{0.0, 0.0, 0.0, 1.0};
@@ -546,7 +550,7 @@ __device__ __forceinline__ int admm_latw(const Lay &L, const HotPtrs &P, Smem &S
         }
         pv2[q] = sx ? g_pe : 0.0; sve[q] = sx ? g_se : 0.0;
         kap[q] = sx ? 1.0 / (cef + g_se + g_oB) : 0.0; okap[q] = sx ? g_oB * kap[q] : 0.0;
-        loA[q] = live ? (is_x ? (s == 0 ? -b_x0 : 0.0) : b_ulo) : 0.0; hiA[q] = live ? (is_x ? (s == 0 ? -b_x0 : 0.0) : b_uhi) : 0.0;
+        loA[q] = live ? (is_x ? b_dyn : b_ulo) : 0.0; hiA[q] = live ? (is_x ? b_dyn : b_uhi) : 0.0;
         loB[q] = live ? (is_x ? b_xlo : b_dlo) : 0.0; hiB[q] = live ? (is_x ? b_xhi : b_dhi) : 0.0;
     }
     const bool u0v = wv == 0 && J == 0 && !is_x && a < nx + nu;      // the first-step rows u_0 - u_{-1} (mpc.py:574): stage 0's inputs

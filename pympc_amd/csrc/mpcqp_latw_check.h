@@ -307,7 +307,7 @@ __device__ __forceinline__ int latw_carry(const RunKArgs &KA, Smem &S, int b, in
     double *Tc = S.T + NB, *Cc = Tc + VS;                  // (owner slot of stage 0's slot a: a)
     if (tid < nu) { const double qj = q_input(c, 0, tid, S.um1s, S.hot + L.ouref); S.Qv[L.n_x + tid] = qj; Tc[nx + tid] = -cc * qj; }
     if (tid < nx) Cc[tid] = -S.x0s[tid];
-    if (r >= 0) { double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi); if (row_type(Er, lo, hi) != ct) *chg = 1; }
+    if (r >= 0) { double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), r, lo, hi); if (row_type(Er, lo, hi) != ct) *chg = 1; }
     __syncthreads();
     const int changed = *chg;
     if (tid == 0) {

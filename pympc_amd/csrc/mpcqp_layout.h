@@ -22,8 +22,10 @@ struct Lay {
     int hot_lds;                  // doubles of the model blob every kernel stages into LDS at its start: hot_sz, or model_sz where the workgroup's LDS has room
                                   // for the weight matrices too (mpcqp_create: kernels that run one or two workgroups per compute unit) -- a termination check
                                   // then reads them where they are instead of copying them in (a global round trip and a barrier per check)
-    int step_sz;                  // [x0 | um1 | xref(N*nx) | du0lo(nu) | du0hi(nu)]  (the last two: raw-vector mode only)
+    int step_sz;                  // [x0 | um1 | xref(N*nx) | du0lo(nu) | du0hi(nu) | d(Np*nx)]  (du0: raw-vector mode only; d: the affine term, read where d_rows > 0)
     int odu0;                     // offset of du0lo in the step blob
+    int od;                       // offset of the affine term d in the step blob (include_ext4/mpcqp_affine.h)
+    int d_rows;                   // 0: no affine term (the dynamics rows behind stage 0 are bounded by 0.0); 1: one offset for every stage; Np: row k belongs to the step k -> k+1
     int raw;                      // 1: q and the bounds are what mpcqp_update_vectors uploaded (not rebuilt from x0, u_{-1}, xref)
     int xref_rows;                // 1 or N
     int fstage;                   // doubles per factor stage (FactorFmt<NB>::STAGE): [forward matrix | packed S^-1 | table]
@@ -84,6 +86,10 @@ template <class PT>
 __device__ __forceinline__ void factor_unshare(const PT &P, int b) {
     if (P.fown && threadIdx.x == 0) { __hip_atomic_store(P.fown + b, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __threadfence(); }
 }
+
+// The affine term of instance b in its step blob (GLOBAL memory, never staged: row_bounds / affine_bound read it where Lay::d_rows > 0).
+template <class PT>
+__device__ __forceinline__ const double *affine_ptr(const Lay &L, const PT &P, int b) { return (const double *)P.step + (size_t)b * L.step_sz + L.od; }
 
 // The instance this workgroup works on.  (Which workgroup handles which instance never changes a result; the map
 // only decides which instances share a CU.)

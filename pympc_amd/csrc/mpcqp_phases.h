@@ -134,7 +134,7 @@ __global__ __launch_bounds__(NT) void k_setup(Lay L, Ptrs P, mpcqp_settings S_, 
     double *om = P.omega + (size_t)b * L.m, *sv = P.s + (size_t)b * L.n;
     int *ct = P.ctype + (size_t)b * L.m;
     for (int r = tid; r < L.m; r += NT) {
-        double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi);
+        double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), r, lo, hi);
         int t = row_type(E[r], lo, hi);
         ct[r] = t;
         om[r] = row_rho(t, rho) * E[r] * E[r];
@@ -219,7 +219,7 @@ __device__ __forceinline__ void begin_body(const Lay &L, const Ptrs &P, const mp
     const double rho = P.rho[b];
     int changed = 0;
     for (int r = tid; r < L.m; r += NT) {
-        double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi);
+        double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), r, lo, hi);
         int t = row_type(E[r], lo, hi);
         if (t != ctp[r]) { changed = 1; ctp[r] = t; om[r] = row_rho(t, rho) * E[r] * E[r]; }
     }
@@ -543,7 +543,7 @@ __device__ __forceinline__ int check_body(const Lay &L, const Ptrs &P, const mpc
         // v = c * delta_y (= E * scaled delta_y), projected on the polar of the recession cone of [l,u]
         double vmax[1] = {0.0}, vs[1] = {0.0};
         for (int r = tid; r < L.m; r += NT) {
-            double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi);
+            double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), r, lo, hi);
             double e = E[r], v = cc * dyg[r];
             if (e * hi > QP_INFTY * MIN_SCALING) { if (e * lo < -QP_INFTY * MIN_SCALING) v = 0.0; else v = fmin(v, 0.0); }
             else if (e * lo < -QP_INFTY * MIN_SCALING) v = fmax(v, 0.0);
@@ -581,7 +581,7 @@ __device__ __forceinline__ int check_body(const Lay &L, const Ptrs &P, const mpc
         }
         for (int r = tid; r < L.m; r += NT) {
             double a = 0.0; A_row(c, r, [&](double co, int idx) { a += co * dxg[idx]; });
-            double lo, hi; row_bounds(c, S.x0s, S.du0, r, lo, hi);
+            double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), r, lo, hi);
             double e = E[r];
             if ((e * hi < QP_INFTY * MIN_SCALING && a > eps * nd) || (e * lo > -QP_INFTY * MIN_SCALING && a < -eps * nd)) bad[0] = 1.0;
         }
@@ -688,14 +688,18 @@ template <int NUT> __device__ __forceinline__ int divu(const Lay &L, int v) { re
 struct OwnRegs {
     double sv_x[2], cq_x[2], sv_e[2], om_s[2], om_d[2];      // per state element: s of x and of its slack, c q, omega of the box row / of the dynamics row
     double sv_u, cq_u, om_i, om_du, om_d0;                    // input element: s, c q, omega of the box row, of Delta-u row nu + cu, of first-step row cu
+    double b_d[2];                                            // per state element: the bound of its dynamics row (-x0 at stage 0, 0.0 - d behind it: affine_bound)
 };
 template <int NB, int NXT, int NUT>
-__device__ __forceinline__ void own_load(const Lay &L, cgdouble *om, cgdouble *sv, cgdouble *qv, double cc, OwnRegs &h) {
+__device__ __forceinline__ void own_load(const Lay &L, cgdouble *om, cgdouble *sv, cgdouble *qv, const double *x0s, const double *dk, double cc, OwnRegs &h) {
     const int tid = threadIdx.x;
+    const int nx = hx<NXT>(L);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int e = tid + NT * j;
         const bool v = e < L.n_x;
+        const int k = divx<NXT>(L, v ? e : 0), a = (v ? e : 0) - k * nx;
+        h.b_d[j] = k == 0 ? -x0s[a] : affine_bound(L, dk, k, a);
         h.sv_x[j] = v ? sv[e] : 0.0; h.cq_x[j] = v ? cc * qv[e] : 0.0; h.sv_e[j] = (v && L.soft) ? sv[L.oe + e] : 0.0;
         h.om_s[j] = v ? om[L.rs + e] : 1.0; h.om_d[j] = v ? om[e] : 1.0;
     }
@@ -810,7 +814,7 @@ __device__ __forceinline__ void own_rhs(const Lay &L, const double *hot, const O
 }
 // slack back-substitution, zt = A xt, relaxation, projection on [l,u], dual update, x update
 template <int NB, int NXT, int NUT>
-__device__ __forceinline__ void own_update(const Lay &L, const double *hot, const double *x0s, const double *du0, const OwnRegs &h, double cc, double alpha,
+__device__ __forceinline__ void own_update(const Lay &L, const double *hot, const double *du0, const OwnRegs &h, double cc, double alpha,
                                            double *X, double *Z, double *Y, double *W, const double *Tc, bool keep_delta, gdouble *dxg, gdouble *dyg) {
     const int tid = opaque_lane(threadIdx.x);
     const int nx = hx<NXT>(L), nu = hu<NUT>(L);
@@ -848,8 +852,7 @@ __device__ __forceinline__ void own_update(const Lay &L, const double *hot, cons
                 for (int i = 0; i < (NUT ? NUT : 1); ++i) if (NUT) zt += Bd[a * nu + i] * up[i];
                 if (!NUT) for (int i = 0; i < nu; ++i) zt += Bd[a * nu + i] * up[i];
             }
-            const double b0 = k == 0 ? -x0s[a] : 0.0;
-            row(e, h.om_d[j], zt, b0, b0);
+            row(e, h.om_d[j], zt, h.b_d[j], h.b_d[j]);
             row(L.rs + e, h.om_s[j], xt + et, hot[L.oxmin + a], hot[L.oxmax + a]);      // state-box row (soft: x + eps)
         }
     }
@@ -985,7 +988,7 @@ __device__ __forceinline__ void gown_rhs(const Lay &L, const double *hot, typena
     else __syncthreads();
 }
 template <int NB, int NXT, int NUT, bool INL = false>
-__device__ __forceinline__ void gown_update(const Lay &L, const double *hot, const double *x0s, const double *du0, typename GPtr<INL>::c *om, typename GPtr<INL>::c *sv, double cc, double alpha,
+__device__ __forceinline__ void gown_update(const Lay &L, const double *hot, const double *x0s, const double *du0, const double *dk, typename GPtr<INL>::c *om, typename GPtr<INL>::c *sv, double cc, double alpha,
                                             double *X, double *Z, double *Y, double *W, const double *Tc, bool keep_delta, gdouble_g *dxg, gdouble_g *dyg) {
     typedef typename GPtr<INL>::m gdouble;
     constexpr int GU = GownCfg<NB>::U;
@@ -1005,10 +1008,12 @@ __device__ __forceinline__ void gown_update(const Lay &L, const double *hot, con
         if (keep_delta) dyg[r] = (w * cinv) * d;
     };
     for (int e0 = tid; e0 < L.n_x; e0 += GU * NT) {
-        double oms[GU], omd[GU], sve[GU], xo[GU], eo[GU], zd[GU], yd[GU], zs[GU], ys[GU];
+        double oms[GU], omd[GU], sve[GU], xo[GU], eo[GU], zd[GU], yd[GU], zs[GU], ys[GU], bd[GU];
 #pragma unroll
         for (int u = 0; u < GU; ++u) {
             const int e = min(e0 + u * NT, L.n_x - 1);
+            bd[u] = 0.0;                               // (the affine term: requested with the element's other loads, and only by a handle that has one)
+            if (L.d_rows) bd[u] = 0.0 - dk[max(e - nx, 0) - (L.d_rows > 1 ? 0 : divx<NXT>(L, max(e - nx, 0)) * nx)];
             oms[u] = om[L.rs + e]; omd[u] = om[e]; xo[u] = Xg[e]; zd[u] = Zg[e]; yd[u] = Yg[e]; zs[u] = Zg[L.rs + e]; ys[u] = Yg[L.rs + e];
             sve[u] = 0.0; eo[u] = 0.0;
             if (L.soft) { sve[u] = sv[L.oe + e]; eo[u] = Xg[L.oe + e]; }
@@ -1035,7 +1040,7 @@ __device__ __forceinline__ void gown_update(const Lay &L, const double *hot, con
                     for (int i = 0; i < (NUT ? NUT : 1); ++i) if (NUT) zt += Bd[a * nu + i] * up[i];
                     if (!NUT) for (int i = 0; i < nu; ++i) zt += Bd[a * nu + i] * up[i];
                 }
-                const double b0 = k == 0 ? -x0s[a] : 0.0;
+                const double b0 = k == 0 ? -x0s[a] : bd[u];      // (affine_bound's rule: entry (k - 1) nx + a = e - nx, or a where one row serves every stage)
                 row(e, omd[u], zt, b0, b0, zd[u], yd[u]);
                 row(L.rs + e, oms[u], xt + et, hot[L.oxmin + a], hot[L.oxmax + a], zs[u], ys[u]);      // state-box row (soft: x + eps)
             }
@@ -1131,7 +1136,7 @@ __device__ __forceinline__ void admm_round_global(const Lay &L, const HotPtrs &P
         TICK(4)
         kkt_core<NB, NB == 16 && (NXT == 0 || NXT == 4)>(core_args(L, opaque_ptr(F), opaque_ptr((const double *)P.omega + (size_t)b * L.m)), Tc);
         if (BORDER) border_post(L, NB, Tc, S.tv);
-        gown_update<NB, NXT, NUT, INL>(L, S.hot, S.x0s, S.du0, gom, gsv, cc, alpha, X, Z, Y, W, Tc, keep_delta, dxg, dyg);
+        gown_update<NB, NXT, NUT, INL>(L, S.hot, S.x0s, S.du0, affine_ptr(L, P, b), gom, gsv, cc, alpha, X, Z, Y, W, Tc, keep_delta, dxg, dyg);
         TICK(5)
     }
     TICK_FLUSH
@@ -1165,7 +1170,7 @@ __device__ __forceinline__ void admm_body(const Lay &L, const HotPtrs &P, Smem &
     const double cc = P.c[b];
     constexpr bool BORDER = MODE == MODE_BORDER;
     OwnRegs hr;
-    own_load<NB, NXT, NUT>(L, gom, gsv, gqv, cc, hr);
+    own_load<NB, NXT, NUT>(L, gom, gsv, gqv, S.x0s, affine_ptr(L, P, b), cc, hr);
     own_rows_w<NB>(L, hr, cc, Z, Y, W, Tc);
     TICK_RESET
     for (int it = 1; it <= iters; ++it) {
@@ -1181,7 +1186,7 @@ __device__ __forceinline__ void admm_body(const Lay &L, const HotPtrs &P, Smem &
         if (BORDER) border_pre<NB>(L, bp.Bb, bp.Zb, bp.Sig, Tc, S.tv, S.red);
         kkt_core<NB, NB == 16 && (NXT == 0 || NXT == 4)>(core_args(L, opaque_ptr(F), opaque_ptr((const double *)P.omega + (size_t)b * L.m)), Tc);
         if (BORDER) border_post(L, NB, Tc, S.tv);
-        own_update<NB, NXT, NUT>(L, S.hot, S.x0s, S.du0, hr, cc, alpha, X, Z, Y, W, Tc, keep_delta, dxg, dyg);
+        own_update<NB, NXT, NUT>(L, S.hot, S.du0, hr, cc, alpha, X, Z, Y, W, Tc, keep_delta, dxg, dyg);
         TICK(5)
     }
     TICK_FLUSH

@@ -43,7 +43,9 @@ static Lay make_layout(int nx, int nu, int Np, int Nc, int soft) {
     L.model_sz = o;
     L.hot_lds = L.hot_sz;                              // (plan_hot_prefix: model_sz where the weight matrices fit in LDS beside everything else)
     L.odu0 = nx + nu + L.N * nx;
-    L.step_sz = L.odu0 + 2 * nu;
+    L.od = L.odu0 + 2 * nu;
+    L.step_sz = L.od + Np * nx;
+    L.d_rows = 0;
     L.raw = 0;
     L.xref_rows = 1;
     L.fstage = L.NB == 16 ? FactorFmt<16>::STAGE : L.NB == 32 ? FactorFmt<32>::STAGE : L.NB == 64 ? WideFmt::STAGE : HugeFmt::STAGE;
@@ -277,15 +279,21 @@ static void plan_dims(const Plan &p, int *n, int *m, int64_t *factor_doubles, in
 //   per round (check)  : residual evaluation inputs (weights, D, E, omega, s, last increments), the round's load/store of
 //                        the LDS-resident iterate and of the per-thread register copies of omega, s, q.
 //   per solve          : the begin phase (step data, E, constraint types, q rebuild) and the solution write-out.
+//   an affine term    : (Lay::d_rows > 0) its Np nx doubles, counted once per solve (begin's type check) -- and once per ITERATION where the iterate is not
+//                        LDS-resident (gown_update); nothing without one.  NOT counted: the owners of the LDS-resident rounds (own_load, admm_tiny, admm_lat,
+//                        admm_latw) read their entry again at the start of every round, Np nx doubles more per round out of L2 -- beside the round's
+//                        3 (n + 2 m) and more it is under 2 %, and the model leaves it out as it leaves out the x0 / bounds they re-read there.
 static void plan_stream_bytes(const Plan &p, int64_t *per_iter, int64_t *per_round, int64_t *per_solve) {
     const Lay &L = p.L;
     const int64_t n = L.n, m = L.m, nq = L.n_x + L.n_u, NB = L.NB;
+    const int64_t aff = L.d_rows ? (int64_t)L.Np * L.nx : 0, step_rd = L.step_sz - (int64_t)L.Np * L.nx + aff;      // (the step blob as a solve reads it)
     const int64_t sinv = L.fstage - L.ffwd - L.ftab;
     int64_t it = (L.dense || L.bcr) ? 0 /* the factor sits in registers for the round */ : !L.ffwd ? 2 * (int64_t)L.N * sinv + (int64_t)L.N * L.ftab + 2 * (int64_t)L.fhead   // S^-1-only build: S^-1 twice, one of the two tables per sweep, [G | G'] by each sweeping wave
                          : (int64_t)(L.N - 1) * L.ffwd + (int64_t)L.N * sinv + (int64_t)(L.N - 1) * L.ftab + L.fhead;   // forward matrices once, S^-1 once, the tables, G / G' once each
     if (L.NB >= 64) it = (3 * (int64_t)L.N - 2) * (int64_t)L.NB * L.NB;      // wide stages: S^-1 of every stage, M and M' of all but the last
     if (L.grp) it = (3 * (int64_t)group_count(L.N, L.grp) - 1) * GroupFmt::NN;      // grouped small stages: S^-1 of every super-stage, forward matrix and its transpose of all but the ends, the middle's second pair
     if (!p.lds_state && !L.lstage) it += (2 * n + 4 * m) /* x, z, y read + written */ + (m + L.n_x) /* omega */ + (n + L.n_x) /* s */ + nq /* q */;
+    if (!p.lds_state && !L.dense && !L.bcr) it += aff;
     if (L.border && !L.dense) it += 2 * (int64_t)L.nu * L.N * NB;      // (the dense inverse holds the held input's couplings itself)
     int64_t rd = (L.model_sz - L.hot_lds) /* the weight matrices, unless they are staged with the hot prefix */ + 2 * n + 2 * m /* D, s, E, omega */ + n + m /* dx, dy */;
     if (L.dense) rd += DenseFmt::DOUBLES;               // the round's load of K^-1 into registers
@@ -297,7 +305,7 @@ static void plan_stream_bytes(const Plan &p, int64_t *per_iter, int64_t *per_rou
     }
     rd += (p.lds_state || L.lstage) ? 2 * (n + 2 * m) /* iterate in and out of LDS */ + (m + L.n_x) + (n + L.n_x) + nq : (n + 2 * m);
     if (L.lstage && L.border) rd += 2 * (int64_t)L.nu * L.N * NB;      // the border matrices staged with it
-    int64_t sv = L.hot_lds + L.step_sz + 3 * m /* E, types, omega */ + nq + 2 * (n + m) /* solution out, iterate read */;
+    int64_t sv = L.hot_lds + step_rd + 3 * m /* E, types, omega */ + nq + 2 * (n + m) /* solution out, iterate read */;
     if (L.bcrtop && L.nw == 8 && (L.bcr + 3) / 4 <= 8 && L.hot_lds > L.hot_sz) {
         // The 512-thread latency round with its own termination test (latw_check): a round boundary moves the level fragments, the increments (written by
         // the last iteration, read back by the test) and the three scalings per lane the test clips the certificates with; the owners' registers are
@@ -305,7 +313,7 @@ static void plan_stream_bytes(const Plan &p, int64_t *per_iter, int64_t *per_rou
         // prefix enter LDS once per kernel prologue -- per queue item of a persistent closed-loop launch, about every fifth solve (QUEUE_ITEMS_PER_SLOT).
         // (Spill traffic around the non-inlined test -- ~ 110 bytes per lane and round in the write counter -- is NOT design traffic and not in here.)
         rd = fr * BcrFmt::NN + 2 * (n + m) /* dx, dy out and back */ + 3 * 64 * 8 /* E of the owned rows */;
-        sv = L.step_sz + 3 * m + nq                                            /* begin: E, types, omega looked at, q written */
+        sv = step_rd + 3 * m + nq                                              /* begin: E, types, omega looked at, q written */
            + (2 * n + 3 * m + nq)                                              /* the round's prologue: x, s, q, omega, z, y */
            + (n + 2 * m) + (n + m)                                             /* the solve's end: iterate, reported solution */
            + ((int64_t)L.bcrtop * L.bcrtop * BcrFmt::NN + L.hot_lds) / 5;     /* kernel prologue, amortised */

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(NT) void k_polish(Lay L, Ptrs P, PolishArgs Q) {
         double *r = Q.r + (size_t)b * L.n, *d = Q.d + (size_t)b * L.n, *e = Q.e + (size_t)b * L.n, *dd = Q.dd + (size_t)b * L.n;
         // 1. active set (OSQP's rule in the scaled space) and the metric of K_pol
         for (int i = tid; i < L.m; i += NT) {
-            double lo, hi; row_bounds(c, S.x0s, S.du0, i, lo, hi);
+            double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), i, lo, hi);
             const int a = kpol_row(E[i], za[i], ya[i], lo, hi, cc, delta, false, om[i]);
             act[i] = a;
             bt[i] = a == 1 ? lo : hi;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(NT) void k_polish(Lay L, Ptrs P, PolishArgs Q) {
         double pri = 0.0, dua = 0.0, obj = 0.0;
         if (!bad) {
             for (int i = tid; i < L.m; i += NT) {
-                double lo, hi; row_bounds(c, S.x0s, S.du0, i, lo, hi);
+                double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), i, lo, hi);
                 double ax = 0.0; A_row(c, i, [&](double co, int idx) { ax += co * x[idx]; });
                 z[i] = fmin(fmax(ax, lo), hi);
             }

@@ -108,10 +108,18 @@ __device__ __forceinline__ void P_row(const Ctx &c, int j, F f) {
 
 // Bounds of row r exactly as mpc.py:551-580 / 404-408 build them, clipped to +-1e30 like osqp's wrapper.
 // x0s: current x0; du0: bounds of the first nu Delta-u rows, [lower | upper] = Dumin/Dumax + u_{-1} (load_common).
-__device__ __forceinline__ void row_bounds(const Ctx &c, const double *x0s, const double *du0, int r, double &lo, double &hi) {
+// dk: the affine term of the prediction model in the instance's step blob (step + Lay::od; include_ext4/mpcqp_affine.h), read only where
+// Lay::d_rows > 0: x_{k+1} = Ad x_k + Bd u_k + d_k bounds dynamics row (k + 1) nx + i by 0.0 - d_k[i] on both sides.
+// The rule for the dynamics rows behind stage 0, ONE home for row_bounds and the hot paths that keep the bound in a register:
+__device__ __forceinline__ int affine_index(const Lay &L, int k, int i) { return (L.d_rows > 1 ? (k - 1) * L.nx : 0) + i; }      // (stage k >= 1, component i)
+__device__ __forceinline__ double affine_bound(const Lay &L, const double *dk, int k, int i) { return L.d_rows ? 0.0 - dk[affine_index(L, k, i)] : 0.0; }
+__device__ __forceinline__ void row_bounds(const Ctx &c, const double *x0s, const double *du0, const double *dk, int r, double &lo, double &hi) {
     const Lay &L = c.L;
-    if (r < L.rs) {
-        lo = hi = (r < L.nx) ? -x0s[r] : 0.0;
+    if (r < L.nx) {
+        lo = hi = -x0s[r];
+    } else if (r < L.rs) {
+        const int k = idiv(r, L.rnx);
+        lo = hi = affine_bound(L, dk, k, r - k * L.nx);
     } else if (r < L.ri) {
         int j = r - L.rs; int k = idiv(j, L.rnx); int i = j - k * L.nx;
         lo = c.hot[L.oxmin + i]; hi = c.hot[L.oxmax + i];

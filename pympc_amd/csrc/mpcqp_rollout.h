@@ -264,7 +264,7 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
             block_reduce<1, 3>(ymx, cnt, S.red);
             const double ytol = Q.weak_tol * fmax(1.0, ymx[0]);
             for (int i = tid; i < L.m; i += NT) {
-                double lo, hi; row_bounds(c, S.x0s, S.du0, i, lo, hi);
+                double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), i, lo, hi);
                 const double zv = za[i], yv = ya[i];
                 const int a = kpol_row(E[i], zv, yv, lo, hi, cc, delta, true, om[i]);
                 if (a != act[i]) cnt[2] += 1.0;

@@ -18,6 +18,9 @@ struct RunArgs {
     const double *Ap, *Bp;        // [batch][nx*nx], [batch][nx*nu] plant matrices, or null (plant = model Ad, Bd)
     const double *xref_traj;      // [nsteps][batch][xref_blk] reference for the solve after step k, or null (unchanged)
     int xref_blk;                 // xref_rows * nx
+    const double *d_traj;         // [..][batch][d_blk] schedule of affine terms (include_ext4/mpcqp_affine.h): the solve after step k of this launch uses entry
+                                  // (d_k0 + k) / d_hold; or null (the step blob's term, if it has one, stays)
+    int d_blk, d_hold, d_k0, d_pad;   // d_rows * nx; steps an entry holds for; the launch's first step within the schedule's run
     int ny;                       // > 0: output feedback through a LinearStateEstimator (pyMPC/kalman.py:109-134)
     const double *C, *Lg, *v;     // [batch][ny*nx], [batch][nx*ny], [nsteps][batch][ny] (or null)
     double *x_true;               // [batch][nx] true plant state (in/out) when the controller only sees the estimate

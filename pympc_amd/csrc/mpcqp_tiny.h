@@ -65,7 +65,7 @@ __device__ __forceinline__ void admm_tiny(const Lay &L, const HotPtrs &P, Smem &
     if (is_x && !odd) {                                       // x_k[a], dynamics row e, row a of [Ad Bd]
         pidx = e; r1idx = e;
         pv = gx[e]; svp = sv[e]; cq = cc * qv[e];
-        const double b0 = k == 0 ? -S.x0s[a] : 0.0;
+        const double b0 = k == 0 ? -S.x0s[a] : affine_bound(L, affine_ptr(L, P, b), k, a);
         tiny_row_load(r1, gz, gy, om, cc, e, b0, b0);
         if (k > 0) {
 #pragma unroll

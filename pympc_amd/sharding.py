@@ -43,10 +43,20 @@ def shard_range(total, rank, world_size):
     return lo, min(lo + per, total)
 
 
+def _refuse_affine(shapes):
+    """An affine term of the prediction model (include_ext4/mpcqp_affine.h) is not among the fields a sharded batch carries: asking ``scatter_instances``
+    for a field 'd' or 'd_traj' is refused.  That is all this module can check -- it moves named arrays and never sees a controller; a rank that
+    calls ``set_affine`` on its own shard gets a term on that shard alone (nothing here gathers or scatters it), and multi-GPU runs with a term are
+    untested."""
+    if any(k in ('d', 'd_traj') for k in shapes):
+        raise NotImplementedError('sharded batches do not carry an affine term d (include_ext4/mpcqp_affine.h): set it per rank with set_affine')
+
+
 def scatter_instances(full, shapes, per_rank=None, device=None, dtype=torch.float64, src=0, total=None):
     """``full``: dict name -> tensor [total, ...] on rank ``src`` (None elsewhere); ``shapes``: dict name -> per-instance shape.
     ``total`` instances in all (default: world * per_rank, the even case).  Returns dict name -> local shard [count, ...] with
     count = this rank's ``shard_range``.  One ``dist.scatter`` of a packed [world * per, width] buffer."""
+    _refuse_affine(shapes)
     rank, ws = world()
     if total is None:
         total = ws * int(per_rank)

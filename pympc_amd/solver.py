@@ -44,7 +44,8 @@ _FEATURES = dict(
     rollout_tv=(_lib.has_rollout_tv, 'no taped rollout under a model schedule (include_ext/mpcqp_rollout_tv.h)'),
     rollout_tv_est=(_lib.has_rollout_tv_est, 'no output-feedback loop under a model schedule (include_ext2/mpcqp_rollout_tv_est.h)'),
     model_update=(_lib.has_model_update, 'no in-place model update (include/mpcqp_model.h)'),
-    model_traj=(_lib.has_model_update, 'no model schedule for the device loop (include/mpcqp_model.h)'))
+    model_traj=(_lib.has_model_update, 'no model schedule for the device loop (include/mpcqp_model.h)'),
+    affine=(_lib.has_affine, 'no affine term in the prediction model (include_ext4/mpcqp_affine.h)'))
 
 
 def _ptr(a):
@@ -335,9 +336,13 @@ class BatchProblem:
         [B, nx], 'umin', 'umax', 'Dumin', 'Dumax' [B, nu] (mpcqp_adjoint_bounds, include/mpcqp_adjoint_bounds.h: the multipliers of the active
         rows summed onto the bound each sits on).  ``batch_sum``: the model and bound gradients come summed
         over the batch, with a leading dimension of 1 -- one model shared by many states; the sum is formed on the device in a fixed order.
+        'd' [B, rows*nx]: the gradient of the affine term in the shape it was set in (mpcqp_adjoint_affine, include_ext4/mpcqp_affine.h; beside a
+        model or bound gradient it is a second call with the same seeds); without a term set it raises.
         Seeds may be numpy arrays or torch device tensors; the results are of the same kind (device tensors: stream-ordered, no wait), or
         are written into the arrays / tensors given in ``out`` (a dict by the same names).  The gradients are those of the active set the
         iterate implies; ``adjoint_info()`` reports weakly active rows."""
+        if 'd' in want:
+            self._need('affine')
         self._need('adjoint')
         if g_w is None and g_u0 is None:
             raise ValueError('adjoint: give g_w, g_u0 or both')
@@ -356,6 +361,12 @@ class BatchProblem:
         bo, btable = self._bound_grads(batch_sum)
         table.update(btable)
         want = list(want)
+        want_d = 'd' in want
+        if want_d:
+            want.remove('d')
+            drows = self.affine_rows()
+            if not drows:
+                raise RuntimeError("adjoint: want 'd' needs an affine term (set_affine)")
         if ('l' in want) != ('u' in want):
             want += ['l' if 'u' in want else 'u']
         model = any(k in mtable for k in want)
@@ -366,6 +377,16 @@ class BatchProblem:
             self._need('adjoint_bounds')
         res = self._grads_out(want, table, out, like)
         self._keep = [gw, gu, res]
+        if want_d:
+            shape = (B, drows * self.nx)
+            res['d'] = _prep_out(out['d'], shape, "out['d']") if out is not None and 'd' in out else self._out(like, shape)
+            seeds = io
+            if model or bounds:                   # (mpcqp_adjoint_affine takes mpcqp_adjoint's outputs only: the seeds again, for the term alone)
+                seeds = _lib.AdjointIO()
+                seeds.struct_size, seeds.g_w, seeds.g_u0 = C.sizeof(_lib.AdjointIO), _ptr(gw), _ptr(gu)
+            _lib.check(self._L.mpcqp_adjoint_affine(self._h, C.byref(seeds), _ptr(res['d'])), 'mpcqp_adjoint_affine')
+            if not (model or bounds):
+                return res
         if bounds:
             _lib.check(self._L.mpcqp_adjoint_bounds(self._h, C.byref(io), C.byref(mo) if model else None, C.byref(bo)), 'mpcqp_adjoint_bounds')
         elif model:
@@ -734,6 +755,40 @@ class BatchProblem:
         if xref is not None:
             self._xref_rows_last = rows
 
+    # -- the affine term of the prediction model (include_ext4/mpcqp_affine.h) --------------------
+    def set_affine(self, d):
+        """The affine term of the prediction model x+ = Ad x + Bd u + d_k (mpcqp_set_affine): ``d`` [B, nx] -- one offset for every stage -- or
+        [B, Np, nx] (row k: the step k -> k+1), numpy or a torch device tensor (stream-ordered); ``None`` clears it.  Step data like the
+        reference: it stays until it is replaced or cleared, ``setup`` clears it; no factorization is made for it.  A library without the
+        call raises NotImplementedError."""
+        self._need('affine')
+        if d is None:
+            _lib.check(self._L.mpcqp_set_affine(self._h, None, 0), 'mpcqp_set_affine')
+            return
+        shape = tuple(d.shape)
+        per = math.prod(shape[1:]) if len(shape) > 1 and shape[0] == self.batch else math.prod(shape)
+        if per not in (self.nx, self.Np * self.nx):
+            raise ValueError('d must hold nx or Np*nx values per instance')
+        a = _prep(d, (self.batch, per), 'd')
+        self._keep = [a]
+        _lib.check(self._L.mpcqp_set_affine(self._h, _ptr(a), per // self.nx), 'mpcqp_set_affine')
+
+    def affine_rows(self):
+        """Rows of the affine term in force: 0 (none), 1 or Np (mpcqp_get_affine)."""
+        self._need('affine')
+        rows = C.c_int()
+        _lib.check(self._L.mpcqp_get_affine(self._h, None, C.byref(rows)), 'mpcqp_get_affine')
+        return rows.value
+
+    def affine(self):
+        """The affine term in force [B, rows, nx] (mpcqp_get_affine; synchronises), or None if there is none."""
+        rows = self.affine_rows()
+        if not rows:
+            return None
+        d = np.empty((self.batch, rows, self.nx))
+        _lib.check(self._L.mpcqp_get_affine(self._h, _ptr(d), C.byref(C.c_int())), 'mpcqp_get_affine')
+        return d
+
     def update_settings(self, **kw):
         kw, polish = _split_polish(kw)
         if polish:
@@ -820,7 +875,7 @@ class BatchProblem:
         buf = np.frombuffer(cb, dtype=np.float64)
         return buf[:n].reshape(1, n), buf[n:].reshape(1, m), info
 
-    def mpc_run(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None):
+    def mpc_run(self, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None, d_traj=None, d_hold=1):
         """Device-side receding-horizon loop (mpcqp_mpc_loop): ``nsteps`` closed-loop steps
         ``u = output(); x = Ap x + Bp u + w[k]; update(x)`` of every instance without host round trips.
 
@@ -830,11 +885,15 @@ class BatchProblem:
         (pyMPC/kalman.py:109-134): the controller is updated with the estimate, ``x_true`` is advanced in place.
         ``model_traj = (Ad [nmodels,B,nx,nx] or None, Bd [nmodels,B,nx,nu] or None, hold)`` schedules the model (mpcqp_mpc_loop_tv): entry
         ``k // hold`` replaces Ad / Bd at the start of step k (``update_model``), for the controller and, without ``Ap``/``Bp``, the plant.
+        ``d_traj`` [nentries, B, nx] or [nentries, B, Np, nx] schedules the affine term (mpcqp_mpc_loop_affine, include_ext4/mpcqp_affine.h): the solve
+        after step k uses entry ``k // d_hold``; the plant does not get the offset (put it into ``w``); the problem is left with the last entry
+        used.  Without it a term set with ``set_affine`` stays in force.  Not with an estimator (NotImplementedError).
         Returns ``(x_traj [nsteps+1,B,nx], u_traj [nsteps,B,nu], status [nsteps,B] int32, iters [nsteps,B] int32)`` as
         numpy arrays (plus ``xhat_traj, y_traj`` with an estimator), or fills the arrays/tensors given in ``out``."""
-        return self._loop('mpcqp_mpc_loop', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj)
+        return self._loop('mpcqp_mpc_loop', nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj,
+                          d_traj=d_traj, d_hold=d_hold)
 
-    def _loop(self, entry, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None, L_traj=None):
+    def _loop(self, entry, nsteps, w=None, Ap=None, Bp=None, out=None, xref_traj=None, estimator=None, model_traj=None, L_traj=None, d_traj=None, d_hold=1):
         """``mpc_run`` through the C entry point ``entry`` -- mpcqp_mpc_loop, or mpcqp_rollout / mpcqp_rollout_est: the same loop, and a tape
         of it; with a ``model_traj``, mpcqp_mpc_loop_tv (or mpcqp_rollout_tv; mpcqp_mpc_loop_tv_est / mpcqp_rollout_tv_est take an estimator
         and a gain schedule ``L_traj`` too)."""
@@ -878,6 +937,20 @@ class BatchProblem:
         io.x_traj, io.u_traj, io.status_traj, io.iter_traj = (_ptr(o) for o in out[:4])
         if ny and len(out) >= 6:
             io.xhat_traj, io.y_traj = _ptr(out[4]), _ptr(out[5])
+        at = None
+        if d_traj is not None:                    # a schedule of affine terms: mpcqp_mpc_loop_affine, with or without a model schedule
+            self._need('affine')
+            if entry != 'mpcqp_mpc_loop':
+                raise NotImplementedError('a schedule of affine terms is for mpc_run (mpcqp_mpc_loop_affine): the taped rollouts do not carry the term')
+            shp = tuple(d_traj.shape)
+            if len(shp) < 3 or shp[1] != B:
+                raise ValueError('d_traj must be [nentries, batch, nx] or [nentries, batch, Np, nx]')
+            per = int(np.prod(shp[2:]))
+            if per not in (nx, self.Np * nx):
+                raise ValueError('d_traj must hold nx or Np*nx values per entry and instance')
+            at = _lib.AffineTraj()
+            at.struct_size, at.hold, at.nentries, at.rows = C.sizeof(_lib.AffineTraj), int(d_hold), int(shp[0]), per // nx
+            at.d = inp(d_traj, (shp[0], B, per), 'd_traj')
         if model_traj is not None:
             self._need('model_traj')
             Adt, Bdt, hold = model_traj
@@ -899,9 +972,15 @@ class BatchProblem:
                     et.struct_size, et.nentries = C.sizeof(_lib.EstTraj), ne
                     et.Lgain_traj = inp(L_traj, (ne, B, nx, ny), 'L_traj')
                 rc = getattr(self._L, entry)(self._h, K, C.byref(io), C.byref(mt), None if et is None else C.byref(et))
+            elif at is not None:
+                entry = 'mpcqp_mpc_loop_affine'
+                rc = self._L.mpcqp_mpc_loop_affine(self._h, K, C.byref(io), C.byref(mt), C.byref(at))
             else:
                 entry = 'mpcqp_rollout_tv' if entry == 'mpcqp_rollout_tv' else 'mpcqp_mpc_loop_tv'
                 rc = getattr(self._L, entry)(self._h, K, C.byref(io), C.byref(mt))
+        elif at is not None:
+            entry = 'mpcqp_mpc_loop_affine'
+            rc = self._L.mpcqp_mpc_loop_affine(self._h, K, C.byref(io), None, C.byref(at))
         else:
             rc = getattr(self._L, entry)(self._h, K, C.byref(io))
         if rc == -4:
@@ -1138,6 +1217,11 @@ class DeviceProblem:
         self.flush()
         one = lambda k, v: np.array([[float(v)]]) if k == 'eps_feas' else np.asarray(v, dtype=float)[None]
         self._bp.update_model(**{k: one(k, v) for k, v in fields.items() if v is not None})
+
+    def set_affine(self, d):
+        """The affine term of the prediction model for the one instance (``BatchProblem.set_affine``): [nx], [Np, nx] or None (clear)."""
+        self.flush()
+        self._bp.set_affine(None if d is None else np.asarray(d, dtype=float).reshape(1, -1))
 
     def warm_start(self, x=None, y=None):
         self.flush()

@@ -123,16 +123,17 @@ def _param_grads(ctx, res, pneed, shared, batch_sum, paths={}, sched=False):
 
 class _MPCStep(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, K, x, u_prev, xref, names, *params):
+    def forward(ctx, K, x, u_prev, xref, d, names, *params):
         if not x.is_cuda:
             raise ValueError('mpc_step works on device tensors (x is on %s)' % x.device)
         with _ordered(K):
             _put_params(ctx, K, names, params)
             u = torch.empty((K.B, K.nu), dtype=torch.float64, device=x.device)
             xr = _det(xref)
-            K.step(_det(x), _det(u_prev), None if xr is None else xr.reshape(K.B, -1), out=u)
+            dd = _det(d)
+            K.step(_det(x), _det(u_prev), None if xr is None else xr.reshape(K.B, -1), out=u, d=None if dd is None else dd.reshape(K.B, -1))
         ctx.K, ctx.count = K, K.solve_count
-        ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (x, u_prev, xref))
+        ctx.shapes = tuple(None if t is None else tuple(t.shape) for t in (x, u_prev, xref, d))
         return u
 
     @staticmethod
@@ -142,26 +143,30 @@ class _MPCStep(torch.autograd.Function):
             raise RuntimeError('mpc_step: the controller has been stepped or solved again since this forward (%d solves then, %d now); '
                                'its solution is no longer the one to differentiate.  Use one controller per step of a rollout.'
                                % (ctx.count, K.solve_count))
-        names = ('x0', 'uminus1', 'xref')
-        want = [n for n, need, shp in zip(names, ctx.needs_input_grad[1:4], ctx.shapes) if need and shp is not None]
-        pneed, shared, batch_sum = _param_want(ctx, ctx.needs_input_grad[5:])
+        names = ('x0', 'uminus1', 'xref', 'd')      # ('d': the affine term the step was made with, mpcqp_adjoint_affine)
+        want = [n for n, need, shp in zip(names, ctx.needs_input_grad[1:5], ctx.shapes) if need and shp is not None]
+        pneed, shared, batch_sum = _param_want(ctx, ctx.needs_input_grad[6:])
         if not want and not pneed:
-            return (None,) * (5 + len(ctx.names))
+            return (None,) * (6 + len(ctx.names))
         with _ordered(K):
             res = K.prob.adjoint(g_u0=grad_u.to(torch.float64).contiguous(), want=want + pneed, batch_sum=batch_sum)
         grads = [res[n].reshape(shp) if n in res else None for n, shp in zip(names, ctx.shapes)]
         return (None,) + tuple(grads) + (None,) + tuple(_param_grads(ctx, res, pneed, shared, batch_sum))
 
 
-def mpc_step(controller, x, u_prev=None, xref=None, params=None, bounds=None):
+def mpc_step(controller, x, u_prev=None, xref=None, params=None, bounds=None, d=None):
     """``u [B,nu] = K(x [B,nx], u_prev [B,nu], xref [B,nx] or [B,Np+1,nx])`` of a set-up ``BatchMPCController``, differentiable with
     respect to the three tensors (float64 device tensors; ``u_prev`` / ``xref`` None: the controller's own, no gradient) and, with
     ``params`` -- a dict of device tensors under any of the names Ad, Bd, Qx, QxN, Qu, QDu, each [B, ...] or unbatched [...] -- with respect
     to the model the step is made with: the controller's model is replaced by them first (``update_model``).  ``bounds``: likewise a dict
     under any of the names xmin, xmax, umin, umax, Dumin, Dumax, each [B, nx | nu] or unbatched [nx | nu] -- the constraint bounds the step is
-    made with, differentiable too."""
+    made with, differentiable too.  ``d`` [B, nx] or [B, Np, nx]: the affine term of the prediction model x+ = Ad x + Bd u + d the step is made
+    with (``set_affine``; it stays in force afterwards), differentiable too; None: the controller's own, if it has one, no gradient.
+    The rollouts below refuse a controller that has a term (NotImplementedError: the tapes do not carry it)."""
     names, tensors = _check_args('mpc_step', controller, params, bounds=bounds)
-    return _MPCStep.apply(controller, x, u_prev, xref, names, *tensors)
+    if d is not None and (not hasattr(d, 'data_ptr') or not d.is_cuda):
+        raise ValueError('mpc_step: d must be a device tensor [B, nx] or [B, Np, nx]')
+    return _MPCStep.apply(controller, x, u_prev, xref, d, names, *tensors)
 
 
 # ---- a closed-loop rollout as one differentiable operation (include/mpcqp_rollout.h, include/mpcqp_rollout_est.h, include_ext*/) ------------

@@ -59,6 +59,11 @@ RICCATI_TRAJ_SYMBOLS = ['mpcqp_dre', 'mpcqp_dre_adjoint']
 # include_ext4/mpcqp_affine.h: likewise -- an affine term d in the prediction model x+ = Ad x + Bd u + d, its schedule in the device loop and its gradient
 AFFINE_SYMBOLS = ['mpcqp_set_affine', 'mpcqp_get_affine', 'mpcqp_mpc_loop_affine', 'mpcqp_adjoint_affine']
 
+# include_ext5/mpcqp_rollout_affine.h: likewise -- the taped rollout with an affine term (constant or scheduled, with or without a model schedule) and its
+# reverse sweep with the gradient of every term
+ROLLOUT_AFFINE_SYMBOLS = ['mpcqp_rollout_affine', 'mpcqp_rollout_affine_tape_bytes', 'mpcqp_rollout_adjoint_affine', 'mpcqp_rollout_affine_get_slot',
+                          'mpcqp_rollout_affine_get_tape', 'mpcqp_gains_affine']
+
 
 class RiccatiSettings(C.Structure):
     """mpcqp_riccati_settings (include/mpcqp_riccati.h)."""
@@ -176,6 +181,11 @@ class ModelTraj(C.Structure):
 class AffineTraj(C.Structure):
     """mpcqp_affine_traj (include_ext4/mpcqp_affine.h): entry e of d is the affine term of the solves after steps e * hold .. e * hold + hold - 1."""
     _fields_ = [('struct_size', C.c_int32), ('hold', C.c_int32), ('nentries', C.c_int32), ('rows', C.c_int32), ('d', C.c_void_p)]
+
+
+class RolloutAffineIO(C.Structure):
+    """mpcqp_rollout_affine_io (include_ext5/mpcqp_rollout_affine.h): the gradient of the affine terms per slot out; a host or device pointer, None = not wanted."""
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('d_d_slots', C.c_void_p)]
 
 
 _lib = None
@@ -329,6 +339,16 @@ def load():
         L.mpcqp_adjoint_affine.argtypes = [H, C.POINTER(AdjointIO), C.c_void_p]
         for name in AFFINE_SYMBOLS:
             getattr(L, name).restype = C.c_int
+    if has_rollout_affine(L):
+        L.mpcqp_rollout_affine.argtypes = [H, C.c_int, C.POINTER(Loop), C.POINTER(ModelTraj), C.POINTER(AffineTraj)]
+        L.mpcqp_rollout_affine_tape_bytes.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        L.mpcqp_rollout_adjoint_affine.argtypes = [H, C.POINTER(RolloutAdjointIO), C.POINTER(AdjointModelIO), C.POINTER(AdjointBoundsIO), C.POINTER(RolloutTVIO),
+                                                   C.POINTER(RolloutAffineIO)]
+        L.mpcqp_rollout_affine_get_slot.argtypes = [H, C.c_int, C.c_void_p]
+        L.mpcqp_rollout_affine_get_tape.argtypes = [H, C.c_int, C.c_void_p]
+        L.mpcqp_gains_affine.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ROLLOUT_AFFINE_SYMBOLS:
+            getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -397,6 +417,11 @@ def has_riccati_traj(L=None):
 def has_affine(L=None):
     """True if the library exports include_ext4/mpcqp_affine.h."""
     return _has(L, AFFINE_SYMBOLS)
+
+
+def has_rollout_affine(L=None):
+    """True if the library exports include_ext5/mpcqp_rollout_affine.h."""
+    return _has(L, ROLLOUT_AFFINE_SYMBOLS)
 
 
 def check(rc, what):

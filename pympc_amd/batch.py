@@ -274,11 +274,13 @@ class BatchMPCController:
 
     def _rollout(self, nsteps, w, Ap, Bp, xref_traj, **form):
         """The taped loop of every form: the ``prob.rollout*`` that takes the options of ``form`` -- ``model_traj``, ``estimator``, ``L_traj``
-        as the public method has them: which are there says which loop, so that the loop refuses one that is None -- then the controller's books."""
+        as the public method has them: which are there says which loop, so that the loop refuses one that is None -- then the controller's books.
+        ``d_hold`` among them: the loop with an affine term, ``prob.rollout_affine``, whose ``model_traj`` and ``d_traj`` may both be None."""
         model_traj, estimator = form.get('model_traj'), form.get('estimator')
         if 'estimator' in form:
             form['estimator'] = _est_dict(estimator)
-        roll = getattr(self.prob, 'rollout' + ('_tv' if 'model_traj' in form else '') + ('_est' if 'estimator' in form else ''))
+        roll = getattr(self.prob, 'rollout_affine' if 'd_hold' in form else
+                       'rollout' + ('_tv' if 'model_traj' in form else '') + ('_est' if 'estimator' in form else ''))
         out = roll(nsteps, w=w, Ap=Ap, Bp=Bp, xref_traj=xref_traj, **form)
         if model_traj is not None:
             self._after_schedule(nsteps, model_traj, estimator, form.get('L_traj'))
@@ -306,6 +308,15 @@ class BatchMPCController:
         entry ('L_traj')."""
         return self._rollout(nsteps, w, Ap, Bp, xref_traj, model_traj=model_traj, estimator=estimator, L_traj=L_traj)
 
+    def rollout_affine(self, nsteps, d_traj=None, d_hold=1, model_traj=None, w=None, Ap=None, Bp=None, xref_traj=None):
+        """``run(d_traj=, d_hold=, model_traj=)`` that keeps a tape (mpcqp_rollout_affine, include_ext5/mpcqp_rollout_affine.h): the same loop with
+        the same indexing -- the solve after step k uses entry ``k // d_hold`` of ``d_traj`` [nent,B,nx] or [nent,B,Np,nx] (numpy or a torch device
+        tensor) -- the same dict, the controller left with the last entry used; ``d_traj=None``: the term set with ``set_affine`` throughout (there
+        must be one).  The tape remembers every term, so that ``rollout_adjoint`` can differentiate a loss on the trajectory with respect to the
+        term the call began under ('d0') and every schedule entry ('d_traj') beside everything else.  The plant does not get the offset.  No
+        estimator."""
+        return self._rollout(nsteps, w, Ap, Bp, xref_traj, d_traj=d_traj, d_hold=d_hold, model_traj=model_traj)
+
     def rollout_est(self, nsteps, estimator, w=None, Ap=None, Bp=None, xref_traj=None):
         """``run(estimator=...)`` that keeps a tape (mpcqp_rollout_est, include/mpcqp_rollout_est.h): the output-feedback loop with a
         ``BatchLinearStateEstimator`` -- the same dict (``x, u, status, iter, xhat, y``), ``estimator.x_true`` advanced in place -- and afterwards
@@ -326,7 +337,11 @@ class BatchMPCController:
         schedule entry e) and 'Ap_traj', 'Bp_traj' (entry e: through the plant while entry e was in force; where the plant followed the
         schedule, add them); 'Ad', 'Bd' are then the share of the model the rollout began with.
         After ``rollout_tv_est``: all of both, and 'Ae_traj' [nseg,B,nx,nx], 'Be_traj' [nseg,B,nx,nu], 'L_traj' [nseg,B,nx,ny] (entry e: through
-        the estimator while entry e was in force); 'Ae', 'Be', 'L' are their sums over the entries."""
+        the estimator while entry e was in force); 'Ae', 'Be', 'L' are their sums over the entries.
+        After ``rollout_affine`` (mpcqp_rollout_adjoint_affine): everything above that its tape allows (the ``_traj`` names where it was given a
+        ``model_traj``), and 'd0' [B,rows*nx] -- through the solves made under the term the call began with: entry 0's, and every entry's where
+        no ``d_traj`` was given -- and 'd_traj' [nent,B,rows*nx], entry e: through the solves made under schedule entry e (an entry no solve
+        used: zeros); ``batch_sum`` sums both over the instances ([1,..] and [nent,1,..]).  On any other tape the two names raise."""
         res = self.prob.rollout_adjoint(g_x=g_x, g_u=g_u, want=want, batch_sum=batch_sum, no_reuse=no_reuse, g_xhat=g_xhat, g_y=g_y)
         _, n_weak, status, n_factor = self.prob.rollout_info()
         res.update(n_weak=n_weak, status=status, n_factor=n_factor)
@@ -337,10 +352,15 @@ class BatchMPCController:
         ``dict(K_x0 [B,nu,nx], K_um1 [B,nu,nu], K_xref [B,nu,rows*nx], K_uref [B,nu,nu], n_weak [B], status [B])`` -- the Jacobians of u_0
         for the active set the iterate implies; the key names follow ``pympc_amd.unconstrained``.  ``like``: a torch device tensor to get
         device tensors back.  ``n_weak > 0``: a kink of the law, one-sided gains; ``status`` 1 computed, 0 not solved (zeros), -1 broken
-        factorization (zeros)."""
+        factorization (zeros).  With an affine term in force (``set_affine``) also ``K_d`` [B,nu,rows*nx] = d u_0 / d d, the feed-forward gain of the
+        term in the shape it was set in (mpcqp_gains_affine: the same factorization and seeds; row j is ``adjoint(g_u0=e_j, want=('d',))['d']``);
+        without a term the dict has no such key."""
         g = self.prob.gains(like=like)
         _, n_weak, status = self.prob.adjoint_info()
-        return dict(K_x0=g['x0'], K_um1=g['uminus1'], K_xref=g['xref'], K_uref=g['uref'], n_weak=n_weak, status=status)
+        res = dict(K_x0=g['x0'], K_um1=g['uminus1'], K_xref=g['xref'], K_uref=g['uref'], n_weak=n_weak, status=status)
+        if 'd' in g:
+            res['K_d'] = g['d']
+        return res
 
     def adjoint(self, g_u0=None, g_w=None, want=('x0', 'uminus1', 'xref', 'uref'), batch_sum=False):
         """Vector-Jacobian products of the last solve (mpcqp_adjoint): for ``g_u0`` [B,nu] = dL/du_0 and / or ``g_w`` [B,n] = dL/dw returns

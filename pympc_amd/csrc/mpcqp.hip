@@ -54,6 +54,7 @@
 #include "../../include_ext2/mpcqp_rollout_tv_est.h"
 #include "../../include/mpcqp_adjoint_bounds.h"
 #include "../../include_ext4/mpcqp_affine.h"
+#include "../../include_ext5/mpcqp_rollout_affine.h"
 
 #include "mpcqp_defs.h"
 
@@ -162,6 +163,8 @@ struct mpcqp_handle : Plan {       // the plan (mpcqp_plan.h: ncu, batch, L, lds
     int tape_xref_rows = 1; bool tape_valid = false;           // the reference shape of its entries; false once the model blob or the scaling the tape was made under is replaced
     const mpcqp_affine_traj *loop_aff = nullptr; size_t loop_aff_k0 = 0;      // mpcqp_mpc_loop_affine: the schedule of affine terms of the call in progress and the first step of its next launch (loop_run)
     double *aff_out = nullptr;           // mpcqp_adjoint_affine: the gradient of the term [batch][Np * nx] (null until first use)
+    double *aff_gain = nullptr;          // mpcqp_gains_affine: K_d [batch][nu][Np * nx] (null until first use)
+    RolloutAffine tape_aff = {};         // nslots > 0: the tape is one of mpcqp_rollout_affine (include_ext5/mpcqp_rollout_affine.h) and carries the terms it was made under
     bool has_solve = false;              // a solve has been launched and nothing k_adjoint reads (step data, model, iterate) was replaced since: what mpcqp_adjoint differentiates
 };
 
@@ -1000,7 +1003,8 @@ static AdjointArgs adjoint_args(const mpcqp_handle *h) {
     Q.delta = h->adj.delta; Q.refine = h->adj.refine_iter; Q.extra = h->adj.extra_iter; Q.weak_tol = h->adj.weak_tol;
     return Q;
 }
-static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const double *gu0, bool raw_out) {
+// od: the gradient of the affine term per seed [batch][nseeds][d_rows nx] (mpcqp_gains_affine), or null.
+static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const double *gu0, bool raw_out, double *od = nullptr) {
     if (flush_puts(h)) return MPCQP_ERR_HIP;
     // mpcqp_mpc_step has left the applied input in the step data as the NEXT u_{-1}, while the iterate belongs to the one before (um1_used):
     // the bounds of the first Delta-u rows (the active set) and the QDu gradient need that one, so the kernels read a copy with it put back.
@@ -1010,7 +1014,7 @@ static int launch_adjoint(mpcqp_handle *h, int nseeds, const double *gw, const d
         hipLaunchKernelGGL(k_adjoint_step, dim3((unsigned)std::min<size_t>(1024, (total + 255) / 256)), dim3(256), 0, h->stream, h->L, h->P.step, h->um1_used, h->adj_step, h->batch);
     }
     AdjointArgs Q = adjoint_args(h);
-    Q.nseeds = nseeds; Q.gw = gw; Q.gu0 = gu0; Q.chain = h->L.raw ? 0 : 1;
+    Q.nseeds = nseeds; Q.gw = gw; Q.gu0 = gu0; Q.chain = h->L.raw ? 0 : 1; Q.od = od;
     if (!raw_out) { Q.oq = nullptr; Q.ol = nullptr; Q.ou = nullptr; }
     KpolLaunch v = kpol_launch(h);
     Lay &G = v.G;
@@ -1222,6 +1226,23 @@ extern "C" int mpcqp_gains(mpcqp_handle *h, double *K_x0, double *K_uminus1, dou
     if (get(h, K_x0, Q.ox0, B * S * L.nx * db) || get(h, K_uminus1, Q.oum1, B * S * L.nu * db) || get(h, K_uref, Q.ouref, B * S * L.nu * db) ||
         get(h, K_xref, Q.oxref, B * S * (size_t)L.xref_rows * L.nx * db)) return MPCQP_ERR_HIP;
     return sync_unless_all_device(h, {K_x0, K_uminus1, K_xref, K_uref});
+}
+// mpcqp_gains that also returns K_d = d u_0 / d d (include_ext5/mpcqp_rollout_affine.h): the same launch -- one factorization, the nu unit seeds, four to a solve where
+// mpcqp_gains does that -- in which k_adjoint writes each seed's row of the term's gradient beside its other outputs.
+extern "C" int mpcqp_gains_affine(mpcqp_handle *h, double *K_x0, double *K_uminus1, double *K_xref, double *K_uref, double *K_d) {
+    if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+    if (h->is_setup && !h->L.d_rows) return fail(MPCQP_ERR_STATE, "mpcqp_gains_affine: the handle has no affine term (mpcqp_set_affine); mpcqp_gains is the call without one");
+    int rc = adjoint_ready(h, "mpcqp_gains_affine", true);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = adjoint_alloc(h))) return rc;
+    const Lay &L = h->L; const size_t B = (size_t)h->batch, db = sizeof(double), S = (size_t)L.nu;
+    if (!h->aff_gain && dalloc(h, &h->aff_gain, B * S * (size_t)L.Np * L.nx)) return MPCQP_ERR_HIP;
+    if ((rc = launch_adjoint(h, L.nu, nullptr, nullptr, false, h->aff_gain))) return rc;
+    const AdjointArgs &Q = h->aq;
+    if (get(h, K_x0, Q.ox0, B * S * L.nx * db) || get(h, K_uminus1, Q.oum1, B * S * L.nu * db) || get(h, K_uref, Q.ouref, B * S * L.nu * db) ||
+        get(h, K_xref, Q.oxref, B * S * (size_t)L.xref_rows * L.nx * db) || get(h, K_d, h->aff_gain, B * S * (size_t)L.d_rows * L.nx * db)) return MPCQP_ERR_HIP;
+    return sync_unless_all_device(h, {K_x0, K_uminus1, K_xref, K_uref, K_d});
 }
 extern "C" int mpcqp_get_adjoint_info(mpcqp_handle *h, int32_t *n_active, int32_t *n_weak, int32_t *status) {
     if (!h) return fail(MPCQP_ERR_ARG, "null handle");
@@ -1460,8 +1481,10 @@ extern "C" int mpcqp_adjoint_affine(mpcqp_handle *h, const mpcqp_adjoint_io *io,
 // ny > 0: a tape of the output-feedback loop -- the plant states, measurements, C, L and the estimator's seeds and gradients behind the rest.
 // nslots > 0: a tape of the loop under a model schedule -- the model slots and their gradients behind the rest (V).
 // both: the gain of every schedule entry and the estimator path's per-entry gradients behind those (X).
+// aslots > 0: a tape of mpcqp_rollout_affine -- its affine area (mpcqp_rollout.h: header, the gradient per slot, the terms per slot) RIGHT BEHIND the
+// block of T.nact, where the sweep looks for it; a tape without one has the layout and the size it always had.
 static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int ny, char *base, RolloutTape *T, int nslots = 0, int hold = 0, RolloutSlots *V = nullptr,
-                         RolloutGains *X = nullptr) {
+                         RolloutGains *X = nullptr, int aslots = 0, int arows = 0, int ahold = 0, RolloutAffine *F = nullptr) {
     const size_t B = (size_t)batch, K = (size_t)nsteps, nx = L.nx, nu = L.nu, xw = (size_t)xref_rows * nx, db = sizeof(double);
     size_t off = 0;
     auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~size_t(255); return q; };
@@ -1475,6 +1498,13 @@ static size_t tape_carve(const Lay &L, int batch, int nsteps, int xref_rows, int
     t.carry = (double *)take(B * (size_t)rollout_carry_doubles(L, ny) * db);
     t.nact = (int *)take((3 * K * B + B) * sizeof(int)); t.nweak = t.nact + K * B; t.st = t.nweak + K * B; t.nfactor = t.st + K * B;
     t.nsteps = nsteps; t.batch = batch;
+    RolloutAffine f; memset(&f, 0, sizeof(f));
+    if (aslots > 0) {
+        const size_t per = (size_t)aslots * B * (size_t)arows * nx * db;
+        f.nslots = aslots; f.rows = arows; f.hold = ahold;
+        f.header = (int *)take(ROLLOUT_AFFINE_HEADER); f.dgrad = (double *)take(per); f.dval = (double *)take(per);
+    }
+    if (F) *F = f;
     if (ny > 0) {
         const size_t q = (size_t)ny;
         t.ny = ny;
@@ -1515,6 +1545,7 @@ extern "C" int mpcqp_rollout_release(mpcqp_handle *h) {
     if (h->tape_buf) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->tape_buf); }
     h->tape_buf = nullptr; h->tape_bytes = 0; h->tape_valid = false; h->tape_ny = 0;
     memset(&h->tape, 0, sizeof(h->tape)); memset(&h->tape_slots, 0, sizeof(h->tape_slots)); memset(&h->tape_gains, 0, sizeof(h->tape_gains));
+    memset(&h->tape_aff, 0, sizeof(h->tape_aff));
     return MPCQP_OK;
 }
 // What the calls that read the tape back refuse: no tape, for the estimator's part a tape without one, an entry k (null: the call takes none) out of range.
@@ -1531,8 +1562,11 @@ static int tape_guard(const mpcqp_handle *h, const std::string &fn, bool est, co
 // copy of what the handle holds now (model blob, D, E, c) into the entry's slot, then the step; slot 0 is what it held when the call began.
 // est (mpcqp_rollout_tv_est): both at once -- the tape keeps the gain of every entry too (et's, or io->Lgain over and over), and the step of
 // entry e runs with its gain.
+// affine (mpcqp_rollout_affine, include_ext5/mpcqp_rollout_affine.h): the loop is mpcqp_mpc_loop_affine's -- every step's launch takes its term from the
+// schedule `at` (null: the handle's own term throughout), and the tape keeps the terms as slots: slot 0 what the handle held when the call began (zeros,
+// written here, where it held none -- into entry 0's step data too, which the sweep reads under the tape's d_rows), slot e + 1 schedule entry e.
 static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in, const std::string &what, const mpcqp_model_traj *mt = nullptr,
-                           bool est = false, const mpcqp_est_traj *et = nullptr) {
+                           bool est = false, const mpcqp_est_traj *et = nullptr, bool affine = false, const mpcqp_affine_traj *at = nullptr) {
     int nseg = 0, rc = 0;
     if (mt && (rc = schedule_check(what, nsteps, io_in, mt, est, et, &nseg))) return rc;      // (the refusals of mpcqp_mpc_loop_tv, in its order)
     const int nslots = mt ? nseg + 1 : 0, hold = mt ? mt->hold : 0;
@@ -1541,13 +1575,16 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in,
     if (Lt) first.Lgain = Lt;                       // (a gain schedule stands in for io->Lgain, which may then be null)
     const mpcqp_loop *io = &first;
     if ((rc = loop_check(h, nsteps, io))) return rc;
-    if (h->L.d_rows) return fail(MPCQP_ERR_UNSUPPORTED, what + ": the handle has an affine term (include_ext4/mpcqp_affine.h: mpcqp_set_affine), which the taped rollouts and their reverse sweeps do not carry; clear it (mpcqp_set_affine(h, NULL, 0)) or run mpcqp_mpc_loop_affine");
+    if (!affine && h->L.d_rows) return fail(MPCQP_ERR_UNSUPPORTED, what + ": the handle has an affine term (include_ext4/mpcqp_affine.h: mpcqp_set_affine), which the taped rollouts and their reverse sweeps do not carry; clear it (mpcqp_set_affine(h, NULL, 0)) or run mpcqp_mpc_loop_affine");
+    if (affine && !at && !h->L.d_rows) return fail(MPCQP_ERR_STATE, what + ": no schedule of terms given and the handle has no affine term (mpcqp_set_affine): mpcqp_rollout is the taped loop without one");
     if (!h->has_solve) return fail(MPCQP_ERR_STATE, what + ": no solve since the last setup, update, model update or warm start: the iterate does not belong to the step data of tape entry 0");
     if (io->xref_traj && io->xref_rows && io->xref_rows != h->L.xref_rows)
         return fail(MPCQP_ERR_UNSUPPORTED, what + ": xref_traj must have the reference shape of the last upload (the entries of a tape have one shape)");
     const Lay &L = h->L;
     const size_t B = (size_t)h->batch, nx = L.nx, nu = L.nu, ny = (size_t)io->ny, db = sizeof(double);
-    const size_t bytes = tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, nullptr, nullptr, nslots, hold);
+    const int arows = !affine ? 0 : at ? at->rows : L.d_rows, ahold = at ? at->hold : 0, aslots = affine ? rollout_affine_nslots(nsteps, ahold) : 0;
+    const int rows_before = L.d_rows;               // (the handle's own term, if any: slot 0)
+    const size_t bytes = tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, nullptr, nullptr, nslots, hold, nullptr, nullptr, aslots, arows, ahold);
     if (!h->tape_buf || bytes > h->tape_bytes) {
         void *q = nullptr;
         if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MPCQP_ERR_HIP, what + ": the tape could not be allocated (" + what + "_tape_bytes says how much it takes)"); }
@@ -1555,8 +1592,18 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in,
         h->tape_buf = q; h->tape_bytes = bytes;
     }
     h->tape_valid = false;
-    RolloutTape T; RolloutSlots V; RolloutGains X;
-    tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, (char *)h->tape_buf, &T, nslots, hold, &V, &X);
+    RolloutTape T; RolloutSlots V; RolloutGains X; RolloutAffine F;
+    tape_carve(L, h->batch, nsteps, L.xref_rows, io->ny, (char *)h->tape_buf, &T, nslots, hold, &V, &X, aslots, arows, ahold, &F);
+    memset(&h->tape_aff, 0, sizeof(h->tape_aff));   // (not an affine tape until this call has made one)
+    if (affine) {                                   // the header the sweep reads, the terms of every slot, a zero gradient until a sweep writes one
+        const size_t aw = (size_t)arows * nx * db;
+        HIPCHK(hipMemsetAsync(F.header, 0, ROLLOUT_AFFINE_HEADER, h->stream));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)F.header, ahold, 1, h->stream));
+        HIPCHK(hipMemsetAsync(F.dgrad, 0, (size_t)aslots * B * aw, h->stream));
+        if (rows_before) HIPCHK(hipMemcpy2DAsync(F.dval, aw, h->P.step + L.od, db * (size_t)L.step_sz, aw, B, hipMemcpyDeviceToDevice, h->stream));
+        else HIPCHK(hipMemsetAsync(F.dval, 0, B * aw, h->stream));
+        if (at) HIPCHK(hipMemcpyAsync(F.dval + B * (size_t)arows * nx, at->d, (size_t)(aslots - 1) * B * aw, hipMemcpyDefault, h->stream));
+    }
     auto keep_slot = [&](int s) -> int {                   // what the handle holds now, as slot s
         const size_t sB = (size_t)s * B;
         HIPCHK(hipMemcpyAsync(const_cast<double *>(V.model) + sB * L.model_sz, h->P.model, B * L.model_sz * db, hipMemcpyDeviceToDevice, h->stream));
@@ -1579,12 +1626,15 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in,
     }
     HIPCHK(hipMemsetAsync(T.nact, 0, (3 * (size_t)nsteps * B + B) * sizeof(int), h->stream));      // (mpcqp_get_rollout_info before a sweep: all zero)
     h->tape = T; h->tape_slots = V; h->tape_gains = X; h->tape_xref_rows = L.xref_rows; h->tape_ny = io->ny;
+    struct AffGuard { mpcqp_handle *h; ~AffGuard() { h->loop_aff = nullptr; h->loop_aff_k0 = 0; } } aff_guard{h};      // (loop_run reads them; cleared however the call ends)
     const size_t per = (size_t)L.n + 2 * (size_t)L.m + L.step_sz + nu + 1;
     const unsigned grid = (unsigned)std::min<size_t>(1024, (B * per + 255) / 256);
     for (int k = 0; k < nsteps; ++k) {
         hipLaunchKernelGGL(k_rollout_tape, dim3(grid), dim3(256), 0, h->stream, h->L, h->P, T, k, (const double *)(h->um1_moved ? h->um1_used : nullptr));
         HIPCHK(hipGetLastError());
         const size_t k0 = (size_t)k;
+        if (affine && k == 0 && !rows_before)       // entry 0 was solved without a term: zeros under the tape's d_rows, not whatever the blob held there
+            HIPCHK(hipMemset2DAsync(T.step + L.od, db * (size_t)L.step_sz, 0, (size_t)arows * nx * db, B, h->stream));
         if (mt && k % hold == 0) {                  // a boundary step: the entry replaces the model under the iterate the tape has just copied
             const size_t e = (size_t)(k / hold);
             mpcqp_model M; memset(&M, 0, sizeof(M));
@@ -1598,8 +1648,10 @@ static int rollout_forward(mpcqp_handle *h, int nsteps, const mpcqp_loop *io_in,
             seg.x_traj = T.xp + k0 * B * nx; seg.y_traj = T.ym + k0 * B * ny;
             if (mt) seg.Lgain = X.Lg + (size_t)(k / hold) * B * nx * ny;
         }
+        h->loop_aff = at; h->loop_aff_k0 = k0;      // (null: the handle's own term stays in force)
         if ((rc = loop_run(h, 1, &seg, k == nsteps - 1))) return rc;
     }
+    if (affine) h->tape_aff = F;
     if (ny && (get(h, io->x_traj, T.xp, ((size_t)nsteps + 1) * B * nx * db) || get(h, io->y_traj, T.ym, (size_t)nsteps * B * ny * db) ||
                get(h, io->x_true, T.xt, B * nx * db))) return MPCQP_ERR_HIP;
     h->tape_valid = true;
@@ -1633,6 +1685,56 @@ extern "C" int mpcqp_rollout_tv_get_slot(mpcqp_handle *h, int s, double *model, 
     const size_t B = (size_t)h->batch, sB = (size_t)s * B, db = sizeof(double);
     if (get(h, model, V.model + sB * L.model_sz, B * L.model_sz * db) || get(h, D, V.D + sB * L.n, B * L.n * db) ||
         get(h, E, V.E + sB * L.m, B * L.m * db) || get(h, c, V.c + sB, B * db)) return MPCQP_ERR_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+// ---- the taped rollout with an affine term in the prediction model (include_ext5/mpcqp_rollout_affine.h) ----------------------------------
+extern "C" int mpcqp_rollout_affine(mpcqp_handle *h, int nsteps, const mpcqp_loop *io, const mpcqp_model_traj *mt, const mpcqp_affine_traj *at) {
+    if (!h || !io || nsteps < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine: bad argument");
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_affine before mpcqp_setup");
+    if (at && h->L.d_rows && h->L.d_rows != at->rows)
+        return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine: the handle's term and the schedule's entries differ in their rows (the entries of a tape have one shape): set the term in the schedule's shape, or clear it");
+    if (at) {                                       // (mpcqp_mpc_loop_affine's refusals, in its order: output feedback last)
+        if (at->struct_size != (int32_t)sizeof(mpcqp_affine_traj)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine: struct_size is not sizeof(mpcqp_affine_traj)");
+        if (at->hold < 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine: hold must be >= 1");
+        if (at->nentries < (nsteps + at->hold - 1) / at->hold) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine: fewer than ceil(nsteps / hold) entries");
+        if (at->rows != 1 && at->rows != h->L.Np) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine: rows must be 1 or Np");
+        if (!at->d) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine: no entries given (at == NULL runs the loop with the handle's own term)");
+    }
+    if (io->ny > 0) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout_affine: output feedback with an affine term is not implemented (the estimator's model has no offset)");
+    return rollout_forward(h, nsteps, io, "mpcqp_rollout_affine", mt, false, nullptr, true, at);
+}
+extern "C" int mpcqp_rollout_affine_tape_bytes(mpcqp_handle *h, int nsteps, int model_hold, int d_hold, int rows, int64_t *bytes) {
+    if (!h || !bytes || nsteps < 1 || model_hold < 0 || d_hold < 0) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine_tape_bytes: bad argument");
+    if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_affine_tape_bytes before mpcqp_setup");
+    if (rows != 1 && rows != h->L.Np) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine_tape_bytes: rows must be 1 or Np");
+    *bytes = (int64_t)tape_carve(h->L, h->batch, nsteps, h->L.xref_rows, 0, nullptr, nullptr, model_hold ? (nsteps + model_hold - 1) / model_hold + 1 : 0, model_hold,
+                                 nullptr, nullptr, rollout_affine_nslots(nsteps, d_hold), rows, d_hold);
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_rollout_affine_get_slot(mpcqp_handle *h, int s, double *d) {
+    if (!h || !d) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine_get_slot: null argument");
+    const int rc = tape_guard(h, "mpcqp_rollout_affine_get_slot", false, nullptr);
+    if (rc) return rc;
+    const RolloutAffine &F = h->tape_aff;
+    if (F.nslots < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_affine_get_slot: the tape is not one of mpcqp_rollout_affine (no term slots)");
+    if (s < 0 || s >= F.nslots) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine_get_slot: s must be in 0 .. nslots - 1");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t per = (size_t)h->batch * (size_t)F.rows * h->L.nx;
+    if (get(h, d, F.dval + (size_t)s * per, per * sizeof(double))) return MPCQP_ERR_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+extern "C" int mpcqp_rollout_affine_get_tape(mpcqp_handle *h, int k, double *d) {
+    if (!h || !d) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_affine_get_tape: null argument");
+    const int rc = tape_guard(h, "mpcqp_rollout_affine_get_tape", false, &k);
+    if (rc) return rc;
+    const RolloutAffine &F = h->tape_aff;
+    if (F.nslots < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_affine_get_tape: the tape is not one of mpcqp_rollout_affine");
+    HIPCHK(hipSetDevice(h->device));
+    const Lay &L = h->L;
+    const size_t B = (size_t)h->batch, w = sizeof(double) * (size_t)F.rows * L.nx;
+    HIPCHK(hipMemcpy2DAsync(d, w, h->tape.step + (size_t)k * B * L.step_sz + L.od, sizeof(double) * (size_t)L.step_sz, w, B, hipMemcpyDefault, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
@@ -1691,10 +1793,12 @@ static int put_seed(mpcqp_handle *h, double *dst, const double *src, size_t byte
 // bo: the bound gradients (mpcqp_rollout_adjoint_bounds), or null.
 // tv: the call is mpcqp_rollout_adjoint_tv; to: its per-slot outputs, or null.
 // tve: the call is mpcqp_rollout_adjoint_tv_est (tv and est are set too); xo: its per-entry estimator outputs, or null.
+// aff: the call is mpcqp_rollout_adjoint_affine (tv: it was given a `to`, as a scheduled tape needs); ao: the gradient of the terms per slot, or null.
 static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo, bool est,
                          const mpcqp_adjoint_bounds_io *bo = nullptr, bool tv = false, const mpcqp_rollout_tv_io *to = nullptr,
-                         bool tve = false, const mpcqp_rollout_tv_est_io *xo = nullptr) {
+                         bool tve = false, const mpcqp_rollout_tv_est_io *xo = nullptr, bool aff = false, const mpcqp_rollout_affine_io *ao = nullptr) {
     if (!h || !io) return fail(MPCQP_ERR_ARG, "null argument");
+    if (ao && ao->struct_size != (int32_t)sizeof(mpcqp_rollout_affine_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_affine: struct_size is not sizeof(mpcqp_rollout_affine_io)");
     if (xo && xo->struct_size != (int32_t)sizeof(mpcqp_rollout_tv_est_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_tv_est: struct_size is not sizeof(mpcqp_rollout_tv_est_io)");
     if (tve && eo && (eo->d_L || eo->d_Ae || eo->d_Be))
         return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_tv_est: d_L, d_Ae, d_Be are per entry under a schedule: ask for them in mpcqp_rollout_tv_est_io");
@@ -1709,7 +1813,7 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (bo) {
         const bool other = io->lam || io->d_uminus1 || io->d_uref || io->d_xref || io->d_Ap || io->d_Bp || m.any ||
                            (eo && (eo->eta || eo->d_C || eo->d_L || eo->d_v || eo->d_Ae || eo->d_Be));
-        if (!tv && !bd.any && !other) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_bounds: no output asked for");
+        if (!tv && !aff && !bd.any && !other) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_bounds: no output asked for");
         if (bd.any && m.any && bd.batch_sum != m.batch_sum) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_bounds: batch_sum of mo and of bo differ");
     }
     if (eo && eo->struct_size != (int32_t)sizeof(mpcqp_rollout_est_io)) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint_est: struct_size is not sizeof(mpcqp_rollout_est_io)");
@@ -1718,11 +1822,16 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     if (io->no_reuse != 0 && io->no_reuse != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: no_reuse is 0 or 1");
     if (m.batch_sum != 0 && m.batch_sum != 1) return fail(MPCQP_ERR_ARG, "mpcqp_rollout_adjoint: batch_sum is 0 or 1");
     if (!h->is_setup) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint before mpcqp_setup");
-    if (h->L.d_rows) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout_adjoint: the handle has an affine term (include_ext4/mpcqp_affine.h: mpcqp_set_affine), which the taped rollouts and their reverse sweeps do not carry");
+    const RolloutAffine &F = h->tape_aff;            // (nslots > 0: a tape of mpcqp_rollout_affine, which has every term it needs on it)
+    const bool aff_tape = h->tape_buf && h->tape.nsteps >= 1 && F.nslots > 0;
+    if (h->L.d_rows && !aff_tape && !aff) return fail(MPCQP_ERR_UNSUPPORTED, "mpcqp_rollout_adjoint: the handle has an affine term (include_ext4/mpcqp_affine.h: mpcqp_set_affine), which the taped rollouts and their reverse sweeps do not carry");
     if (!h->tape_buf || h->tape.nsteps < 1) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the handle holds no tape (call mpcqp_rollout first)");
     if (!h->tape_valid) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the model or the scaling the tape was made under has been replaced (mpcqp_setup*, mpcqp_update_model, mpcqp_update_vectors with l, u) or its rollout failed: roll out again");
     const RolloutSlots &V = h->tape_slots;
     const RolloutGains &X = h->tape_gains;
+    if (!aff && aff_tape) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the tape is one of mpcqp_rollout_affine (an affine term in the prediction model); use mpcqp_rollout_adjoint_affine (include_ext5/mpcqp_rollout_affine.h)");
+    if (aff && !aff_tape) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_affine: the tape is not one of mpcqp_rollout_affine; use the sweep of the call that made it");
+    if (aff && tv != (V.nslots > 0)) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_affine: pass a mpcqp_rollout_tv_io exactly when the tape has a model schedule");
     if (!tve && X.Lg) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the tape is one of mpcqp_rollout_tv_est (an estimator under a model schedule); use mpcqp_rollout_adjoint_tv_est");
     if (tve && !X.Lg) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint_tv_est: the tape is not one of mpcqp_rollout_tv_est; use the sweep of the call that made it");
     if (!tv && V.nslots > 0) return fail(MPCQP_ERR_STATE, "mpcqp_rollout_adjoint: the tape is one of mpcqp_rollout_tv (a model schedule); use mpcqp_rollout_adjoint_tv");
@@ -1735,6 +1844,7 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     KpolLaunch v = kpol_launch(h);
     Lay &G = v.G;
     G.raw = 0; G.xref_rows = h->tape_xref_rows;     // (the tape's entries, whatever the handle has been given since)
+    G.d_rows = aff_tape ? F.rows : 0;               // (likewise the shape of their affine term: every entry reads its own, step + Lay::od)
     RolloutSweep W; memset(&W, 0, sizeof(W));
     adjoint_model_offsets(G, W.off);
     const size_t B = (size_t)h->batch, K = (size_t)T.nsteps, nx = G.nx, nu = G.nu, db = sizeof(double);
@@ -1745,7 +1855,8 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
     AdjointArgs Q = adjoint_args(h);
     Q.nseeds = 1; Q.gw = nullptr; Q.gu0 = nullptr; Q.chain = 1; Q.ncol = 1; Q.cs = 0;
     const bool slot_model = tv && to && (to->d_Ad_slots || to->d_Bd_slots);      // (the Ad, Bd gradients of a scheduled tape are asked for in `to`, not in mo)
-    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = ((m.any || slot_model) ? ROLLOUT_WANT_MODEL : 0) | (bd.any ? ROLLOUT_WANT_BOUNDS : 0);
+    W.mout = h->adjm_out; W.no_reuse = io->no_reuse; W.want_model = ((m.any || slot_model) ? ROLLOUT_WANT_MODEL : 0) | (bd.any ? ROLLOUT_WANT_BOUNDS : 0) |
+                                                                      (aff && ao && ao->d_d_slots ? ROLLOUT_WANT_AFFINE : 0);
     const size_t with_carry = v.smem + db * (size_t)rollout_carry_doubles(G, (int)ny);
     W.carry_lds = with_carry <= 160 * 1024 ? 1 : 0;         // (lam, mu, g behind the common block, or in the tape's few doubles of global memory)
     const size_t smem = W.carry_lds ? with_carry : v.smem;
@@ -1772,6 +1883,7 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
         if (get(h, to->d_Ad_slots, V.dAd, S * B * nx * nx * db) || get(h, to->d_Bd_slots, V.dBd, S * B * nx * nu * db) ||
             get(h, to->d_Ap_entries, V.dAp, (S - 1) * B * nx * nx * db) || get(h, to->d_Bp_entries, V.dBp, (S - 1) * B * nx * nu * db)) return MPCQP_ERR_HIP;
     }
+    if (aff && ao && get(h, ao->d_d_slots, F.dgrad, (size_t)F.nslots * B * (size_t)F.rows * nx * db)) return MPCQP_ERR_HIP;
     if (tve && xo) {
         const size_t S1 = (size_t)V.nslots - 1;
         if (get(h, xo->d_Ae_entries, X.dAe, S1 * B * nx * nx * db) || get(h, xo->d_Be_entries, X.dBe, S1 * B * nx * nu * db) ||
@@ -1792,7 +1904,8 @@ static int rollout_sweep(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, co
                                       eo ? eo->G_xhat : nullptr, eo ? eo->G_y : nullptr, eo ? eo->eta : nullptr, eo ? eo->d_C : nullptr, eo ? eo->d_L : nullptr,
                                       eo ? eo->d_v : nullptr, eo ? eo->d_Ae : nullptr, eo ? eo->d_Be : nullptr,
                                       to ? to->d_Ad_slots : nullptr, to ? to->d_Bd_slots : nullptr, to ? to->d_Ap_entries : nullptr, to ? to->d_Bp_entries : nullptr,
-                                      xo ? xo->d_Ae_entries : nullptr, xo ? xo->d_Be_entries : nullptr, xo ? xo->d_L_entries : nullptr}, &m);
+                                      xo ? xo->d_Ae_entries : nullptr, xo ? xo->d_Be_entries : nullptr, xo ? xo->d_L_entries : nullptr,
+                                      ao ? ao->d_d_slots : nullptr}, &m);
 }
 extern "C" int mpcqp_rollout_adjoint_tv(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo,
                                         const mpcqp_adjoint_bounds_io *bo, const mpcqp_rollout_tv_io *to) {
@@ -1801,6 +1914,10 @@ extern "C" int mpcqp_rollout_adjoint_tv(mpcqp_handle *h, const mpcqp_rollout_adj
 extern "C" int mpcqp_rollout_adjoint_tv_est(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_rollout_est_io *eo, const mpcqp_adjoint_model_io *mo,
                                             const mpcqp_adjoint_bounds_io *bo, const mpcqp_rollout_tv_io *to, const mpcqp_rollout_tv_est_io *xo) {
     return rollout_sweep(h, io, eo, mo, true, bo, true, to, true, xo);
+}
+extern "C" int mpcqp_rollout_adjoint_affine(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo,
+                                            const mpcqp_adjoint_bounds_io *bo, const mpcqp_rollout_tv_io *to, const mpcqp_rollout_affine_io *ao) {
+    return rollout_sweep(h, io, nullptr, mo, false, bo, to != nullptr, to, false, nullptr, true, ao);
 }
 extern "C" int mpcqp_rollout_adjoint(mpcqp_handle *h, const mpcqp_rollout_adjoint_io *io, const mpcqp_adjoint_model_io *mo) {
     return rollout_sweep(h, io, nullptr, mo, false);

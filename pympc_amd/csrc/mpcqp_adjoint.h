@@ -35,7 +35,21 @@ struct AdjointArgs {
     int *nact, *nweak, *status;   // [batch]
     double delta, weak_tol; int refine, extra, nseeds, chain;      // (extra: sweeps beyond refine, at most)
     int ncol, cs;                 // seeds per solve (1 or ADJOINT_COLS) and the distance of their columns in the work area
+    double *od;                   // [batch][nseeds][d_rows nx] the gradient of the affine term per seed (mpcqp_gains_affine, include_ext5/mpcqp_rollout_affine.h), or null:
+                                  // the work area keeps only the last group of seeds, so K_d is written where the group's other outputs are
 };
+
+// Seed sd's r_y = y into its row of the term's gradient: k_affine_grad's rule (mpcqp_affine.h) -- -r_y of row blocks 1 .. Np, d_rows = 1: summed in ascending order
+__device__ __forceinline__ void adjoint_affine_out(const Lay &L, const double *y, double *o) {
+    const int w = L.d_rows * L.nx;
+    const double *ry = y + L.nx;
+    for (int e = threadIdx.x; e < w; e += NT) {
+        double acc = 0.0;
+        if (L.d_rows > 1) acc = -ry[e];
+        else for (int k = 0; k < L.Np; ++k) acc -= ry[k * L.nx + e];
+        o[e] = acc;
+    }
+}
 
 // The passes around the solves, for C seeds at a time (C = 1, or ADJOINT_COLS with the columns in `mask` live): column col of a vector of
 // n (m) doubles lies col n (col m) further on; a row's coefficients are walked once for all its columns.  T: LDS, C m doubles.
@@ -280,6 +294,7 @@ __global__ __launch_bounds__(NT) void k_adjoint(Lay L, Ptrs P, AdjointArgs Q) {
                 // 4. dL/dq, dL/dl, dL/du and the chain rule into the controller's parameters
                 const AdjointOut out = adjoint_out(L, Q, b);
                 for (int col = 0; col < nc; ++col) adjoint_outputs(c, act, xs + (size_t)col * L.n, ys + (size_t)col * L.m, s0 + col, Q.chain, out);
+                if (Q.od) for (int col = 0; col < nc; ++col) adjoint_affine_out(L, ys + (size_t)col * L.m, Q.od + ((size_t)b * ns + s0 + col) * L.d_rows * L.nx);
                 __syncthreads();
             }
         };
@@ -291,5 +306,6 @@ __global__ __launch_bounds__(NT) void k_adjoint(Lay L, Ptrs P, AdjointArgs Q) {
     }
     // 5. not computed: every output is zero
     if (st != 1) adjoint_zero(L, ns, Q.chain, adjoint_out(L, Q, b));
+    if (st != 1 && Q.od) for (int e = tid; e < ns * L.d_rows * L.nx; e += NT) Q.od[(size_t)b * ns * L.d_rows * L.nx + e] = 0.0;
     if (tid == 0) { Q.status[b] = st; Q.nact[b] = nact; Q.nweak[b] = nweak; }
 }

@@ -28,6 +28,10 @@
 //             models and, where given, of observer gains.  The estimator stepped under the slot in force, pi(k) = 1 + k / hold, so its phases
 //             read Ad, Bd of that slot's blob from global memory (S.hot holds the solve's slot sigma(k), another one at every boundary step)
 //             and the gain of entry k / hold (RolloutGains); d_Ae, d_Be, d_L are re-aimed per entry as the plant's d_Ap, d_Bp are.
+//   affine    a RUNTIME path of the state-feedback sweeps, no instantiation of its own (mpcqp_rollout_adjoint_affine, include_ext5/mpcqp_rollout_affine.h): the loop
+//             ran with an affine term in the prediction model.  Every entry reads its bounds under the term in its own step data (step + Lay::od; the
+//             sweep's Lay carries the tape's d_rows), and under ROLLOUT_WANT_AFFINE -r_y of the dynamics row blocks 1 .. Np is added onto the slot
+//             tau(k) the entry was solved under.  A tape without a term has d_rows = 0 and the flag clear: it executes none of it.
 // Every sum over the steps is formed by the thread that owns the entry, in the order K-1 .. 0: no atomics, the same bits every time.
 #pragma once
 
@@ -65,6 +69,22 @@ struct RolloutSweep {
                                   // kernel arguments: the sweep has no scalar register to spare, and one that is not asked for bounds must cost what it did.)
 };
 constexpr int ROLLOUT_WANT_MODEL = 1, ROLLOUT_WANT_BOUNDS = 2;
+// bit 2 (ROLLOUT_WANT_AFFINE, mpcqp_rollout_adjoint_affine, include_ext5/mpcqp_rollout_affine.h): the tape is one of mpcqp_rollout_affine and the gradient of
+// its terms is wanted, per slot.  The same economy: a flag bit and a fixed place -- the tape's affine area, which tape_carve puts right behind the
+// block of T.nact: 256 bytes of header (int hold; 0: one constant term, every entry under slot 0), then d_d_slots [nslots][batch][d_rows nx].  The
+// term an entry was solved with needs neither: it is in the entry's own step data, read where Lay::d_rows > 0 (the sweep's Lay has the tape's).
+constexpr int ROLLOUT_WANT_AFFINE = 4;
+constexpr size_t ROLLOUT_AFFINE_HEADER = 256;
+// The affine area as the host sees it (tape_carve; not a kernel argument).  dval: the terms themselves, for mpcqp_rollout_affine_get_slot.
+struct RolloutAffine {
+    int *header;                          // hold (0: one constant term)
+    double *dgrad, *dval;                 // [nslots][batch][rows nx] x2
+    int nslots, rows, hold;
+};
+__host__ __device__ inline size_t rollout_info_bytes(size_t K, size_t B) { return ((3 * K * B + B) * sizeof(int) + 255) & ~size_t(255); }
+// tau(k): the term slot tape entry k was solved under; the slots a tape of K steps has (the ONE statement of both: kernel and host)
+__host__ __device__ inline int rollout_affine_tau(int k, int hold) { return (k == 0 || hold == 0) ? 0 : 1 + (k - 1) / hold; }
+__host__ __device__ inline int rollout_affine_nslots(int K, int hold) { return hold == 0 ? 1 : 2 + (K - 1) / hold; }      // (slot 0 and ceil(K / hold) entries)
 // The model slots of a scheduled tape (mpcqp_rollout_tv, include_ext/mpcqp_rollout_tv.h): slot 0 is the model the call began under, slot e + 1
 // schedule entry e.  An argument of k_rollout_adjoint_tv alone: the other two sweeps neither take nor read it.
 struct RolloutSlots {
@@ -83,6 +103,13 @@ struct RolloutGains {
 // lam | lam as the plant alone gives it | d_x0 of the step | g | mu | d_uref of the step | d_uref so far
 // with an estimator (ny > 0), behind them: eta | eta before d_x0 | s | xhat[k|k] | t | r | innovation
 __host__ __device__ inline int rollout_carry_doubles(const Lay &L, int ny = 0) { return 3 * L.nx + 4 * L.nu + (ny > 0 ? 4 * L.nx + 3 * ny : 0); }
+
+// Workgroup b's row of slot 0 of the term's gradient in the tape's affine area (w = d_rows nx doubles; slot s lies s batch w further on), and the area's hold.
+__device__ __forceinline__ double *rollout_affine_grad(const RolloutTape &T, int w, int &hold) {
+    const char *area = (const char *)T.nact + rollout_info_bytes((size_t)T.nsteps, (size_t)T.batch);
+    hold = *(const int *)area;
+    return (double *)(area + ROLLOUT_AFFINE_HEADER) + (size_t)blockIdx.x * w;
+}
 
 // Entry k of the tape from what the handle holds now.  um1: the u_{-1} the current solve was made with where the step data no longer have it, else null.
 __global__ __launch_bounds__(256) void k_rollout_tape(Lay L, Ptrs P, RolloutTape T, int k, const double *um1) {
@@ -159,6 +186,14 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
     if (W.want_model & ROLLOUT_WANT_BOUNDS) for (int e = tid; e < adjoint_bounds_entries(L); e += NT) bdst(e) = 0.0;
     for (int e = tid; e < nx * nx; e += NT) dAp[e] = 0.0;
     for (int e = tid; e < nx * nu; e += NT) dBp[e] = 0.0;
+    // the affine area, found behind the flag where it is used (rollout_affine_grad: ONE statement of the place; nothing of it is kept live across the entries, the
+    // sweep has no register to spare) and never in the estimator's instantiations, which no affine tape reaches
+    if constexpr (!EST) if (W.want_model & ROLLOUT_WANT_AFFINE) {
+        int hold;
+        const int w = L.d_rows * nx;                     // every slot of the term's gradient: a slot no entry was solved under stays zero
+        double *add = rollout_affine_grad(T, w, hold);
+        for (int s = 0; s < rollout_affine_nslots(K, hold); ++s) for (int e = tid; e < w; e += NT) add[(size_t)s * B * w + e] = 0.0;
+    }
     if (EST) {                                           // eta_K = G_xh[K]
         for (int i = tid; i < nx; i += NT) { const double v = T.gxh[((size_t)K * B + b) * nx + i]; eta[i] = v; T.eta[((size_t)K * B + b) * nx + i] = v; }
         if constexpr (TV) {
@@ -264,7 +299,7 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
             block_reduce<1, 3>(ymx, cnt, S.red);
             const double ytol = Q.weak_tol * fmax(1.0, ymx[0]);
             for (int i = tid; i < L.m; i += NT) {
-                double lo, hi; row_bounds(c, S.x0s, S.du0, affine_ptr(L, P, b), i, lo, hi);
+                double lo, hi; row_bounds(c, S.x0s, S.du0, step + L.od, i, lo, hi);      // (the term this entry was solved with, where the tape has one: L.d_rows is the tape's)
                 const double zv = za[i], yv = ya[i];
                 const int a = kpol_row(E[i], zv, yv, lo, hi, cc, delta, true, om[i]);
                 if (a != act[i]) cnt[2] += 1.0;
@@ -296,6 +331,19 @@ __device__ __forceinline__ void rollout_adjoint_body(const Lay &L, const Ptrs &P
                 if (W.want_model & ROLLOUT_WANT_MODEL) for (int e = tid; e < EN; e += NT) mdst(e) += adjoint_model_entry(L, M, wa, xs, ya, ys, model, step, e, 0, 1);
                 if (W.want_model & ROLLOUT_WANT_BOUNDS)      // (dL/db = r_y of this entry onto the bounds; a sweep that is not asked runs none of it)
                     for (int e = tid; e < adjoint_bounds_entries(L); e += NT) bdst(e) += adjoint_bounds_entry(L, act, ys, e);
+                if constexpr (!EST) if (W.want_model & ROLLOUT_WANT_AFFINE) {      // (k_affine_grad's rule, mpcqp_affine.h, onto the slot this entry was solved under; the thread that zeroed the element)
+                    int hold;
+                    const int w = L.d_rows * nx;
+                    double *dd = rollout_affine_grad(T, w, hold);
+                    dd += (size_t)rollout_affine_tau(k, hold) * B * w;
+                    const double *ry = ys + nx;              // (row block 1 onwards)
+                    for (int e = tid; e < w; e += NT) {
+                        double acc = 0.0;
+                        if (L.d_rows > 1) acc = -ry[e];
+                        else for (int j = 0; j < L.Np; ++j) acc -= ry[j * nx + e];
+                        dd[e] += acc;
+                    }
+                }
                 __syncthreads();
                 if (EST) for (int i = tid; i < nx; i += NT) { lam[i] = lamn[i]; eta[i] = etan[i] + dx0[i]; }
                 else for (int i = tid; i < nx; i += NT) lam[i] = lamn[i] + dx0[i];

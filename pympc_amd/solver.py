@@ -30,8 +30,9 @@ _FIXED_AT_CREATE = ('rho', 'sigma', 'scaling', 'soft_constraints', 'backend', 't
 _STATUS_STRINGS = {}       # status code -> OSQP's string (filled from mpcqp_status_string on first use)
 
 # the tape a handle holds: its steps, the rows of its references, the outputs of its estimator (0: state feedback), and None or
-# (hold, nseg, the schedule gave Ad, the schedule gave Bd) of the model schedule it was made under
-_Tape = collections.namedtuple('_Tape', 'K rows ny sched')
+# (hold, nseg, the schedule gave Ad, the schedule gave Bd) of the model schedule it was made under, and None or (rows, hold, nslots) of the affine
+# terms it was made under (rollout_affine; hold 0: one constant term, one slot)
+_Tape = collections.namedtuple('_Tape', 'K rows ny sched aff', defaults=(None,))
 
 # the extensions beside include/mpcqp.h: feature -> (is it in the loaded library, what BatchProblem._need says where it is not)
 _FEATURES = dict(
@@ -45,7 +46,8 @@ _FEATURES = dict(
     rollout_tv_est=(_lib.has_rollout_tv_est, 'no output-feedback loop under a model schedule (include_ext2/mpcqp_rollout_tv_est.h)'),
     model_update=(_lib.has_model_update, 'no in-place model update (include/mpcqp_model.h)'),
     model_traj=(_lib.has_model_update, 'no model schedule for the device loop (include/mpcqp_model.h)'),
-    affine=(_lib.has_affine, 'no affine term in the prediction model (include_ext4/mpcqp_affine.h)'))
+    affine=(_lib.has_affine, 'no affine term in the prediction model (include_ext4/mpcqp_affine.h)'),
+    rollout_affine=(_lib.has_rollout_affine, 'no taped rollout with an affine term (include_ext5/mpcqp_rollout_affine.h)'))
 
 
 def _ptr(a):
@@ -398,12 +400,19 @@ class BatchProblem:
     def gains(self, want=('x0', 'uminus1', 'xref', 'uref'), like=None):
         """Jacobians of the first input u_0 of the current solution (mpcqp_gains: one factorization, nu seeds): dict with 'x0' [B, nu, nx],
         'uminus1' [B, nu, nu], 'xref' [B, nu, rows*nx], 'uref' [B, nu, nu] as named in ``want``; numpy, or torch tensors on the device
-        of ``like``."""
+        of ``like``.  On a problem that has an affine term (``set_affine``), where the library has the call (mpcqp_gains_affine,
+        include_ext5/mpcqp_rollout_affine.h: the same factorization and seeds), also 'd' [B, nu, rows*nx] = d u_0 / d d; without a term the dict is
+        as it always was."""
         self._need('adjoint')
         B, nu = self.batch, self.nu
         shapes = dict(x0=(B, nu, self.nx), uminus1=(B, nu, nu), xref=(B, nu, self._xref_rows_last * self.nx), uref=(B, nu, nu))
         res = {k: self._out(like, shapes[k]) for k in want}
         self._keep = [res]
+        drows = self.affine_rows() if _lib.has_rollout_affine(self._L) and _lib.has_affine(self._L) else 0
+        if drows:
+            res['d'] = self._out(like, (B, nu, drows * self.nx))
+            _lib.check(self._L.mpcqp_gains_affine(self._h, *[_ptr(res.get(k)) for k in ('x0', 'uminus1', 'xref', 'uref', 'd')]), 'mpcqp_gains_affine')
+            return res
         _lib.check(self._L.mpcqp_gains(self._h, *[_ptr(res.get(k)) for k in ('x0', 'uminus1', 'xref', 'uref')]), 'mpcqp_gains')
         return res
 
@@ -420,15 +429,29 @@ class BatchProblem:
     _tape = None               # the _Tape the handle holds (None: none)
     rollout_count = 0          # rollouts made so far (pympc_amd.torch_layer: is the tape still the one of a forward?)
 
-    def _taped_loop(self, nsteps, w, Ap, Bp, out, xref_traj, model_traj=None, estimator=None, L_traj=None):
-        """The taped loop of every form: ``_loop`` through mpcqp_rollout, _est, _tv or _tv_est as the options say, then the record of the tape."""
+    def _taped_loop(self, nsteps, w, Ap, Bp, out, xref_traj, model_traj=None, estimator=None, L_traj=None, affine=None):
+        """The taped loop of every form: ``_loop`` through mpcqp_rollout, _est, _tv or _tv_est as the options say -- or, with ``affine = (d_traj or
+        None, d_hold)``, mpcqp_rollout_affine -- then the record of the tape."""
         entry = 'mpcqp_rollout' + ('_tv' if model_traj is not None else '') + ('_est' if estimator is not None else '')
-        res = self._loop(entry, nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj, L_traj=L_traj)
+        aff = None
+        if affine is not None:
+            entry, (d_traj, d_hold) = 'mpcqp_rollout_affine', affine
+            rows = self.affine_rows()                 # (of the handle's own term: the tape's where there is no schedule)
+            if d_traj is None and not rows:
+                raise RuntimeError('rollout_affine: no d_traj given and no affine term set (set_affine); rollout is the taped loop without one')
+            res = self._loop(entry, nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, model_traj=model_traj, d_traj=d_traj, d_hold=d_hold)
+            if d_traj is not None:
+                rows, hold = int(np.prod(tuple(d_traj.shape)[2:])) // self.nx, int(d_hold)
+                aff = (rows, hold, (int(nsteps) + hold - 1) // hold + 1)
+            else:
+                aff = (rows, 0, 1)
+        else:
+            res = self._loop(entry, nsteps, w=w, Ap=Ap, Bp=Bp, out=out, xref_traj=xref_traj, estimator=estimator, model_traj=model_traj, L_traj=L_traj)
         sched = None
         if model_traj is not None:
             hold = int(model_traj[2])
             sched = (hold, (int(nsteps) + hold - 1) // hold, model_traj[0] is not None, model_traj[1] is not None)
-        self._tape = _Tape(int(nsteps), self._xref_rows_last, int(tuple(estimator['C'].shape)[-2]) if estimator is not None else 0, sched)
+        self._tape = _Tape(int(nsteps), self._xref_rows_last, int(tuple(estimator['C'].shape)[-2]) if estimator is not None else 0, sched, aff)
         self.rollout_count += 1
         return res
 
@@ -474,6 +497,30 @@ class BatchProblem:
         if model_traj is None or estimator is None:
             raise ValueError('rollout_tv_est: a model_traj = (Ad, Bd, hold) and an estimator dict(C=, L=, x_true=, v=) are both needed')
         return self._taped_loop(nsteps, w, Ap, Bp, out, xref_traj, model_traj=model_traj, estimator=estimator, L_traj=L_traj)
+
+    def rollout_affine(self, nsteps, d_traj=None, d_hold=1, model_traj=None, w=None, Ap=None, Bp=None, out=None, xref_traj=None):
+        """``mpc_run(d_traj=, d_hold=, model_traj=)`` that keeps a tape (mpcqp_rollout_affine, include_ext5/mpcqp_rollout_affine.h): the same arguments
+        and results, one closed-loop launch per step, and a tape that remembers the affine term of every solve as slots -- slot 0: the term the
+        problem held when the call began (zeros if none), slot e + 1: entry e of ``d_traj``; tape entry k was solved under slot 0 for k = 0 and
+        ``1 + (k - 1) // d_hold`` beyond.  ``d_traj=None``: the problem's own term (``set_affine``) throughout, one slot.  Afterwards
+        ``rollout_adjoint`` differentiates the loop with respect to the terms too ('d0', 'd_traj').  No estimator."""
+        self._need('rollout_affine')
+        return self._taped_loop(nsteps, w, Ap, Bp, out, xref_traj, model_traj=model_traj, affine=(d_traj, d_hold))
+
+    def rollout_affine_tape_bytes(self, nsteps, rows, d_hold=0, model_hold=0):
+        """Device memory the tape of ``rollout_affine`` takes (mpcqp_rollout_affine_tape_bytes; ``d_hold`` 0: no ``d_traj``, ``model_hold`` 0: no
+        ``model_traj``)."""
+        self._need('rollout_affine')
+        return self._tape_bytes('mpcqp_rollout_affine_tape_bytes', nsteps, model_hold, d_hold, rows)
+
+    def rollout_affine_slot(self, s):
+        """The affine term of slot s on the tape of a ``rollout_affine`` [B, rows, nx] (mpcqp_rollout_affine_get_slot; verification)."""
+        self._need('rollout_affine')
+        if self._tape is None or self._tape.aff is None:
+            raise RuntimeError('rollout_affine_slot: the last rollout was not a rollout_affine')
+        d = np.empty((self.batch, self._tape.aff[0], self.nx))
+        _lib.check(self._L.mpcqp_rollout_affine_get_slot(self._h, int(s), _ptr(d)), 'mpcqp_rollout_affine_get_slot')
+        return d
 
     def _tape_bytes(self, fn, *sizes):
         """What the library's ``fn`` says a tape of these sizes takes."""
@@ -541,15 +588,21 @@ class BatchProblem:
         On the tape of a ``rollout_tv_est`` (mpcqp_rollout_adjoint_tv_est): everything the scheduled sweep and the estimator sweep take, and
         'Ae_traj' [nseg, B, nx, nx], 'Be_traj' [nseg, B, nx, nu], 'L_traj' [nseg, B, nx, ny] -- the estimator path of the steps entry e was in
         force; 'Ae', 'Be', 'L' are their sums over the entries."""
+        aff_names = ('d0', 'd_traj')
+        if any(k in aff_names for k in want):
+            self._need('rollout_affine')
         self._need('rollout')
         tape = self._tape
         ny, sched = (tape.ny, tape.sched) if tape is not None else (0, None)
+        aff = tape.aff if tape is not None else None
         est_seeds = g_xhat is not None or g_y is not None
         tv_est_names, tv_names, est_names = ('Ae_traj', 'Be_traj', 'L_traj'), ('Ad_traj', 'Bd_traj', 'Ap_traj', 'Bp_traj'), ('eta', 'C', 'L', 'v', 'Ae', 'Be')
         named = lambda names: any(k in names for k in want)
         # (what was asked for, what the tape must have for it, what is said where it has not); on a scheduled tape without an estimator the
         # estimator's gradients are unknown names like any other
-        refusals = ((named(tv_est_names), sched is not None and ny, 'the gradients %s need the tape of a rollout_tv_est' % ', '.join(tv_est_names)),
+        refusals = ((named(aff_names), aff is not None, 'the gradients %s need the tape of a rollout_affine' % ', '.join(aff_names)),
+                    ('d_traj' in want, aff is not None and aff[1] > 0, "the gradient d_traj needs a rollout_affine that was given a d_traj (this one ran under the problem's own term: 'd0')"),
+                    (named(tv_est_names), sched is not None and ny, 'the gradients %s need the tape of a rollout_tv_est' % ', '.join(tv_est_names)),
                     (named(tv_names), sched is not None, 'the gradients %s need the tape of a rollout_tv (this one was made on one model)' % ', '.join(tv_names)),
                     (est_seeds and sched is not None, ny, 'g_xhat, g_y need the tape of a rollout_est (this one has no estimator)'),
                     ((est_seeds or named(est_names)) and sched is None, ny,
@@ -561,7 +614,7 @@ class BatchProblem:
             raise ValueError('rollout_adjoint: give g_x, g_u or both' + (', or g_xhat, g_y' if ny else ''))
         if tape is None:
             raise RuntimeError('rollout_adjoint: no rollout has been made (mpcqp_rollout)')
-        self._need('rollout' + ('_tv' if sched is not None else '') + ('_est' if ny else ''))
+        self._need('rollout_affine' if aff is not None else 'rollout' + ('_tv' if sched is not None else '') + ('_est' if ny else ''))
         K, rows = tape.K, tape.rows
         B, nx, nu = self.batch, self.nx, self.nu
         like = next(g for g in (g_x, g_u, g_xhat, g_y) if g is not None)
@@ -599,16 +652,22 @@ class BatchProblem:
                          Ad=('d_Ad_slots', nseg + 1, nx, whole(gave_Ad)), Bd=('d_Bd_slots', nseg + 1, nu, whole(gave_Bd)))
             for k, cols in (('Ap', nx), ('Bp', nu)) + ((('Ae', nx), ('Be', nu), ('L', ny)) if ny else ()):      # (per entry; the unsuffixed name: the sum over the entries)
                 split[k + '_traj'], split[k] = ('d_%s_entries' % k, nseg, cols, entries), ('d_%s_entries' % k, nseg, cols, total)
+        ao = _lib.RolloutAffineIO()
+        ao.struct_size = C.sizeof(_lib.RolloutAffineIO)
+        if aff is not None:                       # (the terms' gradients per slot [nslots, B, rows*nx]: slot 0 is 'd0', the slots behind it 'd_traj')
+            split.update(d0=('d_d_slots', aff[2], None, lambda a: a[0]), d_traj=('d_d_slots', aff[2], None, lambda a: a[1:]))
         bufs = {}
         for k in want:
             if k in split and split[k][0] not in bufs:
                 field, lead, cols, _ = split[k]
-                bufs[field] = self._out(like, (lead, B, nx, cols))
-                setattr(xo if hasattr(xo, field) else to, field, _ptr(bufs[field]))
+                bufs[field] = self._out(like, (lead, B, aff[0] * nx) if cols is None else (lead, B, nx, cols))
+                setattr(ao if hasattr(ao, field) else xo if hasattr(xo, field) else to, field, _ptr(bufs[field]))
         res = self._grads_out([k for k in want if k not in split], table, out, like)
         self._keep = [gx, gu, gxh, gy, res, bufs]
         # which C function, with which structs (None: not passed)
-        if sched is not None:
+        if aff is not None:
+            fn, structs = 'mpcqp_rollout_adjoint_affine', (io, mo, bo if bounds else None, to if sched is not None else None, ao)
+        elif sched is not None:
             fn, structs = ('mpcqp_rollout_adjoint_tv_est', (io, eo, mo, bo, to, xo)) if ny else ('mpcqp_rollout_adjoint_tv', (io, mo, bo, to))
         elif bounds:
             fn, structs = 'mpcqp_rollout_adjoint_bounds', (io, eo if ny else None, mo, bo)
@@ -618,7 +677,7 @@ class BatchProblem:
         for k in want:
             if k in split:
                 a = bufs[split[k][0]]
-                res[k] = split[k][3](a.sum(1)[:, None] if batch_sum else a)
+                res[k] = split[k][3](a.sum(1)[:, None] if batch_sum else a)      # ('d0': [B, ..] or [1, ..])
         return res
 
     def rollout_info(self):
@@ -645,6 +704,9 @@ class BatchProblem:
         if ny:                                    # (a rollout_est: the step data begin with the estimate, the plant state and the measurement are beside it)
             r.update(x_plant=np.empty((B, self.nx)), y_meas=np.empty((B, ny)))
             _lib.check(self._L.mpcqp_rollout_get_tape_est(self._h, int(k), _ptr(r['x_plant']), _ptr(r['y_meas'])), 'mpcqp_rollout_get_tape_est')
+        if self._tape.aff is not None:            # (a rollout_affine: the term the entry was solved with lies behind the rest of its step data)
+            r['d'] = np.empty((B, self._tape.aff[0], self.nx))
+            _lib.check(self._L.mpcqp_rollout_affine_get_tape(self._h, int(k), _ptr(r['d'])), 'mpcqp_rollout_affine_get_tape')
         return r
 
     def _finish_init(self, stream):
@@ -940,7 +1002,7 @@ class BatchProblem:
         at = None
         if d_traj is not None:                    # a schedule of affine terms: mpcqp_mpc_loop_affine, with or without a model schedule
             self._need('affine')
-            if entry != 'mpcqp_mpc_loop':
+            if entry not in ('mpcqp_mpc_loop', 'mpcqp_rollout_affine'):
                 raise NotImplementedError('a schedule of affine terms is for mpc_run (mpcqp_mpc_loop_affine): the taped rollouts do not carry the term')
             shp = tuple(d_traj.shape)
             if len(shp) < 3 or shp[1] != B:
@@ -972,12 +1034,16 @@ class BatchProblem:
                     et.struct_size, et.nentries = C.sizeof(_lib.EstTraj), ne
                     et.Lgain_traj = inp(L_traj, (ne, B, nx, ny), 'L_traj')
                 rc = getattr(self._L, entry)(self._h, K, C.byref(io), C.byref(mt), None if et is None else C.byref(et))
+            elif entry == 'mpcqp_rollout_affine':
+                rc = self._L.mpcqp_rollout_affine(self._h, K, C.byref(io), C.byref(mt), None if at is None else C.byref(at))
             elif at is not None:
                 entry = 'mpcqp_mpc_loop_affine'
                 rc = self._L.mpcqp_mpc_loop_affine(self._h, K, C.byref(io), C.byref(mt), C.byref(at))
             else:
                 entry = 'mpcqp_rollout_tv' if entry == 'mpcqp_rollout_tv' else 'mpcqp_mpc_loop_tv'
                 rc = getattr(self._L, entry)(self._h, K, C.byref(io), C.byref(mt))
+        elif entry == 'mpcqp_rollout_affine':
+            rc = self._L.mpcqp_rollout_affine(self._h, K, C.byref(io), None, None if at is None else C.byref(at))
         elif at is not None:
             entry = 'mpcqp_mpc_loop_affine'
             rc = self._L.mpcqp_mpc_loop_affine(self._h, K, C.byref(io), None, C.byref(at))

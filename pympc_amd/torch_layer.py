@@ -25,8 +25,9 @@ is the container of the device buffers and the owner of the graph; no torch oper
   asks the same one adjoint call (mpcqp_adjoint_bounds / mpcqp_rollout_adjoint_bounds, include/mpcqp_adjoint_bounds.h) for their
   gradients too: the multipliers of the active rows summed onto the bound each sits on, zero for a bound that is nowhere active.
 
-A closed-loop rollout is one differentiable operation in four forms -- ``mpc_rollout`` (state feedback on one model), ``mpc_rollout_est``
-(output feedback), ``mpc_rollout_tv`` (under a model schedule), ``mpc_rollout_tv_est`` (both) -- which are one description: each Function
+A closed-loop rollout is one differentiable operation in five forms -- ``mpc_rollout`` (state feedback on one model), ``mpc_rollout_est``
+(output feedback), ``mpc_rollout_tv`` (under a model schedule), ``mpc_rollout_tv_est`` (both), ``mpc_rollout_affine`` (state feedback with an
+affine term in the prediction model, with or without a model schedule) -- which are one description: each Function
 states its inputs and which options are present, ``_rollout_forward`` makes the taped loop of ``BatchProblem`` they pick, ``_rollout_backward``
 asks ONE ``rollout_adjoint`` call for exactly the gradients torch needs, and ``_model_paths`` is the rule by which the gradient of a model
 matrix is added up from its solve, estimator and plant paths.  The Riccati equations (``dare``, ``dre``) and the Kalman gains made of them
@@ -174,7 +175,10 @@ _per = lambda v, shp: v.sum(dim=0) if len(shp) == 2 else v      # (an unbatched 
 # input of a rollout -> (the gradient of rollout_adjoint it is made from, how; its own shape is put on last)
 _ROLLOUT_INPUTS = dict(
     x0=('lam', lambda v, shp: v[0]), w=('lam', lambda v, shp: v[1:]), xhat0=('eta', lambda v, shp: v[0]), v=('v', lambda v, shp: v),
-    u_prev=('uminus1', lambda v, shp: v), xref=('xref', lambda v, shp: v.sum(dim=0)), C=('C', _per), L=('L', _per), Ap=('Ap', _per), Bp=('Bp', _per))
+    u_prev=('uminus1', lambda v, shp: v), xref=('xref', lambda v, shp: v.sum(dim=0)), C=('C', _per), L=('L', _per), Ap=('Ap', _per), Bp=('Bp', _per),
+    d0=('d0', lambda v, shp: v),
+    # (entries beyond the last one a solve could use were never in force: zeros)
+    d=('d_traj', lambda v, shp: torch.cat([v[:shp[0]], v.new_zeros((max(shp[0] - v.shape[0], 0),) + tuple(v.shape[1:]))])))
 
 
 def _model_paths(est, sched, follows, given_Ad=False, given_Bd=False):
@@ -193,18 +197,22 @@ def _model_paths(est, sched, follows, given_Ad=False, given_Bd=False):
     return paths
 
 
-def _rollout_forward(ctx, fn, K, nsteps, inputs, names, params, hold=None):
+def _rollout_forward(ctx, fn, K, nsteps, inputs, names, params, hold=None, d_hold=None):
     """Forward of every form.  ``inputs``: forward's tensor inputs by name, in its order behind (K, nsteps[, hold]) -- keys of _ROLLOUT_INPUTS
     and, under a schedule (``hold``), 'Ad_traj', 'Bd_traj' and, with an estimator ('C' is among them), 'L_traj'.  ``update_model`` of the
     parameters, ``update(x0 or xhat0, u_prev, xref)`` with its solve (tape entry 0), then the taped loop of ``BatchProblem`` the options pick,
-    and the controller's and the context's books."""
+    and the controller's and the context's books.
+    With an affine term (``d_hold``; (K, nsteps, hold, d_hold) stand before the inputs, ``hold`` None without a model schedule): 'd0', the term
+    of that first solve (``set_affine`` before the update; None: the controller's own, or none), and 'd', the schedule of ``rollout_affine``."""
     x0 = inputs['x0']
     if not x0.is_cuda:
         raise ValueError('%s works on device tensors (x0 is on %s)' % (fn, x0.device))
-    est, sched = 'C' in inputs, hold is not None
+    est, sched, aff = 'C' in inputs, hold is not None, d_hold is not None
     B, nx, nu = K.B, K.nx, K.nu
     with _ordered(K):
         _put_params(ctx, K, names, params)
+        if aff and inputs['d0'] is not None:
+            K.set_affine(_det(inputs['d0']).reshape(B, -1))
         xr = _det(inputs['xref'])
         K.update(_det(inputs['xhat0'] if est else x0), _det(inputs['u_prev']), None if xr is None else xr.reshape(B, -1))
         new = lambda rows, cols: torch.empty((rows, B, cols), dtype=torch.float64, device=x0.device)
@@ -224,7 +232,10 @@ def _rollout_forward(ctx, fn, K, nsteps, inputs, names, params, hold=None):
             more['model_traj'] = (last['Ad'], last['Bd'], hold)
             if est:
                 more['L_traj'] = entries(inputs['L_traj'])
-        roll = getattr(K.prob, 'rollout' + ('_tv' if sched else '') + ('_est' if est else ''))
+        if aff:
+            d = _det(inputs['d'])
+            more.update(d_traj=d.reshape(d.shape[0], B, -1), d_hold=d_hold)
+        roll = getattr(K.prob, 'rollout_affine' if aff else 'rollout' + ('_tv' if sched else '') + ('_est' if est else ''))
         roll(nsteps, w=_det(inputs['w']), Ap=_bc(inputs['Ap'], (B, nx, nx)), Bp=_bc(inputs['Bp'], (B, nx, nu)), out=out, **more)
         for n, t in last.items() if sched else ():             # the controller is left with the last entry used: read back when somebody asks (update_model's way)
             if t is not None:
@@ -234,6 +245,7 @@ def _rollout_forward(ctx, fn, K, nsteps, inputs, names, params, hold=None):
         K.x0_rh, K.uminus1_rh, K._um1_on_device, K._u_last = (XH if est else X)[-1], U[-1], True, None
     ctx.K, ctx.count = K, K.prob.rollout_count
     ctx.fn, ctx.est, ctx.sched = fn, est, sched
+    ctx.first = 4 if aff else 3 if sched else 2            # (K, nsteps[, hold[, d_hold]]) stand before the tensor inputs, ``names`` behind them
     ctx.inputs, ctx.shapes = tuple(inputs), tuple(None if t is None else tuple(t.shape) for t in inputs.values())
     ctx.status, ctx.iters = st, it
     return (X, XH, Y, U) if est else (X, U)
@@ -245,7 +257,7 @@ def _rollout_backward(ctx, **seeds):
     if K.prob.rollout_count != ctx.count:
         raise RuntimeError('%s: the controller has been rolled out again since this forward (rollout %d then, %d now); '
                            'its tape is no longer the one to differentiate.' % (fn, ctx.count, K.prob.rollout_count))
-    first = 3 if sched else 2                              # (K, nsteps[, hold]) stand before the tensor inputs, ``names`` behind them
+    first = ctx.first
     ni = first + len(inputs)
     need = {n: bool(v) and shp is not None for n, v, shp in zip(inputs, ctx.needs_input_grad[first:ni], ctx.shapes)}
     shape = dict(zip(inputs, ctx.shapes))
@@ -253,7 +265,8 @@ def _rollout_backward(ctx, **seeds):
     unbatched = lambda n: len(shape[n]) == (3 if n in traj else 2)
     # (under a schedule rollout_adjoint puts these together from per-entry buffers, and batch_sum sums them too)
     split = [n for n in traj + ['Ap', 'Bp', 'L'] if need.get(n)] if sched else []
-    pneed, shared, batch_sum = _param_want(ctx, ctx.needs_input_grad[ni + 1:], [unbatched(n) for n in split])
+    # (the terms of an affine rollout are per instance, and batch_sum would sum their gradients too)
+    pneed, shared, batch_sum = _param_want(ctx, ctx.needs_input_grad[ni + 1:], [unbatched(n) for n in split] + [False for n in ('d0', 'd') if need.get(n)])
     if not any(need.values()) and not pneed:
         return (None,) * (ni + 1 + len(ctx.names))
     paths = _model_paths(est, sched, shape['Ap'] is None, shape.get('Ad_traj') is not None, shape.get('Bd_traj') is not None)
@@ -314,6 +327,53 @@ class _MPCRolloutTV(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_X, grad_U):
         return _rollout_backward(ctx, g_x=grad_X, g_u=grad_U)
+
+
+class _MPCRolloutAffine(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, K, nsteps, hold, d_hold, x0, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, d0, d, names, *params):
+        inputs = dict(x0=x0, u_prev=u_prev, xref=xref, w=w, Ap=Ap, Bp=Bp, Ad_traj=Ad_traj, Bd_traj=Bd_traj, d0=d0, d=d)
+        return _rollout_forward(ctx, 'mpc_rollout_affine', K, nsteps, inputs, names, params, hold, d_hold)
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_U):
+        return _rollout_backward(ctx, g_x=grad_X, g_u=grad_U)
+
+
+def mpc_rollout_affine(controller, x0, nsteps, d, d_hold=1, d0=None, Ad_traj=None, Bd_traj=None, hold=None, u_prev=None, xref=None, w=None, Ap=None, Bp=None,
+                       params=None, bounds=None, offset_in_plant=False):
+    """``mpc_rollout`` / ``mpc_rollout_tv`` with an affine term in the prediction model, x+ = Ad x + Bd u + d: ``(X [K+1,B,nx], U [K,B,nu])`` of
+    ``nsteps`` = K closed-loop steps in which the solve after step k uses entry ``k // d_hold`` of ``d`` [nent,B,nx] or [nent,B,Np,nx] (nent >=
+    ceil(K / d_hold)), as ``BatchMPCController.run(d_traj=, d_hold=)`` does; the first solve uses ``d0`` [B,nx] or [B,Np,nx] in the shape of the
+    entries (None: the controller's own term, or none).  With ``Ad_traj`` / ``Bd_traj`` and ``hold`` the loop runs under a model schedule too, as
+    ``mpc_rollout_tv``: one entry (A_e, B_e, c_e) per relinearisation.  Forward is ``update_model``, ``set_affine(d0)``, ``update`` with its solve,
+    then ONE ``mpcqp_rollout_affine``; backward is ONE ``mpcqp_rollout_adjoint_affine`` (include_ext5/mpcqp_rollout_affine.h).  Differentiable
+    with respect to ``d``, ``d0`` and everything those two layers differentiate.  The plant does not get the offset, unless ``offset_in_plant``:
+    then entry ``k // d_hold`` of a one-row ``d`` is added to ``w[k]`` (in torch: its gradient arrives through ``w``) -- a relinearised plant.
+    The controller is left with the last entry used."""
+    names, tensors = _check_args('mpc_rollout_affine', controller, params, Ap, Bp, bounds)
+    nsteps, d_hold = int(nsteps), int(d_hold)
+    if d_hold < 1:
+        raise ValueError('mpc_rollout_affine: d_hold must be >= 1')
+    nent = (nsteps + d_hold - 1) // d_hold
+    if not hasattr(d, 'data_ptr') or not d.is_cuda or d.dim() not in (3, 4) or d.shape[0] < nent or d.shape[1] != controller.B:
+        raise ValueError('mpc_rollout_affine: d must be a device tensor [nent, B, nx] or [nent, B, Np, nx] with nent >= ceil(nsteps / d_hold)')
+    if d0 is not None and (not hasattr(d0, 'data_ptr') or not d0.is_cuda or d0.numel() != d[0].numel()):
+        raise ValueError('mpc_rollout_affine: d0 must be a device tensor in the shape of an entry of d')
+    sched = Ad_traj is not None or Bd_traj is not None
+    if sched and hold is None:
+        raise ValueError('mpc_rollout_affine: a model schedule needs its hold')
+    if sched:
+        nseg = (nsteps + int(hold) - 1) // int(hold)
+        for n, t in (('Ad_traj', Ad_traj), ('Bd_traj', Bd_traj)):
+            if t is not None and (not hasattr(t, 'data_ptr') or not t.is_cuda or t.dim() not in (3, 4) or t.shape[0] < nseg):
+                raise ValueError('mpc_rollout_affine: %s must be a device tensor [nseg, B, ., .] or [nseg, ., .] with nseg >= ceil(nsteps / hold)' % n)
+    if offset_in_plant:
+        if d.numel() != d.shape[0] * controller.B * controller.nx:
+            raise ValueError('mpc_rollout_affine: offset_in_plant is for a one-row term [nent, B, nx] (the plant steps once: which stage of an Np-row term is its own is not said)')
+        off = d.reshape(d.shape[0], controller.B, controller.nx).repeat_interleave(d_hold, dim=0)[:nsteps]
+        w = off if w is None else w + off
+    return _MPCRolloutAffine.apply(controller, nsteps, int(hold) if sched else None, d_hold, x0, u_prev, xref, w, Ap, Bp, Ad_traj, Bd_traj, d0, d, names, *tensors)
 
 
 def mpc_rollout_tv(controller, x0, nsteps, Ad_traj, Bd_traj, hold, u_prev=None, xref=None, w=None, Ap=None, Bp=None, params=None, bounds=None):

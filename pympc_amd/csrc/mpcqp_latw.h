@@ -320,15 +320,15 @@ __device__ __forceinline__ double latw_dpp(double x) {
     return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
 }
 // Left to itself the compiler requests one or two 16-byte reads at a time and waits for each (an LDS round trip per pair of FMAs: it has ~ 30
-// free registers here), so the reads are issued in groups of H = 2 column pairs behind scheduling fences, and the next
-// group's reads are issued before the current group's FMAs (two groups of registers in flight).  (Requesting a wave's first group of matrix
-// pairs on the other side of the barrier, at the start of level 1 forward -- they depend on nothing the iteration computes -- took 80 cycles off
-// this phase and, through 16 more live registers, added 300 to the owner passes: 7 572 against 7 352 cycles per iteration; not kept.)
+// free registers here), so the reads are issued in groups of H column pairs behind scheduling fences, and the next group's reads are issued
+// before the current group's FMAs (two groups of registers in flight).  H = 1 with eight waves: 24 registers in flight instead of 48 leave the
+// iteration without a scratch reload; H = 2 with four waves, as it always was.  Requesting a wave's first matrix pairs in front of the barrier
+// was measured twice and not kept (LAB_NOTES.md, profiles/top_prefetch.txt).
 // head(): what the wave issues between the requests of its first matrix group and that group's first FMAs, where it would otherwise only wait (latw_top_own)
 struct LatwNone { __device__ __forceinline__ void operator()() const {} };
 template <int N, int W, class Head = LatwNone>
 __device__ __forceinline__ void latw_top_valu(const double *TopL, const double *Xt, double *Cc, int lane, Head head = Head{}) {
-    constexpr int NTOP = BcrFmt::top_count(N), H = 2;
+    constexpr int NTOP = BcrFmt::top_count(N), H = NT == 512 ? 1 : 2;
     static_for<0, NTOP>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
         if constexpr (r % NWAVES == W) {
